@@ -14,12 +14,16 @@ region ends with the single RCCL reduce that merges the per-GPU block hashes (we
 value = frames fused by all ranks / max-over-ranks wall time.
 
 The LAST stdout line is a compact JSON object (< 8 KB, tests/test_bench_line_cpu.py): the contract's keys plus roofline (the integrate
-kernel, HIP-event timed on the volume's own stream; frac = HBM bytes per launch / launch time / 8 TB/s), cpu_baseline (the CPU oracle =
-port of the reference path, timed on this box's host cores on a bounded sample of the same frames; N=1, rank 0 only), parity (the GPU
-volume for that sample compared bit-for-bit with the oracle's), icp (iterations/s at 307 200 points, the figure of the in-tolerance
-mode next to the default's), tracking, multi_gpu.  Everything else the sections measure goes to bench_detail.json next to this file
-(and to gpurun_out/ when that directory exists); `--full` adds the supplementary sections (raycast, volume ops, host images, sum form,
-depth filter), `--counters` re-measures the HBM counters with rocprofv3 instead of taking the committed ones (profiles/).
+kernel, HIP-event timed on the volume's own stream inside the timed steps; frac = HBM bytes per launch / launch time / 8 TB/s) and multi_gpu.
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs DIR), print the line.  The timed steps
+cycle through at most MAX_RESIDENT_FRAMES frames per rank, so any --steps fits in HBM and in the set-up time.
+
+`--full` adds every other measurement, one module per section under benchparts/: the roofline extras (one frame per launch, HBM traffic,
+sum form), cpu_baseline (the CPU oracle = port of the reference path, timed on the host's cores on a bounded sample of the same frames;
+N=1, rank 0 only), parity (the GPU volume for that sample compared bit-for-bit with the oracle's), icp (iterations/s at 307 200 points,
+the figure of the in-tolerance mode next to the default's), tracking, dense fusion, raycast, volume ops, host images, general update and
+depth filter.  Their compact figures join the result line; everything goes to bench_detail.json next to this file (or --detail-file).
+`--counters` re-measures the HBM counters with rocprofv3 instead of taking the committed ones (profiles/).
 
 N > 1: the merge inside the timed region is the PRODUCT's -- op_volume_merge_rccl (csrc/merge_rccl.hip) on an ncclComm_t this script
 makes (ncclGetUniqueId on rank 0, carried over the process group, ncclCommInitRank); `--merge-impl torch` selects the torch.distributed
@@ -48,6 +52,12 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 W, H = 640, 480
+# Frames per rank generated into HBM (2.1 MB and ~1-2 ms of set-up each): step k fuses slot k mod (MAX_RESIDENT_FRAMES / F) of them, so up to
+# 20 steps of 100 frames every step fuses new frames, as before; longer runs fuse the same frames again
+MAX_RESIDENT_FRAMES = 2000
+# --dump-outputs: the voxels of this many blocks (x 512 voxels x 5 float32 = 42 MB) and the per-block arrays of at most DUMP_MAX_BLOCKS (64 B each: 16 MB)
+DUMP_SAMPLE_BLOCKS = 4096
+DUMP_MAX_BLOCKS = 1 << 18
 
 
 def main():
@@ -73,13 +83,16 @@ def main():
     ap.add_argument("--merge-impl", choices=["auto", "cabi", "torch"], default="auto",
                     help="the N > 1 merge: cabi = op_volume_merge_rccl on a communicator made here (the product's path; auto picks it on RCCL), "
                          "torch = the torch.distributed mirror of the same algorithm (auto picks it on the gloo test hook)")
-    ap.add_argument("--full", action="store_true", help="also run the supplementary sections (raycast, volume ops, host images, general update, depth filter, sum form): "
-                                                         "they go to bench_detail.json, never to the result line")
+    ap.add_argument("--full", action="store_true", help="also run every measurement besides the headline figure (roofline extras, CPU baseline + parity, ICP, tracking, "
+                                                         "dense fusion, raycast, volume ops, host images, general update, depth filter, sum form) and write bench_detail.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the fused volume they produced as DIR/<name>.npy "
+                                                                         "(float32 / float64, < 64 MB: every block's key and voxel sums, the voxels of a seeded sample of blocks)")
     ap.add_argument("--counters", action="store_true", help="re-measure roofline.traffic with rocprofv3 PMC passes (~30 s) instead of scaling the committed measurement "
                                                              "(profiles/r06_integrate_counters.json) to this run's launch shape")
     ap.add_argument("--save-counters", action="store_true", help="with --counters: rewrite profiles/r06_integrate_counters.json from this run")
     ap.add_argument("--no-counters", action="store_true", help=argparse.SUPPRESS)   # rounds 3-5: the passes used to be on by default
-    ap.add_argument("--detail-file", default=None, help="where the full (uncompacted) object goes (default: bench_detail.json next to bench.py)")
+    ap.add_argument("--detail-file", default=None, help="where the full (uncompacted) object goes (default with --full: bench_detail.json next to bench.py; "
+                                                             "a plain run writes it only when this is given)")
     ap.add_argument("--profile-every", type=int, default=1, help="HIP-event sample rate for the roofline (every k-th launch group)")
     args = ap.parse_args()
     if args.timed_only:
@@ -126,8 +139,10 @@ def main():
         F //= world     # the step's frames are split: the job fuses K x frames_per_step frames in total at any N
     n_local = K * F
     first = rank * n_local  # contiguous shard of the global sequence
+    K_res = min(K, max(1, MAX_RESIDENT_FRAMES // F))   # steps whose frames are resident; step k fuses slot k % K_res
+    n_res = K_res * F
     # ---- inputs: generated straight into HBM, not timed
-    depth, rgb, poses = S.room_sequence_torch(first, n_local, dev)
+    depth, rgb, poses = S.room_sequence_torch(first, n_res, dev)
     torch.cuda.synchronize()
 
     hv = I.CubeHandler(device=local_rank)  # default pool (2^18 blocks, 2.7 GB); it grows on demand like the reference's map
@@ -161,16 +176,16 @@ def main():
         hv.Raycast(poses[0])
     # ---- warmup: W untimed steps (+ one merge so RCCL is initialised), then start from empty
     for w in range(Wm):
-        s = (w % K) * F
+        s = (w % K_res) * F
         hv.IntegrateSequence(depth[s:s + F], rgb[s:s + F], poses[s:s + F])
     hv.Synchronize()
     if distributed:
         # The warm-up merge must see what the timed one will: its temporaries (a rank's packed blocks, the receive buffers, the root's gathered map: GBs) come from
         # the library's buffer cache, and a cached buffer only serves requests of its size class -- a merge of W steps' blocks would leave the timed merge to
         # hipMalloc its buffers inside the timed region (allocations of that size have taken 0.4 - 1.5 s on this pool, profiles/r05_transform_pool.txt).  So the
-        # shard is fused completely (K steps, ~25 ms per 1000 frames, untimed) before the warm-up merge.
+        # shard is fused completely (its resident frames: the timed steps fuse no others; ~25 ms per 1000 frames, untimed) before the warm-up merge.
         hv.Clear()
-        hv.IntegrateSequence(depth[:n_local], rgb[:n_local], poses[:n_local])
+        hv.IntegrateSequence(depth[:n_res], rgb[:n_res], poses[:n_res])
         hv.Synchronize()
         err = None
         try:
@@ -195,7 +210,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for k in range(K):
-        s = k * F
+        s = (k % K_res) * F
         hv.IntegrateSequence(depth[s:s + F], rgb[s:s + F], poses[s:s + F])
     hv.Synchronize()
     t_fuse = time.perf_counter() - t0
@@ -227,6 +242,8 @@ def main():
     if world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(hv, args.dump_outputs)   # before any section: they reuse the volume
 
     out = None
     if rank == 0:
@@ -253,9 +270,9 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
-            "config": {"workload": "ImageSequenceIntegration: %d-frame synthetic 640x480 room sequence per GPU, %.4g m voxel, "
-                                   "trunc 0.1 m, frames resident in HBM" % (n_local, args.voxel),
-                       "frames_per_step": F, "frames_per_gpu": n_local, "sharding": "contiguous frames per GPU, one RCCL merge at end",
+            "config": {"workload": "ImageSequenceIntegration: %d-frame synthetic 640x480 room sequence per GPU%s, %.4g m voxel, "
+                                   "trunc 0.1 m, frames resident in HBM" % (n_local, " (cycling through its first %d frames)" % n_res if K_res < K else "", args.voxel),
+                       "frames_per_step": F, "frames_per_gpu": n_local, "resident_frames_per_gpu": n_res, "sharding": "contiguous frames per GPU, one RCCL merge at end",
                        "voxel_m": args.voxel, "update_mode": "exact (voxels bit-identical to the reference's CPU path)"},
             "fusion_only_frames_per_s": total_frames / t_fuse_max,
             "pool": growth,   # the pool starts at 2^18 blocks and grows on demand INSIDE the timed region (grows / replayed batches since create)
@@ -288,16 +305,17 @@ def main():
                          "shader_cycles_per_launch": kc_cycles, "shader_clock_ghz": kc_cycles / k3_s / 1e9 if k3_s > 0 else None},
         }
     sections = {}
-    if rank == 0:
-        # ---- everything below is supplementary (rank 0; most of it N = 1 only): one module per section under benchparts/
+    if rank == 0 and (args.full or args.counters):
+        # ---- everything below is supplementary (rank 0; most of it N = 1 only): one module per section under benchparts/.  Only with --full
+        # (--counters alone: the roofline extras that carry the live counters), so that a plain run is the headline figure and nothing else
         import types
         from benchparts import roofline_extras, raycast, volume_ops, host_images, general_update, depth_filter, cpu_baseline, icp, tracking, dense_fusion
-        c = types.SimpleNamespace(args=args, torch=torch, dev=dev, rank=rank, world=world, local_rank=local_rank, hv=hv, depth=depth, rgb=rgb, poses=poses, K=K, F=F,
-                                  n_local=n_local, I=I, S=S, ROOT=ROOT, W=W, H=H, HBM_PEAK_GBS=HBM_PEAK_GBS, stats=stats, prof=prof,
+        c = types.SimpleNamespace(args=args, torch=torch, dev=dev, rank=rank, world=world, local_rank=local_rank, hv=hv, depth=depth, rgb=rgb, poses=poses, K=K_res, F=F,
+                                  n_local=n_res, I=I, S=S, ROOT=ROOT, W=W, H=H, HBM_PEAK_GBS=HBM_PEAK_GBS, stats=stats, prof=prof,
                                   frames_per_launch=frames_per_launch, k3_s=k3_s, kc_cycles=kc_cycles, batch_bytes=batch_bytes)
         single = world == 1
         c.oracle = None
-        if single and not args.no_cpu_baseline:
+        if single and args.full and not args.no_cpu_baseline:
             from oracle import oracle as _oracle   # the cpu_baseline leg: the CPU oracle as the timed baseline and the parity checker, never on the measured path
             c.oracle = _oracle
 
@@ -308,29 +326,27 @@ def main():
 
         if single and args.full:
             section("raycast", raycast.run)            # first: the volume still holds the timed region's frames
-        if not args.timed_only:
-            section("roofline_extras", roofline_extras.run)
+        section("roofline_extras", roofline_extras.run)
         if single and args.full:
             section("volume_ops", volume_ops.run)
             section("host_images", host_images.run)
             section("general_update", general_update.run)
             section("depth_filter", depth_filter.run)
-        if single and not args.no_cpu_baseline:
+        if single and args.full and not args.no_cpu_baseline:
             section("cpu_baseline", cpu_baseline.run)
-        # ICP / tracking do not shard (replicas only): they are one-GPU measurements and run at N = 1 (or with --full), so that an N > 1 run is the
-        # sharded fusion + the merge and nothing else keeps the other ranks waiting at the final barrier
-        if not args.no_icp and (single or args.full):
+        # ICP / tracking do not shard (replicas only): one-GPU measurements, run at any N with --full
+        if args.full and not args.no_icp:
             section("icp", icp.run)
-        if not args.no_tracking and (single or args.full):
+        if args.full and not args.no_tracking:
             section("tracking", tracking.run)
             section("dense_fusion", dense_fusion.run)
-        out["section_seconds"] = sections
-
     if rank == 0:
-        # the whole object goes to a file; the LAST stdout line is its compact form (the driver parses that line: round 5's 28 KB line was not parseable)
-        detail = args.detail_file or os.path.join(ROOT, "bench_detail.json")
+        out["section_seconds"] = sections
+        # the whole object goes to a file (with --full, or where --detail-file names one); the LAST stdout line is its compact form (the driver
+        # parses that line: round 5's 28 KB line was not parseable)
         wrote = []
-        for path in [detail] + ([os.path.join(ROOT, "gpurun_out", "bench_detail.json")] if os.path.isdir(os.path.join(ROOT, "gpurun_out")) and not args.detail_file else []):
+        if args.full or args.detail_file:
+            path = args.detail_file or os.path.join(ROOT, "bench_detail.json")
             try:
                 with open(path, "w") as f:
                     json.dump(out, f, indent=1)
@@ -346,6 +362,27 @@ def main():
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(hv, out_dir):
+    """--dump-outputs: what a caller of the timed path receives, the fused volume (CubeHandler::GetCubeMap: block keys, 512 voxels
+    {sdf, weight, c0, c1, c2} per block), with blocks in (x, y, z) key order.  The samples are drawn with a fixed seed from that order, so
+    two builds that fuse the same volume write the same files:
+      block_keys.npy          float64 [n, 3]         every block's key (a seeded sample of DUMP_MAX_BLOCKS when there are more)
+      block_voxel_sums.npy    float64 [n, 5]         each of those blocks' five voxel fields summed over its 512 voxels
+      sample_block_keys.npy   float64 [m, 3]         the keys of DUMP_SAMPLE_BLOCKS blocks drawn from them
+      sample_voxels.npy       float32 [m, 512, 5]    those blocks' voxels, as stored"""
+    keys, vox = hv.GetCubeMap(sort=False)
+    order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+    rng = np.random.default_rng(20261016)
+    if len(order) > DUMP_MAX_BLOCKS:
+        order = order[np.sort(rng.choice(len(order), DUMP_MAX_BLOCKS, replace=False))]
+    pick = order[np.sort(rng.choice(len(order), min(len(order), DUMP_SAMPLE_BLOCKS), replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "block_keys.npy"), keys[order].astype(np.float64))
+    np.save(os.path.join(out_dir, "block_voxel_sums.npy"), vox.sum(axis=1, dtype=np.float64)[order])
+    np.save(os.path.join(out_dir, "sample_block_keys.npy"), keys[pick].astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_voxels.npy"), np.ascontiguousarray(vox[pick], np.float32))
 
 
 def _r(x, nd=4):

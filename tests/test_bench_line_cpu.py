@@ -6,6 +6,8 @@ import json
 import os
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -74,3 +76,44 @@ def test_compact_line_of_a_two_rank_run_carries_the_merge():
     assert "icp" not in r and "tracking" not in r and "cpu_baseline" not in r
     assert abs(r["value"] * r["ms_per_step"] * 1e-3 * r["steps"] - 2 * r["config"]["frames_per_gpu"]) / (2 * r["config"]["frames_per_gpu"]) < 1e-3
     assert 0 < r["roofline"]["frac"] <= 1
+
+
+class _Volume:
+    """Stands in for CubeHandler.GetCubeMap(sort=False): n blocks in a scrambled order."""
+    def __init__(self, n, seed):
+        rng = np.random.default_rng(seed)
+        keys = np.stack(np.unravel_index(rng.choice(64 ** 3, n, replace=False), (64, 64, 64)), axis=1).astype(np.int32) - 32
+        self.keys, self.vox = keys, rng.standard_normal((n, 512, 5)).astype(np.float32)
+
+    def GetCubeMap(self, sort=True):
+        assert not sort
+        return self.keys, self.vox
+
+
+def test_dump_outputs_writes_float_arrays_in_key_order_and_the_same_sample_for_the_same_volume(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy only, under 64 MB, blocks in key order, and a sample that depends on the volume's content alone
+    (the same blocks listed in another order give the same files); above DUMP_MAX_BLOCKS the per-block arrays are a sample too."""
+    import bench
+    v = _Volume(5000, 1)
+    bench.dump_outputs(v, str(tmp_path / "a"))
+    perm = np.random.default_rng(2).permutation(5000)
+    w = _Volume(5000, 1)
+    w.keys, w.vox = v.keys[perm], v.vox[perm]
+    bench.dump_outputs(w, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["block_keys.npy", "block_voxel_sums.npy", "sample_block_keys.npy", "sample_voxels.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) < 64 << 20
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    keys = np.load(tmp_path / "a" / "block_keys.npy")
+    assert keys.shape == (5000, 3) and np.all(np.diff(keys[:, 0] * 1e6 + keys[:, 1] * 1e3 + keys[:, 2]) > 0)
+    sk, sv = np.load(tmp_path / "a" / "sample_block_keys.npy"), np.load(tmp_path / "a" / "sample_voxels.npy")
+    assert sv.shape == (bench.DUMP_SAMPLE_BLOCKS, 512, 5) and sv.dtype == np.float32
+    row = {tuple(k): i for i, k in enumerate(v.keys.tolist())}
+    idx = [row[tuple(k)] for k in sk.astype(np.int32).tolist()]
+    assert np.array_equal(sv, v.vox[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "block_voxel_sums.npy")[:3], v.vox[[row[tuple(k)] for k in keys[:3].astype(np.int32).tolist()]].sum(axis=1, dtype=np.float64))
+    monkeypatch.setattr(bench, "DUMP_MAX_BLOCKS", 4500)
+    bench.dump_outputs(v, str(tmp_path / "c"))
+    assert np.load(tmp_path / "c" / "block_keys.npy").shape == (4500, 3) and np.load(tmp_path / "c" / "block_voxel_sums.npy").shape == (4500, 5)
