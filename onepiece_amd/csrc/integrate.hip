@@ -393,6 +393,12 @@ void kc_trace_dump(op_volume* v) {
 #else
     (void)v;
 #endif
+#ifdef OP_PX_TRACE
+    unsigned long long pw[2] = {0, 0};
+    if (hipSetDevice(v->device) == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpyFromSymbol(pw, HIP_SYMBOL(g_px_waves), sizeof(pw)) == hipSuccess)
+        fprintf(stderr, "px trace (k_integrate, since load): %llu wave-projections, %llu took the exact fallback (%.3f %%)\n", pw[0], pw[1],
+                pw[0] ? 100.0 * (double)pw[1] / (double)pw[0] : 0.0);
+#endif
 }
 
 } // namespace opv

@@ -75,7 +75,33 @@ struct PxAxis {
     float t_lo, t_hi, h0, h1;
     int base;  // floor(c + 0.5) - 1
     int exact;
+    float k;   // c + 0.5 rounded to fp32
+    float hc;  // certificate of the fast path (px_certified): 0.5 - B, or -1 where the certificate may not be used
 };
+
+// ---- certified fast path (project_pixel<true>, -DOP_PX_CERTIFIED=0 builds without it) --------------------------------------
+// px_pixel_sp needs the correctly rounded quotient a = RN(nx / z) (nx = f * X, z = Z; a dozen instructions on the device).  Its result
+// is trunc(t) of the REAL sum t = a + K, K = c + 0.5, inside the image, i.e. for -1 < t < extent.  The fast path instead forms
+//     t' = RN(nx * y + K')   (one fma; K' = K rounded to fp32, |K' - K| is added to B),   y = the once-refined reciprocal of z,
+// and takes u = trunc(t') (v_cvt_i32_f32) with "inside" = (unsigned)u < extent.  That is the same pixel whenever t and t' lie in the same
+// open unit interval (n, n + 1): trunc is constant there and -1, extent are integers.  The certificate px_certified() accepts a lane only
+// when t' is farther than B from every integer, with B >= |t' - t| derived as follows, for 2^-60 <= |z| < 2^60 (the caller's window)
+// and |t'| <= T = extent + 1:
+//  * y0 = v_rcp(z) with |1 - z y0| = d <= 2^-20 (the hardware gives ~2^-23); e = RN(1 - z y0), y = RN(y0 + e y0) (two fmas):
+//    z y = (1 + d r1 - d^2 (1 + r1)) (1 + r2), |r1|, |r2| <= 2^-24, so |z y - 1| <= dy = 2^-24 + 2^-39.
+//  * q = nx / z (real); a = RN(q) = q (1 + ra), |ra| <= 2^-24; nx y = q (1 + dq), |dq| <= dy.
+//  * s = nx y + K' (exact inside the fma), t' = RN(s): |t' - s| <= 2^-24 |s|, |s| <= S = T / (1 - 2^-24).
+//  * |s - t| = |q dq - q ra + K' - K| <= |q| (dy + 2^-24) + |K' - K|, |q| <= Q = (S + |K|) / (1 - dy) (|K'| <= |K|(1 + 2^-24): absorbed below).
+//  So |t' - t| <= 2^-24 S + Q (dy + 2^-24) + |K' - K|, plus 2^-22 for the fract and the subtraction in px_certified (t' - floor(t') is exact
+//  except on (-1, 0), where it rounds and is clamped below 1 by at most 2^-24; f - 0.5 rounds by at most 2^-26) and for denormals.
+// Lanes with T < |t'| < 2^23 that pass are outside the image on both paths: there |t' - t| < 2^-22 (|t'| + |K|) + 2^-22 < |t'| - extent
+// (t' > T) resp. < |t'| - 1 (t' < -T) because extent < 2^20 and |K| < 2^20 -- so u = trunc(t') answers "outside" correctly.  |t'| >= 2^23
+// has fract 0 and NaN / inf have fract NaN: both fail the certificate, as do all lanes when hc = -1.
+OP_HD double px_cert_bound(double T, double absK) {
+    const double u = 0x1p-24, dy = u + 0x1p-39;
+    const double S = T / (1.0 - u), Q = (S + absK) / (1.0 - dy);
+    return (u * S + Q * (dy + u) + 0x1p-22) * (1.0 + 0x1p-40); // (the last factor covers the rounding of this double evaluation)
+}
 
 OP_HD PxAxis px_axis(float c, int extent) {
     PxAxis s;
@@ -85,6 +111,14 @@ OP_HD PxAxis px_axis(float c, int extent) {
     s.base = (int)ki - 1;
     s.exact = (double)s.t_lo == t_lo && (double)s.t_hi == t_hi && (double)s.h0 == h0 && (double)s.h1 == h1 && kf != 0.0 &&
               fabs((double)c) < 1.0e6 && extent > 0 && extent < (1 << 20);
+    s.k = (float)K;
+    s.hc = -1.0f;
+    if (s.exact) {
+        const double B = px_cert_bound((double)extent + 1.0, fabs(K)) + fabs((double)s.k - K); // (s.k is K rounded to fp32: exact, or off by <= 2^-24 |K|)
+        float hc = (float)(0.5 - B);
+        if ((double)hc > 0.5 - B) hc = nextafterf(hc, 0.0f); // rounded down: never wider than derived
+        s.hc = hc;
+    }
     return s;
 }
 
@@ -95,6 +129,18 @@ OP_HD bool px_pixel_sp(float a, const PxAxis& s, int& u) {
     const int fl = (int)ai + s.base + (af >= s.h0) + (af >= s.h1);
     u = fl < 0 ? 0 : fl;
     return a > s.t_lo && a < s.t_hi;
+}
+// The fast path's certificate on t' (see px_cert_bound): true when trunc(t') is the pixel px_pixel_sp gives, inside or outside.
+OP_HD float px_fract(float t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fractf(t); // v_fract_f32: t - floor(t) clamped below 1; NaN for NaN and +-inf
+#else
+    const float f = t - floorf(t);
+    return f < 1.0f ? f : 0x1.fffffep-1f;
+#endif
+}
+OP_HD bool px_certified(float t, const PxAxis& s) {
+    return fabsf(px_fract(t) - 0.5f) < s.hc; // distance of t to the nearest integer > 0.5 - hc >= B; false for NaN
 }
 OP_HD bool px_pixel_dp(float a, float c, int extent, int& u) {
     u = px_round_dp(a, c);

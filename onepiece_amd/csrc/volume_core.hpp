@@ -201,9 +201,10 @@ __device__ __forceinline__ float div_shared_rcp(float n, float z, float y) {
     r = __builtin_fmaf(-z, q, n);
     return __builtin_fmaf(r, y, q);
 }
-// Pixel index v * width + u of the projection, or -1 when it falls outside the image (Integrator.cpp:20-21,61-63).
+// The pixel (u, v) of the projection and whether each lies inside the image: the exact quotients (fx*X)/Z, (fy*Y)/Z and the
+// reference's rounding of them (Integrator.cpp:20-21,61-63).
 template <bool FAST>
-__device__ __forceinline__ int project_pixel(const CamParams& C, float X, float Y, float Z) {
+__device__ __forceinline__ void project_uv_exact(const CamParams& C, float X, float Y, float Z, int& u, int& v, bool& in_u, bool& in_v) {
     float nx = C.fx * X, ny = C.fy * Y, z = Z;
     const unsigned ez = (__float_as_uint(Z) >> 23) & 0xffu;    // biased exponent of Z
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(ez - 67u < 120u)) != 0ull, 0)) { // some lane outside 2^-60 <= |Z| < 2^60 (never, for a camera):
@@ -216,9 +217,59 @@ __device__ __forceinline__ int project_pixel(const CamParams& C, float X, float 
     const float e = __builtin_fmaf(-z, y, 1.0f);
     y = __builtin_fmaf(e, y, y);
     const float ax = div_shared_rcp(nx, z, y), ay = div_shared_rcp(ny, z, y);
+    in_u = FAST ? px_pixel_sp(ax, C.ax, u) : px_pixel_dp(ax, C.cx, C.width, u);
+    in_v = FAST ? px_pixel_sp(ay, C.ay, v) : px_pixel_dp(ay, C.cy, C.height, v);
+}
+
+// -DOP_PX_CERTIFIED=0 builds project_pixel<true> without the certified fast path (the exact sequence for every lane)
+#ifndef OP_PX_CERTIFIED
+#define OP_PX_CERTIFIED 1
+#endif
+// -DOP_PX_TRACE (development builds only): every translation unit counts the waves that enter project_pixel<true> and those of them that
+// take the exact fallback (g_px_waves[0], [1]; k_integrate's are printed by kc_trace_dump when the volume is destroyed)
+#ifdef OP_PX_TRACE
+static __device__ unsigned long long g_px_waves[2];
+#define OP_PX_COUNT(K) do { if (__lane_id() == (unsigned)__builtin_ctzll(__builtin_amdgcn_read_exec())) atomicAdd(&g_px_waves[K], 1ull); } while (0)
+#else
+#define OP_PX_COUNT(K) do { } while (0)
+#endif
+
+// Pixel index v * width + u of the projection, or -1 when it falls outside the image (Integrator.cpp:20-21,61-63).
+// FAST (px_axis exact on both axes), certified path (px_round.hpp px_cert_bound): t' = fma(f*X, y, c + 0.5) per axis, the pixel is
+// trunc(t') when t' is farther than B from every integer; a wave with any lane that is not (roughly 1 in 10^3..10^4 lane-axes, or |Z|
+// outside the window, or NaN) runs the exact sequence for those lanes out of line.
+template <bool FAST>
+__device__ __forceinline__ int project_pixel(const CamParams& C, float X, float Y, float Z) {
     int u, v;
-    const bool in_u = FAST ? px_pixel_sp(ax, C.ax, u) : px_pixel_dp(ax, C.cx, C.width, u);
-    const bool in_v = FAST ? px_pixel_sp(ay, C.ay, v) : px_pixel_dp(ay, C.cy, C.height, v);
+    bool in_u, in_v;
+    if (FAST && OP_PX_CERTIFIED) {
+        OP_PX_COUNT(0);
+        const float nx = C.fx * X, ny = C.fy * Y;
+        float y = __builtin_amdgcn_rcpf(Z);
+        const float e = __builtin_fmaf(-Z, y, 1.0f);
+        y = __builtin_fmaf(e, y, y);
+        const float tx = __builtin_fmaf(nx, y, C.ax.k), ty = __builtin_fmaf(ny, y, C.ay.k);
+        // 2^-60 <= |Z| < 2^60: the biased exponent (bits 24..31 of the sign-less word shifted left once) in [67, 187)
+        const bool win = (__float_as_uint(Z) << 1) - (67u << 24) < (120u << 24);
+        const bool cx = px_certified(tx, C.ax), cy = px_certified(ty, C.ay);
+        u = (int)tx; v = (int)ty; // v_cvt_i32_f32 truncates toward zero; a certified |t'| is below 2^23
+        // (one ballot per compare: each is the compare's own mask, and the ANDs stay scalar -- a ballot of the combined bool costs
+        // a v_cndmask + v_cmp to rebuild the mask; a && chain becomes nested branches)
+        const unsigned long long ok = __builtin_amdgcn_ballot_w64(win) & __builtin_amdgcn_ballot_w64(cx) & __builtin_amdgcn_ballot_w64(cy);
+        if (__builtin_expect(ok != __builtin_amdgcn_read_exec(), 0)) { // some active lane not certified
+            const bool cert = win & cx & cy;
+            OP_PX_COUNT(1);
+            if (!cert) {
+                project_uv_exact<true>(C, X, Y, Z, u, v, in_u, in_v);
+                u = in_u ? u : -1;
+                v = in_v ? v : -1;
+            }
+        }
+        in_u = (unsigned)u < (unsigned)C.width;
+        in_v = (unsigned)v < (unsigned)C.height;
+    } else {
+        project_uv_exact<FAST>(C, X, Y, Z, u, v, in_u, in_v);
+    }
     return (in_u && in_v) ? (int)__umul24((unsigned)v, (unsigned)C.width) + u : -1; // both factors < 2^20: one full-rate 24-bit multiply
 }
 
