@@ -1,7 +1,10 @@
 // Geometry/Ransac.h -- geometry::EstimateRigidTransformationRANSAC (reference: src/Geometry/Ransac.h:12-13, Ransac.cpp:7-40, which drives the
-// vendored GRANSAC template with src/Geometry/TransformationModel.hpp).  Host C++, on the path of example/DenseFusion only (submap-to-submap
-// registration); not accelerated and NOT part of the pinned parity claim: the reference seeds its samplers from std::random_device, so two runs
-// of the reference itself differ.
+// vendored GRANSAC template with src/Geometry/TransformationModel.hpp).  On the path of example/DenseFusion only (submap-to-submap
+// registration); NOT part of the pinned parity claim: the reference seeds its samplers from std::random_device, so two runs of the reference
+// itself differ.  Two paths (OP_RUNTIME_OPT_GLOBAL_REGISTRATION): 0 (default) host C++ (src/RansacRigid.cpp); 1 the draws (the same
+// std::mt19937 stream per iteration, the same eight indices) and the 8-point fits stay on the host, every hypothesis is scored on the device
+// (op_ransac_count_inliers) and the winner's inliers are gathered there (op_ransac_inlier_ids).  The counts are integers over the same float32
+// test, so the winner, T, the inliers and their order are identical on both paths.
 //
 // What the reference computes, restated (src/RansacRigid.cpp): max_iteration times, draw 8 distinct correspondences, fit the rigid transform of
 // those 8 (geometry::EstimateRigidTransformation), count the correspondences it maps to within `threshold` (Euclidean distance, strictly below);

@@ -1,5 +1,11 @@
-// Registration/3DFeature.h -- FPFH point features (reference: src/Registration/3DFeature.h:16-23, 3DFeature.cpp:9-130).  Host C++ for
-// example/DenseFusion's submap registration; not accelerated, not part of the pinned parity claim (it feeds an RNG-driven RANSAC).
+// Registration/3DFeature.h -- FPFH point features (reference: src/Registration/3DFeature.h:16-23, 3DFeature.cpp:9-130), for
+// example/DenseFusion's submap registration; not part of the pinned parity claim (it feeds an RNG-driven RANSAC).
+// Two paths, chosen by op_runtime_set_option(OP_RUNTIME_OPT_GLOBAL_REGISTRATION): 0 (default) the host loops of src/GlobalRegistration.cpp;
+// 1 the device (op_fpfh_compute: k_fpfh_neighbours, k_spfh, k_fpfh), which restates those loops operation by operation.  Identical on both:
+// the neighbour lists (order and count), the second and third angle's histograms and every feature bin built from them, bit for bit.  The
+// ONE-BIN RULE for the first angle: the host rounds it with its libm's atan2f, the device rounds a double atan2 once; the two differ by at most
+// one ulp, so a pair whose angle lies within an ulp of a bin boundary (boundaries are k * 2 pi / 11 - pi, and the +-pi wrap) may count in the
+// adjacent bin, and the features that include that histogram move by that one increment.  No pair of the tested room clouds does.
 //
 // A feature is a 33-bin histogram (3 angles x 11 bins) held in a geometry::VectorX.  ComputeFPFHFeature follows the reference's arithmetic as
 // written (src/Feature3D.cpp): neighbours = the points whose SQUARED distance is below `radius` (the reference hands the radius to nanoflann's
@@ -9,6 +15,8 @@
 // a third whose neighbour sum is zero stays zero here (the reference multiplies by 100/0 and stores NaN).  The reference's ComputeSPFH takes
 // its KDTree wrapper as an argument and is therefore not part of this surface.
 #pragma once
+#include <vector>
+
 #include "Geometry/Geometry.h"
 #include "Geometry/PointCloud.h"
 
@@ -22,6 +30,10 @@ typedef geometry::PointXList FeatureSet;
 // the three Darboux-frame angles and the distance of an oriented point pair (3DFeature.cpp:9-27): (atan2(w.nt, u.nt), v.nt, u.d, |pt - ps|)
 PairDescriptor ComputePairDescriptor(const geometry::Point3& ps, const geometry::Point3& ns, const geometry::Point3& pt, const geometry::Point3& nt);
 void ComputeFPFHFeature(const geometry::PointCloud& pcd, FeatureSet& fpfh_features, int knn = 100, float radius = 0.1);
+// (not in the reference) the same call, also handing out what it is built from: the neighbour list of every point (the point itself first) and
+// the simplified histograms of the first pass; either pointer may be null.  What examples/cpp/GlobalRegistration.cpp dumps and the tests compare.
+void ComputeFPFHFeatureDebug(const geometry::PointCloud& pcd, FeatureSet& fpfh_features, int knn, float radius, std::vector<std::vector<int> >* neighbours_out,
+                             std::vector<std::vector<float> >* spfh_out);
 
 } // namespace registration
 } // namespace one_piece

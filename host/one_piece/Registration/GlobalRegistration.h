@@ -1,9 +1,13 @@
 // Registration/GlobalRegistration.h -- feature-based global registration (reference: src/Registration/GlobalRegistration.h:12-38,
 // GlobalRegistration.cpp:28-265): FPFH features, nearest-feature matching, three rounds of distance-consistency pruning, RANSAC over the
 // surviving correspondences.  Same names, signatures, defaults and public members as the reference, so that example/DenseFusion (DenseSlam.h:8-9,
-// DenseSlam.cpp:76,107) compiles against it unedited.  Host C++ (src/GlobalRegistration.cpp); it is what the reference runs between submaps, off
-// the fusion / tracking hot path, and it is not accelerated.  Parity: unpinned -- the result depends on the RANSAC sampler's seed, which the
-// reference takes from std::random_device.
+// DenseSlam.cpp:76,107) compiles against it unedited.  It is what the reference runs between submaps, off the fusion / tracking hot path.
+// Parity: unpinned -- the result depends on the RANSAC sampler's seed, which the reference takes from std::random_device.
+// Two paths (OP_RUNTIME_OPT_GLOBAL_REGISTRATION): 0 (default) host C++ throughout (src/GlobalRegistration.cpp); 1 the dense steps on the device --
+// ComputeFPFHFeature (op_fpfh_compute), FeatureMatching3D (op_feature_match: the same sequential 33-term sums, the lowest index on ties, so
+// the same matches bit for bit given the same features) and RANSAC's scoring (Geometry/Ransac.h); DownSampleAndExtractFeature and both
+// RansacRegistration overloads reach them through those functions.  RejectMatchesRanSaPC is host code on both paths.  Given equal features
+// (3DFeature.h: the one-bin rule) every later result -- matches, kept matches, T, inliers, rmse -- is identical.
 #pragma once
 #include <memory>
 #include <random>

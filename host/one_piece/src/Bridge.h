@@ -36,6 +36,11 @@ inline bool Failed(int rc, const char* where) {
     std::cout << RED << "[ERROR]::[" << where << "]::" << op_last_error() << RESET << std::endl;
     return true;
 }
+// OP_RUNTIME_OPT_GLOBAL_REGISTRATION: 1 = ComputeFPFHFeature, FeatureMatching3D and EstimateRigidTransformationRANSAC forward to the device entries
+inline bool DeviceGlobalRegistration() {
+    long long v = 0;
+    return op_runtime_get_option(OP_RUNTIME_OPT_GLOBAL_REGISTRATION, &v) == OP_OK && v == 1;
+}
 inline const float* Floats(const geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 inline float* Floats(geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 static_assert(sizeof(geometry::Point3) == 3 * sizeof(float), "Point3List must be a contiguous xyz float array");

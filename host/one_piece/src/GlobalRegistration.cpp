@@ -1,9 +1,12 @@
 // GlobalRegistration.cpp -- FPFH features (Registration/3DFeature.h) and feature-based global registration (Registration/GlobalRegistration.h).
 // Host C++ on example/DenseFusion's submap path (DenseSlam.cpp:66-118); a restatement of what the reference computes
 // (src/Registration/3DFeature.cpp, GlobalRegistration.cpp), written for this library's types; see the two headers for the arithmetic that is
-// kept and the one deviation.  The neighbour searches are exact (a uniform grid for the 3-D radius search, a threaded exhaustive scan for the
+// kept and the one deviation.  With OP_RUNTIME_OPT_GLOBAL_REGISTRATION at 1 the two dense steps forward to the device (op_fpfh_compute,
+// op_feature_match), which restate these very loops; the loops stay as the default path and as what the device path is tested against.  The neighbour searches are exact (a uniform grid for the 3-D radius search, a threaded exhaustive scan for the
 // 33-D nearest feature) where the reference asks nanoflann with 1024 checks.
 #include "Registration/GlobalRegistration.h"
+
+#include "Bridge.h"
 
 #include <algorithm>
 #include <cmath>
@@ -122,12 +125,35 @@ PairDescriptor ComputePairDescriptor(const geometry::Point3& ps, const geometry:
 }
 
 void ComputeFPFHFeature(const geometry::PointCloud& pcd, FeatureSet& fpfh_features, int knn, float radius) {
+    ComputeFPFHFeatureDebug(pcd, fpfh_features, knn, radius, nullptr, nullptr);
+}
+
+void ComputeFPFHFeatureDebug(const geometry::PointCloud& pcd, FeatureSet& fpfh_features, int knn, float radius, std::vector<std::vector<int> >* neighbours_out,
+                             std::vector<std::vector<float> >* spfh_out) {
     const size_t n = pcd.points.size();
     Feature zero;
     zero.resize(kDim);
     zero.setZero();
     fpfh_features.assign(n, zero);
+    if (neighbours_out) neighbours_out->assign(n, std::vector<int>());
+    if (spfh_out) spfh_out->assign(n, std::vector<float>(kDim, 0.0f));
     if (n == 0 || pcd.normals.size() != n) return;
+    if (bridge::DeviceGlobalRegistration()) { // the same three passes as below, on the device
+        std::vector<float> f(n * kDim), sp(spfh_out ? n * kDim : 0);
+        std::vector<int> nb(neighbours_out && knn > 0 ? n * static_cast<size_t>(knn) : 0);
+        if (bridge::Failed(op_fpfh_compute(bridge::Floats(pcd.points), bridge::Floats(pcd.normals), n, knn, radius, OP_MEM_HOST, bridge::Device(), f.data(),
+                                           nb.empty() ? nullptr : nb.data(), sp.empty() ? nullptr : sp.data()),
+                           "ComputeFPFHFeature"))
+            return;
+        for (size_t i = 0; i < n; ++i) {
+            for (int b = 0; b < kDim; ++b) fpfh_features[i](b) = f[i * kDim + static_cast<size_t>(b)];
+            if (spfh_out) (*spfh_out)[i].assign(sp.begin() + static_cast<long>(i * kDim), sp.begin() + static_cast<long>((i + 1) * kDim));
+            if (neighbours_out)
+                for (int k = 0; k < knn && nb[i * static_cast<size_t>(knn) + static_cast<size_t>(k)] >= 0; ++k)
+                    (*neighbours_out)[i].push_back(nb[i * static_cast<size_t>(knn) + static_cast<size_t>(k)]);
+        }
+        return;
+    }
     std::vector<std::vector<int> > found;
     RadiusNeighbours(pcd.points, radius, knn, found); // `radius` is compared with SQUARED distances, like the reference's search (3DFeature.h header)
     // simplified histograms of every point over its neighbours (3DFeature.cpp:30-84); neighbours[i] = found[i] without the point itself
@@ -169,12 +195,22 @@ void ComputeFPFHFeature(const geometry::PointCloud& pcd, FeatureSet& fpfh_featur
             }
         }
     });
+    if (neighbours_out) neighbours_out->swap(found);
+    if (spfh_out) spfh_out->swap(spfh);
 }
 
 void FeatureMatching3D(const FeatureSet& source_feature, const FeatureSet& target_feature, geometry::FMatchSet& matching_index) {
     const size_t ns = source_feature.size(), nt = target_feature.size();
     std::vector<int> nearest(ns, -1);
-    if (nt) {
+    if (bridge::DeviceGlobalRegistration()) { // the same scan on the device: same sums, same winner on ties
+        std::vector<float> src(ns * kDim), tgt(nt * kDim);
+        for (size_t i = 0; i < ns; ++i)
+            for (int b = 0; b < kDim; ++b) src[i * kDim + b] = b < source_feature[i].rows() ? source_feature[i](b) : 0.0f;
+        for (size_t j = 0; j < nt; ++j)
+            for (int b = 0; b < kDim; ++b) tgt[j * kDim + b] = b < target_feature[j].rows() ? target_feature[j](b) : 0.0f;
+        matching_index.clear();
+        if (ns && bridge::Failed(op_feature_match(src.data(), ns, tgt.data(), nt, OP_MEM_HOST, bridge::Device(), nearest.data()), "FeatureMatching3D")) return;
+    } else if (nt) {
         std::vector<float> tgt(nt * kDim); // contiguous copy: the scan is memory-bound
         for (size_t j = 0; j < nt; ++j)
             for (int b = 0; b < kDim; ++b) tgt[j * kDim + b] = b < target_feature[j].rows() ? target_feature[j](b) : 0.0f;

@@ -3,6 +3,8 @@
 // thread, GRANSAC.hpp:38-44): runs of this library are reproducible, runs of the reference are not.
 #include "Geometry/Ransac.h"
 
+#include "Bridge.h"
+
 #include <algorithm>
 #include <cmath>
 #include <random>
@@ -22,6 +24,79 @@ inline bool Inlier(const TransformationMatrix& T, const PointCorrespondence& c, 
     return std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) < threshold;
 }
 
+// The partial Fisher-Yates draw of the loop below without its O(n) reset: the permutation starts as the identity every iteration and a draw
+// touches at most 16 entries, so only those are recorded.  Same engine, same distributions, same swaps -- the same eight indices.
+struct SparsePermutation {
+    int pos[2 * MIN_INLIER_SIZE_RANSAC_TRANSFORMATION], val[2 * MIN_INLIER_SIZE_RANSAC_TRANSFORMATION], used = 0;
+    int Get(int p) const {
+        for (int i = 0; i < used; ++i) if (pos[i] == p) return val[i];
+        return p;
+    }
+    void Set(int p, int v) {
+        for (int i = 0; i < used; ++i) if (pos[i] == p) { val[i] = v; return; }
+        pos[used] = p; val[used] = v; ++used;
+    }
+};
+
+// OP_RUNTIME_OPT_GLOBAL_REGISTRATION == 1: draws and 8-point fits on the host (every hypothesis bit-identical to the loop below), scoring on the
+// device in batches (op_ransac_count_inliers), the winner's inliers gathered on the device (op_ransac_inlier_ids).
+TransformationMatrix RansacOnDevice(const PointCorrespondenceSet& correspondence_set, PointCorrespondenceSet& inliers, std::vector<int>& inlier_ids,
+                                    int max_iteration, float threshold) {
+    const size_t n = correspondence_set.size(), H = static_cast<size_t>(max_iteration);
+    constexpr int kModel = MIN_INLIER_SIZE_RANSAC_TRANSFORMATION;
+    std::vector<float> src(n * 3), tgt(n * 3), Ts(H * 12);
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) { src[3 * i + k] = correspondence_set[i].first(k); tgt[3 * i + k] = correspondence_set[i].second(k); }
+    std::vector<int> drawn(H * kModel);
+    unsigned nt = std::thread::hardware_concurrency();
+    nt = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
+    if (H < 1024) nt = 1;
+    const size_t per = (H + nt - 1) / nt;
+    auto fit = [&](unsigned t) {
+        PointCorrespondenceSet sample(static_cast<size_t>(kModel));
+        for (size_t it = t * per; it < std::min(H, (t + 1) * per); ++it) {
+            std::mt19937 engine(0x9e3779b9u ^ static_cast<unsigned>(it) * 2654435761u);
+            SparsePermutation perm;
+            for (int k = 0; k < kModel; ++k) {
+                std::uniform_int_distribution<int> pick(k, static_cast<int>(n) - 1);
+                const int r = pick(engine), a = perm.Get(k), b = perm.Get(r); // std::swap(perm[k], perm[r])
+                perm.Set(k, b); perm.Set(r, a);
+                drawn[it * kModel + static_cast<size_t>(k)] = b;
+                sample[static_cast<size_t>(k)] = correspondence_set[static_cast<size_t>(b)];
+            }
+            const TransformationMatrix T = EstimateRigidTransformation(sample);
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 4; ++c) Ts[it * 12 + static_cast<size_t>(r * 4 + c)] = T(r, c);
+        }
+    };
+    if (nt == 1) fit(0);
+    else {
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < nt; ++t) th.emplace_back(fit, t);
+        for (auto& x : th) x.join();
+    }
+    std::vector<unsigned> counts(H, 0u);
+    const size_t batch = 16384;
+    for (size_t h0 = 0; h0 < H; h0 += batch)
+        if (bridge::Failed(op_ransac_count_inliers(src.data(), tgt.data(), n, &Ts[h0 * 12], std::min(batch, H - h0), threshold, OP_MEM_HOST, bridge::Device(), &counts[h0]),
+                           "EstimateRigidTransformationRANSAC"))
+            return TransformationMatrix::Zero();
+    size_t w = H;
+    for (size_t it = 0; it < H; ++it)
+        if (counts[it] > (w == H ? 0u : counts[w])) w = it; // most inliers, the earliest iteration on ties; a draw without inliers never wins
+    if (w == H) return TransformationMatrix::Zero();
+    PointCorrespondenceSet model(static_cast<size_t>(kModel));
+    for (int k = 0; k < kModel; ++k) model[static_cast<size_t>(k)] = correspondence_set[static_cast<size_t>(drawn[w * kModel + static_cast<size_t>(k)])];
+    const TransformationMatrix T = EstimateRigidTransformation(model);
+    std::vector<int> ids(n);
+    size_t n_ids = 0;
+    if (bridge::Failed(op_ransac_inlier_ids(src.data(), tgt.data(), n, &Ts[w * 12], threshold, OP_MEM_HOST, bridge::Device(), ids.data(), &n_ids),
+                       "EstimateRigidTransformationRANSAC"))
+        return TransformationMatrix::Zero();
+    for (size_t k = 0; k < n_ids; ++k) { inliers.push_back(correspondence_set[static_cast<size_t>(ids[k])]); inlier_ids.push_back(ids[k]); }
+    return T;
+}
+
 } // namespace
 
 TransformationMatrix EstimateRigidTransformationRANSAC(const PointCorrespondenceSet& correspondence_set, PointCorrespondenceSet& inliers,
@@ -33,6 +108,7 @@ TransformationMatrix EstimateRigidTransformationRANSAC(const PointCorrespondence
         return TransformationMatrix::Zero();
     }
     if (n == static_cast<size_t>(kModel) || max_iteration <= 0) return TransformationMatrix::Zero(); // GRANSAC::Estimate declines (GRANSAC.hpp:72-76)
+    if (bridge::DeviceGlobalRegistration()) return RansacOnDevice(correspondence_set, inliers, inlier_ids, max_iteration, threshold);
     // Draws are independent: the iterations are split over a few host threads, each with its own engine (seeded by its index), and the
     // winner is the draw with the most inliers, the earliest iteration on ties -- the same result for any thread count.
     unsigned nt = std::thread::hardware_concurrency();

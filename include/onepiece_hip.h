@@ -98,6 +98,10 @@ int op_runtime_hw_queues(int *requested);
  *                                         tracker (profiles/r06_track_depth_probe.txt): what its pipeline needs is a hardware queue per tracker stream
  *                                         (op_runtime_configure(16)).  Results do not depend on it.
  *   OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT     iterations op_icp_run_many keeps enqueued at a time, in turn over its fp64-mode contexts (default 4, 1 .. 1024)
+ *   OP_RUNTIME_OPT_GLOBAL_REGISTRATION    0 (default): the class surface's global registration (registration::ComputeFPFHFeature, FeatureMatching3D, DownSampleAndExtractFeature,
+ *                                         RansacRegistration, geometry::EstimateRigidTransformationRANSAC) runs its host loops, exactly as before the option existed.  1: the
+ *                                         same functions forward to op_fpfh_compute / op_feature_match / op_ransac_count_inliers / op_ransac_inlier_ids.  The C-ABI entries
+ *                                         themselves do not look at it; op_runtime_get_option lets the class surface read it.
  * op_runtime_set_rccl_library(path): the RCCL to bind at the first merge instead of "librccl.so.1" (a site build; the test suite names a
  *   host-memory double that runs several ranks on one device); NULL = the system's.  Fails once RCCL has been bound. */
 #define OP_RUNTIME_OPT_MERGE_ALGORITHM 0
@@ -111,9 +115,11 @@ int op_runtime_hw_queues(int *requested);
 #define OP_RUNTIME_OPT_TRACKER_DEFAULT_SUMS 8
 #define OP_RUNTIME_OPT_TRACKER_BATCH_SUMS 9
 #define OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT 10
+#define OP_RUNTIME_OPT_GLOBAL_REGISTRATION 11
 #define OP_MERGE_OWNER_EXCHANGE 0
 #define OP_MERGE_DENSE_REDUCE 1
 int op_runtime_set_option(int option, long long value);
+int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION only: the others are read inside the library */
 int op_runtime_set_rccl_library(const char *path);
 /* Images that are used more than once -- a frame is tracked against twice and fused once (example/DenseFusion/DenseSlam.cpp:24-33,
  * DenseFusion.cpp:86-96) -- can be brought to the device ONCE and then handed to op_tracker_dense_tracking(_enqueue) /
@@ -540,6 +546,35 @@ int op_points_from_rgbd(const op_camera *cam, const void *depth, int depth_fmt, 
  * undetermined (as in the reference, whose disambiguation is #if 0'd out); < 3 neighbours -> 0. */
 int op_estimate_normals(const float *xyz, size_t n, float radius, int knn, int mem, int device,
                         float *normals_out);
+
+/* ---- global registration (Registration/3DFeature.h, GlobalRegistration.h, Geometry/Ransac.h) ----
+ * The device counterparts of the three dense loops of submap registration; each restates the host loop of host/one_piece/src operation by
+ * operation in float32 (GlobalRegistration.cpp, RansacRigid.cpp there; the reference symbols are named per entry).  The random parts -- the
+ * match pruning and RANSAC's draws -- and the 8-point fits stay on the host.
+ *
+ * op_fpfh_compute == registration::ComputeFPFHFeature (3DFeature.cpp:86-130, with ComputePairDescriptor :9-27 and ComputeSPFH :30-84).
+ *   Neighbours: the points of the 27 cells of edge sqrtf(radius) around a point whose SQUARED distance is below `radius` (the reference hands
+ *   the radius to nanoflann's L2 adaptor unsquared), ordered by (squared distance, index), the first knn (1 .. 256) of them; the point itself
+ *   comes first (an exact duplicate with a lower index precedes it, as on the host).  neighbours_out rows are padded with -1.  SPFH and FPFH
+ *   are bit-identical to the host path except the first angle's bins: its atan2 is evaluated in double and rounded to float once, where the
+ *   host calls its libm's atan2f, so a pair within an ulp of a bin boundary may fall into the adjacent bin.  A third whose neighbour sum is 0
+ *   stays 0.  The cells are formed and sorted on the host (O(n log n)); with OP_MEM_DEVICE the points are read back once for that.
+ * op_feature_match == registration::FeatureMatching3D (GlobalRegistration.cpp:28-78), exhaustive: nearest_out[i] = the target row with the
+ *   smallest squared distance (summed over the 33 bins in order), the lowest index on ties; -1 when nt == 0.
+ * op_ransac_count_inliers == the scoring loop of GRANSAC::Estimate (GRANSAC.hpp:96-118) with TransformationModel::ComputeDistanceMeasure
+ *   (TransformationModel.hpp:37-49): counts_out[h] = the correspondences i with |R_h src_i + t_h - tgt_i| < threshold (float, strictly below).
+ * op_ransac_inlier_ids == the inlier gathering of geometry::EstimateRigidTransformationRANSAC (Ransac.cpp:32-39) for one transform: the
+ *   indices counted above, ascending; ids_out holds up to n, *n_out (always host memory) the count.
+ * `mem` covers every array argument; counts and ids follow it too. */
+int op_fpfh_compute(const float *xyz, const float *normals, size_t n, int knn, float radius, int mem, int device,
+                    float *fpfh_out /* n x 33 */, int *neighbours_out /* NULL or n x knn, -1 padded, self first */,
+                    float *spfh_out /* NULL or n x 33 */);
+int op_feature_match(const float *src /* ns x 33 */, size_t ns, const float *tgt /* nt x 33 */, size_t nt,
+                     int mem, int device, int *nearest_out /* ns; -1 when nt == 0 */);
+int op_ransac_count_inliers(const float *src_xyz, const float *tgt_xyz, size_t n, const float *T /* H x 12, row-major 3x4 */,
+                            size_t H, float threshold, int mem, int device, unsigned *counts_out /* H */);
+int op_ransac_inlier_ids(const float *src_xyz, const float *tgt_xyz, size_t n, const float *T /* 12 */, float threshold,
+                         int mem, int device, int *ids_out, size_t *n_out);
 
 /* ---- dense RGB-D tracker (Odometry/Odometry.h:38-175) ------------------------
  * Boundary = the inputs of Odometry::MultiScaleComputing (Odometry.cpp:621-636): image pyramids

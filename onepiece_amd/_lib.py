@@ -59,7 +59,7 @@ OP_DEPTH_F32, OP_DEPTH_U16 = 0, 1
 OP_VOLUME_OPT_UPDATE, OP_VOLUME_UPDATE_EXACT, OP_VOLUME_UPDATE_SUM_FORM = 0, 0, 1
 OP_VOLUME_OPT_SELECT, OP_VOLUME_SELECT_AUTO, OP_VOLUME_SELECT_DIRECT = 1, 0, -1
 OP_VOLUME_OPT_RAYCAST_PRUNE = 2
-OP_RUNTIME_OPT_MERGE_ALGORITHM, OP_RUNTIME_OPT_MERGE_SLICE_BLOCKS, OP_RUNTIME_OPT_MERGE_FORCE_SINGLE_RANK, OP_RUNTIME_OPT_TRACKER_GRAPH, OP_RUNTIME_OPT_COPY_THREADS, OP_RUNTIME_OPT_CACHE_DEVICE_BYTES, OP_RUNTIME_OPT_MERGE_FAULT, OP_RUNTIME_OPT_ICP_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_BATCH_SUMS, OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+OP_RUNTIME_OPT_MERGE_ALGORITHM, OP_RUNTIME_OPT_MERGE_SLICE_BLOCKS, OP_RUNTIME_OPT_MERGE_FORCE_SINGLE_RANK, OP_RUNTIME_OPT_TRACKER_GRAPH, OP_RUNTIME_OPT_COPY_THREADS, OP_RUNTIME_OPT_CACHE_DEVICE_BYTES, OP_RUNTIME_OPT_MERGE_FAULT, OP_RUNTIME_OPT_ICP_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_BATCH_SUMS, OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT, OP_RUNTIME_OPT_GLOBAL_REGISTRATION = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 OP_MERGE_OWNER_EXCHANGE, OP_MERGE_DENSE_REDUCE = 0, 1
 OP_MEM_HOST, OP_MEM_DEVICE = 0, 1
 OP_ICP_POINT_TO_POINT, OP_ICP_POINT_TO_PLANE = 0, 1
@@ -83,6 +83,7 @@ SIGNATURES = {
     "op_runtime_hw_queues": (C.c_int, [C.POINTER(C.c_int)]),
     "op_runtime_configure": (C.c_int, [C.c_int]),
     "op_runtime_set_option": (C.c_int, [C.c_int, C.c_longlong]),
+    "op_runtime_get_option": (C.c_int, [C.c_int, C.POINTER(C.c_longlong)]),
     "op_runtime_set_rccl_library": (C.c_int, [C.c_char_p]),
     "op_device_alloc": (C.c_int, [C.c_size_t, C.c_int, C.POINTER(_vp)]),
     "op_device_write": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int]),
@@ -161,6 +162,10 @@ SIGNATURES = {
     "op_icp_register": (C.c_int, [C.c_int, _fp, C.c_size_t, _fp, _fp, C.c_size_t, _fp, C.c_int,
                                   C.c_double, C.c_int, C.POINTER(IcpResult), _ip, C.c_size_t]),
     "op_estimate_normals": (C.c_int, [_vp, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, _vp]),
+    "op_fpfh_compute": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "op_feature_match": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
+    "op_ransac_count_inliers": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_float, C.c_int, C.c_int, _vp]),
+    "op_ransac_inlier_ids": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_float, C.c_int, C.c_int, _vp, C.POINTER(C.c_size_t)]),
     "op_estimate_rigid_point_to_plane": (C.c_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "op_estimate_rigid_transformation": (C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "op_estimate_rigid_point_to_plane_ex": (C.c_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp]),

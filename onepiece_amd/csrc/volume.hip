@@ -688,6 +688,9 @@ int op_runtime_set_option(int option, long long value) {
         case OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT:
             if (value < 1 || value > 1024) return fail(OP_ERR_INVALID, "op_runtime_set_option: %lld iterations in flight", value);
             o.icp_many_in_flight.store((int)value); return OP_OK;
+        case OP_RUNTIME_OPT_GLOBAL_REGISTRATION:
+            if (value != 0 && value != 1) return fail(OP_ERR_INVALID, "op_runtime_set_option: global registration path %lld (0 host, 1 device)", value);
+            o.global_registration.store((int)value); return OP_OK;
         case OP_RUNTIME_OPT_MERGE_FAULT:
             if (value < 0) return fail(OP_ERR_INVALID, "op_runtime_set_option: merge fault %lld", value);
             o.merge_fault.store(value); return OP_OK;
@@ -697,6 +700,13 @@ int op_runtime_set_option(int option, long long value) {
         default: break;
     }
     return fail(OP_ERR_INVALID, "op_runtime_set_option: unknown option %d", option);
+}
+
+int op_runtime_get_option(int option, long long* value) {
+    if (!value) return fail(OP_ERR_INVALID, "null value");
+    if (option != OP_RUNTIME_OPT_GLOBAL_REGISTRATION) return fail(OP_ERR_INVALID, "op_runtime_get_option: option %d cannot be read", option);
+    *value = op::runtime_options().global_registration.load();
+    return OP_OK;
 }
 
 const char* op_last_error(void) { return op::g_last_error; }

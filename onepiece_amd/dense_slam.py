@@ -2,9 +2,10 @@
 (/root/reference/example/DenseFusion/DenseSlam.{h,cpp}): per frame `Odometry::DenseTracking(last
 tracked frame, current frame, Identity)` and the pose chaining of DenseSlam.cpp:21-33.
 
-Not mirrored (out of scope): submap models, FPFH + RANSAC registration and FastBA
-(`RegisterSubmap`, `Optimize`) -- they only touch the poses every `step` frames; without them the
-trajectory is pure frame-to-frame odometry, which is what this module reports.
+Not mirrored: submap models, the RANSAC sampler and FastBA (`RegisterSubmap`, `Optimize`) -- they only touch
+the poses every `step` frames; without them the trajectory is pure frame-to-frame odometry, which is what this
+module reports.  The dense parts of the submap registration do have mirrors: registration.ComputeFPFHFeature,
+FeatureMatching3D and CountInliersRANSAC (op_fpfh_compute, op_feature_match, op_ransac_count_inliers).
 The tracking itself runs inside libonepiece_hip.so (op_tracker_dense_tracking).
 """
 import numpy as np

@@ -178,3 +178,57 @@ def EstimateRigidTransformation(correspondence_set, device=0, finish="reference"
     L.check(L.load().op_estimate_rigid_transformation_ex(C.c_void_p(pairs.ctypes.data), len(pairs), L.OP_MEM_HOST, device,
                                                          {"reference": L.OP_ICP_FINISH_REFERENCE, "fp64": L.OP_ICP_FINISH_FP64}[finish], _fp(T)))
     return T.reshape(4, 4)
+
+
+def ComputeFPFHFeature(pcd, knn=100, radius=0.1, device=0, return_debug=False):
+    """registration::ComputeFPFHFeature (Registration/3DFeature.cpp:86-130) on the GPU -> features [n,33] float32.
+    `radius` is compared with SQUARED distances, as in the reference.  return_debug: also the neighbour lists
+    [n,knn] int32 (-1 padded, the point itself first) and the simplified histograms [n,33]."""
+    if not pcd.HasNormals():
+        raise ValueError("ComputeFPFHFeature needs normals")
+    n = len(pcd.points)
+    fpfh = np.zeros((n, 33), np.float32)
+    nb = np.full((n, int(knn)), -1, np.int32) if return_debug else None
+    spfh = np.zeros((n, 33), np.float32) if return_debug else None
+    L.check(L.load().op_fpfh_compute(C.c_void_p(pcd.points.ctypes.data), C.c_void_p(pcd.normals.ctypes.data), n, int(knn), float(radius), L.OP_MEM_HOST, device,
+                                     C.c_void_p(fpfh.ctypes.data), C.c_void_p(nb.ctypes.data) if return_debug else None,
+                                     C.c_void_p(spfh.ctypes.data) if return_debug else None))
+    return (fpfh, nb, spfh) if return_debug else fpfh
+
+
+def FeatureMatching3D(src_feat, tgt_feat, device=0):
+    """registration::FeatureMatching3D (GlobalRegistration.cpp:28-78), exhaustive, on the GPU -> matches [m,2] int32:
+    (source index, index of the nearest target feature; the lowest index on ties); empty without targets."""
+    s = np.ascontiguousarray(src_feat, np.float32).reshape(-1, 33)
+    t = np.ascontiguousarray(tgt_feat, np.float32).reshape(-1, 33)
+    nearest = np.full(len(s), -1, np.int32)
+    L.check(L.load().op_feature_match(C.c_void_p(s.ctypes.data), len(s), C.c_void_p(t.ctypes.data), len(t), L.OP_MEM_HOST, device, C.c_void_p(nearest.ctypes.data)))
+    keep = nearest >= 0
+    return np.stack([np.arange(len(s), dtype=np.int32)[keep], nearest[keep]], axis=1)
+
+
+def CountInliersRANSAC(src, tgt, Ts, threshold, device=0):
+    """The scoring loop of geometry::EstimateRigidTransformationRANSAC (GRANSAC.hpp:96-118, TransformationModel.hpp:37-49) on the
+    GPU: for every transform of Ts ([H,3,4] or [H,4,4]) the number of pairs with |R src + t - tgt| < threshold -> [H] uint32."""
+    s = np.ascontiguousarray(src, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tgt, np.float32).reshape(-1, 3)
+    if len(s) != len(t):
+        raise ValueError("src and tgt must pair up")
+    Ts = np.asarray(Ts, np.float32)
+    Ts = np.ascontiguousarray(Ts.reshape(-1, Ts.shape[-2], 4)[:, :3, :]).reshape(-1, 12)
+    counts = np.zeros(len(Ts), np.uint32)
+    L.check(L.load().op_ransac_count_inliers(C.c_void_p(s.ctypes.data), C.c_void_p(t.ctypes.data), len(s), C.c_void_p(Ts.ctypes.data), len(Ts), float(threshold),
+                                             L.OP_MEM_HOST, device, C.c_void_p(counts.ctypes.data)))
+    return counts
+
+
+def InlierIdsRANSAC(src, tgt, T, threshold, device=0):
+    """The inliers of one transform (Ransac.cpp:32-39), ascending -> [k] int32."""
+    s = np.ascontiguousarray(src, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tgt, np.float32).reshape(-1, 3)
+    T12 = np.ascontiguousarray(np.asarray(T, np.float32)[:3, :]).reshape(12)
+    ids = np.zeros(max(len(s), 1), np.int32)
+    n = C.c_size_t(0)
+    L.check(L.load().op_ransac_inlier_ids(C.c_void_p(s.ctypes.data), C.c_void_p(t.ctypes.data), len(s), C.c_void_p(T12.ctypes.data), float(threshold), L.OP_MEM_HOST, device,
+                                          C.c_void_p(ids.ctypes.data), C.byref(n)))
+    return ids[:n.value].copy()
