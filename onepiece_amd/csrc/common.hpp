@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/onepiece_hip.h"
@@ -55,6 +56,15 @@ inline int fail(int code, const char* fmt, ...) {
         int rc_ = (expr);             \
         if (rc_ != OP_OK) return rc_; \
     } while (0)
+
+// Run-time value -> template argument: calls f(std::integral_constant<int, I>) with I = i for i in [0, N - 1), N - 1 for everything else.
+template <int N, class F>
+void with_constant(int i, F&& f) {
+    if constexpr (N > 1) {
+        if (i != N - 1 && i >= 0 && i < N) return with_constant<N - 1>(i, f);
+    }
+    f(std::integral_constant<int, N - 1>{});
+}
 
 // Selects `device` after checking that a usable GPU exists; there is no CPU fallback anywhere.
 inline int use_device(int device) {

@@ -1,5 +1,5 @@
-// icp.hip -- a registration (icp_core.hpp lists the translation units): the iteration loop in both summation modes, the ordered inlier rows and the sequential
-// float32 sums behind the reference-order modes, the finish (RegistrationResult), op_icp_run / _many / _enqueue / _register and the stand-alone estimators.
+// icp.hip -- a registration (icp_core.hpp lists the translation units): the iteration loop in both summation modes, the ordered inlier rows of the
+// reference-order modes (their sequential float32 sums: seq_sums.hip), the finish (RegistrationResult), op_icp_run / _many / _enqueue / _register and the stand-alone estimators.
 //
 // What it replaces (file:line under /root/reference/src):
 //   registration::PointToPlane                       Registration/ICP.cpp:146-224
@@ -20,7 +20,6 @@
 // The 6x6 solve / SE3 exp / Kabsch stay on the host (host_math.hpp) exactly as north_star asks;
 // this accumulation is 2*27*N flops -- not a dense contraction, so no MFMA.
 #include "icp_core.hpp"
-#include "seq_sums.hpp"
 
 namespace {
 
@@ -148,31 +147,17 @@ void expand_plane_sums(const double in[kNSums], double JTJ[36], double JTr[6]) {
     for (int a = 0; a < 6; ++a) JTr[a] = in[21 + a];
 }
 
+// The 36 + 6 sequential float32 sums of a point-to-plane iteration by one wave on the device (k_seq_sums: the tracker's kernel, same row layout {J[6], r}): the ordered
+// rows never leave HBM, 42 numbers come back -- ~1.4 ms for 3e5 inliers (10 shader cycles per row) instead of an 11 MB transfer and a pass on one host core.
+// false (the device may not run the kernel, or its three small buffers are not to be had) = sum on the host as before
+bool seq_ready(op_icp* c) {
+    if (c->seq_sums.reserve(c->device, true) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
 // Compacts the rows of the current inlier set (c->inl, written by a pass with write_inl) in ascending source
 // index, copies the first n_rows of them to pinned host memory and waits.  The transform is read from c->T_dev.
-// k_seq_sums needs ~150 KB of dynamic LDS (opt-in attribute) and three small buffers; false = sum on the host as before
-bool seq_device_ok(op_icp* c) {
-    if (c->seq_ok < 0) {
-        int lds_max = 0;
-        bool ok = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) == hipSuccess && (size_t)lds_max >= seq_lds_bytes(42, 7, 1) &&
-                  hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seq_sums<42, 7, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)seq_lds_bytes(42, 7, 1)) == hipSuccess;
-        if (ok) ok = op::cached_malloc((void**)&c->seq_out, 64 * sizeof(float)) == hipSuccess && op::cached_malloc((void**)&c->seq_total, sizeof(unsigned)) == hipSuccess &&
-                     op::cached_host_malloc((void**)&c->seq_host, 64 * sizeof(float)) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        c->seq_ok = ok ? 1 : 0;
-    }
-    return c->seq_ok == 1;
-}
-
-// The reference-order contexts of one op_icp_run_many call take their sequential sums TOGETHER when there are nine or more of them (seq_sums.hpp: SeqRendezvous): every such context has a submitter
-// thread (its iterations synchronise the stream anyway) and each iteration ends in k_seq_sums -- ONE workgroup, ~1.4 ms for 3e5 rows; K independent runs scale to
-// the number of hardware queues of the process (GPU_MAX_HW_QUEUES) and no further, K workgroups of one launch do not have that limit.  One rendezvous per device.
-using IcpSeqBatch = SeqRendezvous<42, 7, 1, 9>;
-IcpSeqBatch* icp_seq_batch(int device) {
-    static IcpSeqBatch pool[16];
-    return device >= 0 && device < 16 ? &pool[device] : nullptr;
-}
-
 int emit_rows(op_icp* c, int kind, size_t n_rows, const float** rows) {
     if (rows) *rows = nullptr;
     if (!c->n || !n_rows) return OP_OK;
@@ -194,10 +179,10 @@ int emit_rows(op_icp* c, int kind, size_t n_rows, const float** rows) {
     const unsigned g256 = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_inl_flag, dim3(g256), dim3(256), 0, c->stream, (const int*)c->inl, n, c->flag);
     scan_launch((const unsigned*)c->flag, n, c->scan_tot, c->start, c->stream);
-#define OP_EMIT(K) hipLaunchKernelGGL(k_emit_rows<K>, dim3(g256), dim3(256), 0, c->stream, (const float*)c->T_dev, (const float*)c->src, \
-                                      (const float*)c->tgt_orig, (const float*)c->nrm_orig, (const int*)c->inl, (const unsigned*)c->start, n, c->rows_dev)
-    if (kind == 1) OP_EMIT(1); else if (kind == 2) OP_EMIT(2); else if (kind == 3) OP_EMIT(3); else OP_EMIT(0);
-#undef OP_EMIT
+    op::with_constant<4>(kind, [&](auto K) {
+        hipLaunchKernelGGL(k_emit_rows<decltype(K)::value>, dim3(g256), dim3(256), 0, c->stream, (const float*)c->T_dev, (const float*)c->src,
+                           (const float*)c->tgt_orig, (const float*)c->nrm_orig, (const int*)c->inl, (const unsigned*)c->start, n, c->rows_dev);
+    });
     OP_HIP(hipGetLastError());
     if (!rows) return OP_OK; // enqueue only: the caller copies c->rows_dev itself
     const size_t w = kind == 1 ? 9 : 6;
@@ -207,39 +192,10 @@ int emit_rows(op_icp* c, int kind, size_t n_rows, const float** rows) {
     return OP_OK;
 }
 
-} // namespace
 
-extern "C" {
-
-int op_icp_iterate(op_icp* c, const float T[16], int mode, double sums[42], uint64_t* n_inliers, double* sum_sq_err) {
-    if (!c || !T || !sums) return fail(OP_ERR_INVALID, "null argument");
-    OP_ICP_NOT_BUSY(c, "op_icp_iterate");
-    OP_HIP(hipSetDevice(c->device));
-    if (!c->src && c->n) return fail(OP_ERR_INVALID, "op_icp_set_source has not been called");
-    if (mode == OP_ICP_POINT_TO_PLANE && !c->has_normals)
-        return fail(OP_ERR_NO_NORMALS, "[ERROR]::[ICPPointToPlane]::target point cloud need to have normals.");
-    double r[kNSums];
-    OP_TRY(run_pass(c, mode == OP_ICP_POINT_TO_PLANE ? 1 : 0, T, false, r));
-    std::memset(sums, 0, 42 * sizeof(double));
-    if (mode == OP_ICP_POINT_TO_PLANE) expand_plane_sums(r, sums, sums + 36);
-    else std::memcpy(sums, r, 15 * sizeof(double));
-    if (n_inliers) *n_inliers = (uint64_t)(r[28] + 0.5);
-    if (sum_sq_err) *sum_sq_err = r[27];
-    return OP_OK;
-}
-
-static int icp_run_impl(op_icp* c, int mode, const float init_T[16], int max_iteration, op_icp_result* result, int32_t* pairs, size_t pairs_cap,
-                        int32_t* per_iter_inliers, float* per_iter_T);
-
-int op_icp_run(op_icp* c, int mode, const float init_T[16], int max_iteration, op_icp_result* result, int32_t* pairs, size_t pairs_cap,
-               int32_t* per_iter_inliers, float* per_iter_T) {
-    if (!c || !init_T || !result) return fail(OP_ERR_INVALID, "null argument");
-    OP_ICP_NOT_BUSY(c, "op_icp_run");
-    return icp_run_impl(c, mode, init_T, max_iteration, result, pairs, pairs_cap, per_iter_inliers, per_iter_T);
-}
-
-// ---- one registration = head (checks, resets) -> the iteration loop -> finish (final CountInliers, RegistrationResult).  The fp64-mode loop is a small state
-// machine (IcpLoop: launch an iteration / complete it) so that ONE host thread can keep several contexts' iterations in flight (op_icp_run_many).
+// ---- one registration = head (checks, resets) -> the iteration loop -> finish (final CountInliers, RegistrationResult).  The loop is a small state machine
+// (IcpLoop) for both summation modes; in the fp64 mode an iteration splits into launch / complete so that ONE host thread can keep several contexts' iterations
+// in flight (op_icp_run_many).
 static int icp_run_head(op_icp* c, int mode, int max_iteration) {
     OP_HIP(hipSetDevice(c->device));
     if (mode == OP_ICP_POINT_TO_PLANE && !c->has_normals) // ICP.cpp:159-163: error line + default result
@@ -260,7 +216,7 @@ static int icp_run_head(op_icp* c, int mode, int max_iteration) {
 struct IcpLoop {
     op_icp* c = nullptr;
     int pass_mode = 1, max_iteration = 0, it = 0;
-    bool detect = false;
+    bool detect = false, strict = false;
     float cur[16], last_search_T[16];
     int32_t* per_iter_inliers = nullptr;
     float* per_iter_T = nullptr;
@@ -270,21 +226,27 @@ static int icp_loop_begin(IcpLoop& L, op_icp* c, int mode, const float init_T[16
     L.per_iter_inliers = per_iter_inliers; L.per_iter_T = per_iter_T;
     std::memcpy(L.cur, init_T, sizeof(L.cur));
     std::memcpy(L.last_search_T, init_T, sizeof(L.last_search_T));
+    L.strict = c->sums == OP_ICP_SUMS_REFERENCE_F32;
     L.detect = c->ties == OP_ICP_TIES_REFERENCE;
-    if (L.detect) OP_TRY(ensure_tie_buffers(c));
+    if (L.detect && !L.strict) OP_TRY(ensure_tie_buffers(c)); // (the reference-order mode's passes see to it themselves: run_pass)
     return OP_OK;
 }
-static int icp_loop_launch(IcpLoop& L) { // enqueue iteration L.it (does not wait)
+// the end of every iteration: the step joins the pose, the per-iteration records are written
+static void icp_loop_chain(IcpLoop& L, const float step_T[16], double n_inliers) {
+    op_host::mat4_mul(step_T, L.cur, L.cur); // ICP.cpp:198
+    if (L.per_iter_inliers) L.per_iter_inliers[L.it] = (int32_t)(n_inliers + 0.5);
+    if (L.per_iter_T) std::memcpy(L.per_iter_T + 16 * L.it, L.cur, sizeof(L.cur));
+    ++L.it;
+}
+static int icp_loop_launch(IcpLoop& L) { // fp64 mode: enqueue iteration L.it (does not wait)
     op_icp* c = L.c;
     std::memcpy(L.last_search_T, L.cur, sizeof(L.cur));
     c->seq += 1.0;
-    if (L.detect) { if (L.pass_mode == 1) launch_pass(c, 1, true, false, L.cur, c->seq); else launch_pass(c, 0, true, false, L.cur, c->seq); }
-    else if (L.pass_mode == 1) launch_pass(c, 1, false, false, L.cur, c->seq);
-    else launch_pass(c, 0, false, false, L.cur, c->seq);
+    launch_pass(c, L.pass_mode, L.detect, false, L.cur, c->seq);
     OP_HIP(hipGetLastError());
     return OP_OK;
 }
-static int icp_loop_complete(IcpLoop& L) { // wait for the sums of iteration L.it, solve, chain the pose
+static int icp_loop_complete(IcpLoop& L) { // fp64 mode: wait for the sums of iteration L.it, solve, chain the pose
     op_icp* c = L.c;
     double r[kNSums];
     float tmp_T[16];
@@ -299,84 +261,39 @@ static int icp_loop_complete(IcpLoop& L) { // wait for the sums of iteration L.i
     } else {
         op_host::kabsch_from_sums(r[28], r, r + 3, r + 6, tmp_T); // ICP.cpp:79
     }
-    op_host::mat4_mul(tmp_T, L.cur, L.cur); // ICP.cpp:198
-    if (L.per_iter_inliers) L.per_iter_inliers[L.it] = (int32_t)(r[28] + 0.5);
-    if (L.per_iter_T) std::memcpy(L.per_iter_T + 16 * L.it, L.cur, sizeof(L.cur));
-    ++L.it;
+    icp_loop_chain(L, tmp_T, r[28]);
     return OP_OK;
 }
-
-static int icp_run_finish(op_icp* c, const float start_T[16], const float last_search_T[16], int max_iteration, op_icp_result* result, int32_t* pairs, size_t pairs_cap);
-
-static int icp_run_impl(op_icp* c, int mode, const float init_T[16], int max_iteration, op_icp_result* result, int32_t* pairs, size_t pairs_cap,
-                        int32_t* per_iter_inliers, float* per_iter_T) {
-    OP_TRY(icp_run_head(c, mode, max_iteration));
-    float start_T[16], last_search_T[16];
-    std::memcpy(last_search_T, init_T, sizeof(last_search_T));
-    double r[kNSums];
-    const int pass_mode = mode == OP_ICP_POINT_TO_PLANE ? 1 : 0;
-    const bool strict = c->sums == OP_ICP_SUMS_REFERENCE_F32;
-    if (strict) {
-        // Validation mode: every iteration's inlier rows come to the host in inlier order and are summed there
-        // sequentially in float32, as the reference's loops do (ICP.cpp:121-136 / Geometry.cpp:117-133 via :76-79);
-        // the search, the inlier test and the rows themselves still come from the kernels.
-        float cur[16], tmp_T[16];
-        std::memcpy(cur, init_T, sizeof(cur));
-        for (int it = 0; it < max_iteration; ++it) {
-            std::memcpy(last_search_T, cur, sizeof(cur));
-            OP_TRY(run_pass(c, pass_mode, cur, true, r)); // leaves `cur` in c->T_dev; with OP_ICP_TIES_REFERENCE, tied queries are re-decided inside
-            const size_t n_it = (size_t)(r[28] + 0.5);
-            const float* rows = nullptr;
-            if (pass_mode == 1 && seq_device_ok(c) && n_it) {
-                // the 36 + 6 sequential float32 sums by one wave on the device (k_seq_sums: the tracker's kernel, same row layout {J[6], r}): the ordered rows never
-                // leave HBM, 42 numbers come back -- ~1.4 ms for 3e5 inliers (10 shader cycles per row) instead of an 11 MB transfer and a pass on one host core
-                OP_TRY(emit_rows(c, 3, n_it, nullptr));
-                const unsigned n_rows_u = (unsigned)n_it;
-                OP_HIP(hipMemcpyAsync(c->seq_total, &n_rows_u, sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
-                hipError_t eb = hipErrorNotReady;
-                if (c->seq_batch) // with the other contexts of the op_icp_run_many call: one launch, a workgroup each (hipErrorNotReady: too few of them -- alone, below)
-                    eb = static_cast<IcpSeqBatch*>(c->seq_batch)->submit(c->rows_dev, c->seq_total, c->seq_out, c->seq_host, c->seq_ev, c->stream);
-                if (eb != hipSuccess && eb != hipErrorNotReady) return fail(OP_ERR_HIP, "icp: the batched sequential sums failed: %s", hipGetErrorString(eb));
-                if (eb == hipErrorNotReady) {
-                    hipLaunchKernelGGL((k_seq_sums<42, 7, 1>), dim3(1), dim3(kSeqThreads), seq_lds_bytes(42, 7, 1), c->stream, (const float*)c->rows_dev, (const unsigned*)c->seq_total, c->seq_out);
-                    OP_HIP(hipMemcpyAsync(c->seq_host, c->seq_out, 43 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-                    OP_HIP(hipStreamSynchronize(c->stream));
-                }
-                double JTJ[36], JTr[6];
-                float x[6];
-                for (int k = 0; k < 36; ++k) JTJ[k] = c->seq_host[k];
-                for (int k = 0; k < 6; ++k) JTr[k] = c->seq_host[36 + k];
-                op_host::solve6_psd<true>(JTJ, JTr, x);
-                op_host::se3_exp(x, tmp_T);
-                op_host::mat4_mul(tmp_T, cur, cur);
-                if (per_iter_inliers) per_iter_inliers[it] = (int32_t)n_it;
-                if (per_iter_T) std::memcpy(per_iter_T + 16 * it, cur, sizeof(cur));
-                continue;
-            }
-            if (c->seq_batch) static_cast<IcpSeqBatch*>(c->seq_batch)->pass(); // nothing for the batched launch from this context in this iteration
-            OP_TRY(emit_rows(c, pass_mode == 1 ? 1 : 2, n_it, &rows));
-            if (pass_mode == 1) {
-                double JTJ[36], JTr[6];
-                float x[6];
-                op_host::plane_sums_reference_order(rows, n_it, JTJ, JTr);
-                op_host::solve6_psd<true>(JTJ, JTr, x);
-                op_host::se3_exp(x, tmp_T);
-            } else {
-                op_host::kabsch_reference_order<true>(rows, n_it, tmp_T);
-            }
-            op_host::mat4_mul(tmp_T, cur, cur);
-            if (per_iter_inliers) per_iter_inliers[it] = (int32_t)n_it;
-            if (per_iter_T) std::memcpy(per_iter_T + 16 * it, cur, sizeof(cur));
-        }
-        std::memcpy(start_T, cur, sizeof(cur));
+// Reference-order mode, iteration L.it from start to end: the inlier rows are put in inlier order and summed sequentially in float32, as the reference's loops do
+// (ICP.cpp:121-136 / Geometry.cpp:117-133 via :76-79) -- point-to-plane on the device (seq_ready), everything else on this host thread; the search, the inlier test
+// and the rows themselves still come from the kernels.
+static int icp_loop_step(IcpLoop& L) {
+    op_icp* c = L.c;
+    double r[kNSums], JTJ[36], JTr[6];
+    float x[6], tmp_T[16];
+    std::memcpy(L.last_search_T, L.cur, sizeof(L.cur));
+    OP_TRY(run_pass(c, L.pass_mode, L.cur, true, r)); // leaves the pose in c->T_dev; with OP_ICP_TIES_REFERENCE, tied queries are re-decided inside
+    const size_t n_it = (size_t)(r[28] + 0.5);
+    const float* rows = nullptr;
+    if (L.pass_mode == 1 && seq_ready(c) && n_it) {
+        OP_TRY(emit_rows(c, 3, n_it, nullptr));
+        const unsigned n_rows = (unsigned)n_it;
+        OP_HIP(c->seq_sums.run(kSeqOneRow, c->rows_dev, &n_rows, c->stream, c->seq_batch)); // (seq_batch: with the other contexts of the op_icp_run_many call)
+        for (int k = 0; k < 36; ++k) JTJ[k] = c->seq_sums.host[k];
+        for (int k = 0; k < 6; ++k) JTr[k] = c->seq_sums.host[36 + k];
     } else {
-        IcpLoop L;
-        OP_TRY(icp_loop_begin(L, c, mode, init_T, max_iteration, per_iter_inliers, per_iter_T));
-        while (L.it < max_iteration) { OP_TRY(icp_loop_launch(L)); OP_TRY(icp_loop_complete(L)); }
-        std::memcpy(start_T, L.cur, sizeof(L.cur));
-        std::memcpy(last_search_T, L.last_search_T, sizeof(last_search_T));
+        if (c->seq_batch) c->seq_batch->pass(); // nothing for the batched launch from this context in this iteration
+        OP_TRY(emit_rows(c, L.pass_mode == 1 ? 1 : 2, n_it, &rows));
+        if (L.pass_mode == 1) op_host::plane_sums_reference_order(rows, n_it, JTJ, JTr);
     }
-    return icp_run_finish(c, start_T, last_search_T, max_iteration, result, pairs, pairs_cap);
+    if (L.pass_mode == 1) {
+        op_host::solve6_psd<true>(JTJ, JTr, x);
+        op_host::se3_exp(x, tmp_T);
+    } else {
+        op_host::kabsch_reference_order<true>(rows, n_it, tmp_T);
+    }
+    icp_loop_chain(L, tmp_T, r[28]);
+    return OP_OK;
 }
 
 static int icp_run_finish(op_icp* c, const float start_T[16], const float last_search_T[16], int max_iteration, op_icp_result* result, int32_t* pairs, size_t pairs_cap) {
@@ -474,6 +391,47 @@ static int icp_run_finish(op_icp* c, const float start_T[16], const float last_s
     return OP_OK;
 }
 
+static int icp_run_impl(op_icp* c, int mode, const float init_T[16], int max_iteration, op_icp_result* result, int32_t* pairs, size_t pairs_cap,
+                        int32_t* per_iter_inliers, float* per_iter_T) {
+    OP_TRY(icp_run_head(c, mode, max_iteration));
+    IcpLoop L;
+    OP_TRY(icp_loop_begin(L, c, mode, init_T, max_iteration, per_iter_inliers, per_iter_T));
+    while (L.it < max_iteration) {
+        if (L.strict) { OP_TRY(icp_loop_step(L)); continue; }
+        OP_TRY(icp_loop_launch(L));
+        OP_TRY(icp_loop_complete(L));
+    }
+    return icp_run_finish(c, L.cur, L.last_search_T, max_iteration, result, pairs, pairs_cap);
+}
+
+} // namespace
+
+extern "C" {
+
+int op_icp_iterate(op_icp* c, const float T[16], int mode, double sums[42], uint64_t* n_inliers, double* sum_sq_err) {
+    if (!c || !T || !sums) return fail(OP_ERR_INVALID, "null argument");
+    OP_ICP_NOT_BUSY(c, "op_icp_iterate");
+    OP_HIP(hipSetDevice(c->device));
+    if (!c->src && c->n) return fail(OP_ERR_INVALID, "op_icp_set_source has not been called");
+    if (mode == OP_ICP_POINT_TO_PLANE && !c->has_normals)
+        return fail(OP_ERR_NO_NORMALS, "[ERROR]::[ICPPointToPlane]::target point cloud need to have normals.");
+    double r[kNSums];
+    OP_TRY(run_pass(c, mode == OP_ICP_POINT_TO_PLANE ? 1 : 0, T, false, r));
+    std::memset(sums, 0, 42 * sizeof(double));
+    if (mode == OP_ICP_POINT_TO_PLANE) expand_plane_sums(r, sums, sums + 36);
+    else std::memcpy(sums, r, 15 * sizeof(double));
+    if (n_inliers) *n_inliers = (uint64_t)(r[28] + 0.5);
+    if (sum_sq_err) *sum_sq_err = r[27];
+    return OP_OK;
+}
+
+int op_icp_run(op_icp* c, int mode, const float init_T[16], int max_iteration, op_icp_result* result, int32_t* pairs, size_t pairs_cap,
+               int32_t* per_iter_inliers, float* per_iter_T) {
+    if (!c || !init_T || !result) return fail(OP_ERR_INVALID, "null argument");
+    OP_ICP_NOT_BUSY(c, "op_icp_run");
+    return icp_run_impl(c, mode, init_T, max_iteration, result, pairs, pairs_cap, per_iter_inliers, per_iter_T);
+}
+
 // K registrations on K contexts, driven by ONE host thread (round-5 review: four submitter threads contend in the runtime's launch path -- k_icp_iter 21 -> 33 us,
 // host side 19 -> 33 us at K = 4).  fp64-mode contexts: all K iterations are enqueued, then the thread goes round: wait for context k's sums (they arrive in
 // host-mapped memory), solve, enqueue its next iteration, move on -- while it looks at one context the other K - 1 iterations run on the chip.  The finishes
@@ -495,16 +453,25 @@ int op_icp_run_many(op_icp* const* ctxs, int k, int mode, const float* init_T, i
     std::vector<int> live; // indices of fp64-mode contexts whose loop is running here
     std::vector<int> threaded;
     std::vector<int> strict; // reference-order contexts
+    // The reference-order contexts of this call take their sequential sums TOGETHER when there are nine or more of them (seq_sums.hpp: SeqRendezvous): every such context
+    // has a submitter thread (its iterations synchronise the stream anyway) and each iteration ends in k_seq_sums -- ONE workgroup, ~1.4 ms for 3e5 rows; K independent runs
+    // scale to the number of hardware queues of the process (GPU_MAX_HW_QUEUES) and no further, K workgroups of one launch do not have that limit.  The meeting (one per
+    // device among the contexts) lives in this call -- all its submitter threads are joined before it returns -- so two calls at the same time never share a round.
+    std::map<int, SeqRendezvous> meetings;
+    std::vector<SeqRendezvous::Membership> members((size_t)k);
+    auto meeting_on = [&](int device) -> SeqRendezvous* {
+        auto it = meetings.find(device);
+        if (it == meetings.end())
+            if (hipStream_t s = seq_meeting_stream(device, kSeqOneRow)) it = meetings.try_emplace(device, kSeqOneRow, 9, device, s).first;
+        return it == meetings.end() ? nullptr : &it->second;
+    };
     for (int i = 0; i < k; ++i) {
         op_icp* c = ctxs[i];
         const float* T0 = init_T ? init_T + 16 * (size_t)i : kIdentity;
-        if (c->sums == OP_ICP_SUMS_REFERENCE_F32) { // own submitter thread; the sequential sums of all of them in one launch per round (SeqBatch)
-            if (mode == OP_ICP_POINT_TO_PLANE && hipSetDevice(c->device) == hipSuccess && seq_device_ok(c)) {
-                if (!c->seq_ev && op::cached_event(&c->seq_ev) != hipSuccess) { c->seq_ev = nullptr; (void)hipGetLastError(); }
-                IcpSeqBatch* b = icp_seq_batch(c->device);
-                if (c->seq_ev && b && b->usable(c->device)) { c->seq_batch = b; b->join(); }
-            }
-            strict.push_back(i); // (its submitter thread starts below, once every participant of the batch is counted)
+        if (c->sums == OP_ICP_SUMS_REFERENCE_F32) { // own submitter thread
+            if (mode == OP_ICP_POINT_TO_PLANE && hipSetDevice(c->device) == hipSuccess && seq_ready(c))
+                if ((c->seq_batch = meeting_on(c->device))) members[(size_t)i] = c->seq_batch->join();
+            strict.push_back(i); // (its submitter thread starts below, once every participant of the meeting is counted)
             continue;
         }
         int r = icp_run_head(c, mode, max_iteration);
@@ -513,24 +480,17 @@ int op_icp_run_many(op_icp* const* ctxs, int k, int mode, const float* init_T, i
     }
     for (int i : strict) {
         op_icp* c = ctxs[i];
-        const float* T0 = init_T ? init_T + 16 * (size_t)i : kIdentity;
         std::array<float, 16> T0a;
-        std::memcpy(T0a.data(), T0, sizeof(float) * 16);
+        std::memcpy(T0a.data(), init_T ? init_T + 16 * (size_t)i : kIdentity, sizeof(float) * 16);
         op_icp_result* res_i = &results[i];
-        c->worker_active = true; c->worker_rc = OP_OK; c->worker_err[0] = 0;
-        try {
-            c->worker = std::thread([=] {
-                c->worker_rc = icp_run_impl(c, mode, T0a.data(), max_iteration, res_i, nullptr, 0, nullptr, nullptr);
-                if (c->worker_rc != OP_OK) std::snprintf(c->worker_err, sizeof(c->worker_err), "%s", op::g_last_error);
-                if (c->seq_batch) static_cast<IcpSeqBatch*>(c->seq_batch)->leave(); // (on every exit: nobody may go on waiting for this context)
-            });
-            threaded.push_back(i);
-        } catch (const std::exception& e) {
-            c->worker_active = false;
-            if (c->seq_batch) { static_cast<IcpSeqBatch*>(c->seq_batch)->leave(); c->seq_batch = nullptr; }
-            note(fail(OP_ERR_INVALID, "op_icp_run_many: could not start a submitter thread: %s", e.what()));
-        }
+        // (the membership travels with the thread's function and leaves the meeting on every exit -- also when no thread could be started: nobody may go on waiting for this context)
+        const int r = c->worker.start("op_icp_run_many: could not start a submitter thread", [=, member = std::move(members[(size_t)i])] {
+            (void)member;
+            return icp_run_impl(c, mode, T0a.data(), max_iteration, res_i, nullptr, 0, nullptr, nullptr);
+        });
+        if (r == OP_OK) threaded.push_back(i); else { c->seq_batch = nullptr; note(r); }
     }
+
     // fp64-mode contexts: at most kInFlight of them are ACTIVE at a time, each with one iteration enqueued; the submitter waits for the oldest launch's sums, solves,
     // enqueues that context's next iteration.  One k_icp_iter launch already fills more than half of the chip (4 800 of 8 192 wave slots): two overlap, so
     // more iterations in flight only slow each other down.  A context whose loop is over hands its finish (final CountInliers + the reference-order Kabsch over
@@ -577,29 +537,17 @@ int op_icp_run_many(op_icp* const* ctxs, int k, int mode, const float* init_T, i
 
 int op_icp_run_enqueue(op_icp* c, int mode, const float init_T[16], int max_iteration, op_icp_result* result, int32_t* pairs, size_t pairs_cap) {
     if (!c || !init_T || !result) return fail(OP_ERR_INVALID, "null argument");
-    if (c->worker_active) return fail(OP_ERR_INVALID, "op_icp_run_enqueue: an enqueued run has not been waited for");
+    if (c->worker.active) return fail(OP_ERR_INVALID, "op_icp_run_enqueue: an enqueued run has not been waited for");
     std::array<float, 16> T0;
     std::memcpy(T0.data(), init_T, sizeof(float) * 16);
-    c->worker_active = true; c->worker_rc = OP_OK; c->worker_err[0] = 0;
-    try {
-        c->worker = std::thread([=] {
-            c->worker_rc = icp_run_impl(c, mode, T0.data(), max_iteration, result, pairs, pairs_cap, nullptr, nullptr);
-            if (c->worker_rc != OP_OK) std::snprintf(c->worker_err, sizeof(c->worker_err), "%s", op::g_last_error); // (the error text is thread-local: hand it over)
-        });
-    } catch (const std::exception& e) { // std::system_error (no thread to be had) must not cross the extern "C" boundary
-        c->worker_active = false;
-        return fail(OP_ERR_INVALID, "op_icp_run_enqueue: could not start the submitter thread: %s", e.what());
-    }
-    return OP_OK;
+    return c->worker.start("op_icp_run_enqueue: could not start the submitter thread",
+                           [=] { return icp_run_impl(c, mode, T0.data(), max_iteration, result, pairs, pairs_cap, nullptr, nullptr); });
 }
 
 int op_icp_wait(op_icp* c) {
     if (!c) return fail(OP_ERR_INVALID, "null argument");
-    if (!c->worker_active) return fail(OP_ERR_INVALID, "op_icp_wait: nothing has been enqueued");
-    c->worker.join();
-    c->worker_active = false;
-    if (c->worker_rc != OP_OK) return fail(c->worker_rc, "%s", c->worker_err);
-    return OP_OK;
+    if (!c->worker.active) return fail(OP_ERR_INVALID, "op_icp_wait: nothing has been enqueued");
+    return c->worker.join();
 }
 
 int op_icp_register(int mode, const float* src_xyz, size_t n, const float* tgt_xyz, const float* tgt_normals, size_t m, const float init_T[16],

@@ -4,8 +4,9 @@
 //                  the other users of that grid and of the scan: EstimateNormals (k_estimate_normals), LoadFromDepth / LoadFromRGBD (k_depth_*)
 //   icp_iter.hip   one pass: k_icp_iter<MODE, DETECT> (transform + 1-NN + CountInliers + sums + their reduction), its launch / wait, the re-decision of exactly
 //                  equidistant candidates and of the final count's doubtful correspondences in the tree nanoflann would build
-//   icp.hip        a registration: the iteration loop in both summation modes, ordered inlier rows + sequential float32 sums (k_emit_rows, k_seq_sums), the
-//                  finish (RegistrationResult), op_icp_run / _many / _enqueue / _register, the stand-alone estimators (k_pair_sums)
+//   icp.hip        a registration: the iteration loop (one for both summation modes), the ordered inlier rows (k_emit_rows), the finish (RegistrationResult),
+//                  op_icp_run / _many / _enqueue / _register, the stand-alone estimators (k_pair_sums)
+//   seq_sums.hip   shared with the dense tracker: the sequential float32 sums of the reference-order modes (k_seq_sums, SeqSums, SeqRendezvous; seq_sums.hpp)
 // C-ABI entry points op_icp_* / op_points_from_* / op_estimate_* are declared in include/onepiece_hip.h.
 //
 // What it replaces (file:line under /root/reference/src):
@@ -39,6 +40,7 @@
 #include <condition_variable>
 #include <deque>
 #include <limits>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -46,7 +48,9 @@
 
 #include "common.hpp"
 #include "host_math.hpp"
+#include "host_thread.hpp"
 #include "nn_tree.hpp"
+#include "seq_sums.hpp"
 
 namespace opi {
 
@@ -159,11 +163,8 @@ struct op_icp {
     unsigned *flag = nullptr, *start = nullptr, *scan_tot = nullptr;
     float *rows_dev = nullptr, *rows_host = nullptr; // src_cap x 9 floats each; rows_host is pinned
     size_t rows_cap = 0;
-    // reference-order point-to-plane sums on the device (k_seq_sums, seq_sums.hpp): the 42 results + the row count, and whether the kernel may have its LDS
-    float* seq_out = nullptr;
-    float* seq_host = nullptr;       // pinned
-    unsigned* seq_total = nullptr;
-    int seq_ok = -1;                 // -1: not asked yet
+    SeqSums seq_sums;                       // reference-order point-to-plane sums on the device (seq_sums.hpp): the 42 results + the row count
+    SeqRendezvous* seq_batch = nullptr; // set for the duration of an op_icp_run_many call: this context's sequential sums are taken in one launch with the other contexts'
     // op_icp_run_enqueue / op_icp_wait: the loop needs the host after every iteration (the 6x6 solve), so an enqueued run proceeds on a host
     // thread of the context's own -- K contexts (each with its stream) register K frame pairs side by side: ICP's only parallel axis (replicas)
     // OP_ICP_TIES_REFERENCE (default): queries whose nearest candidates are exactly equidistant are re-decided on the host in the tree the reference would build
@@ -184,17 +185,12 @@ struct op_icp {
     unsigned* fin_list = nullptr;       // device, src_cap entries
     size_t fin_cap = 0;
     uint64_t fin_redecided = 0;         // since the context was created
-    void* seq_batch = nullptr;          // icp.hip: the SeqRendezvous<42, 7, 1, 9> of the device (seq_sums.hpp), set for the duration of an op_icp_run_many call: this context's sequential sums are taken in one launch with the other contexts'
-    hipEvent_t seq_ev = nullptr;        // "my ordered rows are in place" (recorded on the context's stream for the batch's stream to wait on)
-    std::thread worker;
-    bool worker_active = false;
-    int worker_rc = OP_OK;
-    char worker_err[512] = "";
+    op::HostThread worker;
 };
 
 // While a run enqueued with op_icp_run_enqueue is in flight its worker thread owns the context (nn, tie buffers, fin_aux, seq, the stream): every other
 // entry point refuses instead of racing with it.
-#define OP_ICP_NOT_BUSY(c, what) do { if ((c)->worker_active) return fail(OP_ERR_INVALID, what ": a run enqueued with op_icp_run_enqueue has not been waited for (op_icp_wait)"); } while (0)
+#define OP_ICP_NOT_BUSY(c, what) do { if ((c)->worker.active) return fail(OP_ERR_INVALID, what ": a run enqueued with op_icp_run_enqueue has not been waited for (op_icp_wait)"); } while (0)
 
 
 namespace opi {

@@ -442,7 +442,7 @@ int op_icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, doub
 }
 
 int op_icp_destroy(op_icp* c) {
-    if (c && c->worker_active) { c->worker.join(); c->worker_active = false; }
+    if (c && c->worker.active) (void)c->worker.join();
     if (!c) return OP_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -455,10 +455,7 @@ int op_icp_destroy(op_icp* c) {
     for (hipEvent_t ev : c->chunk_ev)
         op::release_event(ev, c->device);
     if (c->rows_host) op::cached_free(c->rows_host);
-    if (c->seq_ev) op::release_event(c->seq_ev, c->device);
-    if (c->seq_out) op::cached_free(c->seq_out);
-    if (c->seq_total) op::cached_free(c->seq_total);
-    if (c->seq_host) op::cached_free(c->seq_host);
+    c->seq_sums.release(c->device);
     if (c->fin_aux) op::cached_free(c->fin_aux);
     if (c->fin_list) op::cached_free(c->fin_list);
     if (c->tgt_host) op::cached_free(c->tgt_host);

@@ -22,6 +22,7 @@
 // (one HIP stream each) keep independent frame pairs in flight; one call's ~100 launches are captured
 // into a hipGraph on first use and replayed afterwards.
 #include "odometry_core.hpp"
+#include "host_thread.hpp"
 #include "seq_sums.hpp"
 
 using namespace op;
@@ -444,26 +445,19 @@ struct op_tracker {
     // The reference-order modes (OP_TRACK_SUMS_REFERENCE_F32*) need the host after every iteration, so an "enqueued" run of theirs executes on a host
     // thread of the tracker's own: op_tracker_dense_tracking_enqueue still returns at once and several trackers still run side by side (their
     // sequential one-wave sums on different CUs).  op_tracker_wait joins it.
-    std::thread worker;
-    bool worker_active = false;
-    int worker_rc = OP_OK;
-    char worker_err[512] = "";
+    op::HostThread worker;
     size_t pix_cap = 0;              // workspace capacity in pixels
     int* pair_p = nullptr;           // per source pixel: candidate target pixel index p(s) or -1
     int* pair_t = nullptr;           // per source pixel: accepted target pixel index or -1
     unsigned short* code = nullptr;  // per source pixel: acceptance link code
     int lds_cap = 0;                 // dynamic LDS bytes available to one k_track_iter workgroup
     int sums = OP_TRACK_SUMS_FP64;   // OP_TRACK_OPT_SUMS
-    bool seq_ok = false;             // k_seq_sums may have its LDS (else OP_TRACK_SUMS_REFERENCE_F32 sums on the host like _F32_HOST)
     float* rows_dev = nullptr;       // validation mode: 14 floats per source pixel
     float* rows_host = nullptr;      // pinned
     int* pair_host = nullptr;        // pinned
     size_t rows_cap = 0;             // pixels
     size_t rows_host_cap = 0;        // pixels (rows_host / pair_host)
-    float* seq_out = nullptr;        // device: the 42 (+ count) results of k_seq_sums
-    float* seq_host = nullptr;       // pinned copy
-    unsigned* seq_total = nullptr;   // device: number of accepted pixels (k_emit_scan)
-    hipEvent_t seq_ev = nullptr;     // "my ordered rows are in place" (for the rendezvous of trackers that sum together, seq_sums.hpp)
+    SeqSums seq_sums;                // reference-order sums on the device (seq_sums.hpp; where the kernel may not run they are taken on the host like _F32_HOST): its `total` is k_emit_scan's count of accepted pixels
     int lds_total = 0, lds_static = 0, n_cu = 256;
     double* partials = nullptr;
     unsigned* wg_count = nullptr;
@@ -530,10 +524,11 @@ IterGeom iter_geom(const op_tracker* t, size_t npix) {
     return g;
 }
 
-template <int TERM>
-void launch_iter(op_tracker* t, int l, const IterGeom& g) {
-    hipLaunchKernelGGL(k_track_iter<TERM>, dim3(g.n_wg), dim3(kIterThreads), g.lds_bytes, t->stream, t->st, l, g.win_cap,
-                       t->pair_p, t->code, t->pair_t, t->partials);
+void launch_iter(op_tracker* t, int term, int l, const IterGeom& g) { // term 0 .. 2: the loop's term_type; 3: the NormalizeIntensity pass
+    op::with_constant<4>(term, [&](auto TERM) {
+        hipLaunchKernelGGL(k_track_iter<decltype(TERM)::value>, dim3(g.n_wg), dim3(kIterThreads), g.lds_bytes, t->stream, t->st, l, g.win_cap,
+                           t->pair_p, t->code, t->pair_t, t->partials);
+    });
 }
 
 } // namespace
@@ -561,17 +556,12 @@ int op_tracker_create(int device, op_tracker** out) {
     t->lds_total = lds_max; t->lds_static = lds_static;
     t->lds_cap = lds_max - lds_static;
     if (hipDeviceGetAttribute(&t->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || t->n_cu <= 0) t->n_cu = 256;
-    bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_track_iter<0>), hipFuncAttributeMaxDynamicSharedMemorySize, t->lds_cap) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&k_track_iter<1>), hipFuncAttributeMaxDynamicSharedMemorySize, t->lds_cap) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&k_track_iter<2>), hipFuncAttributeMaxDynamicSharedMemorySize, t->lds_cap) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&k_track_iter<3>), hipFuncAttributeMaxDynamicSharedMemorySize, t->lds_cap) == hipSuccess;
+    bool attr_ok = true;
+    for (int term = 0; term < 4; ++term)
+        op::with_constant<4>(term, [&](auto TERM) {
+            attr_ok = attr_ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_track_iter<decltype(TERM)::value>), hipFuncAttributeMaxDynamicSharedMemorySize, t->lds_cap) == hipSuccess;
+        });
     if (!attr_ok) { (void)hipGetLastError(); t->lds_total = 65536; t->lds_cap = 65536 - lds_static; }
-    // k_seq_sums (reference-order sums) double-buffers its product tiles in ~150 KB of LDS
-    t->seq_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seq_sums<42, 14, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)seq_lds_bytes(42, 14, 2)) == hipSuccess &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seq_sums<42, 7, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)seq_lds_bytes(42, 7, 1)) == hipSuccess &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seq_sums<2, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)seq_lds_bytes(2, 2, 1)) == hipSuccess &&
-                (size_t)lds_max >= seq_lds_bytes(42, 14, 2);
-    if (!t->seq_ok) (void)hipGetLastError();
     if (!op::runtime_options().tracker_graph.load()) t->graph_ok = 0; // OP_RUNTIME_OPT_TRACKER_GRAPH
     t->sums = op::runtime_options().tracker_default_sums.load();       // OP_RUNTIME_OPT_TRACKER_DEFAULT_SUMS: the reference's own sums unless the process opted out
     *out = t;
@@ -580,20 +570,18 @@ int op_tracker_create(int device, op_tracker** out) {
 
 int op_tracker_set_option(op_tracker* t, int option, int value) {
     if (!t) return fail(OP_ERR_INVALID, "null tracker");
-    if (t->worker_active) return fail(OP_ERR_INVALID, "op_tracker_set_option: an enqueued run has not been waited for");
+    if (t->worker.active) return fail(OP_ERR_INVALID, "op_tracker_set_option: an enqueued run has not been waited for");
     if (option == OP_TRACK_OPT_SUMS && (value == OP_TRACK_SUMS_FP64 || value == OP_TRACK_SUMS_REFERENCE_F32 || value == OP_TRACK_SUMS_REFERENCE_F32_HOST)) { t->sums = value; return OP_OK; }
     return fail(OP_ERR_INVALID, "op_tracker_set_option: unknown option %d / value %d", option, value);
 }
 
 int op_tracker_destroy(op_tracker* t) {
     if (!t) return OP_OK;
-    if (t->worker_active) { t->worker.join(); t->worker_active = false; }
+    if (t->worker.active) (void)t->worker.join();
     (void)hipSetDevice(t->device);
     if (t->stream) (void)hipStreamSynchronize(t->stream);
     (void)hipFree(t->rows_dev);
-    (void)hipFree(t->seq_out); (void)hipFree(t->seq_total);
-    if (t->seq_ev) (void)hipEventDestroy(t->seq_ev);
-    if (t->seq_host) (void)hipHostFree(t->seq_host);
+    t->seq_sums.release(t->device);
     if (t->rows_host) (void)hipHostFree(t->rows_host);
     if (t->pair_host) (void)hipHostFree(t->pair_host);
     (void)hipFree(t->pair_t); (void)hipFree(t->pair_p); (void)hipFree(t->code); (void)hipFree(t->partials); (void)hipFree(t->wg_count); (void)hipFree(t->pix_out); (void)hipFree(t->pts_out);
@@ -611,8 +599,7 @@ int op_tracker_destroy(op_tracker* t) {
 // Enqueues the coarse-to-fine loop + result assembly over the level descriptors already stored in
 // t->st_host->lv (device pointers) on t->stream and returns; track_finish() synchronises and reads the
 // result.  The pinned buffers are only touched between a finish and the next enqueue.
-static void fill_loop_header(op_tracker* t, int full_width, int full_height, int term_type, const float init_T[16]) {
-    TrackState* h = t->st_host;
+static void fill_loop_header(TrackState* h, int full_width, int full_height, int term_type, const float init_T[16]) {
     std::memcpy(h->T, init_T, sizeof(h->T));
     h->full_w = full_width; h->full_h = full_height; h->term = term_type;
     h->stop_level = -1; h->iters_done = 0; h->last_level = -1; h->n_last = 0; h->n_emit = 0; h->rmse = 0; h->success = 0;
@@ -623,38 +610,32 @@ static void fill_loop_header(op_tracker* t, int full_width, int full_height, int
 // SeqRendezvous; with twelve or more trackers running, below that each launches its own).  OFF by default (OP_RUNTIME_OPT_TRACKER_BATCH_SUMS): what the pipeline
 // needed was a hardware queue per tracker stream (GPU_MAX_HW_QUEUES = 16: 349 -> 489 frames/s with 16 pairs in flight, profiles/r06_track_hw_queues.txt); meeting in
 // lock step costs every round the largest pyramid level's sum (profiles/r06_track_depth_probe.txt).  One rendezvous per device; hybrid term only.
-using TrackSeqBatch = SeqRendezvous<42, 14, 2, 12>;
-static TrackSeqBatch* track_seq_batch(int device) {
-    static TrackSeqBatch pool[16];
-    return device >= 0 && device < 16 ? &pool[device] : nullptr;
+// The meeting is between independent op_tracker_*_enqueue calls, so no call owns it: it is created on first use and stays.
+static SeqRendezvous* track_seq_batch(int device) {
+    static std::mutex mu;
+    static std::map<int, std::unique_ptr<SeqRendezvous>> pool;
+    std::lock_guard<std::mutex> lk(mu);
+    std::unique_ptr<SeqRendezvous>& m = pool[device];
+    if (!m)
+        if (hipStream_t s = seq_meeting_stream(device, kSeqTwoRows)) m.reset(new SeqRendezvous(kSeqTwoRows, 12, device, s));
+    return m.get();
 }
-struct TrackBatchMembership { // leaves on every exit of the run
-    TrackSeqBatch* b = nullptr;
-    ~TrackBatchMembership() { if (b) b->leave(); }
-};
 
 static int track_enqueue(op_tracker* t, int n_levels, const int32_t* iters_per_level, int full_width, int full_height, int term_type,
                          const float init_T[16], bool want_points, bool want_logs) {
     TrackState* h = t->st_host;
-    fill_loop_header(t, full_width, full_height, term_type, init_T);
+    fill_loop_header(h, full_width, full_height, term_type, init_T);
     // header of the state only (the per-iteration logs are outputs)
     OP_HIP(hipMemcpyAsync(t->st, h, offsetof(TrackState, per_iter_count), hipMemcpyHostToDevice, t->stream));
     size_t max_pix = 0;
     int it = 0;
     const bool strict = t->sums != OP_TRACK_SUMS_FP64;
-    const bool on_device = t->sums == OP_TRACK_SUMS_REFERENCE_F32 && t->seq_ok; // the sequential float32 sums in k_seq_sums; else on one host thread
-    if (strict && !t->seq_out) {
-        OP_HIP(hipMalloc(&t->seq_out, 64 * sizeof(float)));
-        OP_HIP(hipHostMalloc(&t->seq_host, 64 * sizeof(float), hipHostMallocDefault));
-        OP_HIP(hipMalloc(&t->seq_total, sizeof(unsigned)));
-    }
-    TrackSeqBatch* batch = nullptr;
-    TrackBatchMembership member;
-    if (strict && on_device && term_type == 0 && op::runtime_options().tracker_batch_sums.load()) {
-        if (!t->seq_ev && hipEventCreateWithFlags(&t->seq_ev, hipEventDisableTiming) != hipSuccess) { t->seq_ev = nullptr; (void)hipGetLastError(); }
-        TrackSeqBatch* b = track_seq_batch(t->device);
-        if (t->seq_ev && b && b->usable(t->device)) { batch = b; b->join(); member.b = b; }
-    }
+    const bool on_device = t->sums == OP_TRACK_SUMS_REFERENCE_F32 && seq_device_ok(t->device); // the sequential float32 sums in k_seq_sums; else on one host thread
+    if (on_device) OP_HIP(t->seq_sums.reserve(t->device, false));
+    SeqRendezvous* batch = nullptr;
+    SeqRendezvous::Membership member; // leaves on every exit of the run
+    if (on_device && term_type == 0 && op::runtime_options().tracker_batch_sums.load())
+        if ((batch = track_seq_batch(t->device))) member = batch->join();
     float cur[16];
     std::memcpy(cur, init_T, sizeof(cur));
     for (int l = n_levels - 1; l >= 0; --l) {
@@ -678,9 +659,7 @@ static int track_enqueue(op_tracker* t, int n_levels, const int32_t* iters_per_l
         }
         for (int j = 0; j < iters_per_level[l]; ++j, ++it) {
             hipLaunchKernelGGL(k_track_assoc, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, t->pair_p, t->code);
-            if (term_type == 0) launch_iter<0>(t, l, g);
-            else if (term_type == 1) launch_iter<1>(t, l, g);
-            else launch_iter<2>(t, l, g);
+            launch_iter(t, term_type, l, g);
             if (!strict) {
                 hipLaunchKernelGGL(k_track_solve, dim3(1), dim3(1024), 0, t->stream, t->st, l, it, t->partials, g.n_wg);
                 continue;
@@ -691,40 +670,23 @@ static int track_enqueue(op_tracker* t, int n_levels, const int32_t* iters_per_l
             // back into the device state for the next iteration.
             float JTJ[36], JTr[6], x[6], D[16];
             size_t n_pairs = 0;
-            bool batched_now = false;
             if (on_device) {
                 hipLaunchKernelGGL(k_rows_count, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, t->wg_count);
-                launch_emit_scan(dim3(1), dim3(1024), t->stream, t->st, t->wg_count, n_wg_a, t->seq_total);
-                if (term_type == 0) {
-                    hipLaunchKernelGGL(k_track_rows_compact<0>, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, (const unsigned*)t->wg_count, t->rows_dev);
-                    hipError_t eb = hipErrorNotReady;
-                    if (batch) { // with the other trackers running now: one launch, a workgroup each; the sums land in t->seq_host (hipErrorNotReady: too few of them)
-                        OP_HIP(hipGetLastError());
-                        eb = batch->submit(t->rows_dev, t->seq_total, t->seq_out, t->seq_host, t->seq_ev, t->stream);
-                        if (eb != hipSuccess && eb != hipErrorNotReady) return fail(OP_ERR_HIP, "tracker: the batched sequential sums failed: %s", hipGetErrorString(eb));
-                    }
-                    batched_now = eb == hipSuccess;
-                    if (!batched_now)
-                        hipLaunchKernelGGL((k_seq_sums<42, 14, 2>), dim3(1), dim3(kSeqThreads), seq_lds_bytes(42, 14, 2), t->stream, (const float*)t->rows_dev, (const unsigned*)t->seq_total, t->seq_out);
-                } else {
-                    if (term_type == 1) hipLaunchKernelGGL(k_track_rows_compact<1>, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, (const unsigned*)t->wg_count, t->rows_dev);
-                    else hipLaunchKernelGGL(k_track_rows_compact<2>, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, (const unsigned*)t->wg_count, t->rows_dev);
-                    hipLaunchKernelGGL((k_seq_sums<42, 7, 1>), dim3(1), dim3(kSeqThreads), seq_lds_bytes(42, 7, 1), t->stream, (const float*)t->rows_dev, (const unsigned*)t->seq_total, t->seq_out);
-                }
+                launch_emit_scan(dim3(1), dim3(1024), t->stream, t->st, t->wg_count, n_wg_a, t->seq_sums.total);
+                op::with_constant<3>(term_type, [&](auto TERM) {
+                    hipLaunchKernelGGL(k_track_rows_compact<decltype(TERM)::value>, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, (const unsigned*)t->wg_count, t->rows_dev);
+                });
                 OP_HIP(hipGetLastError());
-                if (!batched_now) {
-                    OP_HIP(hipMemcpyAsync(t->seq_host, t->seq_out, 43 * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-                    OP_HIP(hipStreamSynchronize(t->stream));
-                }
-                std::memcpy(JTJ, t->seq_host, sizeof(JTJ));
-                std::memcpy(JTr, t->seq_host + 36, sizeof(JTr));
-                unsigned n32;
-                std::memcpy(&n32, t->seq_host + 42, sizeof(n32));
-                n_pairs = n32;
+                // (hybrid term: two rows per pixel, and with the other trackers running now if they meet -- one launch, a workgroup each)
+                const SeqLayout layout = term_type == 0 ? kSeqTwoRows : kSeqOneRow;
+                OP_HIP(t->seq_sums.run(layout, t->rows_dev, nullptr, t->stream, batch));
+                std::memcpy(JTJ, t->seq_sums.host, sizeof(JTJ));
+                std::memcpy(JTr, t->seq_sums.host + 36, sizeof(JTr));
+                n_pairs = t->seq_sums.count(layout);
             } else {
-                if (term_type == 0) hipLaunchKernelGGL(k_track_rows<0>, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, t->rows_dev);
-                else if (term_type == 1) hipLaunchKernelGGL(k_track_rows<1>, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, t->rows_dev);
-                else hipLaunchKernelGGL(k_track_rows<2>, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, t->rows_dev);
+                op::with_constant<3>(term_type, [&](auto TERM) {
+                    hipLaunchKernelGGL(k_track_rows<decltype(TERM)::value>, dim3(n_wg_a), dim3(kThreads), 0, t->stream, t->st, l, (const int*)t->pair_t, t->rows_dev);
+                });
                 OP_HIP(hipGetLastError());
                 OP_HIP(hipMemcpyAsync(t->rows_host, t->rows_dev, np * 14 * sizeof(float), hipMemcpyDeviceToHost, t->stream));
                 OP_HIP(hipMemcpyAsync(t->pair_host, t->pair_t, np * sizeof(int), hipMemcpyDeviceToHost, t->stream));
@@ -820,7 +782,7 @@ int op_tracker_track(op_tracker* t, const op_track_level* levels, int n_levels, 
         max_pix = np > max_pix ? np : max_pix;
         image_floats += 8 * np;
     }
-    if (t->pending || t->worker_active) return fail(OP_ERR_INVALID, "op_tracker_track: an enqueued run has not been waited for");
+    if (t->pending || t->worker.active) return fail(OP_ERR_INVALID, "op_tracker_track: an enqueued run has not been waited for");
     OP_TRY(use_device(t->device));
     OP_TRY(tracker_reserve(t, max_pix, mem == OP_MEM_HOST ? image_floats : 0));
     TrackState* h = t->st_host;
@@ -854,32 +816,6 @@ static float* pyr_image(const op_tracker* t, int f, int k, int l) {
     size_t per_set = 0;
     for (int q = 0; q < t->pyr_levels; ++q) per_set += (size_t)(t->pyr_w >> q) * (t->pyr_h >> q);
     return t->pyr + (size_t)(f * 6 + k) * per_set + off;
-}
-
-static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n_levels, const int32_t* iters_per_level,
-                                      const uint8_t* source_rgb, const uint8_t* target_rgb, const void* source_depth, const void* target_depth,
-                                      int depth_fmt, const float init_T[16], int term_type, int mem, int want_point_corr);
-
-int op_tracker_dense_tracking_enqueue(op_tracker* t, const op_camera* cam, int n_levels, const int32_t* iters_per_level,
-                                      const uint8_t* source_rgb, const uint8_t* target_rgb, const void* source_depth, const void* target_depth,
-                                      int depth_fmt, const float init_T[16], int term_type, int mem, int want_point_corr) {
-    if (!t || !cam || !iters_per_level || !source_rgb || !target_rgb || !source_depth || !target_depth || !init_T)
-        return fail(OP_ERR_INVALID, "op_tracker_dense_tracking: NULL argument");
-    if (t->pending || t->worker_active) return fail(OP_ERR_INVALID, "op_tracker_dense_tracking: an enqueued run has not been waited for");
-    if (t->sums == OP_TRACK_SUMS_FP64)
-        return dense_tracking_enqueue_now(t, cam, n_levels, iters_per_level, source_rgb, target_rgb, source_depth, target_depth, depth_fmt, init_T, term_type, mem, want_point_corr);
-    // reference-order sums: the run synchronises with the host every iteration -- on the tracker's own host thread (the images must stay valid until op_tracker_wait, as for any enqueue)
-    OP_TRY(check_iters("op_tracker_dense_tracking", n_levels, iters_per_level, term_type));
-    const op_camera cam_copy = *cam;
-    const std::vector<int32_t> iters(iters_per_level, iters_per_level + n_levels);
-    std::array<float, 16> T0;
-    std::memcpy(T0.data(), init_T, sizeof(float) * 16);
-    t->worker_active = true; t->worker_rc = OP_OK; t->worker_err[0] = 0;
-    t->worker = std::thread([=] {
-        t->worker_rc = dense_tracking_enqueue_now(t, &cam_copy, n_levels, iters.data(), source_rgb, target_rgb, source_depth, target_depth, depth_fmt, T0.data(), term_type, mem, want_point_corr);
-        if (t->worker_rc != OP_OK) std::snprintf(t->worker_err, sizeof(t->worker_err), "%s", op::g_last_error); // (the error text is thread-local: hand it over)
-    });
-    return OP_OK;
 }
 
 static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n_levels, const int32_t* iters_per_level,
@@ -934,14 +870,10 @@ static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n
         D.tcdx = pyr_image(t, 1, 2, l); D.tcdy = pyr_image(t, 1, 3, l); D.tddx = pyr_image(t, 1, 4, l); D.tddy = pyr_image(t, 1, 5, l);
         fx /= 2; fy /= 2; cx /= 2; cy /= 2;
     }
-    {
-        const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        std::memcpy(h->T, I4, sizeof(I4));
-        h->full_w = W; h->full_h = H; h->term = 3; h->stop_level = -1;
-        h->iters_done = 0; h->last_level = -1; h->n_last = 0; h->n_emit = 0; h->rmse = 0; h->success = 0;
-        std::memcpy(t->st_host->lv, h->lv, sizeof(h->lv));
-    }
-    fill_loop_header(t, W, H, term_type, init_T);
+    const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    fill_loop_header(h, W, H, 3, I4);
+    std::memcpy(t->st_host->lv, h->lv, sizeof(h->lv));
+    fill_loop_header(t->st_host, W, H, term_type, init_T);
 
     // One call = ~100 small launches.  With device-resident frames the sequence depends on the call only through
     // the three pinned buffers filled above, so it is captured once into a hipGraph and replayed afterwards.
@@ -972,30 +904,22 @@ static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n
         OP_HIP(hipMemcpyAsync(t->st, t->st_host_norm, offsetof(TrackState, per_iter_count), hipMemcpyHostToDevice, t->stream));
         const IterGeom g = iter_geom(t, np);
         hipLaunchKernelGGL(k_track_assoc, dim3(n_wg0), dim3(kThreads), 0, t->stream, t->st, 0, t->pair_p, t->code);
-        launch_iter<3>(t, 0, g);
+        launch_iter(t, 3, 0, g);
         if (t->sums != OP_TRACK_SUMS_FP64) {
             // reference-order mode: NormalizeIntensity's two means summed like the reference does (DenseOdometryFunction.cpp:131-141):
             // sequentially in float32 over the identity-pose pairs in raster order -- by k_seq_sums, or (_HOST variant) on one host thread
             float mean_s = 0.0f, mean_t = 0.0f;
             size_t cnt = 0;
-            if (t->sums == OP_TRACK_SUMS_REFERENCE_F32 && t->seq_ok) {
-                if (!t->seq_out) {
-                    OP_HIP(hipMalloc(&t->seq_out, 64 * sizeof(float)));
-                    OP_HIP(hipHostMalloc(&t->seq_host, 64 * sizeof(float), hipHostMallocDefault));
-                    OP_HIP(hipMalloc(&t->seq_total, sizeof(unsigned)));
-                }
+            if (t->sums == OP_TRACK_SUMS_REFERENCE_F32 && seq_device_ok(t->device)) {
+                OP_HIP(t->seq_sums.reserve(t->device, false));
                 float* pairs2 = reinterpret_cast<float*>(t->pix_out); // 2 floats per accepted pixel; pix_out (16 B per pixel) is idle until the run's final emit
                 hipLaunchKernelGGL(k_rows_count, dim3(n_wg0), dim3(kThreads), 0, t->stream, t->st, 0, (const int*)t->pair_t, t->wg_count);
-                launch_emit_scan(dim3(1), dim3(1024), t->stream, t->st, t->wg_count, n_wg0, t->seq_total);
+                launch_emit_scan(dim3(1), dim3(1024), t->stream, t->st, t->wg_count, n_wg0, t->seq_sums.total);
                 hipLaunchKernelGGL(k_norm_pairs_compact, dim3(n_wg0), dim3(kThreads), 0, t->stream, (const float*)pyr_image(t, 0, 0, 0), (const float*)pyr_image(t, 1, 0, 0), (int)np,
                                    (const int*)t->pair_t, (const unsigned*)t->wg_count, pairs2);
-                hipLaunchKernelGGL((k_seq_sums<2, 2, 1>), dim3(1), dim3(kSeqThreads), seq_lds_bytes(2, 2, 1), t->stream, (const float*)pairs2, (const unsigned*)t->seq_total, t->seq_out);
                 OP_HIP(hipGetLastError());
-                OP_HIP(hipMemcpyAsync(t->seq_host, t->seq_out, 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-                OP_HIP(hipStreamSynchronize(t->stream));
-                unsigned n32;
-                std::memcpy(&n32, t->seq_host + 2, sizeof(n32));
-                mean_s = t->seq_host[0]; mean_t = t->seq_host[1]; cnt = n32;
+                OP_HIP(t->seq_sums.run(kSeqTwoValues, pairs2, nullptr, t->stream, nullptr));
+                mean_s = t->seq_sums.host[0]; mean_t = t->seq_sums.host[1]; cnt = t->seq_sums.count(kSeqTwoValues);
             } else {
                 std::vector<int> pt(np);
                 std::vector<float> gs(np), gt(np);
@@ -1053,13 +977,31 @@ static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n
     return rc;
 }
 
+int op_tracker_dense_tracking_enqueue(op_tracker* t, const op_camera* cam, int n_levels, const int32_t* iters_per_level,
+                                      const uint8_t* source_rgb, const uint8_t* target_rgb, const void* source_depth, const void* target_depth,
+                                      int depth_fmt, const float init_T[16], int term_type, int mem, int want_point_corr) {
+    if (!t || !cam || !iters_per_level || !source_rgb || !target_rgb || !source_depth || !target_depth || !init_T)
+        return fail(OP_ERR_INVALID, "op_tracker_dense_tracking: NULL argument");
+    if (t->pending || t->worker.active) return fail(OP_ERR_INVALID, "op_tracker_dense_tracking: an enqueued run has not been waited for");
+    if (t->sums == OP_TRACK_SUMS_FP64)
+        return dense_tracking_enqueue_now(t, cam, n_levels, iters_per_level, source_rgb, target_rgb, source_depth, target_depth, depth_fmt, init_T, term_type, mem, want_point_corr);
+    // reference-order sums: the run synchronises with the host every iteration -- on the tracker's own host thread (the images must stay valid until op_tracker_wait, as for any enqueue)
+    OP_TRY(check_iters("op_tracker_dense_tracking", n_levels, iters_per_level, term_type));
+    const op_camera cam_copy = *cam;
+    const std::vector<int32_t> iters(iters_per_level, iters_per_level + n_levels);
+    std::array<float, 16> T0;
+    std::memcpy(T0.data(), init_T, sizeof(float) * 16);
+    return t->worker.start("op_tracker_dense_tracking: could not start the tracker's host thread", [=] {
+        return dense_tracking_enqueue_now(t, &cam_copy, n_levels, iters.data(), source_rgb, target_rgb, source_depth, target_depth, depth_fmt, T0.data(), term_type, mem, want_point_corr);
+    });
+}
+
 int op_tracker_wait(op_tracker* t, op_track_result* result, int32_t* pixel_corr, float* point_corr, size_t corr_cap) {
     if (!t || !result) return fail(OP_ERR_INVALID, "op_tracker_wait: NULL argument");
     OP_TRY(use_device(t->device));
-    if (t->worker_active) { // a reference-order run on the tracker's own host thread
-        t->worker.join();
-        t->worker_active = false;
-        if (t->worker_rc != OP_OK) { t->pending = false; return fail(t->worker_rc, "%s", t->worker_err); }
+    if (t->worker.active) { // a reference-order run on the tracker's own host thread
+        const int rc = t->worker.join();
+        if (rc != OP_OK) { t->pending = false; return rc; }
     }
     return track_finish(t, result, pixel_corr, point_corr, corr_cap, nullptr, nullptr);
 }
@@ -1076,7 +1018,7 @@ int op_tracker_dense_tracking(op_tracker* t, const op_camera* cam, int n_levels,
 
 int op_tracker_read_pyramid(op_tracker* t, int frame, int kind, int level, float* out, size_t cap) {
     if (!t || !out) return fail(OP_ERR_INVALID, "op_tracker_read_pyramid: NULL argument");
-    if (t->pending || t->worker_active) return fail(OP_ERR_INVALID, "op_tracker_read_pyramid: an enqueued run has not been waited for");
+    if (t->pending || t->worker.active) return fail(OP_ERR_INVALID, "op_tracker_read_pyramid: an enqueued run has not been waited for");
     if (!t->pyr || frame < 0 || frame > 1 || kind < 0 || kind > 5 || level < 0 || level >= t->pyr_levels || (frame == 0 && kind > 1))
         return fail(OP_ERR_INVALID, "op_tracker_read_pyramid: no such image (frame %d kind %d level %d)", frame, kind, level);
     const size_t n = (size_t)(t->pyr_w >> level) * (t->pyr_h >> level);

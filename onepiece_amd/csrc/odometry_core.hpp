@@ -3,6 +3,7 @@
 //   odometry.hip        the tracker: association + acceptance chain + Jacobian rows + sums + solve (k_track_*: the iteration family), the reference-order row
 //                       compaction, the host object and the C-ABI (op_tracker_*, op_dense_track)
 //   odometry_prep.hip   Odometry::DenseTracking's image preparation (k_prep_convert_blur / pyrdown / sobel) and NormalizeIntensity's scale (k_norm_*)
+//   seq_sums.hip        shared with ICP: the sequential float32 sums of the reference-order mode (k_seq_sums, SeqSums, SeqRendezvous; seq_sums.hpp)
 //   odometry_emit.hip   correspondence_set / pixel_correspondence_set / rmse of the last executed iteration (k_emit_*)
 #pragma once
 #include <array>
@@ -10,7 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
+#include <map>
 #include <vector>
 
 #include "common.hpp"

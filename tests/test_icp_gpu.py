@@ -676,7 +676,7 @@ def test_run_many_gives_every_context_the_result_it_gets_alone(hip):
     cases = [(room_cloud(1, 1), room_cloud(0, 1), L.OP_ICP_SUMS_FP64), (room_cloud(3, 1), room_cloud(2, 1), L.OP_ICP_SUMS_FP64),
              (room_cloud(101, 4), room_cloud(100, 4), L.OP_ICP_SUMS_REFERENCE_F32), (room_cloud(5, 2), room_cloud(4, 2), L.OP_ICP_SUMS_FP64),
              (room_cloud(7, 1), room_cloud(6, 1), L.OP_ICP_SUMS_REFERENCE_F32), (room_cloud(9, 2), room_cloud(8, 2), L.OP_ICP_SUMS_REFERENCE_F32),
-             (room_cloud(11, 1), room_cloud(10, 1), L.OP_ICP_SUMS_FP64)]   # three reference-order contexts: their sequential sums meet in one launch per round
+             (room_cloud(11, 1), room_cloud(10, 1), L.OP_ICP_SUMS_FP64)]   # three reference-order contexts: too few to meet (nine or more do, see the test below), each launches its own sums
     ctxs = []
     try:
         for (_, src, _n), (_, tgt, nrm), sums in cases:
@@ -715,3 +715,99 @@ def test_run_many_gives_every_context_the_result_it_gets_alone(hip):
     finally:
         for h in ctxs:
             lib.op_icp_destroy(h)
+
+
+def _meeting_contexts(lib, L, first_frame, n_ref=10, n_fp64=2):
+    """n_ref reference-order point-to-plane contexts on small clouds of different sizes (context 1 with an EMPTY source: it has nothing to sum and passes
+    every round) interleaved with n_fp64 fp64-mode contexts, and what op_icp_run gives each of them alone.  Nine or more reference-order contexts in one
+    op_icp_run_many call take their sequential sums in one k_seq_sums_many launch per round."""
+    import ctypes as C
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    modes = [L.OP_ICP_SUMS_REFERENCE_F32] * n_ref
+    for j in range(n_fp64):
+        modes.insert(3 + 4 * j, L.OP_ICP_SUMS_FP64)
+    ctxs, alone, keep = [], [], []
+    K = len(modes)
+    T0s = np.tile(np.eye(4, dtype=np.float32).reshape(16), K).astype(np.float32)
+    T0s[3] = 0.002; T0s[2 * 16 + 7] = -0.001          # different initial poses for contexts 0 and 2
+    for k, sums in enumerate(modes):
+        _, src, _ = room_cloud(first_frame + 2 * k + 1, 4)
+        _, tgt, nrm = room_cloud(first_frame + 2 * k, 4)
+        src = np.ascontiguousarray(src[:0 if k == 1 else len(src) - 1500 * (k % 5)])
+        keep.append((src, tgt, nrm))
+        h = C.c_void_p()
+        L.check(lib.op_icp_create(C.c_void_p(tgt.ctypes.data), C.c_void_p(nrm.ctypes.data), len(tgt), 0.03, L.OP_MEM_HOST, 0, C.byref(h)))
+        ctxs.append(h)
+        L.check(lib.op_icp_set_source(h, C.c_void_p(tgt.ctypes.data if not len(src) else src.ctypes.data), len(src), L.OP_MEM_HOST))
+        L.check(lib.op_icp_set_option(h, L.OP_ICP_OPT_SUMS, sums))
+        r = L.IcpResult()
+        L.check(lib.op_icp_run(h, 1, fp(T0s[16 * k:16 * k + 16].copy()), 10, C.byref(r), None, 0, None, None))
+        alone.append(r)
+    return ctxs, alone, T0s, modes
+
+
+def _same_result(a, b):
+    import struct
+    return (bytes(a.T) == bytes(b.T) and bytes(a.last_T) == bytes(b.last_T) and a.n_inliers == b.n_inliers and a.iterations == b.iterations
+            and struct.pack("d", a.rmse) == struct.pack("d", b.rmse))   # (bit for bit: the empty context's rmse is 0 / 0)
+
+
+def test_run_many_where_the_reference_order_contexts_meet_gives_every_context_the_result_it_gets_alone(hip):
+    """The assertions of test_run_many_gives_every_context_the_result_it_gets_alone on an input that reaches the meeting: ten reference-order point-to-plane
+    contexts (nine is where op_icp_run_many starts to sum them in one launch per round) of different sizes, one of them with an empty source, mixed with two
+    fp64-mode contexts.  Three repetitions; every entry bit-equal to op_icp_run on the same context alone."""
+    import ctypes as C
+    from onepiece_amd import _lib as L
+    lib = L.load()
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    ctxs = []
+    try:
+        ctxs, alone, T0s, modes = _meeting_contexts(lib, L, 500)
+        K = len(ctxs)
+        assert sum(m == L.OP_ICP_SUMS_REFERENCE_F32 for m in modes) >= 9 and alone[1].n_inliers == 0
+        assert all(alone[k].n_inliers > 5000 and alone[k].iterations == 10 for k in range(K) if k != 1)
+        arr = (C.c_void_p * K)(*[c.value for c in ctxs])
+        for rep in range(3):
+            many = (L.IcpResult * K)()
+            L.check(lib.op_icp_run_many(arr, K, 1, fp(T0s), 10, C.cast(many, C.c_void_p)))
+            for k in range(K):
+                assert _same_result(many[k], alone[k]), (rep, k)
+    finally:
+        for h in ctxs:
+            lib.op_icp_destroy(h)
+
+
+def test_two_run_many_calls_at_the_same_time_each_give_their_sequential_results(hip):
+    """Two op_icp_run_many calls of ten reference-order contexts (+ two fp64-mode ones) each, from two threads at the same time on one device: what the
+    other call does must not change a result -- both bit-equal to op_icp_run on every context alone."""
+    import ctypes as C
+    import threading
+    from onepiece_amd import _lib as L
+    lib = L.load()
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    groups = []
+    try:
+        for first in (600, 700):
+            groups.append(_meeting_contexts(lib, L, first))
+        out, rcs = [None, None], [None, None]
+
+        def call(g):
+            ctxs, _alone, T0s, _modes = groups[g]
+            K = len(ctxs)
+            arr = (C.c_void_p * K)(*[c.value for c in ctxs])
+            out[g] = (L.IcpResult * K)()
+            rcs[g] = lib.op_icp_run_many(arr, K, 1, fp(T0s), 10, C.cast(out[g], C.c_void_p))
+
+        threads = [threading.Thread(target=call, args=(g,)) for g in (0, 1)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        assert rcs == [0, 0]
+        for g in (0, 1):
+            for k, a in enumerate(groups[g][1]):
+                assert _same_result(out[g][k], a), (g, k)
+    finally:
+        for ctxs, *_ in groups:
+            for h in ctxs:
+                lib.op_icp_destroy(h)

@@ -379,6 +379,42 @@ def test_pipelined_dense_slam_equals_sequential():
     assert all(np.array_equal(x[1], y[1]) for x, y in zip(seen[1], seen[4]))
 
 
+def test_pipelined_dense_slam_with_the_trackers_summing_together_equals_sequential():
+    """test_pipelined_dense_slam_equals_sequential with OP_RUNTIME_OPT_TRACKER_BATCH_SUMS = 1 and twelve pairs in flight in the reference-order mode (the
+    default): from twelve trackers running at the same time on, their per-iteration sequential sums are taken in one launch (seq_sums.hpp).  Poses, flags and
+    callbacks equal the sequential chain's.  The option is silent: that twelve trackers DID meet in a given round depends on their threads' timing and is not
+    observable from here -- what this pins is that results do not depend on whether they do."""
+    import torch
+    from onepiece_amd import dense_slam as DS, synthetic as S, _lib as L
+    lib = L.load()
+    n = 30
+    dev = torch.device("cuda", 0)
+    depth, rgb, _poses = S.room_sequence_torch(200, n, dev)
+    depth = depth.clone()
+    depth[6] = 0.0                                     # frame 6 cannot be tracked; 7 must be tracked against 5
+    cam = I.PinholeCamera("OPEN3D_DATASET")
+    seen = {1: [], 12: []}
+    runs = {}
+    for p in (1, 12):
+        L.check(lib.op_runtime_set_option(L.OP_RUNTIME_OPT_TRACKER_BATCH_SUMS, 1 if p > 1 else 0))
+        try:
+            slam = DS.DenseSlam(cam, pipeline=p, on_tracked=lambda fid, c, d, T, p=p: seen[p].append((fid, T.copy())))
+            slam.SetSums("reference_f32")
+            for i in range(n):
+                slam.UpdateFrame(rgb[i], depth[i])
+            slam.Finish()
+        finally:
+            L.check(lib.op_runtime_set_option(L.OP_RUNTIME_OPT_TRACKER_BATCH_SUMS, 0))
+        runs[p] = slam
+    a, b = runs[1], runs[12]
+    assert a.tracking_success == b.tracking_success and a.tracking_success[6] is False and all(a.tracking_success[:6]) and all(a.tracking_success[7:])
+    assert a.last_tracking_frame_id == b.last_tracking_frame_id == n - 1
+    for i in range(n):
+        assert np.array_equal(a.global_poses[i], b.global_poses[i]), i
+    assert [f for f, _ in seen[1]] == [f for f, _ in seen[12]] == [i for i in range(n) if i != 6]
+    assert all(np.array_equal(x[1], y[1]) for x, y in zip(seen[1], seen[12]))
+
+
 def test_dense_tracking_odd_image_size(oracle, odo):
     """Odd width/height: pyrDown targets (cols/2, rows/2), so 161x121 -> 80x60 -> 40x30; preparation and tracking
     agree with the oracle there too."""
