@@ -194,12 +194,13 @@ class Odometry:
                                                            iters.ctypes.data_as(L._ip), cs, ct, ps, pt, fs, T0.ctypes.data_as(L._fp),
                                                            int(term_type), ms, 1 if want_point_correspondences else 0))
 
-    def Wait(self, want_correspondences=False):
-        """Second half: synchronise this tracker's stream and return the DenseTrackingResult."""
+    def Wait(self, want_correspondences=False, want_points=True):
+        """Second half: synchronise this tracker's stream and return the DenseTrackingResult.
+        want_points=False returns the pixel pairs alone (the xyz pairs need `want_point_correspondences` at enqueue)."""
         res = L.TrackResult()
         cap = int(self.camera.width) * int(self.camera.height) if want_correspondences else 0
         pix = np.empty((cap, 4), np.int32) if want_correspondences else None
-        pts = np.empty((cap, 6), np.float32) if want_correspondences else None
+        pts = np.empty((cap, 6), np.float32) if want_correspondences and want_points else None
         vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
         L.check(L.load().op_tracker_wait(self._h, C.byref(res), vp(pix), vp(pts), cap))
         self._inflight = None
@@ -211,17 +212,20 @@ class Odometry:
         out.n_correspondences = int(res.n_correspondences)
         if want_correspondences:
             out.pixel_correspondence_set = pix[:out.n_correspondences].copy()
-            out.correspondence_set = pts[:out.n_correspondences].reshape(-1, 2, 3).copy()
+            if pts is not None:
+                out.correspondence_set = pts[:out.n_correspondences].reshape(-1, 2, 3).copy()
         return out
 
     def DenseTracking(self, source_color, target_color, source_depth, target_depth, initial_T=None, term_type=0,
-                      want_correspondences=True):
+                      want_correspondences=True, want_points=True):
         """Odometry::DenseTracking, cv::Mat overload (Odometry.cpp:463-524), end to end on the GPU
         (op_tracker_dense_tracking): image preparation, NormalizeIntensity, pyramids, MultiScaleComputing.
-        colour: (h,w,3) uint8; depth: (h,w) float32 metres or uint16 raw; numpy or CUDA torch tensors."""
+        colour: (h,w,3) uint8; depth: (h,w) float32 metres or uint16 raw; numpy or CUDA torch tensors.
+        want_points=False: pixel pairs without the xyz pairs -- with device-resident frames in the fp64 mode that is the
+        call whose launches are captured once and replayed."""
         self.DenseTrackingEnqueue(source_color, target_color, source_depth, target_depth, initial_T, term_type,
-                                  want_point_correspondences=want_correspondences)
-        return self.Wait(want_correspondences)
+                                  want_point_correspondences=want_correspondences and want_points)
+        return self.Wait(want_correspondences, want_points)
 
     def ReadPyramid(self, frame, kind, level):
         """Image prepared by the last DenseTracking call (frame 0 source / 1 target; kind index into

@@ -110,3 +110,65 @@ def squared_distances(target, q):
     """nanoflann's L2_Simple_Adaptor: ((0 + dx*dx) + dy*dy) + dz*dz in float32."""
     d = q[None, :] - target
     return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+
+
+# ---- raw frames for the dense tracker's image preparation (tests/test_tracker_prep_gpu.py) ----
+PREP_DEPTH_F32_PLANTED = (0.5, float(np.nextafter(np.float32(0.5), np.float32(1))), 4.0, float(np.nextafter(np.float32(4), np.float32(0))),
+                          0.0, -1.0, float("nan"), float("inf"), 3.999)
+
+
+def prep_depth_u16_planted(scale):
+    """Raw values on and next to the validity thresholds 0.5 * scale and 4 * scale, and the ends of the type."""
+    s = int(scale)
+    return tuple(v for v in (s // 2, s // 2 + 1, 4 * s - 1, 4 * s, 0, 65535) if v <= 65535)
+
+
+def prep_color(w, h, seed, special=False):
+    """(h,w,3) uint8, uniform per channel.  special (where the image has room): the eight corner triples of the RGB cube
+    and a run of sixteen triples whose exact grey value 0.299 R + 0.587 G + 0.114 B lies within 0.02 of some k + 0.5,
+    i.e. on the rounding boundary of the fixed-point formula (found by search, in integers: 299 R + 587 G + 114 B mod 1000 in [480, 520])."""
+    rng = np.random.default_rng(seed)
+    img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    if special and w * h >= 64:
+        corners = np.array([[r, g, b] for r in (0, 255) for g in (0, 255) for b in (0, 255)], np.uint8)
+        cand = rng.integers(0, 256, (8192, 3)).astype(np.int64)
+        m = (cand @ np.array([299, 587, 114])) % 1000
+        near = cand[(m >= 480) & (m <= 520)][:16].astype(np.uint8)
+        assert len(near) == 16
+        flat = img.reshape(-1, 3)
+        k0 = (w * h) // 3
+        flat[k0:k0 + 8] = corners
+        flat[k0 + 8:k0 + 24] = near
+    return img
+
+
+def prep_depth(w, h, seed, u16_scale=None):
+    """Depth frame 1.5 m + 1 cm of noise (two such frames pair up under the identity pose: |d_t - d_s| < 0.05 nearly
+    everywhere), float32 metres or, with u16_scale, uint16 raw units.  Planted, where the image can hold them three pixels
+    apart (slots on a 3-pixel grid that keeps two pixels from every border): the values on and next to the validity
+    thresholds, the non-finite and non-positive ones, one 2x2 invalid block and one invalid pixel on each border.  One
+    invalid corner pixel always."""
+    rng = np.random.default_rng(seed)
+    base = 1.5 + 0.01 * rng.standard_normal((h, w))
+    if u16_scale is None:
+        d = base.astype(np.float32)
+        planted = PREP_DEPTH_F32_PLANTED
+    else:
+        d = np.round(base * u16_scale).astype(np.uint16)
+        planted = prep_depth_u16_planted(u16_scale)
+    slots = [(y, x) for y in range(2, h - 2, 3) for x in range(2, w - 2, 3)]
+    d[h - 1, w - 1] = 0
+    if len(slots) >= len(planted) + 1:
+        order = rng.permutation(len(slots) - 1)[:len(planted)]
+        for v, k in zip(planted, order):
+            d[slots[k]] = v
+        y, x = slots[-1]                      # the last slot has no slot to its right or below: the block stays three pixels from the rest
+        d[y:y + 2, x:x + 2] = 0
+        d[0, w // 2] = 0; d[h - 1, w // 3] = 0; d[h // 2, 0] = 0; d[h // 2, w - 1] = 0
+    return d
+
+
+def prep_pair(w, h, seed, u16_scale=None):
+    """(source_color, target_color, source_depth, target_depth); the source colour carries the special triples."""
+    return (prep_color(w, h, 4 * seed, special=True), prep_color(w, h, 4 * seed + 1),
+            prep_depth(w, h, 4 * seed + 2, u16_scale), prep_depth(w, h, 4 * seed + 3, u16_scale))
