@@ -37,7 +37,8 @@ class PointCloud {
     void EstimateNormals(float radius = 0.1, int knn = 30);
     void Transform(const TransformationMatrix& T);
     // one point per occupied grid cell of edge grid_len (floor(p / grid_len)): the mean of the cell's points, colours and
-    // normals, cells in order of first appearance (PointCloud.cpp:145-189)
+    // normals, cells in order of first appearance (PointCloud.cpp:145-189).  op_runtime_set_option(OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, 1)
+    // moves the loop to the device (op_point_cloud_downsample): the same bits
     std::shared_ptr<PointCloud> DownSample(float grid_len) const;
     bool WriteToPLY(const std::string& fileName) const;
     // appends another cloud; refuses (message) when colours / normals would no longer match the points (PointCloud.cpp:49-67)

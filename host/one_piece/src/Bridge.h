@@ -41,6 +41,11 @@ inline bool DeviceGlobalRegistration() {
     long long v = 0;
     return op_runtime_get_option(OP_RUNTIME_OPT_GLOBAL_REGISTRATION, &v) == OP_OK && v == 1;
 }
+// OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE: 1 = PointCloud::DownSample forwards to op_point_cloud_downsample
+inline bool DeviceDownSample() {
+    long long v = 0;
+    return op_runtime_get_option(OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, &v) == OP_OK && v == 1;
+}
 inline const float* Floats(const geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 inline float* Floats(geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 static_assert(sizeof(geometry::Point3) == 3 * sizeof(float), "Point3List must be a contiguous xyz float array");

@@ -85,9 +85,28 @@ void PointCloud::MergePCD(const PointCloud& another_pcd) {
     normals.insert(normals.end(), another_pcd.normals.begin(), another_pcd.normals.end());
 }
 
+// Two paths (OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE): 0 (default) the host loop below; 1 op_point_cloud_downsample, which restates that loop bit for
+// bit on the device and refuses what it cannot key (non-finite or out-of-int cells, a cloud more than 2^21 cells wide): those come back here.
 std::shared_ptr<PointCloud> PointCloud::DownSample(float grid_len) const {
     std::shared_ptr<PointCloud> out = std::make_shared<PointCloud>();
     const bool has_c = HasColors(), has_n = HasNormals();
+    if (bridge::DeviceDownSample() && !points.empty()) {
+        out->points.resize(points.size());
+        if (has_c) out->colors.resize(points.size());
+        if (has_n) out->normals.resize(points.size());
+        size_t n = 0;
+        const int rc = op_point_cloud_downsample(bridge::Floats(points), has_c ? bridge::Floats(colors) : nullptr, has_n ? bridge::Floats(normals) : nullptr, points.size(),
+                                                 grid_len, OP_MEM_HOST, bridge::Device(), bridge::Floats(out->points), has_c ? bridge::Floats(out->colors) : nullptr,
+                                                 has_n ? bridge::Floats(out->normals) : nullptr, &n);
+        if (rc != OP_ERR_INVALID && rc != OP_ERR_CAPACITY) {
+            if (bridge::Failed(rc, "PointCloud::DownSample")) n = 0;
+            out->points.resize(n);
+            if (has_c) out->colors.resize(n);
+            if (has_n) out->normals.resize(n);
+            return out;
+        }
+        out->Reset();
+    }
     std::unordered_map<Point3i, std::pair<size_t, int>, VoxelGridHasher> cells; // cell -> (output index, members)
     for (size_t i = 0; i != points.size(); ++i) {
         const Point3& p = points[i];

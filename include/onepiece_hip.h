@@ -102,6 +102,9 @@ int op_runtime_hw_queues(int *requested);
  *                                         RansacRegistration, geometry::EstimateRigidTransformationRANSAC) runs its host loops, exactly as before the option existed.  1: the
  *                                         same functions forward to op_fpfh_compute / op_feature_match / op_ransac_count_inliers / op_ransac_inlier_ids.  The C-ABI entries
  *                                         themselves do not look at it; op_runtime_get_option lets the class surface read it.
+ *   OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE 0 (default): geometry::PointCloud::DownSample of the class surface runs its host loop, exactly as before the option existed.
+ *                                         1: it forwards to op_point_cloud_downsample (bit-identical), and falls back to the host loop for a cloud the device entry
+ *                                         refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).  Read through op_runtime_get_option like the option above.
  * op_runtime_set_rccl_library(path): the RCCL to bind at the first merge instead of "librccl.so.1" (a site build; the test suite names a
  *   host-memory double that runs several ranks on one device); NULL = the system's.  Fails once RCCL has been bound. */
 #define OP_RUNTIME_OPT_MERGE_ALGORITHM 0
@@ -116,10 +119,11 @@ int op_runtime_hw_queues(int *requested);
 #define OP_RUNTIME_OPT_TRACKER_BATCH_SUMS 9
 #define OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT 10
 #define OP_RUNTIME_OPT_GLOBAL_REGISTRATION 11
+#define OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE 12
 #define OP_MERGE_OWNER_EXCHANGE 0
 #define OP_MERGE_DENSE_REDUCE 1
 int op_runtime_set_option(int option, long long value);
-int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION only: the others are read inside the library */
+int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION and OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE: the others are read inside the library */
 int op_runtime_set_rccl_library(const char *path);
 /* Images that are used more than once -- a frame is tracked against twice and fused once (example/DenseFusion/DenseSlam.cpp:24-33,
  * DenseFusion.cpp:86-96) -- can be brought to the device ONCE and then handed to op_tracker_dense_tracking(_enqueue) /
@@ -546,6 +550,28 @@ int op_points_from_rgbd(const op_camera *cam, const void *depth, int depth_fmt, 
  * undetermined (as in the reference, whose disambiguation is #if 0'd out); < 3 neighbours -> 0. */
 int op_estimate_normals(const float *xyz, size_t n, float radius, int knn, int mem, int device,
                         float *normals_out);
+
+/* ---- voxel-grid down-sampling (Geometry/PointCloud.h, example/DenseFusion/DenseSlam.h) ----
+ * op_point_cloud_downsample == geometry::PointCloud::DownSample (Geometry/PointCloud.cpp:145-189), bit-identical to the host loop of
+ *   host/one_piece/src/PointCloud.cpp: the cell of a point is (int)floorf(p / grid_len) per axis (IEEE float divide); output point j belongs to
+ *   the j-th distinct cell in order of first appearance in the input; each of its values is ((v_i0 + v_i1) + v_i2) + ... in float32 over the
+ *   cell's members i0 < i1 < ... in input order, divided once by (float)count.  colors / normals are carried (same rule) when given.  Every
+ *   array follows `mem`; the outputs need room for n points; *n_out (always host memory) is the number of cells.
+ *   Refused, with nothing written: grid_len not positive and finite, a non-finite coordinate or a cell outside the int range (the host's cast
+ *   is undefined there) -> OP_ERR_INVALID; a cloud more than 2^21 cells wide on an axis (the three axes share one 63-bit sort key) ->
+ *   OP_ERR_CAPACITY.  n == 0 is OP_OK with *n_out = 0.
+ *   The sum of a cell is one chain of adds in member order, by definition: a cloud that falls into ONE cell takes n dependent adds.
+ * op_points_from_rgbd_downsampled == the body of Submap::GenerateSubmapModel's loop (DenseSlam.h:24-28) for one frame without leaving the device:
+ *   points and colours exactly as op_points_from_rgbd produces them (compacted, row-major), then geometry::TransformPoint of the class surface
+ *   (host/one_piece/src/Geometry.cpp:19-23: ((T(r,0) x + T(r,1) y) + T(r,2) z) + T(r,3) 1.0f per row, the first three divided by the fourth), then the down-sampling above.  Colours are
+ *   not transformed.  depth, rgb and the outputs (room for width * height points each) follow `mem`; T and *n_out are always host memory. */
+int op_point_cloud_downsample(const float *xyz, const float *colors /* NULL or n x 3 */, const float *normals /* NULL or n x 3 */,
+                              size_t n, float grid_len, int mem, int device,
+                              float *xyz_out, float *colors_out, float *normals_out /* each n x 3 capacity, same mem */,
+                              size_t *n_out /* always host */);
+int op_points_from_rgbd_downsampled(const op_camera *cam, const void *depth, int depth_fmt, const uint8_t *rgb,
+                                    const float *T /* 16 row-major, NULL = no transform */, float grid_len,
+                                    int mem, int device, float *xyz_out, float *colors_out /* width*height x 3 capacity */, size_t *n_out);
 
 /* ---- global registration (Registration/3DFeature.h, GlobalRegistration.h, Geometry/Ransac.h) ----
  * The device counterparts of the three dense loops of submap registration; each restates the host loop of host/one_piece/src operation by

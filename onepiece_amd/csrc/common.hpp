@@ -30,6 +30,7 @@ struct RuntimeOptions {
     std::atomic<int> tracker_batch_sums{0};            // OP_RUNTIME_OPT_TRACKER_BATCH_SUMS: 1 = twelve or more reference-order trackers running at the same time sum in one launch per round (measured: no gain, off by default)
     std::atomic<int> icp_many_in_flight{4};            // OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT: iterations op_icp_run_many keeps enqueued at a time over its fp64-mode contexts
     std::atomic<int> global_registration{0};           // OP_RUNTIME_OPT_GLOBAL_REGISTRATION: read by the class surface (op_runtime_get_option); 1 = its global registration runs on the device
+    std::atomic<int> point_cloud_downsample{0};        // OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE: read by the class surface likewise; 1 = PointCloud::DownSample runs on the device
     std::atomic<long long> merge_fault{0};             // TEST HOOK (OP_RUNTIME_OPT_MERGE_FAULT): stage * 1024 + rank + 1 -- that rank's allocation of that merge stage "fails"; 0 = off
     std::atomic<long long> cache_device_bytes{32ll << 30}; // released device buffers kept for reuse, per device (buffer cache below); 0 = keep none
 };
@@ -225,6 +226,51 @@ inline void release_cached_memory() {
     for (hipStream_t s : st) (void)hipStreamDestroy(s);
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
 }
+
+// device buffers of one call: inputs in OP_MEM_HOST are copied in, OP_MEM_DEVICE inputs are used in place; everything allocated here goes back
+// to the buffer cache when the call ends
+struct Scope {
+    std::vector<void*> owned;
+    hipStream_t stream = nullptr;
+    int device = 0;
+    ~Scope() {
+        if (stream) { (void)hipStreamSynchronize(stream); op::release_stream(stream, device); }
+        for (void* p : owned) op::cached_free(p);
+    }
+    int open(int dev) {
+        OP_TRY(op::use_device(dev));
+        device = dev;
+        OP_HIP(op::cached_stream(&stream));
+        return OP_OK;
+    }
+    template <class T> int alloc(T** out, size_t count) {
+        void* p = nullptr;
+        OP_HIP(op::cached_malloc(&p, count * sizeof(T)));
+        owned.push_back(p);
+        *out = static_cast<T*>(p);
+        return OP_OK;
+    }
+    template <class T> int input(const T* src, size_t count, int mem, const T** out) {
+        if (mem == OP_MEM_DEVICE) { *out = src; return OP_OK; }
+        T* d = nullptr;
+        OP_TRY(alloc(&d, count));
+        if (count) OP_HIP(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice)); // blocking: the caller's buffer is free on return
+        *out = d;
+        return OP_OK;
+    }
+    template <class T> int upload(const std::vector<T>& v, T** out) {
+        OP_TRY(alloc(out, v.size()));
+        if (!v.empty()) OP_HIP(hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return OP_OK;
+    }
+    template <class T> int output(T* dst, const T* d_src, size_t count, int mem) {
+        if (count) OP_HIP(hipMemcpyAsync(dst, d_src, count * sizeof(T), mem == OP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+        OP_HIP(hipStreamSynchronize(stream));
+        return OP_OK;
+    }
+};
+
+inline int check_mem(int mem) { return mem == OP_MEM_HOST || mem == OP_MEM_DEVICE ? OP_OK : fail(OP_ERR_INVALID, "mem must be OP_MEM_HOST or OP_MEM_DEVICE"); }
 
 constexpr int kWave = 64; // gfx950 wavefront width
 

@@ -299,50 +299,8 @@ __global__ __launch_bounds__(kRiThreads) void k_ransac_inlier_ids(const float* _
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
 
-// device buffers of one call: inputs in OP_MEM_HOST are copied in, OP_MEM_DEVICE inputs are used in place; everything allocated here goes back
-// to the buffer cache when the call ends
-struct Scope {
-    std::vector<void*> owned;
-    hipStream_t stream = nullptr;
-    int device = 0;
-    ~Scope() {
-        if (stream) { (void)hipStreamSynchronize(stream); op::release_stream(stream, device); }
-        for (void* p : owned) op::cached_free(p);
-    }
-    int open(int dev) {
-        OP_TRY(op::use_device(dev));
-        device = dev;
-        OP_HIP(op::cached_stream(&stream));
-        return OP_OK;
-    }
-    template <class T> int alloc(T** out, size_t count) {
-        void* p = nullptr;
-        OP_HIP(op::cached_malloc(&p, count * sizeof(T)));
-        owned.push_back(p);
-        *out = static_cast<T*>(p);
-        return OP_OK;
-    }
-    template <class T> int input(const T* src, size_t count, int mem, const T** out) {
-        if (mem == OP_MEM_DEVICE) { *out = src; return OP_OK; }
-        T* d = nullptr;
-        OP_TRY(alloc(&d, count));
-        if (count) OP_HIP(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice)); // blocking: the caller's buffer is free on return
-        *out = d;
-        return OP_OK;
-    }
-    template <class T> int upload(const std::vector<T>& v, T** out) {
-        OP_TRY(alloc(out, v.size()));
-        if (!v.empty()) OP_HIP(hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-        return OP_OK;
-    }
-    template <class T> int output(T* dst, const T* d_src, size_t count, int mem) {
-        if (count) OP_HIP(hipMemcpyAsync(dst, d_src, count * sizeof(T), mem == OP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-        OP_HIP(hipStreamSynchronize(stream));
-        return OP_OK;
-    }
-};
-
-inline int check_mem(int mem) { return mem == OP_MEM_HOST || mem == OP_MEM_DEVICE ? OP_OK : fail(OP_ERR_INVALID, "mem must be OP_MEM_HOST or OP_MEM_DEVICE"); }
+using op::Scope;      // the device buffers of one call (common.hpp)
+using op::check_mem;
 
 } // namespace
 

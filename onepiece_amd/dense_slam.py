@@ -5,7 +5,9 @@ tracked frame, current frame, Identity)` and the pose chaining of DenseSlam.cpp:
 Not mirrored: submap models, the RANSAC sampler and FastBA (`RegisterSubmap`, `Optimize`) -- they only touch
 the poses every `step` frames; without them the trajectory is pure frame-to-frame odometry, which is what this
 module reports.  The dense parts of the submap registration do have mirrors: registration.ComputeFPFHFeature,
-FeatureMatching3D and CountInliersRANSAC (op_fpfh_compute, op_feature_match, op_ransac_count_inliers).
+FeatureMatching3D and CountInliersRANSAC (op_fpfh_compute, op_feature_match, op_ransac_count_inliers); so do the dense parts of the submap
+model (Submap::GenerateSubmapModel): registration.PointCloud.DownSample (op_point_cloud_downsample) and, for a frame's LoadFromRGBD +
+Transform + DownSample in one call, registration.LoadFromRGBDDownSampled (op_points_from_rgbd_downsampled).
 The tracking itself runs inside libonepiece_hip.so (op_tracker_dense_tracking).
 """
 import numpy as np

@@ -49,6 +49,53 @@ class PointCloud:
         L.check(L.load().op_points_from_depth(C.byref(camera), p, fmt, mem, device, C.c_void_p(xyz.ctypes.data), C.byref(n)))
         return PointCloud(xyz[:n.value].copy())
 
+    def DownSample(self, grid_len, colors=None, device=0):
+        """PointCloud::DownSample (Geometry/PointCloud.cpp:145-189) on the GPU -> (PointCloud, colors or None): one point per occupied
+        cell floor(p / grid_len), cells in order of first appearance, each value the in-order float32 sum of the cell's members over their
+        number -- the bits of the class surface's host loop.  Normals are carried when the cloud has them."""
+        xyz, col, nrm = DownSampleArrays(self.points, colors, self.normals if self.HasNormals() else None, grid_len, device)
+        return PointCloud(xyz, nrm), col
+
+
+def DownSampleArrays(points, colors, normals, grid_len, device=0):
+    """op_point_cloud_downsample over [n,3] float32 arrays, all numpy (host memory) or all CUDA torch tensors (device memory, nothing but
+    the count comes back) -> (points, colors or None, normals or None) of the same kind."""
+    on_device = not isinstance(points, np.ndarray)
+    if on_device:
+        import torch
+        prep = lambda a: None if a is None else L.torch_ready(a.to(torch.float32).contiguous().reshape(-1, 3))
+        ptr = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+        like = lambda a: None if a is None else torch.empty_like(a)
+    else:
+        prep = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        like = lambda a: None if a is None else np.empty_like(a)
+    ins = [prep(a) for a in (points, colors, normals)]
+    if any(a is not None and len(a) != len(ins[0]) for a in ins):
+        raise ValueError("colors and normals must pair up with the points")
+    outs = [like(a) for a in ins]
+    n = C.c_size_t(0)
+    L.check(L.load().op_point_cloud_downsample(ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), len(ins[0]), float(grid_len), L.OP_MEM_DEVICE if on_device else L.OP_MEM_HOST,
+                                               device, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), C.byref(n)))
+    return tuple(None if a is None else (a[:n.value].clone() if on_device else a[:n.value].copy()) for a in outs)
+
+
+def LoadFromRGBDDownSampled(rgb, depth, camera, T=None, grid_len=0.025, device=0):
+    """LoadFromRGBD + Transform(T) + DownSample(grid_len) of one frame without leaving the device -- the body of
+    Submap::GenerateSubmapModel's loop (DenseSlam.h:24-28) -> (PointCloud, colors [m,3]).  T: 4x4 or None (no transform)."""
+    from .integration import _image_arg
+    p, fmt, mem, _k0 = _image_arg(depth, "depth")
+    c, _, memc, _k1 = _image_arg(rgb, "rgb")
+    if mem != L.OP_MEM_HOST or memc != L.OP_MEM_HOST:
+        raise ValueError("LoadFromRGBDDownSampled mirror takes host images")
+    T16 = None if T is None else np.ascontiguousarray(T, np.float32).reshape(16)
+    npix = camera.width * camera.height
+    xyz, col = np.empty((npix, 3), np.float32), np.empty((npix, 3), np.float32)
+    n = C.c_size_t(0)
+    L.check(L.load().op_points_from_rgbd_downsampled(C.byref(camera), p, fmt, c, None if T16 is None else C.c_void_p(T16.ctypes.data), float(grid_len), mem, device,
+                                                     C.c_void_p(xyz.ctypes.data), C.c_void_p(col.ctypes.data), C.byref(n)))
+    return PointCloud(xyz[:n.value].copy()), col[:n.value].copy()
+
 
 def LoadFromRGBD(rgb, depth, camera, device=0):
     """PointCloud::LoadFromRGBD (Geometry/PointCloud.cpp:17-48) on the GPU -> (PointCloud, colors [n,3])."""
