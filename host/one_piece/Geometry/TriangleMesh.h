@@ -32,7 +32,8 @@ class TriangleMesh {
     // concatenation with re-based triangle indices (TriangleMesh.cpp:72-94)
     void LoadFromMeshes(const std::vector<TriangleMesh>& meshes);
     // vertex clustering on a grid of edge grid_len: the corners of all triangles that fall into one cell collapse onto
-    // the mean of those corner positions, triangles with two corners in one cell disappear (MeshSimplification.cpp:579-657)
+    // the mean of those corner positions, triangles with two corners in one cell disappear (MeshSimplification.cpp:579-657).
+    // op_runtime_set_option(OP_RUNTIME_OPT_MESH_CLUSTERING, 1) moves the loop to the device (op_mesh_cluster_simplify): the same bits
     std::shared_ptr<geometry::TriangleMesh> ClusteringSimplify(float grid_len) const;
     // drops every edge-connected component with at most min_points vertices (MeshSimplification.cpp:658-740)
     std::shared_ptr<geometry::TriangleMesh> Prune(size_t min_points) const;

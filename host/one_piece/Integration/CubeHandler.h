@@ -123,6 +123,10 @@ class CubeHandler {
     void AddTransformedCube(const VoxelCube& v_cube, const geometry::TransformationMatrix& trans);
     void AddTransformedCubeNearest(const VoxelCube& v_cube, const geometry::TransformationMatrix& trans);
     void ExtractTriangleMesh(geometry::TriangleMesh& mesh);
+    // equals ExtractTriangleMesh(mesh) followed by mesh = *mesh.ClusteringSimplify(grid_len), bit for bit -- the tail of the reference's fusion
+    // drivers (example/DenseFusion/DenseFusion.cpp:104-105) in one device call (op_volume_extract_mesh_clustered): the triangle soup never reaches
+    // the host.  Not in the reference.  What the device entry refuses (a grid_len that is not positive, a mesh too wide to key) takes the two calls.
+    void ExtractSimplifiedTriangleMesh(geometry::TriangleMesh& mesh, float grid_len);
     void GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh);
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;

@@ -46,9 +46,17 @@ inline bool DeviceDownSample() {
     long long v = 0;
     return op_runtime_get_option(OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, &v) == OP_OK && v == 1;
 }
+// OP_RUNTIME_OPT_MESH_CLUSTERING: 1 = TriangleMesh::ClusteringSimplify forwards to op_mesh_cluster_simplify
+inline bool DeviceMeshClustering() {
+    long long v = 0;
+    return op_runtime_get_option(OP_RUNTIME_OPT_MESH_CLUSTERING, &v) == OP_OK && v == 1;
+}
 inline const float* Floats(const geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 inline float* Floats(geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 static_assert(sizeof(geometry::Point3) == 3 * sizeof(float), "Point3List must be a contiguous xyz float array");
+inline const uint32_t* Indices(const geometry::Point3uiList& v) { return v.empty() ? nullptr : v[0].data(); }
+inline uint32_t* Indices(geometry::Point3uiList& v) { return v.empty() ? nullptr : v[0].data(); }
+static_assert(sizeof(geometry::Point3ui) == 3 * sizeof(uint32_t), "Point3uiList must be a contiguous index array");
 
 } // namespace bridge
 } // namespace one_piece

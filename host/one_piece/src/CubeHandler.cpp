@@ -319,6 +319,36 @@ void CubeHandler::ExtractTriangleMesh(geometry::TriangleMesh& mesh) {
     AppendMesh(vol, nullptr, mesh, "ExtractTriangleMesh");
     std::cout << BLUE << "[ExtractTriangleMesh]::[INFO]::Finish Extracting Mesh, " << mesh.triangles.size() << " triangles." << RESET << std::endl;
 }
+void CubeHandler::ExtractSimplifiedTriangleMesh(geometry::TriangleMesh& mesh, float grid_len) {
+    mesh.Reset();
+    Pending();
+    if (!vol) return;
+    const int *tri = nullptr, *edges = nullptr;
+    GetMarchingCubeTables(&tri, &edges);
+    size_t nv = 0, nt = 0; // the sizing call returns upper bounds (the soup's sizes), the filling call the true sizes
+    int rc = op_volume_extract_mesh_clustered(vol, tri, edges, nullptr, grid_len, nullptr, nullptr, 0, nullptr, 0, &nv, &nt);
+    if (rc == OP_OK && nt > 0) {
+        mesh.points.resize(nv);
+        mesh.colors.resize(nv);
+        mesh.triangles.resize(nt);
+        rc = op_volume_extract_mesh_clustered(vol, tri, edges, nullptr, grid_len, bridge::Floats(mesh.points), bridge::Floats(mesh.colors), nv, bridge::Indices(mesh.triangles), nt,
+                                              &nv, &nt);
+        if (rc != OP_OK) nv = nt = 0;
+        mesh.points.resize(nv);
+        mesh.colors.resize(nv);
+        mesh.triangles.resize(nt);
+    }
+    if (rc == OP_ERR_INVALID || rc == OP_ERR_CAPACITY) {
+        // Refused: the two calls this one stands for (ExtractTriangleMesh prints its own line).  A grid_len that is not positive is refused before any
+        // kernel runs; a mesh too wide to key has by then cost the count pass of the sizing call and the count + emit passes and the clustering's
+        // bounds kernel of the filling call, and the volume is extracted once more here -- the price of a rare refusal, not of the usual call.
+        ExtractTriangleMesh(mesh);
+        mesh = *mesh.ClusteringSimplify(grid_len);
+        return;
+    }
+    if (Failed(rc, "ExtractSimplifiedTriangleMesh")) return;
+    std::cout << BLUE << "[ExtractTriangleMesh]::[INFO]::Finish Extracting Mesh, " << mesh.triangles.size() << " triangles after simplification." << RESET << std::endl;
+}
 void CubeHandler::GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh) {
     Pending();
     if (!vol) return;

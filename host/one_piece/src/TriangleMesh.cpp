@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <unordered_map>
 
+#include "Bridge.h"
 #include "MeshIO.h"
 
 namespace one_piece {
@@ -103,11 +104,36 @@ void TriangleMesh::LoadFromMeshes(const std::vector<TriangleMesh>& meshes) {
     }
 }
 
+// Two paths (OP_RUNTIME_OPT_MESH_CLUSTERING): 0 (default) the host loop below; 1 op_mesh_cluster_simplify, which restates that loop and Compact bit for
+// bit on the device and refuses what it cannot key (an index beyond the vertices, non-finite or out-of-int cells, a mesh more than 2^21 cells wide):
+// those come back here.
 std::shared_ptr<geometry::TriangleMesh> TriangleMesh::ClusteringSimplify(float grid_len) const {
     std::shared_ptr<TriangleMesh> out = std::make_shared<TriangleMesh>(*this);
     if (grid_len <= 0) {
         std::cout << RED << "[ClusteringMeshSimplification]::[ERROR]::Grid length cannot be less than 0." << RESET << std::endl;
         return out;
+    }
+    if (bridge::DeviceMeshClustering() && !triangles.empty()) {
+        const bool has_c = HasColors(), has_n = HasNormals();
+        const size_t cap = std::min(points.size(), 3 * triangles.size());
+        TriangleMesh& m = *out; // Compact drops the arrays the mesh does not have in full
+        m.points.resize(cap);
+        m.colors.resize(has_c ? cap : 0);
+        m.normals.resize(has_n ? cap : 0);
+        size_t nv = 0, nt = 0;
+        const int rc = op_mesh_cluster_simplify(bridge::Floats(points), has_c ? bridge::Floats(colors) : nullptr, has_n ? bridge::Floats(normals) : nullptr, points.size(),
+                                                bridge::Indices(triangles), triangles.size(), grid_len, OP_MEM_HOST, bridge::Device(), bridge::Floats(m.points),
+                                                has_c ? bridge::Floats(m.colors) : nullptr, has_n ? bridge::Floats(m.normals) : nullptr, bridge::Indices(m.triangles), &nv, &nt);
+        if (rc != OP_ERR_INVALID && rc != OP_ERR_CAPACITY) {
+            if (bridge::Failed(rc, "TriangleMesh::ClusteringSimplify")) nv = nt = 0;
+            m.points.resize(nv);
+            if (has_c) m.colors.resize(nv);
+            if (has_n) m.normals.resize(nv);
+            m.triangles.resize(nt);
+            std::cout << GREEN << "[ClusteringMeshSimplification]::[INFO]::Simplify done." << RESET << std::endl;
+            return out;
+        }
+        *out = *this;
     }
     struct Cell { unsigned representative; unsigned count; double sum[3]; };
     std::unordered_map<Point3i, Cell, VoxelGridHasher> cells;

@@ -225,5 +225,26 @@ inline int ExtractTriangleMesh(op_volume* vol, const int* tri_table, const int* 
     return OP_OK;
 }
 
+// ExtractTriangleMesh followed by ClusteringSimplify(grid_len) (MeshSimplification.cpp:579-657) in one device call: the triangle soup never reaches
+// the host.  mesh.points / colors / triangles are REPLACED; Point3 / Point3ui must be three contiguous floats / unsigned ints.
+template <class Point3, class Point3ui, class Mesh>
+inline int ExtractSimplifiedTriangleMesh(op_volume* vol, const int* tri_table, const int* edge_pairs, const int* only_block, float grid_len, Mesh& mesh) {
+    static_assert(sizeof(Point3) == 3 * sizeof(float) && sizeof(Point3ui) == 3 * sizeof(uint32_t), "contiguous rows");
+    mesh.points.clear(); mesh.colors.clear(); mesh.triangles.clear();
+    size_t nv = 0, nt = 0;   // upper bounds from the sizing call, the true sizes from the filling one
+    int rc = op_volume_extract_mesh_clustered(vol, tri_table, edge_pairs, only_block, grid_len, nullptr, nullptr, 0, nullptr, 0, &nv, &nt);
+    if (rc != OP_OK || nt == 0) return rc;
+    std::vector<float> p(3 * nv), c(3 * nv);
+    std::vector<uint32_t> t(3 * nt);
+    rc = op_volume_extract_mesh_clustered(vol, tri_table, edge_pairs, only_block, grid_len, p.data(), c.data(), nv, t.data(), nt, &nv, &nt);
+    if (rc != OP_OK) return rc;
+    for (size_t k = 0; k < nv; ++k) {
+        mesh.points.push_back(Point3(p[3 * k], p[3 * k + 1], p[3 * k + 2]));
+        mesh.colors.push_back(Point3(c[3 * k], c[3 * k + 1], c[3 * k + 2]));
+    }
+    for (size_t k = 0; k < nt; ++k) mesh.triangles.push_back(Point3ui(t[3 * k], t[3 * k + 1], t[3 * k + 2]));
+    return OP_OK;
+}
+
 } // namespace hip_shim
 } // namespace one_piece

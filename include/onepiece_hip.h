@@ -105,6 +105,9 @@ int op_runtime_hw_queues(int *requested);
  *   OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE 0 (default): geometry::PointCloud::DownSample of the class surface runs its host loop, exactly as before the option existed.
  *                                         1: it forwards to op_point_cloud_downsample (bit-identical), and falls back to the host loop for a cloud the device entry
  *                                         refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).  Read through op_runtime_get_option like the option above.
+ *   OP_RUNTIME_OPT_MESH_CLUSTERING        0 (default): geometry::TriangleMesh::ClusteringSimplify of the class surface runs its host loop, exactly as before the option existed.
+ *                                         1: it forwards to op_mesh_cluster_simplify (bit-identical), and falls back to the host loop for a mesh the device entry
+ *                                         refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).  Read through op_runtime_get_option like the two options above.
  * op_runtime_set_rccl_library(path): the RCCL to bind at the first merge instead of "librccl.so.1" (a site build; the test suite names a
  *   host-memory double that runs several ranks on one device); NULL = the system's.  Fails once RCCL has been bound. */
 #define OP_RUNTIME_OPT_MERGE_ALGORITHM 0
@@ -120,10 +123,11 @@ int op_runtime_hw_queues(int *requested);
 #define OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT 10
 #define OP_RUNTIME_OPT_GLOBAL_REGISTRATION 11
 #define OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE 12
+#define OP_RUNTIME_OPT_MESH_CLUSTERING 13
 #define OP_MERGE_OWNER_EXCHANGE 0
 #define OP_MERGE_DENSE_REDUCE 1
 int op_runtime_set_option(int option, long long value);
-int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION and OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE: the others are read inside the library */
+int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE and OP_RUNTIME_OPT_MESH_CLUSTERING: the others are read inside the library */
 int op_runtime_set_rccl_library(const char *path);
 /* Images that are used more than once -- a frame is tracked against twice and fused once (example/DenseFusion/DenseSlam.cpp:24-33,
  * DenseFusion.cpp:86-96) -- can be brought to the device ONCE and then handed to op_tracker_dense_tracking(_enqueue) /
@@ -572,6 +576,35 @@ int op_point_cloud_downsample(const float *xyz, const float *colors /* NULL or n
 int op_points_from_rgbd_downsampled(const op_camera *cam, const void *depth, int depth_fmt, const uint8_t *rgb,
                                     const float *T /* 16 row-major, NULL = no transform */, float grid_len,
                                     int mem, int device, float *xyz_out, float *colors_out /* width*height x 3 capacity */, size_t *n_out);
+
+/* ---- clustering mesh simplification (Geometry/TriangleMesh.h, the tail of the fusion drivers) ----
+ * op_mesh_cluster_simplify == geometry::TriangleMesh::ClusteringSimplify (Geometry/MeshSimplification.cpp:579-657), bit-identical to the host loop of
+ *   host/one_piece/src/TriangleMesh.cpp (ClusteringSimplify + Compact).  Corner c = 3 t + k of triangle t is vertex v = triangles[3 t + k] at points[v]; its
+ *   cell is (int)floorf(p / grid_len) per axis (IEEE float divide); cells exist in order of first appearance over the corners.  A cell's representative is the
+ *   vertex of its first corner (also when that corner's triangle is dropped); its position is (float)(sum / (double)count) per axis, sum the double chain
+ *   ((0.0 + p_c0) + p_c1) + ... over ALL its corners in corner order (a vertex shared by m corners counts m times, corners of dropped triangles count).
+ *   Triangle t becomes its three representatives and is dropped when two are equal.  Output vertices are numbered by first appearance among the corners of
+ *   the kept triangles, in order; cells no kept triangle refers to and vertices nothing refers to vanish; colours and normals of an output vertex are its
+ *   representative's own (copied, not averaged).
+ *   Every array follows `mem`; points_out / colors_out / normals_out need room for min(nv, 3 nt) rows, triangles_out for nt; *nv_out and *nt_out are
+ *   always host memory.  nt == 0 is OP_OK with both 0.
+ *   Refused, with nothing written: grid_len not positive and finite, a triangle index >= nv, a non-finite coordinate at a referenced vertex or a cell
+ *   outside the int range -> OP_ERR_INVALID; a mesh more than 2^21 cells wide on an axis (the three axes share one 63-bit sort key), or 3 nt beyond
+ *   32-bit corner indices -> OP_ERR_CAPACITY.
+ *   The sum of a cell is one chain of double adds in corner order, by definition: a mesh that falls into ONE cell takes 3 nt dependent adds.
+ * op_volume_extract_mesh_clustered == CubeHandler::ExtractTriangleMesh (Integration/CubeHandler.cpp:9-44) followed by ClusteringSimplify(grid_len)
+ *   (MeshSimplification.cpp:579-657) without the triangle soup leaving the device: the count and emit passes of op_volume_extract_mesh into device
+ *   buffers, the simplification above on that soup (triangles[c] = c, colours carried), only the simplified mesh copied out (host memory).
+ *   Sizes: a call with points, colors or triangles NULL returns UPPER BOUNDS in *n_vertices / *n_triangles -- the soup's own vertex and triangle counts
+ *   (the exact sizes would take the whole pipeline) -- and writes nothing; the filling call returns the TRUE sizes.  Buffers smaller than the true
+ *   sizes -> OP_ERR_CAPACITY with nothing written and the true sizes in the counts.  Other refusals as above (counts 0). */
+int op_mesh_cluster_simplify(const float *points, const float *colors /* NULL or nv x 3 */, const float *normals /* NULL or nv x 3 */, size_t nv,
+                             const uint32_t *triangles /* nt x 3 */, size_t nt, float grid_len, int mem, int device,
+                             float *points_out, float *colors_out, float *normals_out /* each min(nv, 3 nt) x 3 capacity, same mem */,
+                             uint32_t *triangles_out /* nt x 3 capacity, same mem */, size_t *nv_out, size_t *nt_out /* always host */);
+int op_volume_extract_mesh_clustered(op_volume *v, const int32_t *tri_table, const int32_t *edge_pairs, const int32_t *only_block, float grid_len,
+                                     float *points, float *colors, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles,
+                                     size_t *n_vertices, size_t *n_triangles);
 
 /* ---- global registration (Registration/3DFeature.h, GlobalRegistration.h, Geometry/Ransac.h) ----
  * The device counterparts of the three dense loops of submap registration; each restates the host loop of host/one_piece/src operation by

@@ -24,6 +24,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "cell_keys.hpp"
 #include "common.hpp"
 
 namespace {
@@ -32,50 +33,18 @@ using op::check_mem;
 using op::fail;
 using op::Scope;
 
-constexpr int kThreads = 256;
-constexpr int kAxisBits = 21;   // widest extent of one axis, in cells: 3 x 21 = 63 key bits
-constexpr unsigned kBadPoint = 1u;
+using op::cells::blocks_for;
+using op::cells::Bounds;
+using op::cells::cell_of;
+using op::cells::check_grid_len;
+using op::cells::kBadPoint;
+using op::cells::KeyLayout;
+using op::cells::kThreads;
+using op::cells::load_points;
 constexpr int kSumAhead = 8;   // members whose loads k_ds_sum issues before it adds them
-
-// The 7 words the host reads back after k_ds_bounds.
-struct Bounds { unsigned error; int lo[3]; int hi[3]; };
-
-// (int)floorf(p / grid_len): what PointCloud.cpp:94 computes.  ok = the host's cast is defined (finite, inside int).
-__device__ inline int cell_of(float p, float grid_len, bool& ok) {
-    const float f = floorf(p / grid_len);
-    ok = ok && f >= -2147483648.0f && f < 2147483648.0f; // false for NaN; an infinite p gives an infinite f
-    return ok ? (int)f : 0;
-}
-
-// A workgroup's 3 * kThreads consecutive floats -> one point per thread.  The loads are consecutive dwords per lane (a 12-byte read per lane
-// would touch three cache lines a wave-instruction); the LDS reads have stride 3, which is odd: no bank conflict.
-__device__ inline void load_points(const float* __restrict__ xyz, size_t n, float (&tile)[3 * kThreads], float& x, float& y, float& z) {
-    const size_t base = (size_t)blockIdx.x * kThreads * 3, end = n * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const size_t e = base + (size_t)k * kThreads + threadIdx.x;
-        tile[k * kThreads + threadIdx.x] = e < end ? xyz[e] : 0.0f;
-    }
-    __syncthreads();
-    x = tile[3 * threadIdx.x]; y = tile[3 * threadIdx.x + 1]; z = tile[3 * threadIdx.x + 2];
-}
-
-__device__ inline int wave_min(int v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = min(v, __shfl_xor(v, m, op::kWave));
-    return v;
-}
-__device__ inline int wave_max(int v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m, op::kWave));
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void k_ds_bounds(const float* __restrict__ xyz, size_t n, float grid_len, Bounds* __restrict__ bounds) {
     __shared__ float tile[3 * kThreads];
-    __shared__ int part[kThreads / op::kWave][6];
-    __shared__ unsigned bad_any;
-    if (threadIdx.x == 0) bad_any = 0u;
     float p[3];
     load_points(xyz, n, tile, p[0], p[1], p[2]);
     const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
@@ -83,24 +52,8 @@ __global__ __launch_bounds__(kThreads) void k_ds_bounds(const float* __restrict_
     int c[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = cell_of(p[k], grid_len, ok);
-    const bool mine = i < n && ok;
-    if (i < n && !ok) atomicOr(&bad_any, kBadPoint);
-    const int lane = threadIdx.x & (op::kWave - 1), wave = threadIdx.x / op::kWave;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int lo = wave_min(mine ? c[k] : INT_MAX), hi = wave_max(mine ? c[k] : INT_MIN);
-        if (lane == 0) { part[wave][k] = lo; part[wave][3 + k] = hi; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        int v = part[0][threadIdx.x];
-        for (int w = 1; w < kThreads / op::kWave; ++w) v = threadIdx.x < 3 ? min(v, part[w][threadIdx.x]) : max(v, part[w][threadIdx.x]);
-        if (threadIdx.x < 3) atomicMin(&bounds->lo[threadIdx.x], v); else atomicMax(&bounds->hi[threadIdx.x - 3], v);
-    }
-    if (threadIdx.x == 0 && bad_any) atomicOr(&bounds->error, bad_any);
+    op::cells::fold_bounds(i < n && ok, c, i < n && !ok ? kBadPoint : 0u, bounds);
 }
-
-struct KeyLayout { int lo[3]; int shift[3]; }; // key = sum over the axes of (cell - lo) << shift
 
 __global__ __launch_bounds__(kThreads) void k_ds_keys(const float* __restrict__ xyz, size_t n, float grid_len, KeyLayout layout,
                                                       unsigned long long* __restrict__ keys, unsigned* __restrict__ index) {
@@ -109,12 +62,7 @@ __global__ __launch_bounds__(kThreads) void k_ds_keys(const float* __restrict__ 
     load_points(xyz, n, tile, p[0], p[1], p[2]);
     const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
-    bool ok = true;
-    unsigned long long key = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) // every point passed k_ds_bounds: 0 <= cell - lo < 2^21, formed in 64 bits (the difference of two ints)
-        key |= (unsigned long long)((long long)cell_of(p[k], grid_len, ok) - (long long)layout.lo[k]) << layout.shift[k];
-    keys[i] = key;
+    keys[i] = op::cells::pack_key(p, grid_len, layout);
     index[i] = (unsigned)i;
 }
 
@@ -187,15 +135,6 @@ __global__ __launch_bounds__(kThreads) void k_ds_transform(float* __restrict__ x
     }
 }
 
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-// bits that hold 0 .. extent - 1
-inline int bits_for(long long extent) {
-    int b = 0;
-    while ((1ll << b) < extent) ++b;
-    return b;
-}
-
 // The down-sampling proper, on device arrays (d_colors / d_normals may be null); the outputs follow `mem`.
 int downsample_device(Scope& s, const float* d_xyz, const float* d_colors, const float* d_normals, size_t n, float grid_len, int mem, float* xyz_out,
                       float* colors_out, float* normals_out, size_t* n_out) {
@@ -211,16 +150,7 @@ int downsample_device(Scope& s, const float* d_xyz, const float* d_colors, const
         return fail(OP_ERR_INVALID, "a coordinate is not finite, or its cell at grid_len %g is outside the int range", (double)grid_len);
     KeyLayout layout;
     int total_bits = 0;
-    for (int k = 2; k >= 0; --k) { // z lowest, as the library's other packed cell keys
-        const long long extent = (long long)bounds.hi[k] - (long long)bounds.lo[k] + 1;
-        if (extent > (1ll << kAxisBits))
-            return fail(OP_ERR_CAPACITY, "the cloud spans %lld cells of %g on axis %d (cells %d .. %d): more than the 2^%d a packed key holds", extent,
-                        (double)grid_len, k, bounds.lo[k], bounds.hi[k], kAxisBits);
-        layout.lo[k] = bounds.lo[k];
-        layout.shift[k] = total_bits;
-        total_bits += bits_for(extent);
-    }
-    if (total_bits < 1) total_bits = 1; // one cell: a one-bit sort of equal keys
+    OP_TRY(op::cells::key_layout(bounds, grid_len, "cloud", &layout, &total_bits));
 
     unsigned long long *d_keys = nullptr, *d_keys_sorted = nullptr;
     unsigned *d_index = nullptr, *d_index_sorted = nullptr, *d_flag = nullptr, *d_slot = nullptr, *d_start = nullptr;
@@ -266,10 +196,6 @@ int downsample_device(Scope& s, const float* d_xyz, const float* d_colors, const
     OP_HIP(hipStreamSynchronize(s.stream));
     *n_out = cells;
     return OP_OK;
-}
-
-inline int check_grid_len(float grid_len) {
-    return grid_len > 0.0f && std::isfinite(grid_len) ? OP_OK : fail(OP_ERR_INVALID, "grid_len must be positive and finite (got %g)", (double)grid_len);
 }
 
 } // namespace

@@ -801,9 +801,13 @@ int op_volume_point_cloud(op_volume* v, float* xyz, float* colors, size_t cap, s
 }
 
 
-int op_volume_extract_mesh(op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, float* points,
-                           float* colors, size_t cap_vertices, size_t* n_vertices) {
-    OP_VOL(v);
+} // extern "C"
+
+// The count and emit passes of k_mesh into device buffers: *d_pts / *d_col (three unshared vertices per triangle; the caller returns them with
+// op::cached_free) when `emit` and the soup has at most cap_vertices vertices, the vertex count alone otherwise.  Complete on return (the volume's
+// stream is synchronised).
+int opv::vol_mesh_soup(op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, bool emit, size_t cap_vertices, float** d_pts_out,
+                       float** d_col_out, size_t* n_vertices) {
     if (!tri_table || !edge_pairs || !n_vertices) return fail(OP_ERR_INVALID, "null argument");
     for (int c = 0; c < 256; ++c)
         for (int i = 0; i < 16; ++i) {
@@ -858,7 +862,7 @@ int op_volume_extract_mesh(op_volume* v, const int32_t* tri_table, const int32_t
     }
     const size_t total = total_tri * 3;
     *n_vertices = total;
-    if (e == hipSuccess && points && colors && total) {
+    if (e == hipSuccess && emit && total) {
         if (total > cap_vertices) rc = fail(OP_ERR_CAPACITY, "mesh has %zu vertices, buffer holds %zu", total, cap_vertices);
         else if (total_tri > 0xffffffffull / 3) rc = fail(OP_ERR_CAPACITY, "mesh too large");
         else {
@@ -870,15 +874,37 @@ int op_volume_extract_mesh(op_volume* v, const int32_t* tri_table, const int32_t
                                    (const unsigned*)d_list, (const int*)d_nbs, (unsigned*)nullptr, (const unsigned*)d_offsets, d_pts, d_col);
                 e = hipStreamSynchronize(v->stream);
             }
-            if (e == hipSuccess) e = hipMemcpy(points, d_pts, total * 12, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(colors, d_col, total * 12, hipMemcpyDeviceToHost);
         }
     }
-    void* ptrs[] = {d_list, d_counts, d_offsets, d_tri, d_edge, d_nbs, d_pts, d_col};
+    void* ptrs[] = {d_list, d_counts, d_offsets, d_tri, d_edge, d_nbs};
     for (void* p : ptrs)
         if (p) op::cached_free(p);
+    if (e != hipSuccess || rc != OP_OK) {
+        if (d_pts) op::cached_free(d_pts);
+        if (d_col) op::cached_free(d_col);
+        return e != hipSuccess ? fail(OP_ERR_HIP, "mesh extraction failed: %s", hipGetErrorString(e)) : rc;
+    }
+    *d_pts_out = d_pts;
+    *d_col_out = d_col;
+    return OP_OK;
+}
+
+extern "C" {
+
+int op_volume_extract_mesh(op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, float* points,
+                           float* colors, size_t cap_vertices, size_t* n_vertices) {
+    OP_VOL(v);
+    float *d_pts = nullptr, *d_col = nullptr;
+    OP_TRY(vol_mesh_soup(v, tri_table, edge_pairs, only_block, points && colors, cap_vertices, &d_pts, &d_col, n_vertices));
+    hipError_t e = hipSuccess;
+    if (d_pts && d_col) {
+        e = hipMemcpy(points, d_pts, *n_vertices * 12, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(colors, d_col, *n_vertices * 12, hipMemcpyDeviceToHost);
+    }
+    if (d_pts) op::cached_free(d_pts);
+    if (d_col) op::cached_free(d_col);
     if (e != hipSuccess) return fail(OP_ERR_HIP, "mesh extraction failed: %s", hipGetErrorString(e));
-    return rc;
+    return OP_OK;
 }
 
 int op_volume_write_file(op_volume* v, const char* path) {

@@ -358,6 +358,23 @@ class CubeHandler:
             L.check(self._lib.op_volume_extract_mesh(self._h, _ip(tt), _ip(ep), obp, _fp(pts), _fp(col), n.value, C.byref(n)))
         return pts[:n.value].copy(), col[:n.value].copy()
 
+    def ExtractSimplifiedTriangleMesh(self, tri_table, edge_pairs, grid_len, only_block=None):
+        """ExtractTriangleMesh followed by TriangleMesh::ClusteringSimplify(grid_len) (MeshSimplification.cpp:579-657) in one device call
+        (op_volume_extract_mesh_clustered): the triangle soup never leaves the device -> (points [m,3], colors [m,3], triangles [k,3] uint32),
+        the bits of registration.cluster_simplify over ExtractTriangleMesh's soup."""
+        tt = np.ascontiguousarray(tri_table, np.int32).reshape(256 * 16)
+        ep = np.ascontiguousarray(edge_pairs, np.int32).reshape(24)
+        ob = None if only_block is None else np.ascontiguousarray(only_block, np.int32).reshape(3)
+        obp = None if ob is None else _ip(ob)
+        nv, nt = C.c_size_t(0), C.c_size_t(0)  # upper bounds from the sizing call, the true sizes from the filling one
+        L.check(self._lib.op_volume_extract_mesh_clustered(self._h, _ip(tt), _ip(ep), obp, float(grid_len), None, None, 0, None, 0, C.byref(nv), C.byref(nt)))
+        pts, col = np.empty((max(nv.value, 1), 3), np.float32), np.empty((max(nv.value, 1), 3), np.float32)
+        tri = np.empty((max(nt.value, 1), 3), np.uint32)
+        if nt.value:
+            L.check(self._lib.op_volume_extract_mesh_clustered(self._h, _ip(tt), _ip(ep), obp, float(grid_len), C.c_void_p(pts.ctypes.data), C.c_void_p(col.ctypes.data),
+                                                               nv.value, C.c_void_p(tri.ctypes.data), nt.value, C.byref(nv), C.byref(nt)))
+        return pts[:nv.value].copy(), col[:nv.value].copy(), tri[:nt.value].copy()
+
     def GenerateMeshByCube(self, cube_id, tri_table, edge_pairs):
         """CubeHandler::GenerateMeshByCube (CubeHandler.cpp:70-114) for one block."""
         return self.ExtractTriangleMesh(tri_table, edge_pairs, only_block=cube_id)
