@@ -24,6 +24,7 @@ class TriangleMesh {
     bool LoadFromOBJ(const std::string& filename);
     bool LoadFromFile(const std::string& filename);
     // per vertex: the normalised sum of the unit normals (p2 - p1) x (p3 - p1) of its triangles (TriangleMesh.cpp:95-127)
+    // op_runtime_set_option(OP_RUNTIME_OPT_MESH_POSTPROCESS, 1) moves this loop and Prune's to the device (op_mesh_compute_normals, op_mesh_prune): the same bits
     void ComputeNormals();
     void Transform(const geometry::TransformationMatrix& T);
     bool HasColors() const { return colors.size() == points.size() && colors.size() > 0; }

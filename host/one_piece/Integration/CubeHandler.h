@@ -127,6 +127,11 @@ class CubeHandler {
     // drivers (example/DenseFusion/DenseFusion.cpp:104-105) in one device call (op_volume_extract_mesh_clustered): the triangle soup never reaches
     // the host.  Not in the reference.  What the device entry refuses (a grid_len that is not positive, a mesh too wide to key) takes the two calls.
     void ExtractSimplifiedTriangleMesh(geometry::TriangleMesh& mesh, float grid_len);
+    // equals ExtractTriangleMesh(mesh), then mesh = *mesh.ClusteringSimplify(grid_len) if grid_len > 0, then mesh = *mesh.Prune(min_points) if
+    // min_points > 0, then mesh.ComputeNormals() if compute_normals, bit for bit -- the whole tail of the reference's fusion drivers
+    // (example/MergeMultipleSubmaps.cpp:45-46, ImageIntegration.cpp:45) in one device call (op_volume_extract_mesh_processed): only the finished mesh
+    // reaches the host.  Not in the reference.  What the device entry refuses takes the separate calls.
+    void ExtractProcessedTriangleMesh(geometry::TriangleMesh& mesh, float grid_len, size_t min_points, bool compute_normals);
     void GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh);
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;

@@ -51,6 +51,11 @@ inline bool DeviceMeshClustering() {
     long long v = 0;
     return op_runtime_get_option(OP_RUNTIME_OPT_MESH_CLUSTERING, &v) == OP_OK && v == 1;
 }
+// OP_RUNTIME_OPT_MESH_POSTPROCESS: 1 = TriangleMesh::ComputeNormals and Prune forward to op_mesh_compute_normals / op_mesh_prune
+inline bool DeviceMeshPostprocess() {
+    long long v = 0;
+    return op_runtime_get_option(OP_RUNTIME_OPT_MESH_POSTPROCESS, &v) == OP_OK && v == 1;
+}
 inline const float* Floats(const geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 inline float* Floats(geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 static_assert(sizeof(geometry::Point3) == 3 * sizeof(float), "Point3List must be a contiguous xyz float array");

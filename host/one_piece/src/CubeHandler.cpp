@@ -349,6 +349,37 @@ void CubeHandler::ExtractSimplifiedTriangleMesh(geometry::TriangleMesh& mesh, fl
     if (Failed(rc, "ExtractSimplifiedTriangleMesh")) return;
     std::cout << BLUE << "[ExtractTriangleMesh]::[INFO]::Finish Extracting Mesh, " << mesh.triangles.size() << " triangles after simplification." << RESET << std::endl;
 }
+void CubeHandler::ExtractProcessedTriangleMesh(geometry::TriangleMesh& mesh, float grid_len, size_t min_points, bool compute_normals) {
+    mesh.Reset();
+    Pending();
+    if (!vol) return;
+    const int *tri = nullptr, *edges = nullptr;
+    GetMarchingCubeTables(&tri, &edges);
+    size_t nv = 0, nt = 0; // the sizing call returns upper bounds (the soup's sizes), the filling call the true sizes
+    int rc = op_volume_extract_mesh_processed(vol, tri, edges, nullptr, grid_len, min_points, nullptr, nullptr, nullptr, 0, nullptr, 0, &nv, &nt);
+    if (rc == OP_OK && nt > 0) {
+        mesh.points.resize(nv);
+        mesh.colors.resize(nv);
+        if (compute_normals) mesh.normals.resize(nv);
+        mesh.triangles.resize(nt);
+        rc = op_volume_extract_mesh_processed(vol, tri, edges, nullptr, grid_len, min_points, bridge::Floats(mesh.points), bridge::Floats(mesh.colors),
+                                              compute_normals ? bridge::Floats(mesh.normals) : nullptr, nv, bridge::Indices(mesh.triangles), nt, &nv, &nt);
+        if (rc != OP_OK) nv = nt = 0;
+        mesh.points.resize(nv);
+        mesh.colors.resize(nv);
+        if (compute_normals) mesh.normals.resize(nv);
+        mesh.triangles.resize(nt);
+    }
+    if (rc == OP_ERR_INVALID || rc == OP_ERR_CAPACITY) { // refused: the calls this one stands for (see ExtractSimplifiedTriangleMesh for what that costs)
+        ExtractTriangleMesh(mesh);
+        if (grid_len > 0 || grid_len < 0) mesh = *mesh.ClusteringSimplify(grid_len);
+        if (min_points > 0) mesh = *mesh.Prune(min_points);
+        if (compute_normals) mesh.ComputeNormals();
+        return;
+    }
+    if (Failed(rc, "ExtractProcessedTriangleMesh")) return;
+    std::cout << BLUE << "[ExtractTriangleMesh]::[INFO]::Finish Extracting Mesh, " << mesh.triangles.size() << " triangles after post-processing." << RESET << std::endl;
+}
 void CubeHandler::GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh) {
     Pending();
     if (!vol) return;

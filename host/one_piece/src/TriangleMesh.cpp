@@ -79,8 +79,18 @@ std::shared_ptr<geometry::PointCloud> TriangleMesh::GetPointCloud() const {
     return pcd;
 }
 
+// Two paths (OP_RUNTIME_OPT_MESH_POSTPROCESS): 0 (default) the host loop below; 1 op_mesh_compute_normals, which restates that loop bit for bit on the
+// device and refuses what it cannot take (an index beyond the vertices, a non-finite coordinate at a referenced vertex): those come back here.
 void TriangleMesh::ComputeNormals() {
     normals.assign(points.size(), Point3(0, 0, 0));
+    if (bridge::DeviceMeshPostprocess() && !points.empty()) {
+        const int rc = op_mesh_compute_normals(bridge::Floats(points), points.size(), bridge::Indices(triangles), triangles.size(), OP_MEM_HOST, bridge::Device(),
+                                               bridge::Floats(normals));
+        if (rc != OP_ERR_INVALID && rc != OP_ERR_CAPACITY) {
+            bridge::Failed(rc, "TriangleMesh::ComputeNormals"); // (a refusal writes nothing: the zeros stand)
+            return;
+        }
+    }
     for (size_t t = 0; t < triangles.size(); ++t) {
         const Point3ui& tri = triangles[t];
         Point3 n = Cross(points[tri(1)] - points[tri(0)], points[tri(2)] - points[tri(0)]);
@@ -168,8 +178,31 @@ std::shared_ptr<geometry::TriangleMesh> TriangleMesh::ClusteringSimplify(float g
     return out;
 }
 
+// Two paths (OP_RUNTIME_OPT_MESH_POSTPROCESS), as for ComputeNormals: 1 forwards to op_mesh_prune, which gives the result of the loop and Compact below.
 std::shared_ptr<geometry::TriangleMesh> TriangleMesh::Prune(size_t min_points) const {
     std::shared_ptr<TriangleMesh> out = std::make_shared<TriangleMesh>(*this);
+    if (bridge::DeviceMeshPostprocess() && !triangles.empty()) {
+        const bool has_c = HasColors(), has_n = HasNormals();
+        const size_t cap = std::min(points.size(), 3 * triangles.size());
+        TriangleMesh& m = *out; // Compact drops the arrays the mesh does not have in full
+        m.points.resize(cap);
+        m.colors.resize(has_c ? cap : 0);
+        m.normals.resize(has_n ? cap : 0);
+        size_t nv = 0, nt = 0, pruned = 0;
+        const int rc = op_mesh_prune(bridge::Floats(points), has_c ? bridge::Floats(colors) : nullptr, has_n ? bridge::Floats(normals) : nullptr, points.size(),
+                                     bridge::Indices(triangles), triangles.size(), min_points, OP_MEM_HOST, bridge::Device(), bridge::Floats(m.points),
+                                     has_c ? bridge::Floats(m.colors) : nullptr, has_n ? bridge::Floats(m.normals) : nullptr, bridge::Indices(m.triangles), &nv, &nt, &pruned);
+        if (rc != OP_ERR_INVALID && rc != OP_ERR_CAPACITY) {
+            if (bridge::Failed(rc, "TriangleMesh::Prune")) nv = nt = 0;
+            m.points.resize(nv);
+            if (has_c) m.colors.resize(nv);
+            if (has_n) m.normals.resize(nv);
+            m.triangles.resize(nt);
+            std::cout << GREEN << "[MeshPruning]::[INFO]::Prune mesh done. " << pruned << " points are pruned. " << RESET << std::endl;
+            return out;
+        }
+        *out = *this;
+    }
     // connected components over the triangles' edges: union-find on the vertices
     std::vector<unsigned> parent(points.size());
     for (size_t v = 0; v < parent.size(); ++v) parent[v] = static_cast<unsigned>(v);

@@ -108,6 +108,9 @@ int op_runtime_hw_queues(int *requested);
  *   OP_RUNTIME_OPT_MESH_CLUSTERING        0 (default): geometry::TriangleMesh::ClusteringSimplify of the class surface runs its host loop, exactly as before the option existed.
  *                                         1: it forwards to op_mesh_cluster_simplify (bit-identical), and falls back to the host loop for a mesh the device entry
  *                                         refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).  Read through op_runtime_get_option like the two options above.
+ *   OP_RUNTIME_OPT_MESH_POSTPROCESS       0 (default): geometry::TriangleMesh::ComputeNormals and Prune of the class surface run their host loops, exactly as before the option
+ *                                         existed.  1: they forward to op_mesh_compute_normals / op_mesh_prune (bit-identical), and fall back to the host loop for a mesh the
+ *                                         device entry refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).  Read through op_runtime_get_option like the three options above.
  * op_runtime_set_rccl_library(path): the RCCL to bind at the first merge instead of "librccl.so.1" (a site build; the test suite names a
  *   host-memory double that runs several ranks on one device); NULL = the system's.  Fails once RCCL has been bound. */
 #define OP_RUNTIME_OPT_MERGE_ALGORITHM 0
@@ -124,10 +127,11 @@ int op_runtime_hw_queues(int *requested);
 #define OP_RUNTIME_OPT_GLOBAL_REGISTRATION 11
 #define OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE 12
 #define OP_RUNTIME_OPT_MESH_CLUSTERING 13
+#define OP_RUNTIME_OPT_MESH_POSTPROCESS 14
 #define OP_MERGE_OWNER_EXCHANGE 0
 #define OP_MERGE_DENSE_REDUCE 1
 int op_runtime_set_option(int option, long long value);
-int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE and OP_RUNTIME_OPT_MESH_CLUSTERING: the others are read inside the library */
+int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, OP_RUNTIME_OPT_MESH_CLUSTERING and OP_RUNTIME_OPT_MESH_POSTPROCESS: the others are read inside the library */
 int op_runtime_set_rccl_library(const char *path);
 /* Images that are used more than once -- a frame is tracked against twice and fused once (example/DenseFusion/DenseSlam.cpp:24-33,
  * DenseFusion.cpp:86-96) -- can be brought to the device ONCE and then handed to op_tracker_dense_tracking(_enqueue) /
@@ -605,6 +609,41 @@ int op_mesh_cluster_simplify(const float *points, const float *colors /* NULL or
 int op_volume_extract_mesh_clustered(op_volume *v, const int32_t *tri_table, const int32_t *edge_pairs, const int32_t *only_block, float grid_len,
                                      float *points, float *colors, size_t cap_vertices, uint32_t *triangles, size_t cap_triangles,
                                      size_t *n_vertices, size_t *n_triangles);
+
+/* ---- vertex normals and small-component pruning of a mesh (Geometry/TriangleMesh.h, the rest of the fusion drivers' tail) ----
+ * op_mesh_compute_normals == geometry::TriangleMesh::ComputeNormals (Geometry/TriangleMesh.cpp; example/ImageIntegration.cpp:45, MCGenerateMesh.cpp:24,
+ *   MergeMultipleSubmaps.cpp:46), bit-identical to the host loop of host/one_piece/src/TriangleMesh.cpp.  All in float32 without FMA: the face normal of
+ *   triangle t is (p1 - p0) x (p2 - p0), every product rounded before the subtraction, divided by len = sqrtf((n0 n0 + n1 n1) + n2 n2) when len > 0
+ *   (IEEE sqrt and divide).  normals[v] is ((+0 + n_c0) + n_c1) + ... over the corners c = 3 t + k that refer to v, in corner order (a vertex used
+ *   twice by one triangle receives its normal twice), then normalised the same way.  A vertex nothing refers to keeps (0, 0, 0); a -0 component of
+ *   a face normal becomes +0 in the vertex.  Every array follows `mem`; normals_out holds nv rows and is overwritten.  nt == 0 is OP_OK: nv rows of zeros.
+ *   Refused, with nothing written: a triangle index >= nv, a non-finite coordinate at a referenced vertex (elsewhere it is not read) -> OP_ERR_INVALID;
+ *   3 nt beyond 32-bit corner indices -> OP_ERR_CAPACITY.
+ *   The sum of a vertex is one chain of float32 adds in corner order, by definition: a vertex of valence m takes m dependent adds.
+ * op_mesh_prune == geometry::TriangleMesh::Prune (Geometry/TriangleMesh.cpp; example/PruneMesh.cpp:15), the result of the host loop of
+ *   host/one_piece/src/TriangleMesh.cpp (Prune + Compact).  Two vertices are connected when a triangle contains both; the size of a component is its
+ *   number of referenced vertices; a triangle is kept exactly when its component's size is > min_points.  Output vertices are numbered by first appearance
+ *   among the corners of the kept triangles; points, colours and normals are carried; vertices nothing kept refers to vanish.  *pruned_out is the
+ *   number of referenced vertices in dropped components (what Prune prints).  Every array follows `mem`; points_out / colors_out / normals_out need room
+ *   for min(nv, 3 nt) rows, triangles_out for nt; the three counts are always host memory.  nt == 0 is OP_OK with all three 0.
+ *   Refused, with nothing written: a triangle index >= nv -> OP_ERR_INVALID; 3 nt beyond 32-bit corner indices -> OP_ERR_CAPACITY.
+ * op_volume_extract_mesh_processed == CubeHandler::ExtractTriangleMesh (Integration/CubeHandler.cpp:9-44), then ClusteringSimplify(grid_len)
+ *   (MeshSimplification.cpp:579-657) if grid_len > 0, then Prune(min_points) if min_points > 0, then ComputeNormals if `normals` is given -- the tail of
+ *   example/MergeMultipleSubmaps.cpp:45-46 and ImageIntegration.cpp:45 -- all in device buffers; only the finished mesh is copied out (host memory).
+ *   With grid_len == 0 the mesh is the soup, triangles[c] = c.  Sizes as for op_volume_extract_mesh_clustered: a call with points, colors or triangles
+ *   NULL returns UPPER BOUNDS (the soup's sizes) and writes nothing; the filling call returns the TRUE sizes; buffers smaller than those ->
+ *   OP_ERR_CAPACITY with nothing written and the true sizes in the counts.  grid_len negative or not finite -> OP_ERR_INVALID; the refusals of the
+ *   stages pass through (counts 0). */
+int op_mesh_compute_normals(const float *points, size_t nv, const uint32_t *triangles /* nt x 3 */, size_t nt, int mem, int device,
+                            float *normals_out /* nv x 3, same mem */);
+int op_mesh_prune(const float *points, const float *colors /* NULL or nv x 3 */, const float *normals /* NULL or nv x 3 */, size_t nv,
+                  const uint32_t *triangles /* nt x 3 */, size_t nt, size_t min_points, int mem, int device,
+                  float *points_out, float *colors_out, float *normals_out /* each min(nv, 3 nt) x 3 capacity, same mem */,
+                  uint32_t *triangles_out /* nt x 3 capacity, same mem */, size_t *nv_out, size_t *nt_out, size_t *pruned_out /* always host */);
+int op_volume_extract_mesh_processed(op_volume *v, const int32_t *tri_table, const int32_t *edge_pairs, const int32_t *only_block,
+                                     float grid_len /* 0: no clustering */, size_t min_points /* 0: no pruning */,
+                                     float *points, float *colors, float *normals /* NULL: no normals */, size_t cap_vertices,
+                                     uint32_t *triangles, size_t cap_triangles, size_t *n_vertices, size_t *n_triangles);
 
 /* ---- global registration (Registration/3DFeature.h, GlobalRegistration.h, Geometry/Ransac.h) ----
  * The device counterparts of the three dense loops of submap registration; each restates the host loop of host/one_piece/src operation by

@@ -62,6 +62,7 @@ OP_VOLUME_OPT_RAYCAST_PRUNE = 2
 OP_RUNTIME_OPT_MERGE_ALGORITHM, OP_RUNTIME_OPT_MERGE_SLICE_BLOCKS, OP_RUNTIME_OPT_MERGE_FORCE_SINGLE_RANK, OP_RUNTIME_OPT_TRACKER_GRAPH, OP_RUNTIME_OPT_COPY_THREADS, OP_RUNTIME_OPT_CACHE_DEVICE_BYTES, OP_RUNTIME_OPT_MERGE_FAULT, OP_RUNTIME_OPT_ICP_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_BATCH_SUMS, OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT, OP_RUNTIME_OPT_GLOBAL_REGISTRATION = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE = 12
 OP_RUNTIME_OPT_MESH_CLUSTERING = 13
+OP_RUNTIME_OPT_MESH_POSTPROCESS = 14
 OP_MERGE_OWNER_EXCHANGE, OP_MERGE_DENSE_REDUCE = 0, 1
 OP_MEM_HOST, OP_MEM_DEVICE = 0, 1
 OP_ICP_POINT_TO_POINT, OP_ICP_POINT_TO_PLANE = 0, 1
@@ -171,6 +172,9 @@ SIGNATURES = {
     "op_point_cloud_downsample": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _szp]),
     "op_mesh_cluster_simplify": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _szp, _szp]),
     "op_volume_extract_mesh_clustered": (C.c_int, [_vp, _ip, _ip, _ip, C.c_float, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _szp, _szp]),
+    "op_mesh_compute_normals": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
+    "op_mesh_prune": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _szp, _szp, _szp]),
+    "op_volume_extract_mesh_processed": (C.c_int, [_vp, _ip, _ip, _ip, C.c_float, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _szp, _szp]),
     "op_points_from_rgbd_downsampled": (C.c_int, [C.POINTER(Camera), _vp, C.c_int, _vp, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _szp]),
     "op_estimate_rigid_point_to_plane": (C.c_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "op_estimate_rigid_transformation": (C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _fp]),

@@ -33,6 +33,7 @@
 
 #include "cell_keys.hpp"
 #include "common.hpp"
+#include "mesh_ops.hpp"
 #include "volume_core.hpp"
 
 namespace {
@@ -40,6 +41,7 @@ namespace {
 using op::check_mem;
 using op::fail;
 using op::Scope;
+using op::mesh::cluster_device;
 using op::cells::blocks_for;
 using op::cells::Bounds;
 using op::cells::cell_of;
@@ -179,9 +181,11 @@ __global__ __launch_bounds__(kThreads) void k_mc_triangles(const unsigned* __res
     for (int k = 0; k < 3; ++k) triangles_out[3 * o + k] = number_of_segment[segment_of_corner[3 * t + k]];
 }
 
+} // namespace
+
 // The simplification proper, on device arrays (d_colors / d_normals may be null; d_triangles null = a soup, triangle t = vertices 3t .. 3t + 2).
-// The outputs follow `mem` and are written only when both counts fit their capacities.
-int cluster_device(Scope& s, const float* d_xyz, const float* d_colors, const float* d_normals, size_t nv, const unsigned* d_triangles, size_t nt, float grid_len, int mem,
+// The outputs follow `mem` and are written only when both counts fit their capacities.  (Declared in mesh_ops.hpp: mesh_post.hip runs it too.)
+int op::mesh::cluster_device(Scope& s, const float* d_xyz, const float* d_colors, const float* d_normals, size_t nv, const unsigned* d_triangles, size_t nt, float grid_len, int mem,
                    float* xyz_out, float* colors_out, float* normals_out, size_t cap_vertices, unsigned* triangles_out, size_t cap_triangles, size_t* nv_out, size_t* nt_out) {
     const size_t n = 3 * nt;
     Bounds* d_bounds = nullptr;
@@ -282,8 +286,6 @@ int cluster_device(Scope& s, const float* d_xyz, const float* d_colors, const fl
     OP_HIP(hipStreamSynchronize(s.stream));
     return OP_OK;
 }
-
-} // namespace
 
 extern "C" {
 

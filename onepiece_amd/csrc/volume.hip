@@ -697,6 +697,9 @@ int op_runtime_set_option(int option, long long value) {
         case OP_RUNTIME_OPT_MESH_CLUSTERING:
             if (value != 0 && value != 1) return fail(OP_ERR_INVALID, "op_runtime_set_option: mesh clustering path %lld (0 host, 1 device)", value);
             o.mesh_clustering.store((int)value); return OP_OK;
+        case OP_RUNTIME_OPT_MESH_POSTPROCESS:
+            if (value != 0 && value != 1) return fail(OP_ERR_INVALID, "op_runtime_set_option: mesh post-processing path %lld (0 host, 1 device)", value);
+            o.mesh_postprocess.store((int)value); return OP_OK;
         case OP_RUNTIME_OPT_MERGE_FAULT:
             if (value < 0) return fail(OP_ERR_INVALID, "op_runtime_set_option: merge fault %lld", value);
             o.merge_fault.store(value); return OP_OK;
@@ -713,6 +716,7 @@ int op_runtime_get_option(int option, long long* value) {
     if (option == OP_RUNTIME_OPT_GLOBAL_REGISTRATION) { *value = op::runtime_options().global_registration.load(); return OP_OK; }
     if (option == OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE) { *value = op::runtime_options().point_cloud_downsample.load(); return OP_OK; }
     if (option == OP_RUNTIME_OPT_MESH_CLUSTERING) { *value = op::runtime_options().mesh_clustering.load(); return OP_OK; }
+    if (option == OP_RUNTIME_OPT_MESH_POSTPROCESS) { *value = op::runtime_options().mesh_postprocess.load(); return OP_OK; }
     return fail(OP_ERR_INVALID, "op_runtime_get_option: option %d cannot be read", option);
 }
 

@@ -375,6 +375,25 @@ class CubeHandler:
                                                                nv.value, C.c_void_p(tri.ctypes.data), nt.value, C.byref(nv), C.byref(nt)))
         return pts[:nv.value].copy(), col[:nv.value].copy(), tri[:nt.value].copy()
 
+    def ExtractProcessedTriangleMesh(self, tri_table, edge_pairs, grid_len=0.0, min_points=0, compute_normals=False, only_block=None):
+        """ExtractTriangleMesh, then ClusteringSimplify(grid_len) if grid_len > 0, then Prune(min_points) if min_points > 0, then ComputeNormals if asked,
+        in one device call (op_volume_extract_mesh_processed): only the finished mesh leaves the device ->
+        (points [m,3], colors [m,3], normals [m,3] or None, triangles [k,3] uint32)."""
+        tt = np.ascontiguousarray(tri_table, np.int32).reshape(256 * 16)
+        ep = np.ascontiguousarray(edge_pairs, np.int32).reshape(24)
+        ob = None if only_block is None else np.ascontiguousarray(only_block, np.int32).reshape(3)
+        obp = None if ob is None else _ip(ob)
+        nv, nt = C.c_size_t(0), C.c_size_t(0)  # upper bounds from the sizing call, the true sizes from the filling one
+        L.check(self._lib.op_volume_extract_mesh_processed(self._h, _ip(tt), _ip(ep), obp, float(grid_len), int(min_points), None, None, None, 0, None, 0, C.byref(nv), C.byref(nt)))
+        pts, col = np.empty((max(nv.value, 1), 3), np.float32), np.empty((max(nv.value, 1), 3), np.float32)
+        nrm = np.empty((max(nv.value, 1), 3), np.float32) if compute_normals else None
+        tri = np.empty((max(nt.value, 1), 3), np.uint32)
+        if nt.value:
+            L.check(self._lib.op_volume_extract_mesh_processed(self._h, _ip(tt), _ip(ep), obp, float(grid_len), int(min_points), C.c_void_p(pts.ctypes.data),
+                                                               C.c_void_p(col.ctypes.data), None if nrm is None else C.c_void_p(nrm.ctypes.data), nv.value,
+                                                               C.c_void_p(tri.ctypes.data), nt.value, C.byref(nv), C.byref(nt)))
+        return pts[:nv.value].copy(), col[:nv.value].copy(), None if nrm is None else nrm[:nv.value].copy(), tri[:nt.value].copy()
+
     def GenerateMeshByCube(self, cube_id, tri_table, edge_pairs):
         """CubeHandler::GenerateMeshByCube (CubeHandler.cpp:70-114) for one block."""
         return self.ExtractTriangleMesh(tri_table, edge_pairs, only_block=cube_id)

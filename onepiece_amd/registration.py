@@ -113,6 +113,59 @@ def cluster_simplify(points, colors, normals, triangles, grid_len, device_memory
     return tuple(None if a is None else a[:nv_out.value].copy() for a in outs) + (tout[:nt_out.value].copy(),)
 
 
+def compute_mesh_normals(points, triangles, device_memory=False, device=0):
+    """op_mesh_compute_normals == TriangleMesh::ComputeNormals, the bits of the class surface's host loop -> normals [nv,3] float32: per vertex the
+    float32 chain of its corners' unit face normals in corner order, normalised.  device_memory as for cluster_simplify."""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    tri = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    nv, nt = len(pts), len(tri)
+    if device_memory:
+        import torch
+        dev = torch.device("cuda", device)
+        pin, tin = L.torch_ready(torch.tensor(pts, device=dev)), L.torch_ready(torch.tensor(tri.view(np.int32), device=dev))
+        out = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
+        ptr = lambda a: C.c_void_p(a.data_ptr())
+    else:
+        pin, tin, out = pts, tri, np.empty((max(nv, 1), 3), np.float32)
+        ptr = lambda a: C.c_void_p(a.ctypes.data)
+    L.check(L.load().op_mesh_compute_normals(ptr(pin), nv, ptr(tin), nt, L.OP_MEM_DEVICE if device_memory else L.OP_MEM_HOST, device, ptr(out)))
+    if device_memory:
+        out = out.cpu().numpy()
+    return out[:nv].copy()
+
+
+def prune_mesh(points, colors, normals, triangles, min_points, device_memory=False, device=0):
+    """op_mesh_prune == TriangleMesh::Prune(min_points), the result of the class surface's host loop and its Compact ->
+    (points, colors or None, normals or None, triangles [k,3] uint32, pruned): components of at most min_points referenced vertices are dropped,
+    `pruned` is the number of vertices they held.  device_memory as for cluster_simplify."""
+    arrays = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (points, colors, normals)]
+    tri = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    if any(a is not None and len(a) != len(arrays[0]) for a in arrays):
+        raise ValueError("colors and normals must pair up with the points")
+    nv, nt = len(arrays[0]), len(tri)
+    cap = max(min(nv, 3 * nt), 1)
+    nv_out, nt_out, pruned = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    if device_memory:
+        import torch
+        dev = torch.device("cuda", device)
+        ins = [None if a is None else L.torch_ready(torch.tensor(a, device=dev)) for a in arrays]
+        tin = L.torch_ready(torch.tensor(tri.view(np.int32), device=dev))
+        outs = [None if a is None else torch.empty((cap, 3), dtype=torch.float32, device=dev) for a in arrays]
+        tout = torch.empty((max(nt, 1), 3), dtype=torch.int32, device=dev)
+        ptr = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+    else:
+        ins, tin = arrays, tri
+        outs = [None if a is None else np.empty((cap, 3), np.float32) for a in arrays]
+        tout = np.empty((max(nt, 1), 3), np.uint32)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+    L.check(L.load().op_mesh_prune(ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), nv, ptr(tin), nt, int(min_points), L.OP_MEM_DEVICE if device_memory else L.OP_MEM_HOST, device,
+                                   ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(tout), C.byref(nv_out), C.byref(nt_out), C.byref(pruned)))
+    if device_memory:
+        outs = [None if a is None else a.cpu().numpy() for a in outs]
+        tout = tout.cpu().numpy().view(np.uint32)
+    return tuple(None if a is None else a[:nv_out.value].copy() for a in outs) + (tout[:nt_out.value].copy(), pruned.value)
+
+
 def LoadFromRGBDDownSampled(rgb, depth, camera, T=None, grid_len=0.025, device=0):
     """LoadFromRGBD + Transform(T) + DownSample(grid_len) of one frame without leaving the device -- the body of
     Submap::GenerateSubmapModel's loop (DenseSlam.h:24-28) -> (PointCloud, colors [m,3]).  T: 4x4 or None (no transform)."""
