@@ -190,6 +190,16 @@ int op_debug_project_px(float a, float c, int fast);
  * IEEE division.  out: n x {u, v, u_plain, v_plain}; INT_MIN stands for "no int can hold it". */
 int op_debug_project_uv(float fx, float fy, float cx, float cy, const float *X, const float *Y, const float *Z,
                         size_t n, int device, int32_t *out);
+/* Test hook (device): TSDFVoxel::operator+ with other = (new_sdf, 1, rgb / 255) (Integration/TSDFVoxel.h:24-39; Integrator.cpp:74-87)
+ * for n stored voxels {s, w, c0, c1, c2} and observations {new_sdf, rgba}, lanes packed 64 to a wave in input order.
+ * out_fast: the fusion kernel's update of a volume it alone has written (csrc/integrate.hip voxel_update<true>: one hardware
+ * reciprocal of the integer weight sum, three operations per quotient); out_ref: the two-branch form with four IEEE divisions
+ * (voxel_update<false>).  Both n x {s, w, c0, c1, c2}.  Runs on device 0. */
+int op_debug_voxel_update(const float *s, const float *w, const float *c0, const float *c1, const float *c2,
+                          const float *new_sdf, const unsigned *rgba, long long n, float *out_fast, float *out_ref);
+/* Test hook (device): out[i] = v_rcp_f32(x[i]), the unrefined hardware reciprocal (csrc/integrate.hip voxel_update<true>:
+ * y = __builtin_amdgcn_rcpf(wsum)).  Runs on device 0. */
+int op_debug_rcp(const float *x, long long n, float *out);
 /* geometry::Se3ToSE3 (Geometry/Geometry.cpp:9-13). */
 int op_se3_exp(const float x[6], float T[16]);
 

@@ -15,11 +15,17 @@ typedef unsigned int kc_v2u __attribute__((ext_vector_type(2)));
 // numerators w*c + n never cancel), and the update can be evaluated
 //   * branch-free: an invalid voxel (TSDFVoxel::IsValid false) is the valid formula with weight 0 --
 //     (0*s + new)/(0 + 1) = new exactly for finite s -- instead of a second code path with five selects;
-//   * with ONE refined reciprocal of wsum shared by the four quotients (the compiler's own v_rcp + FMA sequence, spelled
-//     out as in project_uv): bit-identical to the IEEE division whenever v_div_scale would not rescale, i.e. for
-//     wsum in [1, 2^25] and a numerator that is 0 or >= 2^-100 in magnitude.  Colour numerators are 0 or >= 2^-32
-//     (no cancellation); the sdf numerator CAN cancel to something tiny, so it alone is guarded: a lane whose
-//     |w*s + new| is non-zero and below 2^-100 takes the plain division (never, in practice).
+//   * with ONE unrefined reciprocal y = v_rcp_f32(wsum) shared by the four quotients, each of them one multiply and one
+//     residual/correction pair (div_int_rcp, volume_core.hpp: its comment carries the proof): bit-identical to the IEEE
+//     division because the divisor is an integer.  The proof needs wsum <= 2^19 and quotient, residual and correction
+//     that are 0 or normal floats.  For a numerator n with |n| >= 2^-60 and wsum <= 2^19: |q0| >= 2^-60 * 2^-19 * (1 - 2^-23)
+//     > 2^-80, so ulp(q0) >= 2^-103; a non-zero residual is a multiple of ulp(q0)/2, >= 2^-104; its correction r*y is
+//     >= 2^-104 * 2^-19 * (1 - 2^-23) > 2^-124: all above 2^-126, whatever the denormal mode.  (2^-100, the bound of the
+//     five-operation form this replaces, would leave r as small as 2^-144.)  Colour numerators are 0 or >= 2^-32 (no
+//     cancellation: at least one byte/255 term, or all zero); the sdf numerator CAN cancel to something tiny.  So ONE guard,
+//     one ballot: a lane with wsum > 2^19 (a voxel seen in more than half a million frames), or whose |w*s + new| is below
+//     2^-60, takes the plain division for all four of its quotients, out of line (never, in practice).
+//     wsum = 1 (a first observation or an invalid voxel): y = 1, q0 = n, r = 0 -- the numerator exactly.
 // Without PLAIN (arbitrary uploaded data: NaN, infinities, denormals, fractional weights) the update is the reference's
 // two-branch form with four true divisions.
 // ---------------------------------------------------------------------------------------------
@@ -46,20 +52,18 @@ __device__ __forceinline__ void voxel_update(float& s, float& w, float& c0, floa
         // TSDFVoxel::IsValid (TSDFVoxel.h:75-78) false -> weight 0 in the same formula (see the PLAIN comment above)
         const float wv = (s >= 1 || w <= 0) ? 0.0f : w;
         const float wsum = wv + 1.0f;
-        float y = __builtin_amdgcn_rcpf(wsum);
-        const float e = __builtin_fmaf(-wsum, y, 1.0f);
-        y = __builtin_fmaf(e, y, y);
+        const float y = __builtin_amdgcn_rcpf(wsum);            // unrefined: div_int_rcp needs 1 ulp only
         const float ns = wv * s + 1.0f * new_sdf;
         const float m0 = wv * c0 + 1.0f * n0, m1 = wv * c1 + 1.0f * n1, m2 = wv * c2 + 1.0f * n2;
-        float qs = div_shared_rcp(ns, wsum, y);
-        const bool tiny = !(fabsf(ns) >= 0x1p-100f) && ns != 0.0f;
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(tiny) != 0ull, 0)) {
-            if (tiny) qs = ns / wsum;
+        float qs = div_int_rcp(ns, wsum, y), q0 = div_int_rcp(m0, wsum, y), q1 = div_int_rcp(m1, wsum, y), q2 = div_int_rcp(m2, wsum, y);
+        // outside div_int_rcp's hypotheses (see the PLAIN comment above).  | and not ||: two compares whose masks meet in scalar registers,
+        // no divergent region for the right-hand side.  A numerator of exactly 0 would pass through div_int_rcp unharmed (q0 = r = 0), but
+        // telling it from a tiny one costs a third compare per update; it is as rare as a tiny one and the division gives the same 0.
+        const bool slow = (wsum > 0x1p19f) | !(fabsf(ns) >= 0x1p-60f);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(slow) != 0ull, 0)) {
+            if (slow) { qs = ns / wsum; q0 = m0 / wsum; q1 = m1 / wsum; q2 = m2 / wsum; }
         }
-        s = qs;
-        c0 = div_shared_rcp(m0, wsum, y);
-        c1 = div_shared_rcp(m1, wsum, y);
-        c2 = div_shared_rcp(m2, wsum, y);
+        s = qs; c0 = q0; c1 = q1; c2 = q2;
         w = wsum;
     } else if (!(s >= 1 || w <= 0)) { // TSDFVoxel::IsValid (TSDFVoxel.h:75-78)
         const float wsum = w + 1.0f;  // TSDFVoxel::operator+ with other = (new_sdf, 1.0, c) (TSDFVoxel.h:24-39)
@@ -344,6 +348,26 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
     }
 }
 
+// test hooks: both forms of the voxel update for n operand sets, lanes packed 64 to a wave in input order (see op_debug_voxel_update),
+// and the hardware reciprocal div_int_rcp's proof starts from (op_debug_rcp)
+__global__ __launch_bounds__(256) void k_debug_voxel_update(const float* __restrict__ s, const float* __restrict__ w, const float* __restrict__ c0, const float* __restrict__ c1,
+                                                            const float* __restrict__ c2, const float* __restrict__ new_sdf, const unsigned* __restrict__ rgba, long long n,
+                                                            float* __restrict__ out_fast, float* __restrict__ out_ref) {
+    __shared__ float s_c255[256];
+    s_c255[threadIdx.x] = (float)threadIdx.x / 255.0f;
+    __syncthreads();
+    const long long i = blockIdx.x * 256ll + threadIdx.x;
+    if (i >= n) return;
+    float a[5] = {s[i], w[i], c0[i], c1[i], c2[i]}, b[5] = {a[0], a[1], a[2], a[3], a[4]};
+    voxel_update<true>(a[0], a[1], a[2], a[3], a[4], new_sdf[i], rgba[i], s_c255);
+    voxel_update<false>(b[0], b[1], b[2], b[3], b[4], new_sdf[i], rgba[i], s_c255);
+    for (int k = 0; k < 5; ++k) { out_fast[5 * i + k] = a[k]; out_ref[5 * i + k] = b[k]; }
+}
+__global__ void k_debug_rcp(const float* __restrict__ x, long long n, float* __restrict__ out) {
+    const long long i = blockIdx.x * 256ll + threadIdx.x;
+    if (i < n) out[i] = __builtin_amdgcn_rcpf(x[i]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // export / import / merge kernels
 // ---------------------------------------------------------------------------------------------
@@ -402,3 +426,50 @@ void kc_trace_dump(op_volume* v) {
 }
 
 } // namespace opv
+
+extern "C" {
+
+int op_debug_voxel_update(const float* s, const float* w, const float* c0, const float* c1, const float* c2, const float* new_sdf, const unsigned* rgba, long long n,
+                          float* out_fast, float* out_ref) {
+    if (!s || !w || !c0 || !c1 || !c2 || !new_sdf || !rgba || !out_fast || !out_ref) return fail(OP_ERR_INVALID, "null argument");
+    if (n < 0 || n > (1ll << 28)) return fail(OP_ERR_INVALID, "n out of range [0, 2^28]");
+    OP_TRY(op::use_device(0));
+    if (n == 0) return OP_OK;
+    const size_t N = (size_t)n;
+    float* d_in = nullptr;   // 7 operand planes of n words
+    float* d_out = nullptr;  // out_fast, out_ref: n x 5 each
+    OP_HIP(op::cached_malloc((void**)&d_in, 7 * N * 4));
+    hipError_t e = op::cached_malloc((void**)&d_out, 10 * N * 4);
+    const void* src[7] = {s, w, c0, c1, c2, new_sdf, rgba};
+    for (int k = 0; k < 7 && e == hipSuccess; ++k) e = hipMemcpy(d_in + k * N, src[k], N * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_debug_voxel_update, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const float*)d_in, (const float*)(d_in + N), (const float*)(d_in + 2 * N),
+                           (const float*)(d_in + 3 * N), (const float*)(d_in + 4 * N), (const float*)(d_in + 5 * N), (const unsigned*)(d_in + 6 * N), n, d_out, d_out + 5 * N);
+        e = hipMemcpy(out_fast, d_out, 5 * N * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out_ref, d_out + 5 * N, 5 * N * 4, hipMemcpyDeviceToHost);
+    }
+    op::cached_free(d_in);
+    if (d_out) op::cached_free(d_out);
+    if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_voxel_update failed: %s", hipGetErrorString(e));
+    return OP_OK;
+}
+
+int op_debug_rcp(const float* x, long long n, float* out) {
+    if (!x || !out) return fail(OP_ERR_INVALID, "null argument");
+    if (n < 0 || n > (1ll << 28)) return fail(OP_ERR_INVALID, "n out of range [0, 2^28]");
+    OP_TRY(op::use_device(0));
+    if (n == 0) return OP_OK;
+    const size_t N = (size_t)n;
+    float* d = nullptr;      // x, then out
+    OP_HIP(op::cached_malloc((void**)&d, 2 * N * 4));
+    hipError_t e = hipMemcpy(d, x, N * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_debug_rcp, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const float*)d, n, d + N);
+        e = hipMemcpy(out, d + N, N * 4, hipMemcpyDeviceToHost);
+    }
+    op::cached_free(d);
+    if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_rcp failed: %s", hipGetErrorString(e));
+    return OP_OK;
+}
+
+} // extern "C"

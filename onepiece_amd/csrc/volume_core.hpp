@@ -201,6 +201,32 @@ __device__ __forceinline__ float div_shared_rcp(float n, float z, float y) {
     r = __builtin_fmaf(-z, q, n);
     return __builtin_fmaf(r, y, q);
 }
+// The quotient n / b, correctly rounded, for an INTEGER divisor 1 <= b <= 2^19 and ANY approximation y of its reciprocal
+// with |y - 1/b| <= 2^-23 / b -- what v_rcp_f32 delivers unrefined (1 ulp; tests/test_voxel_update_gpu.py checks it for every
+// such b): one multiply and one residual/correction pair, where div_shared_rcp above needs a refined y and two pairs for its
+// arbitrary divisor.  Hypotheses besides b and y: n is a finite float and q0, r and r*y below are 0 or normal (the caller's
+// guard: |n| = 0 or >= 2^-60; see voxel_update<true> in integrate.hip).  With u = ulp(q0):
+//   1. q0 = RN(n*y) and n*y = (n/b)(1 + e), |e| <= 2^-23: |n*y - n/b| <= 2^-23 |n/b| < 2 u, plus half an ulp of rounding,
+//      so |q0 - n/b| <= 2.5 u.
+//   2. r = n - b*q0 = b*(n/b - q0) is formed EXACTLY by the FMA: b*q0 is a multiple of u because b is an integer, n is a
+//      multiple of its own ulp, which is no finer than u unless q0 was rounded up into the next binade above n (b = 1, y > 1:
+//      then r is a multiple of u/2 and still |r| <= 2.5 u); and |r| / u <= 2.5 b < 2^24, so r has at most 24 significant bits.
+//   3. So the last FMA rounds the exact value q0 + r*y = n/b + r*(y - 1/b), and |r*(y - 1/b)| <= 2.5 b u * 2^-23 / b
+//      = 2.5 * 2^-23 u: the FMA rounds a value within 2^-21.6 ulp of n/b.
+//   4. n/b is never a rounding midpoint (2Q + 1) * u/2 with Q >= 2^23: n = b * (2Q + 1) * u/2 would have an odd part of at
+//      least 2^24 + 1, more than the 24 bits of a float.
+//   5. n/b is at least u / (2b) away from every midpoint m: n - b*m is a non-zero multiple of u/2 (n is a multiple of u or,
+//      across a binade, of u/2; b*m is a multiple of u/2).  With b <= 2^19 that is >= 2^-20 u -- more than the error of 3,
+//      also when u is the ulp of the binade below the quotient's (factor 2: 5 * 2^-23 < 2^-20).
+//   6. Hence RN(q0 + r*y) = RN(n/b): the bit pattern of the IEEE division and of div_shared_rcp.  The limit on b is step 5's:
+//      2.5 * 2^-23 < 1 / (2b) needs b < 2^21.6 / 2; 2^19 leaves the factor 2 of the binade case and a margin.
+// b = 1: y = 1 (v_rcp_f32 of 1 is exact), q0 = n, r = 0: the numerator comes back unchanged.  tests/test_voxel_quotient_cpu.py
+// checks the sequence in exact rational arithmetic, tests/test_voxel_update_gpu.py against the plain division on the device.
+__device__ __forceinline__ float div_int_rcp(float n, float b, float y) {
+    const float q0 = n * y;
+    const float r = __builtin_fmaf(-b, q0, n);
+    return __builtin_fmaf(r, y, q0);
+}
 // The pixel (u, v) of the projection and whether each lies inside the image: the exact quotients (fx*X)/Z, (fy*Y)/Z and the
 // reference's rounding of them (Integrator.cpp:20-21,61-63).
 template <bool FAST>
