@@ -116,6 +116,11 @@ class CubeHandler {
     void PrepareCubes(const cv::Mat& depth, const geometry::TransformationMatrix& pose, std::vector<CubeID>& cube_id_list);
     void IntegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& pose);
     void IntegrateImage(const geometry::RGBDFrame& rgbd, const geometry::TransformationMatrix& pose);
+    // EXTENSION (not in the reference): IntegrateImage(depth, tool::AlignColorToDepth(rgb, depth, rgb_camera, this camera, color_to_depth), pose) for a
+    // colour image from a second camera (the ScanNet flow, example/GenerateModelFromScannet.cpp) -> op_volume_integrate_unaligned: the alignment runs
+    // on the volume's stream and the aligned image never leaves the device
+    void IntegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& pose, const camera::PinholeCamera& rgb_camera,
+                        const geometry::TransformationMatrix& color_to_depth = geometry::TransformationMatrix::Identity());
     CubeID GetCubeID(const geometry::Point3& point) const { return c_para.GetCubeID(point); }
     void AddCube(const CubeID& cube_id);
     // allocate the blocks the voxel centres of v_cube land in after trans: their eight trilinear neighbours / the voxel

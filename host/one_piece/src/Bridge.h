@@ -56,6 +56,11 @@ inline bool DeviceMeshPostprocess() {
     long long v = 0;
     return op_runtime_get_option(OP_RUNTIME_OPT_MESH_POSTPROCESS, &v) == OP_OK && v == 1;
 }
+// OP_RUNTIME_OPT_COLOR_ALIGNMENT: 1 = tool::AlignColorToDepth forwards to op_align_color_to_depth
+inline bool DeviceColorAlignment() {
+    long long v = 0;
+    return op_runtime_get_option(OP_RUNTIME_OPT_COLOR_ALIGNMENT, &v) == OP_OK && v == 1;
+}
 inline const float* Floats(const geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 inline float* Floats(geometry::Point3List& v) { return v.empty() ? nullptr : v[0].data(); }
 static_assert(sizeof(geometry::Point3) == 3 * sizeof(float), "Point3List must be a contiguous xyz float array");

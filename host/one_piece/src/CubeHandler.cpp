@@ -212,6 +212,23 @@ void CubeHandler::IntegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const
     static const bool verbose = std::getenv("ONEPIECE_HIP_VERBOSE") != nullptr;
     if (verbose) std::cout << GREEN << "[IntegrateImage]::[Info]::Image queued for integration." << RESET << std::endl;
 }
+void CubeHandler::IntegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& pose, const camera::PinholeCamera& rgb_camera,
+                                 const geometry::TransformationMatrix& color_to_depth) {
+    Pending();
+    if (!Ensure()) return;
+    Touch();
+    if (depth.rows != camera.Pod().height || depth.cols != camera.Pod().width || rgb.type() != CV_8UC3) {
+        std::cout << RED << "[ERROR]::[IntegrateImage]::the depth image must have the volume camera's size, the colour image three byte channels." << RESET << std::endl;
+        return;
+    }
+    float p[16], pi[16], m[16];
+    bridge::RowMajor(pose, p);
+    bridge::RowMajor(pose.inverse(), pi);
+    bridge::RowMajor(color_to_depth, m);
+    // both images are only borrowed for the call
+    if (op_volume_integrate_unaligned(vol, depth.data, bridge::DepthFormat(depth), rgb.data, rgb.rows, rgb.cols, &rgb_camera.Pod(), m, OP_MEM_HOST, p, pi) != OP_OK)
+        Report("IntegrateImage");
+}
 void CubeHandler::IntegrateImage(const geometry::RGBDFrame& rgbd, const geometry::TransformationMatrix& pose) {
     if (!rgbd.on_device) { IntegrateImage(rgbd.depth, rgbd.rgb, pose); return; }
     // the frame's images are on the device already (the tracker put them there): fused in place, nothing crosses PCIe again

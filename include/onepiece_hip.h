@@ -111,6 +111,9 @@ int op_runtime_hw_queues(int *requested);
  *   OP_RUNTIME_OPT_MESH_POSTPROCESS       0 (default): geometry::TriangleMesh::ComputeNormals and Prune of the class surface run their host loops, exactly as before the option
  *                                         existed.  1: they forward to op_mesh_compute_normals / op_mesh_prune (bit-identical), and fall back to the host loop for a mesh the
  *                                         device entry refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).  Read through op_runtime_get_option like the three options above.
+ *   OP_RUNTIME_OPT_COLOR_ALIGNMENT        0 (default): tool::AlignColorToDepth of the class surface runs its host loop.  1: it forwards to op_align_color_to_depth
+ *                                         (bit-identical), and falls back to the host loop for images the device entry refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).
+ *                                         Read through op_runtime_get_option like the four options above.
  * op_runtime_set_rccl_library(path): the RCCL to bind at the first merge instead of "librccl.so.1" (a site build; the test suite names a
  *   host-memory double that runs several ranks on one device); NULL = the system's.  Fails once RCCL has been bound. */
 #define OP_RUNTIME_OPT_MERGE_ALGORITHM 0
@@ -128,10 +131,11 @@ int op_runtime_hw_queues(int *requested);
 #define OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE 12
 #define OP_RUNTIME_OPT_MESH_CLUSTERING 13
 #define OP_RUNTIME_OPT_MESH_POSTPROCESS 14
+#define OP_RUNTIME_OPT_COLOR_ALIGNMENT 15
 #define OP_MERGE_OWNER_EXCHANGE 0
 #define OP_MERGE_DENSE_REDUCE 1
 int op_runtime_set_option(int option, long long value);
-int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, OP_RUNTIME_OPT_MESH_CLUSTERING and OP_RUNTIME_OPT_MESH_POSTPROCESS: the others are read inside the library */
+int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, OP_RUNTIME_OPT_MESH_CLUSTERING, OP_RUNTIME_OPT_MESH_POSTPROCESS and OP_RUNTIME_OPT_COLOR_ALIGNMENT: the others are read inside the library */
 int op_runtime_set_rccl_library(const char *path);
 /* Images that are used more than once -- a frame is tracked against twice and fused once (example/DenseFusion/DenseSlam.cpp:24-33,
  * DenseFusion.cpp:86-96) -- can be brought to the device ONCE and then handed to op_tracker_dense_tracking(_enqueue) /
@@ -290,6 +294,32 @@ int op_volume_integrate_cubes(op_volume *v, const void *depth, int depth_fmt, co
 int op_volume_integrate_sequence(op_volume *v, const void *depth, size_t depth_stride_bytes,
                                  int depth_fmt, const uint8_t *rgb, size_t rgb_stride_bytes,
                                  const float *poses, size_t n_frames);
+/* tool::AlignColorToDepth (Tool/IO.cpp:9-58): the colour image of a second camera re-sampled onto the depth pixels.  aligned_out is
+ * depth_cam->height x depth_cam->width x 3 bytes.  Per depth pixel (v, u) with z = depth(v, u) (uint16: (float)d / depth_cam->depth_scale): nothing is
+ * sampled (0, 0, 0) unless z > 0; x = ((float)u - cx_d) * z / fx_d, y likewise; q = color_to_depth (x, y, z, 1), p = q.xyz / q.w; a = p0 / p2, b = p1 / p2,
+ * c = p2 / p2; uf = fx_c * a + cx_c * c, vf = fy_c * b + cy_c * c (float32, no contraction); cu = (int)((double)uf + 0.5), cv likewise (truncation);
+ * the pixel copies color(cv, cu) when 0 <= cu < color_cam->width and 0 <= cv < DEPTH_cam->height -- the reference's own bound (IO.cpp:33).  Only z of the
+ * depth-camera point is tested; a point behind the colour camera is sampled like any other.  Defined here where the reference is not: a NaN or a value
+ * whose truncation does not fit an int is rejected, and so is a (cv, cu) outside the color_rows x color_cols image that was passed (the reference reads
+ * past its image there).  The depth image has the depth camera's size; color_to_depth is row-major, NULL = identity.  Host or device buffers (mem), like
+ * op_points_from_rgbd; synchronous. */
+int op_align_color_to_depth(const op_camera *color_cam, const op_camera *depth_cam, const uint8_t *color, int color_rows, int color_cols,
+                            const void *depth, int depth_fmt, const float *color_to_depth /* NULL = identity */, int mem, int device,
+                            uint8_t *aligned_out);
+/* IntegrateImage(depth, AlignColorToDepth(color, depth, color_cam, volume camera, color_to_depth), pose) (Tool/IO.cpp:9-58, then CubeHandler.cpp:197-210):
+ * the aligned image is made on the volume's stream into a ring of 64 images the volume owns, and the frame joins the queue of op_volume_integrate as a
+ * device-resident frame.  A ring slot is rewritten only after the batch that reads it is confirmed complete (a replay after pool growth reads it again);
+ * if the device is that far behind, the call waits.  OP_MEM_HOST images are copied before the call returns; OP_MEM_DEVICE: the colour image is read by
+ * work enqueued here, the depth image is used in place -- both must stay valid until the next synchronising call. */
+int op_volume_integrate_unaligned(op_volume *v, const void *depth, int depth_fmt, const uint8_t *color, int color_rows, int color_cols,
+                                  const op_camera *color_cam, const float *color_to_depth, int mem, const float pose[16],
+                                  const float *pose_inv);
+/* Multi-frame form for frames resident on the device (Tool/IO.cpp:9-58 per frame), mirroring op_volume_integrate_sequence: frame f uses
+ * depth + f*depth_stride_bytes, color + f*color_stride_bytes, poses + 16*f; one colour camera, one color_to_depth.  Bit-identical to n_frames
+ * op_volume_integrate_unaligned calls. */
+int op_volume_integrate_unaligned_sequence(op_volume *v, const void *depth, size_t depth_stride_bytes, int depth_fmt, const uint8_t *color,
+                                           size_t color_stride_bytes, int color_rows, int color_cols, const op_camera *color_cam,
+                                           const float *color_to_depth, const float *poses, size_t n_frames);
 /* Counters since create/clear (synchronises): frames integrated, sum over frames of
  * len(cube_id_list), of voxels visited (512 x len) and of voxels that passed the update predicate
  * (Integrator.cpp:63,70,74). */

@@ -63,6 +63,7 @@ OP_RUNTIME_OPT_MERGE_ALGORITHM, OP_RUNTIME_OPT_MERGE_SLICE_BLOCKS, OP_RUNTIME_OP
 OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE = 12
 OP_RUNTIME_OPT_MESH_CLUSTERING = 13
 OP_RUNTIME_OPT_MESH_POSTPROCESS = 14
+OP_RUNTIME_OPT_COLOR_ALIGNMENT = 15
 OP_MERGE_OWNER_EXCHANGE, OP_MERGE_DENSE_REDUCE = 0, 1
 OP_MEM_HOST, OP_MEM_DEVICE = 0, 1
 OP_ICP_POINT_TO_POINT, OP_ICP_POINT_TO_PLANE = 0, 1
@@ -178,6 +179,9 @@ SIGNATURES = {
     "op_mesh_prune": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _szp, _szp, _szp]),
     "op_volume_extract_mesh_processed": (C.c_int, [_vp, _ip, _ip, _ip, C.c_float, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _szp, _szp]),
     "op_points_from_rgbd_downsampled": (C.c_int, [C.POINTER(Camera), _vp, C.c_int, _vp, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _szp]),
+    "op_align_color_to_depth": (C.c_int, [C.POINTER(Camera), C.POINTER(Camera), _vp, C.c_int, C.c_int, _vp, C.c_int, _fp, C.c_int, C.c_int, _vp]),
+    "op_volume_integrate_unaligned": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.POINTER(Camera), _fp, C.c_int, _fp, _fp]),
+    "op_volume_integrate_unaligned_sequence": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(Camera), _fp, _fp, C.c_size_t]),
     "op_estimate_rigid_point_to_plane": (C.c_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "op_estimate_rigid_transformation": (C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "op_estimate_rigid_point_to_plane_ex": (C.c_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp]),

@@ -700,6 +700,9 @@ int op_runtime_set_option(int option, long long value) {
         case OP_RUNTIME_OPT_MESH_POSTPROCESS:
             if (value != 0 && value != 1) return fail(OP_ERR_INVALID, "op_runtime_set_option: mesh post-processing path %lld (0 host, 1 device)", value);
             o.mesh_postprocess.store((int)value); return OP_OK;
+        case OP_RUNTIME_OPT_COLOR_ALIGNMENT:
+            if (value != 0 && value != 1) return fail(OP_ERR_INVALID, "op_runtime_set_option: colour alignment path %lld (0 host, 1 device)", value);
+            o.color_alignment.store((int)value); return OP_OK;
         case OP_RUNTIME_OPT_MERGE_FAULT:
             if (value < 0) return fail(OP_ERR_INVALID, "op_runtime_set_option: merge fault %lld", value);
             o.merge_fault.store(value); return OP_OK;
@@ -717,6 +720,7 @@ int op_runtime_get_option(int option, long long* value) {
     if (option == OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE) { *value = op::runtime_options().point_cloud_downsample.load(); return OP_OK; }
     if (option == OP_RUNTIME_OPT_MESH_CLUSTERING) { *value = op::runtime_options().mesh_clustering.load(); return OP_OK; }
     if (option == OP_RUNTIME_OPT_MESH_POSTPROCESS) { *value = op::runtime_options().mesh_postprocess.load(); return OP_OK; }
+    if (option == OP_RUNTIME_OPT_COLOR_ALIGNMENT) { *value = op::runtime_options().color_alignment.load(); return OP_OK; }
     return fail(OP_ERR_INVALID, "op_runtime_get_option: option %d cannot be read", option);
 }
 
@@ -886,6 +890,7 @@ int op_volume_destroy(op_volume* v) {
         if (r.copied) (void)hipEventDestroy(r.copied);
     }
     if (v->hstat) op::cached_free(v->hstat);
+    vol_release_aligned(v);
     op::release_stream(v->copy_stream, v->device); // both were synchronised above
     op::release_stream(v->stream, v->device);
     delete v;

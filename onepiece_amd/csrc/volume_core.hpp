@@ -499,6 +499,21 @@ struct op_volume {
     BatchFwd pend_F;
     BatchInv pend_I;
     BatchPtrs pend_P;
+    // Aligned-colour ring of op_volume_integrate_unaligned (align_color.hip): kUaSlots images of the volume camera's size, written by k_align_color on
+    // `stream`; for host frames also the device copies of their depth images (ua_depth, allocated with the first one) and two staging buffers for
+    // the colour image the kernel reads.  ua_frame[s] = ordinal (frames_accepted) of the frame slot s was last given to: the slot is free once that
+    // many frames are confirmed complete -- a queued frame and a replayable batch keep their images.
+    static constexpr int kUaSlots = 2 * kMaxBatch;
+    unsigned char* ua_rgb = nullptr;
+    unsigned char* ua_depth = nullptr;
+    size_t ua_px = 0;
+    uint64_t ua_frame[kUaSlots] = {};
+    unsigned ua_next = 0;
+    unsigned char* ua_color[2] = {nullptr, nullptr};
+    size_t ua_color_cap[2] = {0, 0};
+    hipEvent_t ua_color_done[2] = {nullptr, nullptr};
+    bool ua_color_used[2] = {false, false};
+    unsigned ua_color_next = 0;
 
     VolView view() const {
         VolView V;
@@ -522,6 +537,11 @@ int vol_reserve(op_volume* v, unsigned long long need);
 int vol_block_count(op_volume* v, unsigned* n);
 void vol_mark_foreign(op_volume* v, unsigned long long bound);
 int check_cam(const op_camera* cam);
+void vol_retire(op_volume* v);               // retires the log entries of batches the device has reported complete; never blocks
+void frame_params(const op_volume* v, const float pose[16], const float* pose_inv, PoseFwd* fwd, PoseInv* inv);
+int write_staged(void* dst, size_t n_parts, const void* const* parts, const size_t* bytes, const size_t* offsets, int device); // pageable host -> device through the pinned stage, complete on return
+// align_color.hip
+void vol_release_aligned(op_volume* v);      // the aligned-colour ring of op_volume_integrate_unaligned
 // ---- kernel launchers (a kernel is launched from the translation unit that defines it)
 // select.hip: KA over the batch's frames (kKaFrames per launch); KB in the form the batch takes (cube_keys: k_mark_cubes instead); k_finish_select
 void launch_prepare_frames(op_volume* v, const BatchFwd& F, int nf, const CamParams& C, const BatchPtrs& Q, unsigned seq);

@@ -206,6 +206,50 @@ class CubeHandler:
         if len(self._alive) > 4096:
             self.Synchronize()
 
+    def IntegrateImageUnaligned(self, depth, rgb, pose, rgb_camera, color_to_depth=None, pose_inv=None):
+        """Extension: IntegrateImage(depth, tool::AlignColorToDepth(rgb, depth, rgb_camera, this camera, color_to_depth), pose) for a colour image
+        from a second camera ([hc, wc, 3], any size) -- the ScanNet flow (example/GenerateModelFromScannet.cpp, Tool/IO.cpp:9-58).  The alignment
+        runs on the volume's stream into a ring the volume owns (op_volume_integrate_unaligned); asynchronous like IntegrateImage."""
+        pd, fmt, mem, _k1 = _image_arg(depth, "depth")
+        pr, _f, mem2, _k2 = _image_arg(rgb, "rgb")
+        if mem != mem2:
+            raise ValueError("depth and rgb must both be host arrays or both be device tensors")
+        if len(_k2.shape) != 3 or _k2.shape[2] != 3:
+            raise ValueError("rgb must be [rows, cols, 3]")
+        if tuple(_k1.shape) != (self.camera.height, self.camera.width):
+            raise ValueError("the depth image must have the volume camera's size")
+        pose = _f32(pose).reshape(16)
+        pinv = _f32(pose_inv).reshape(16) if pose_inv is not None else None
+        m = _f32(color_to_depth).reshape(16) if color_to_depth is not None else None
+        L.check(self._lib.op_volume_integrate_unaligned(self._h, pd, fmt, pr, int(_k2.shape[0]), int(_k2.shape[1]), C.byref(rgb_camera),
+                                                        _fp(m) if m is not None else None, mem, _fp(pose), _fp(pinv) if pinv is not None else None))
+        if mem == L.OP_MEM_DEVICE:
+            self._alive.append((_k1, _k2))
+            if len(self._alive) > 4096:
+                self.Synchronize()
+
+    def IntegrateSequenceUnaligned(self, depth, rgb, poses, rgb_camera, color_to_depth=None):
+        """n device-resident frames (torch tensors [n, h, w] / [n, hc, wc, 3]) with one colour camera and one color_to_depth; identical to n
+        IntegrateImageUnaligned calls in order (op_volume_integrate_unaligned_sequence)."""
+        n = depth.shape[0]
+        pd, fmt, mem, _k1 = _image_arg(depth, "depth")
+        pr, _f, mem2, _k2 = _image_arg(rgb, "rgb")
+        if mem != L.OP_MEM_DEVICE or mem2 != L.OP_MEM_DEVICE:
+            raise ValueError("IntegrateSequenceUnaligned needs device-resident frames")
+        if len(rgb.shape) != 4 or rgb.shape[0] != n or rgb.shape[3] != 3:
+            raise ValueError("rgb must be [n, rows, cols, 3]")
+        if tuple(depth.shape) != (n, self.camera.height, self.camera.width):
+            raise ValueError("depth must be [n, h, w] of the volume camera's size")
+        poses = _f32(poses).reshape(n, 16)
+        m = _f32(color_to_depth).reshape(16) if color_to_depth is not None else None
+        npx = self.camera.width * self.camera.height
+        rows, cols = int(rgb.shape[1]), int(rgb.shape[2])
+        L.check(self._lib.op_volume_integrate_unaligned_sequence(self._h, pd, npx * (2 if fmt == L.OP_DEPTH_U16 else 4), fmt, pr, rows * cols * 3, rows, cols,
+                                                                 C.byref(rgb_camera), _fp(m) if m is not None else None, _fp(poses), n))
+        self._alive.append((_k1, _k2))
+        if len(self._alive) > 4096:
+            self.Synchronize()
+
     def Flush(self):
         """launch the queued frames now (a batch smaller than 32) without waiting for them"""
         L.check(self._lib.op_volume_flush(self._h))

@@ -161,3 +161,37 @@ def image_normals(depth, fx=FX, fy=FY, cx=CX, cy=CY):
     n = np.cross(du, dv)
     n /= np.maximum(np.linalg.norm(n, axis=-1, keepdims=True), 1e-12)
     return np.ascontiguousarray(n.reshape(-1, 3)[depth.reshape(-1) > 0], np.float32)
+
+
+# the second camera of room_render_two_cameras: a small rigid offset between the sensors (4 cm sideways, 1 cm up, ~1 degree about y), as the
+# matrix tool::AlignColorToDepth takes: it maps depth-camera coordinates to colour-camera coordinates
+COLOR_TO_DEPTH = np.array([[0.99984770, 0.0, 0.01745241, 0.04],
+                           [0.0, 1.0, 0.0, -0.01],
+                           [-0.01745241, 0.0, 0.99984770, 0.002],
+                           [0.0, 0.0, 0.0, 1.0]], np.float32)
+
+
+def two_camera_intrinsics(width=W, height=H, color_width=1296, color_height=968):
+    """(depth camera, colour camera) as (fx, fy, cx, cy, width, height) tuples: the OPEN3D preset scaled to the depth size; a colour camera of its
+    own size with a slightly wider field of view, so that every depth pixel's ray lands inside the colour image."""
+    sx, sy = width / float(W), height / float(H)
+    dcam = (FX * sx, FY * sy, CX * sx, CY * sy, width, height)
+    kx, ky = color_width / float(W), color_height / float(H)
+    ccam = (0.9 * FX * kx, 0.9 * FY * ky, 0.5 * color_width - 0.3, 0.5 * color_height + 0.2, color_width, color_height)
+    return dcam, ccam
+
+
+def room_render_two_cameras(pose, width=W, height=H, color_width=1296, color_height=968, color_to_depth=None, tint=0):
+    """The analytic room seen by a ScanNet-style sensor pair: depth from the depth camera at `pose`, colour from a second camera with its own
+    size, intrinsics and rigid offset.  -> (depth [h, w] f32, colour [hc, wc, 3] u8, depth camera, colour camera, color_to_depth).
+    A colour pixel is room_render's function of the world point its ray hits, so the colour a depth pixel should receive after alignment is
+    room_render's colour of that depth pixel's own hit point (up to the re-sampling).  `tint` is added to every channel (mod 256): frames of one
+    pose are told apart by it."""
+    M = COLOR_TO_DEPTH if color_to_depth is None else np.asarray(color_to_depth, np.float32).reshape(4, 4)
+    dcam, ccam = two_camera_intrinsics(width, height, color_width, color_height)
+    depth, _ = room_render(pose, width=width, height=height, fx=dcam[0], fy=dcam[1], cx=dcam[2], cy=dcam[3])
+    color_pose = (np.asarray(pose, np.float64) @ np.linalg.inv(M.astype(np.float64))).astype(np.float32)
+    _, color = room_render(color_pose, width=color_width, height=color_height, fx=ccam[0], fy=ccam[1], cx=ccam[2], cy=ccam[3])
+    if tint:
+        color = ((color.astype(np.int32) + int(tint)) % 256).astype(np.uint8)
+    return depth, color, dcam, ccam, M
