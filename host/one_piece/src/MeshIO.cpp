@@ -1,5 +1,6 @@
 // MeshIO.cpp -- see MeshIO.h.
 #include "MeshIO.h"
+#include "Tool/PLYManager.h"
 
 #include <cstdint>
 #include <cstdio>
@@ -64,10 +65,71 @@ void Message(const char* what, const std::string& file) {
     std::cout << RED << "[ERROR]::[MeshIO]::" << what << " " << file << RESET << std::endl;
 }
 
+// ---- additional scalar vertex properties (Tool/PLYManager.h) ----
+tinyply::Type PublicType(Scalar s) {
+    static const tinyply::Type t[] = {tinyply::Type::INT8, tinyply::Type::UINT8, tinyply::Type::INT16, tinyply::Type::UINT16, tinyply::Type::INT32,
+                                      tinyply::Type::UINT32, tinyply::Type::FLOAT32, tinyply::Type::FLOAT64, tinyply::Type::INVALID};
+    return t[s];
+}
+Scalar InternalType(tinyply::Type t) {
+    switch (t) {
+        case tinyply::Type::INT8: return I8;
+        case tinyply::Type::UINT8: return U8;
+        case tinyply::Type::INT16: return I16;
+        case tinyply::Type::UINT16: return U16;
+        case tinyply::Type::INT32: return I32;
+        case tinyply::Type::UINT32: return U32;
+        case tinyply::Type::FLOAT32: return F32;
+        default: return BAD; // (double properties are not among the additional ones this surface carries)
+    }
+}
+const char* TypeName(Scalar s) {
+    static const char* n[] = {"char", "uchar", "short", "ushort", "int", "uint", "float", "double", "?"};
+    return n[s];
+}
+// the value a property of type t holds, from the double Body::Next returned (exact for every type but F64, which is not stored)
+void StoreScalar(Scalar t, double d, unsigned char* out) {
+    switch (t) {
+        case I8: { const int8_t v = static_cast<int8_t>(d); std::memcpy(out, &v, 1); break; }
+        case U8: { const uint8_t v = static_cast<uint8_t>(d); std::memcpy(out, &v, 1); break; }
+        case I16: { const int16_t v = static_cast<int16_t>(d); std::memcpy(out, &v, 2); break; }
+        case U16: { const uint16_t v = static_cast<uint16_t>(d); std::memcpy(out, &v, 2); break; }
+        case I32: { const int32_t v = static_cast<int32_t>(d); std::memcpy(out, &v, 4); break; }
+        case U32: { const uint32_t v = static_cast<uint32_t>(d); std::memcpy(out, &v, 4); break; }
+        case F32: { const float v = static_cast<float>(d); std::memcpy(out, &v, 4); break; }
+        default: break;
+    }
+}
+void PrintScalar(std::ostream& os, Scalar t, const unsigned char* in) {
+    char buf[32];
+    switch (t) {
+        case I8: { int8_t v; std::memcpy(&v, in, 1); os << static_cast<int>(v); break; }
+        case U8: { uint8_t v; std::memcpy(&v, in, 1); os << static_cast<unsigned>(v); break; }
+        case I16: { int16_t v; std::memcpy(&v, in, 2); os << v; break; }
+        case U16: { uint16_t v; std::memcpy(&v, in, 2); os << v; break; }
+        case I32: { int32_t v; std::memcpy(&v, in, 4); os << v; break; }
+        case U32: { uint32_t v; std::memcpy(&v, in, 4); os << v; break; }
+        case F32: { float v; std::memcpy(&v, in, 4); std::snprintf(buf, sizeof(buf), "%.9g", v); os << buf; break; }
+        default: break;
+    }
+}
+bool ScalarVertexElement(const tool::AdditionalElement& a) {
+    return a.element_key == "vertex" && a.element_property.size() == 1 && a.list_type == tinyply::Type::INVALID && a.list_count == 0;
+}
+
+bool ReadPlyImpl(const std::string& file, geometry::Point3List& points, geometry::Point3List& normals, geometry::Point3List& colors,
+                 geometry::Point3uiList* triangles, std::vector<tool::AdditionalElement>* extra);
+
 } // namespace
 
 bool ReadPly(const std::string& file, geometry::Point3List& points, geometry::Point3List& normals, geometry::Point3List& colors,
              geometry::Point3uiList* triangles) {
+    return ReadPlyImpl(file, points, normals, colors, triangles, nullptr);
+}
+
+namespace {
+bool ReadPlyImpl(const std::string& file, geometry::Point3List& points, geometry::Point3List& normals, geometry::Point3List& colors,
+                 geometry::Point3uiList* triangles, std::vector<tool::AdditionalElement>* extra) {
     std::ifstream is(file.c_str(), std::ios::binary);
     if (!is) { Message("cannot open", file); return false; }
     std::string line;
@@ -118,6 +180,23 @@ bool ReadPly(const std::string& file, geometry::Point3List& points, geometry::Po
                 if (s >= 0 && !el.props[k].is_list) { has[s] = true; if (s >= 6 && (el.props[k].type == F32 || el.props[k].type == F64)) color_is_byte = false; }
             }
             const bool want_n = has[3] && has[4] && has[5], want_c = has[6] && has[7] && has[8];
+            // additional properties: which AdditionalElement (if any) takes property k
+            std::vector<int> taker(el.props.size(), -1);
+            std::vector<unsigned char*> sink(extra ? extra->size() : 0, nullptr);
+            if (extra)
+                for (size_t a = 0; a < extra->size(); ++a)
+                    for (size_t k = 0; k < el.props.size(); ++k) {
+                        if (el.props[k].name != (*extra)[a].element_property[0]) continue;
+                        if (el.props[k].is_list || el.props[k].type == F64) { Message("an additional property must be a scalar of at most 4 bytes in", file); return false; }
+                        taker[k] = static_cast<int>(a);
+                        tool::AdditionalElement& ae = (*extra)[a];
+                        ae.type = PublicType(el.props[k].type);
+                        ae.count = el.count;
+                        ae.byte_size = el.count * SizeOf(el.props[k].type);
+                        ae.data = new unsigned char[ae.byte_size ? ae.byte_size : 1];
+                        sink[a] = ae.data;
+                        break;
+                    }
             points.resize(el.count);
             if (want_n) normals.resize(el.count);
             if (want_c) colors.resize(el.count);
@@ -135,6 +214,7 @@ bool ReadPly(const std::string& file, geometry::Point3List& points, geometry::Po
                     const double d = body.Next(p.type);
                     const int s = Slot(p.name);
                     if (s >= 0) v[s] = static_cast<float>(d);
+                    if (taker[k] >= 0 && body.ok) StoreScalar(p.type, d, sink[static_cast<size_t>(taker[k])] + i * SizeOf(p.type));
                 }
                 points[i] = geometry::Point3(v[0], v[1], v[2]);
                 if (want_n) normals[i] = geometry::Point3(v[3], v[4], v[5]);
@@ -170,36 +250,69 @@ bool ReadPly(const std::string& file, geometry::Point3List& points, geometry::Po
     return true;
 }
 
+bool WritePlyImpl(const std::string& file, const geometry::Point3List& pts, const geometry::Point3List& nrm, const geometry::Point3List& col,
+                  const geometry::Point3uiList* tri, const std::vector<std::string>& comments, const std::vector<tool::AdditionalElement>& extra, bool ascii);
+} // namespace
+
 bool WritePly(const std::string& file, const geometry::Point3List& pts, const geometry::Point3List& nrm, const geometry::Point3List& col,
               const geometry::Point3uiList* tri) {
+    return WritePlyImpl(file, pts, nrm, col, tri, std::vector<std::string>(), std::vector<tool::AdditionalElement>(), false);
+}
+
+namespace {
+bool WritePlyImpl(const std::string& file, const geometry::Point3List& pts, const geometry::Point3List& nrm, const geometry::Point3List& col,
+                  const geometry::Point3uiList* tri, const std::vector<std::string>& comments, const std::vector<tool::AdditionalElement>& extra, bool ascii) {
+    std::vector<Scalar> xt(extra.size(), BAD);
+    for (size_t a = 0; a < extra.size(); ++a) {
+        xt[a] = ScalarVertexElement(extra[a]) ? InternalType(extra[a].type) : BAD;
+        if (xt[a] == BAD || extra[a].count != pts.size() || (!extra[a].data && !pts.empty())) {
+            Message("an additional element must be one scalar `vertex` property (char ... uint, float) with one value per vertex:", file);
+            return false;
+        }
+    }
     std::ofstream os(file.c_str(), std::ios::binary);
     if (!os) { Message("cannot open", file); return false; }
     const bool has_n = nrm.size() == pts.size() && !pts.empty(), has_c = col.size() == pts.size() && !pts.empty();
-    os << "ply\nformat binary_little_endian 1.0\nelement vertex " << pts.size() << "\nproperty float x\nproperty float y\nproperty float z\n";
+    os << "ply\nformat " << (ascii ? "ascii" : "binary_little_endian") << " 1.0\n";
+    for (size_t k = 0; k < comments.size(); ++k) os << "comment " << comments[k] << "\n";
+    os << "element vertex " << pts.size() << "\nproperty float x\nproperty float y\nproperty float z\n";
     if (has_n) os << "property float nx\nproperty float ny\nproperty float nz\n";
     if (has_c) os << "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+    for (size_t a = 0; a < extra.size(); ++a) os << "property " << TypeName(xt[a]) << " " << extra[a].element_property[0] << "\n";
     if (tri) os << "element face " << tri->size() << "\nproperty list uchar uint vertex_indices\n";
     os << "end_header\n";
+    char buf[32];
     for (size_t i = 0; i < pts.size(); ++i) {
-        os.write(reinterpret_cast<const char*>(pts[i].data()), 12);
-        if (has_n) os.write(reinterpret_cast<const char*>(nrm[i].data()), 12);
-        if (has_c) {
-            unsigned char rgb[3];
+        unsigned char rgb[3] = {0, 0, 0};
+        if (has_c)
             for (int k = 0; k < 3; ++k) {
                 const float v = col[i](k) * 255.0f;
                 rgb[k] = static_cast<unsigned char>(v < 0 ? 0 : (v > 255 ? 255 : v));
             }
-            os.write(reinterpret_cast<const char*>(rgb), 3);
+        if (ascii) {
+            for (int k = 0; k < 3; ++k) { std::snprintf(buf, sizeof(buf), "%.9g", pts[i](k)); os << (k ? " " : "") << buf; }
+            if (has_n) for (int k = 0; k < 3; ++k) { std::snprintf(buf, sizeof(buf), "%.9g", nrm[i](k)); os << " " << buf; }
+            if (has_c) for (int k = 0; k < 3; ++k) os << " " << static_cast<unsigned>(rgb[k]);
+            for (size_t a = 0; a < extra.size(); ++a) { os << " "; PrintScalar(os, xt[a], extra[a].data + i * SizeOf(xt[a])); }
+            os << "\n";
+            continue;
         }
+        os.write(reinterpret_cast<const char*>(pts[i].data()), 12);
+        if (has_n) os.write(reinterpret_cast<const char*>(nrm[i].data()), 12);
+        if (has_c) os.write(reinterpret_cast<const char*>(rgb), 3);
+        for (size_t a = 0; a < extra.size(); ++a) os.write(reinterpret_cast<const char*>(extra[a].data + i * SizeOf(xt[a])), static_cast<std::streamsize>(SizeOf(xt[a])));
     }
     if (tri)
         for (size_t i = 0; i < tri->size(); ++i) {
+            if (ascii) { os << "3 " << (*tri)[i](0) << " " << (*tri)[i](1) << " " << (*tri)[i](2) << "\n"; continue; }
             const unsigned char three = 3;
             os.write(reinterpret_cast<const char*>(&three), 1);
             os.write(reinterpret_cast<const char*>((*tri)[i].data()), 12);
         }
+    os.flush();
     return static_cast<bool>(os);
 }
+} // namespace
 
 bool ReadObj(const std::string& file, geometry::Point3List& points, geometry::Point3List& normals, geometry::Point3List& colors,
              geometry::Point3uiList* triangles) {
@@ -279,4 +392,28 @@ bool WriteObj(const std::string& file, const geometry::Point3List& pts, const ge
 }
 
 } // namespace meshio
+
+// ---- Tool/PLYManager.h ----
+namespace tool {
+
+bool ReadPLY(const std::string& filename, geometry::Point3List& points, geometry::Point3List& normals, geometry::Point3List& colors,
+             geometry::Point3uiList& triangles, std::vector<AdditionalElement>& additional_labels) {
+    for (size_t a = 0; a < additional_labels.size(); ++a) {
+        AdditionalElement& ae = additional_labels[a];
+        if (ae.element_key != "vertex" || ae.element_property.size() != 1) {
+            std::cout << RED << "[ERROR]::[ReadPLY]::additional elements are read as one scalar property of `vertex` (list properties and other elements are not supported)." << RESET << std::endl;
+            return false;
+        }
+        ae.type = tinyply::Type::INVALID; ae.list_type = tinyply::Type::INVALID; ae.list_count = 0; ae.count = 0; ae.byte_size = 0; ae.data = nullptr;
+    }
+    return meshio::ReadPlyImpl(filename, points, normals, colors, &triangles, &additional_labels);
+}
+
+bool WritePLY(const std::string& filename, const geometry::Point3List& points, const geometry::Point3List& normals, const geometry::Point3List& colors,
+              const geometry::Point3uiList& triangles, const std::vector<std::string>& comments, const std::vector<AdditionalElement>& additional_labels,
+              bool use_ascii) {
+    return meshio::WritePlyImpl(filename, points, normals, colors, triangles.empty() ? nullptr : &triangles, comments, additional_labels, use_ascii);
+}
+
+} // namespace tool
 } // namespace one_piece

@@ -6,6 +6,8 @@
 //        vertex_indices / vertex_index (triangles kept, larger polygons fanned); other elements skipped.
 //        Written: binary little endian, float x y z [nx ny nz] [uchar red green blue], face list uchar + 3 x uint --
 //        the layout the reference's writer produces (PLYManager.cpp:243-254).
+//        tool::ReadPLY / tool::WritePLY (Tool/PLYManager.h) are the same reader and writer with additional scalar vertex properties, header comments
+//        and an ascii body; they are defined in MeshIO.cpp next to these.
 //   OBJ  `v x y z [r g b]`, `vn`, `f a b c` with a, a/t, a/t/n or a//n indices (1-based, negative = relative).
 #pragma once
 #include <string>

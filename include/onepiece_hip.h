@@ -56,6 +56,7 @@ typedef struct {
 typedef struct op_volume op_volume; /* device-resident integration::CubeHandler state */
 typedef struct op_icp op_icp;       /* device-resident target cloud + search grid */
 typedef struct op_tracker op_tracker; /* dense RGB-D tracker workspace (stream, device state) */
+typedef struct op_nn_index op_nn_index; /* a target cloud and its search grid for batches of exact 1-NN queries */
 
 /* ---- library ----------------------------------------------------------------------------- */
 int op_abi_version(void);
@@ -114,6 +115,10 @@ int op_runtime_hw_queues(int *requested);
  *   OP_RUNTIME_OPT_COLOR_ALIGNMENT        0 (default): tool::AlignColorToDepth of the class surface runs its host loop.  1: it forwards to op_align_color_to_depth
  *                                         (bit-identical), and falls back to the host loop for images the device entry refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).
  *                                         Read through op_runtime_get_option like the four options above.
+ *   OP_RUNTIME_OPT_NEAREST_BATCH          0 (default): geometry::KDTree<3>::NearestBatch and tool::TransferLabels of the class surface run the loop of KnnSearch(q, ..., 1)
+ *                                         that example/GetLabelUsingKDTree.cpp writes.  1: they forward to op_nn_index_query / op_nn_index_transfer_labels (the same
+ *                                         indices and distance bits), and fall back to the host loop for input the device entry refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).
+ *                                         Read through op_runtime_get_option like the five options above.
  * op_runtime_set_rccl_library(path): the RCCL to bind at the first merge instead of "librccl.so.1" (a site build; the test suite names a
  *   host-memory double that runs several ranks on one device); NULL = the system's.  Fails once RCCL has been bound. */
 #define OP_RUNTIME_OPT_MERGE_ALGORITHM 0
@@ -132,10 +137,11 @@ int op_runtime_hw_queues(int *requested);
 #define OP_RUNTIME_OPT_MESH_CLUSTERING 13
 #define OP_RUNTIME_OPT_MESH_POSTPROCESS 14
 #define OP_RUNTIME_OPT_COLOR_ALIGNMENT 15
+#define OP_RUNTIME_OPT_NEAREST_BATCH 16
 #define OP_MERGE_OWNER_EXCHANGE 0
 #define OP_MERGE_DENSE_REDUCE 1
 int op_runtime_set_option(int option, long long value);
-int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, OP_RUNTIME_OPT_MESH_CLUSTERING, OP_RUNTIME_OPT_MESH_POSTPROCESS and OP_RUNTIME_OPT_COLOR_ALIGNMENT: the others are read inside the library */
+int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, OP_RUNTIME_OPT_MESH_CLUSTERING, OP_RUNTIME_OPT_MESH_POSTPROCESS, OP_RUNTIME_OPT_COLOR_ALIGNMENT and OP_RUNTIME_OPT_NEAREST_BATCH: the others are read inside the library */
 int op_runtime_set_rccl_library(const char *path);
 /* Images that are used more than once -- a frame is tracked against twice and fused once (example/DenseFusion/DenseSlam.cpp:24-33,
  * DenseFusion.cpp:86-96) -- can be brought to the device ONCE and then handed to op_tracker_dense_tracking(_enqueue) /
@@ -598,6 +604,33 @@ int op_points_from_rgbd(const op_camera *cam, const void *depth, int depth_fmt, 
  * undetermined (as in the reference, whose disambiguation is #if 0'd out); < 3 neighbours -> 0. */
 int op_estimate_normals(const float *xyz, size_t n, float radius, int knn, int mem, int device,
                         float *normals_out);
+
+/* ---- batched exact nearest-neighbour queries and label transfer (example/GetLabelUsingKDTree.cpp) ----
+ * What example/GetLabelUsingKDTree.cpp does per vertex -- KDTree<>::KnnSearch(q, indices, dists, 1) (Geometry/KDTree.h:147-196), then
+ * `dists[0] < max_distance`, then labels[i] = reference_labels[indices[0]] -- for a whole batch of queries against one target cloud.  Every
+ * index is the one nanoflann 1.3.2 reports (queries whose runner-up is as near as the best, or within 2^-15 of it relatively -- the reach of
+ * the rounding in the tree's pruning bound -- are re-decided on the host in the tree that library would build), every distance is its
+ * L2_Simple_Adaptor in float32 (d = 0; d += dx*dx; d += dy*dy; d += dz*dz).  max_sq_dist is compared with the SQUARED distance, strictly,
+ * as the example does; INFINITY = no cutoff.  A query with no target below the cutoff gets index -1, distance +infinity and the default label.
+ * OP_ERR_INVALID for a non-finite coordinate (target or query), a target whose grid cannot be sized, and 2^28 or more targets or queries
+ * (the packed (distance, index) key, 32-bit record offsets).  n = 0 succeeds and writes nothing; m = 0 answers -1 / default_label
+ * everywhere.  Host or device buffers (mem); synchronous; an index is used by one thread at a time. */
+/* replaces kdtree.BuildTree(reference_mesh.points) of example/GetLabelUsingKDTree.cpp:45-46 (Geometry/KDTree.h:147-196 searches it): built once, queried many times */
+int op_nn_index_create(const float *tgt_xyz, size_t m, int mem, int device, op_nn_index **index);
+/* the end of that kdtree's life (example/GetLabelUsingKDTree.cpp:45, rebuilt at :96 and :119; Geometry/KDTree.h:147-196): releases the index; NULL is accepted */
+int op_nn_index_destroy(op_nn_index *index);
+/* replaces the loop of KnnSearch(q, indices, dists, 1) + cutoff of example/GetLabelUsingKDTree.cpp:49-56 (Geometry/KDTree.h:147-196): out_idx n x int32, out_sq_dist n floats */
+int op_nn_index_query(op_nn_index *index, const float *query_xyz, size_t n, int mem, float max_sq_dist, int32_t *out_idx, float *out_sq_dist /* may be NULL */);
+/* replaces the whole loop of example/GetLabelUsingKDTree.cpp:49-60 / 98-108 / 121-132 (Geometry/KDTree.h:147-196 per query): out_labels[i] = out_idx[i] >= 0 ?
+ * tgt_labels[out_idx[i]] : default_label; labels are int32 (the example's unsigned short semantic labels are widened by the caller) */
+int op_nn_index_transfer_labels(op_nn_index *index, const int32_t *tgt_labels /* m x int32 */, const float *query_xyz, size_t n, int mem, float max_sq_dist,
+                                int32_t default_label, int32_t *out_labels, int32_t *out_idx /* may be NULL */);
+/* since the index was created: queries answered, and how many of them the host re-decided in the tree because their runner-up was exactly as
+ * near as the best (tied) or within the bound chain's rounding of it (doubtful) -- what example/GetLabelUsingKDTree.cpp's KnnSearch (Geometry/KDTree.h:147-196) decides by traversal */
+int op_nn_index_stats(op_nn_index *index, uint64_t *queries, uint64_t *tied, uint64_t *doubtful);
+/* one pass of example/GetLabelUsingKDTree.cpp (BuildTree + the loop, Geometry/KDTree.h:147-196) in one call: create, transfer, destroy */
+int op_transfer_labels(const float *tgt_xyz, const int32_t *tgt_labels, size_t m, const float *query_xyz, size_t n, int mem, int device, float max_sq_dist,
+                       int32_t default_label, int32_t *out_labels, int32_t *out_idx /* may be NULL */);
 
 /* ---- voxel-grid down-sampling (Geometry/PointCloud.h, example/DenseFusion/DenseSlam.h) ----
  * op_point_cloud_downsample == geometry::PointCloud::DownSample (Geometry/PointCloud.cpp:145-189), bit-identical to the host loop of

@@ -64,6 +64,7 @@ OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE = 12
 OP_RUNTIME_OPT_MESH_CLUSTERING = 13
 OP_RUNTIME_OPT_MESH_POSTPROCESS = 14
 OP_RUNTIME_OPT_COLOR_ALIGNMENT = 15
+OP_RUNTIME_OPT_NEAREST_BATCH = 16
 OP_MERGE_OWNER_EXCHANGE, OP_MERGE_DENSE_REDUCE = 0, 1
 OP_MEM_HOST, OP_MEM_DEVICE = 0, 1
 OP_ICP_POINT_TO_POINT, OP_ICP_POINT_TO_PLANE = 0, 1
@@ -182,6 +183,12 @@ SIGNATURES = {
     "op_align_color_to_depth": (C.c_int, [C.POINTER(Camera), C.POINTER(Camera), _vp, C.c_int, C.c_int, _vp, C.c_int, _fp, C.c_int, C.c_int, _vp]),
     "op_volume_integrate_unaligned": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.POINTER(Camera), _fp, C.c_int, _fp, _fp]),
     "op_volume_integrate_unaligned_sequence": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(Camera), _fp, _fp, C.c_size_t]),
+    "op_nn_index_create": (C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "op_nn_index_destroy": (C.c_int, [_vp]),
+    "op_nn_index_query": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_float, _vp, _vp]),
+    "op_nn_index_transfer_labels": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_float, C.c_int32, _vp, _vp]),
+    "op_nn_index_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
+    "op_transfer_labels": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int32, _vp, _vp]),
     "op_estimate_rigid_point_to_plane": (C.c_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "op_estimate_rigid_transformation": (C.c_int, [_vp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "op_estimate_rigid_point_to_plane_ex": (C.c_int, [_vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp]),

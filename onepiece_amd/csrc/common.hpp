@@ -34,6 +34,7 @@ struct RuntimeOptions {
     std::atomic<int> mesh_clustering{0};               // OP_RUNTIME_OPT_MESH_CLUSTERING: read by the class surface likewise; 1 = TriangleMesh::ClusteringSimplify runs on the device
     std::atomic<int> mesh_postprocess{0};              // OP_RUNTIME_OPT_MESH_POSTPROCESS: read by the class surface likewise; 1 = TriangleMesh::ComputeNormals and Prune run on the device
     std::atomic<int> color_alignment{0};               // OP_RUNTIME_OPT_COLOR_ALIGNMENT: read by the class surface likewise; 1 = tool::AlignColorToDepth runs on the device
+    std::atomic<int> nearest_batch{0};                 // OP_RUNTIME_OPT_NEAREST_BATCH: read by the class surface likewise; 1 = KDTree<3>::NearestBatch and tool::TransferLabels run on the device
     std::atomic<long long> merge_fault{0};             // TEST HOOK (OP_RUNTIME_OPT_MERGE_FAULT): stage * 1024 + rank + 1 -- that rank's allocation of that merge stage "fails"; 0 = off
     std::atomic<long long> cache_device_bytes{32ll << 30}; // released device buffers kept for reuse, per device (buffer cache below); 0 = keep none
 };

@@ -196,6 +196,11 @@ struct op_icp {
 namespace opi {
 // icp_grid.hip
 int device_exclusive_scan(const unsigned* d_count, size_t n, unsigned* d_start, hipStream_t stream, unsigned* total_out);
+// the grid build for another user of the search structure (nn_batch.hip): a context that holds only the target, its grid and its cell-sorted records, the cell
+// sized for about points_per_cell targets per occupied cell (icp_create's comment); and the same counting sort (count -> scan -> scatter into xyz + original
+// index records) of ANOTHER cloud over a grid that exists -- the queries of a batch, so that a wave's lanes walk neighbouring cells
+int grid_context_create(const float* tgt_xyz, size_t m, double points_per_cell, int mem, int device, op_icp** out);
+int cell_sort_points(const float* d_xyz, size_t n, const Grid& g, size_t ncell, float4* d_sorted, hipStream_t stream);
 void scan_launch(const unsigned* d_count, size_t n, unsigned* d_tot, unsigned* d_start, hipStream_t stream); // the three scan kernels, totals in the caller's buffer ((n + 1023) / 1024 + 1 words)
 // icp_iter.hip
 // one fused pass (transform + NN + inliers + sums + reduction) of kernel mode 0 .. 4 (k_icp_iter's MODE); start_T is read from c->T_dev unless host_T is given

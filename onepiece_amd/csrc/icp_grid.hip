@@ -329,12 +329,19 @@ extern "C" {
 
 // extent_divisor > 0: the cell is the largest extent of the bounding box / extent_divisor instead of the threshold
 // (EstimateNormals' k-NN grid; the box comes from the device either way)
-static int icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, double threshold, double extent_divisor, int mem, int device,
+// per_cell > 0: the cell is sized from the target's DENSITY instead (the batched nearest-neighbour index, nn_batch.hip), aiming at about per_cell
+// points per occupied cell.  The occupied cells of a cloud are not known before the grid exists, so both shapes a cloud usually has are
+// estimated from the box and the finer answer is taken (empty cells cost a ring walk two loads per row, crowded ones cost every query):
+//   a surface (a mesh's vertices, a depth cloud): occupied cells ~ box surface / cell^2   -> cell = sqrt(surface * per_cell / m)
+//   a filled volume (uniform test clouds):        occupied cells ~ box volume / cell^3    -> cell = cbrt(volume * per_cell / m)
+// (a box that is flat along one or two axes falls back to the area / the length it has).  The cell is never finer than 2^-12 of the
+// largest coordinate magnitude: cell_coord works in float32, and below that a cell's width approaches the rounding of (p - origin) * inv_cell.
+static int icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, double threshold, double extent_divisor, double per_cell, int mem, int device,
                       op_icp** out) {
     if (!out) return fail(OP_ERR_INVALID, "null out");
     *out = nullptr;
     if (!tgt_xyz && m) return fail(OP_ERR_INVALID, "null target");
-    if (!(threshold > 0) && !(extent_divisor > 0)) return fail(OP_ERR_INVALID, "threshold must be > 0");
+    if (!(threshold > 0) && !(extent_divisor > 0) && !(per_cell > 0)) return fail(OP_ERR_INVALID, "threshold must be > 0");
     if (m >= kMaxPoints) return fail(OP_ERR_INVALID, "target too large (at most %zu points)", kMaxPoints - 1);
     OP_TRY(op::use_device(device));
     op_icp* c = new op_icp();
@@ -383,6 +390,19 @@ static int icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, 
     if (extent_divisor > 0) {
         const float ext = std::max(mx[0] - mn[0], std::max(mx[1] - mn[1], mx[2] - mn[2]));
         cell = ext > 0 ? (double)ext / extent_divisor : 1.0;
+        c->threshold = cell;
+    }
+    if (per_cell > 0) {
+        double e[3], mag = 0;
+        for (int k = 0; k < 3; ++k) { e[k] = (double)mx[k] - (double)mn[k]; mag = std::max(mag, std::max(std::fabs((double)mx[k]), std::fabs((double)mn[k]))); }
+        std::sort(e, e + 3); // e[0] <= e[1] <= e[2]
+        const double per = per_cell / (double)(m ? m : 1);
+        cell = 1.0;
+        if (e[0] > 0) cell = std::min(std::sqrt(2.0 * (e[0] * e[1] + e[1] * e[2] + e[0] * e[2]) * per), std::cbrt(e[0] * e[1] * e[2] * per));
+        else if (e[1] > 0) cell = std::sqrt(e[1] * e[2] * per);
+        else if (e[2] > 0) cell = e[2] * per;
+        cell = std::max(cell, std::ldexp(mag, -12));
+        if (!(cell > 0) || !std::isfinite(cell)) cell = 1.0;
         c->threshold = cell;
     }
     for (int k = 0; k < 3; ++k)
@@ -434,7 +454,7 @@ static int icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, 
 
 int op_icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, double threshold, int mem, int device, op_icp** out) {
     if (!(threshold > 0)) return fail(OP_ERR_INVALID, "threshold must be > 0");
-    OP_TRY(icp_create(tgt_xyz, tgt_normals, m, threshold, 0.0, mem, device, out));
+    OP_TRY(icp_create(tgt_xyz, tgt_normals, m, threshold, 0.0, 0.0, mem, device, out));
     // OP_RUNTIME_OPT_ICP_DEFAULT_SUMS: the reference's own sequential float32 sums unless the process opted into the fp64 reduction (the mode that is
     // within north_star's 1e-4 of the CPU path on every pair is the default of the drop-in surface)
     (*out)->sums = op::runtime_options().icp_default_sums.load();
@@ -604,7 +624,7 @@ int op_estimate_normals(const float* xyz, size_t n, float radius, int knn, int m
     // find their 30 neighbours within the first ring (27 cells); measured 1.35 / 1.03 / 1.12 / 1.12 / 1.46 ms for
     // divisors 400 / 300 / 250 / 200 / 150 (tools/ab_normals_cell.sh)
     op_icp* c = nullptr;
-    OP_TRY(icp_create(xyz, nullptr, n, 0.0, 300.0, mem, device, &c));
+    OP_TRY(icp_create(xyz, nullptr, n, 0.0, 300.0, 0.0, mem, device, &c));
     float* d_nrm = nullptr;
     hipError_t e = op::cached_malloc((void**)&d_nrm, n * 12);
     if (e == hipSuccess) e = hipMemsetAsync(d_nrm, 0, n * 12, c->stream);
@@ -627,3 +647,34 @@ int op_estimate_normals(const float* xyz, size_t n, float radius, int knn, int m
 }
 
 } // extern "C"
+
+namespace opi {
+
+int grid_context_create(const float* tgt_xyz, size_t m, double points_per_cell, int mem, int device, op_icp** out) {
+    return icp_create(tgt_xyz, nullptr, m, 0.0, 0.0, points_per_cell, mem, device, out);
+}
+
+int cell_sort_points(const float* d_xyz, size_t n, const Grid& g, size_t ncell, float4* d_sorted, hipStream_t stream) {
+    if (!n) return OP_OK;
+    const size_t n_tab = ncell + 4;
+    unsigned *d_count = nullptr, *d_start = nullptr;
+    hipError_t e = op::cached_malloc((void**)&d_count, n_tab * sizeof(unsigned));
+    if (e == hipSuccess) e = op::cached_malloc((void**)&d_start, n_tab * sizeof(unsigned));
+    int rc = OP_OK;
+    if (e == hipSuccess) e = hipMemsetAsync(d_count, 0, n_tab * sizeof(unsigned), stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_xyz, n, g, d_count);
+        rc = device_exclusive_scan(d_count, n_tab, d_start, stream, nullptr);
+        if (rc == OP_OK) {
+            hipLaunchKernelGGL(k_cell_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_xyz, n, g, (const unsigned*)d_start, d_count, d_sorted);
+            e = hipStreamSynchronize(stream); // the two tables go back to the buffer cache below
+        }
+    }
+    if (d_count) op::cached_free(d_count);
+    if (d_start) op::cached_free(d_start);
+    if (rc != OP_OK) return rc;
+    if (e != hipSuccess) return fail(OP_ERR_HIP, "cell sort failed: %s", hipGetErrorString(e));
+    return OP_OK;
+}
+
+} // namespace opi

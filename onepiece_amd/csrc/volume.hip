@@ -703,6 +703,9 @@ int op_runtime_set_option(int option, long long value) {
         case OP_RUNTIME_OPT_COLOR_ALIGNMENT:
             if (value != 0 && value != 1) return fail(OP_ERR_INVALID, "op_runtime_set_option: colour alignment path %lld (0 host, 1 device)", value);
             o.color_alignment.store((int)value); return OP_OK;
+        case OP_RUNTIME_OPT_NEAREST_BATCH:
+            if (value != 0 && value != 1) return fail(OP_ERR_INVALID, "op_runtime_set_option: batched nearest-neighbour path %lld (0 host, 1 device)", value);
+            o.nearest_batch.store((int)value); return OP_OK;
         case OP_RUNTIME_OPT_MERGE_FAULT:
             if (value < 0) return fail(OP_ERR_INVALID, "op_runtime_set_option: merge fault %lld", value);
             o.merge_fault.store(value); return OP_OK;
@@ -721,6 +724,7 @@ int op_runtime_get_option(int option, long long* value) {
     if (option == OP_RUNTIME_OPT_MESH_CLUSTERING) { *value = op::runtime_options().mesh_clustering.load(); return OP_OK; }
     if (option == OP_RUNTIME_OPT_MESH_POSTPROCESS) { *value = op::runtime_options().mesh_postprocess.load(); return OP_OK; }
     if (option == OP_RUNTIME_OPT_COLOR_ALIGNMENT) { *value = op::runtime_options().color_alignment.load(); return OP_OK; }
+    if (option == OP_RUNTIME_OPT_NEAREST_BATCH) { *value = op::runtime_options().nearest_batch.load(); return OP_OK; }
     return fail(OP_ERR_INVALID, "op_runtime_get_option: option %d cannot be read", option);
 }
 
