@@ -5,11 +5,13 @@
  * import or call this.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg do,
  * and only as the checker / the timed CPU baseline.
  *
- * PARITY STATUS: "parity unpinned" against the compiled reference.  The reference hot-path
- * translation units all include <opencv2/...> (src/Geometry/Geometry.h:4-8), OpenCV is neither
- * vendored nor installed, and building the reference against stand-in headers is not allowed, so
- * the reference itself cannot be run here.  The reference ships no tests/golden vectors
- * (SURVEY.md section 4).  What this restatement IS pinned against:
+ * PARITY STATUS: partially pinned against the compiled reference.  The reference hot-path
+ * translation units all include <opencv2/...> (src/Geometry/Geometry.h:4-8) and OpenCV is neither
+ * vendored nor installed; the reference ships no tests/golden vectors.
+ * What this restatement IS pinned against:
+ *   - the reference's own integration::CubeHandler (fusion, Transform / TransformNearest, Merge, GetPointCloud, the mesh calls, AddCube,
+ *     the .map formats), the sources of its Integration/ directory compiled in place against a cv::Mat stand-in by oracle/tools/gen_volume_golden.py:
+ *     tests/golden/volume_ops_reference.npz, reproduced bit for bit (tests/test_volume_golden_cpu.py);
  *   - the reference's vendored third-party arithmetic (Eigen 3.3.7 4x4 SSE inverse, fixed-size
  *     product / dot evaluation order, JacobiSVD solve, Sophus SE3::exp), through golden vectors
  *     generated in the build container by oracle/tools/gen_eigen_golden.cpp and committed under

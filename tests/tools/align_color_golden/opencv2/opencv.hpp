@@ -1,5 +1,5 @@
-// A stand-in for the part of OpenCV that the reference's Tool/IO.cpp, Tool/ImageProcessing.cpp and Geometry/Geometry.cpp touch, so that those units
-// compile and link in a container without OpenCV (tests/tools/gen_align_color_golden.py).  A continuous row-major image container and the names
+// A stand-in for the part of OpenCV that the reference's Tool/IO.cpp, Tool/ImageProcessing.cpp, Geometry/*.cpp and Integration/*.cpp touch, so that those
+// units compile and link in a container without OpenCV (tests/tools/gen_align_color_golden.py, oracle/tools/gen_volume_golden.py).  A continuous row-major image container and the names
 // the headers mention; the image-processing calls are declared here and defined as aborting stubs in main.cpp -- the generator never reaches them.
 #pragma once
 #include <cmath>
@@ -25,7 +25,11 @@
 #define CV_RGB2GRAY 7
 
 namespace cv {
-struct Vec3b { unsigned char val[3]; };
+struct Vec3b {
+    unsigned char val[3];
+    unsigned char& operator[](int i) { return val[i]; }
+    const unsigned char& operator[](int i) const { return val[i]; }
+};
 struct Scalar {
     double v[4];
     Scalar(double a = 0, double b = 0, double c = 0, double d = 0) { v[0] = a; v[1] = b; v[2] = c; v[3] = d; }
@@ -55,6 +59,7 @@ class Mat {
         buf_ = std::make_shared<std::vector<unsigned char> >((size_t)r * c * elemSize());
         data = buf_->empty() ? nullptr : buf_->data();
     }
+    void release() { rows = cols = 0; data = nullptr; buf_.reset(); }
     int type() const { return type_; }
     int depth() const { return type_ & 7; }
     int channels() const { return (type_ >> 3) + 1; }
