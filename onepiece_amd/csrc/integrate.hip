@@ -26,6 +26,27 @@ typedef unsigned int kc_v2u __attribute__((ext_vector_type(2)));
 //     one ballot: a lane with wsum > 2^19 (a voxel seen in more than half a million frames), or whose |w*s + new| is below
 //     2^-60, takes the plain division for all four of its quotients, out of line (never, in practice).
 //     wsum = 1 (a first observation or an invalid voxel): y = 1, q0 = n, r = 0 -- the numerator exactly.
+// LEAN (PLAIN, and besides: every frame the volume has fused since it was created / cleared was fused by the exact update with a
+// truncation T <= 0.5, and there were at most 2^19 of them; the host tracks it, launch_integrate): the validity select of the first item
+// goes too, wv = w.  It is dead code under these hypotheses, because no stored voxel can be invalid with a weight other than 0:
+//   hypotheses: a stored voxel is the default {999, 0, -1, -1, -1} (TSDFVoxel.h:79-81; k_fill_pool) or the result of k >= 1 updates with
+//     observations |o| < T (the band test), each update s' = RN(RN(RN(w*s) + o) / (w + 1)) with the integer weight w = k - 1 <= 2^19 - 1
+//     (at most one update per fused frame).  The short quotient is that division bit for bit (div_int_rcp), the guard's division is it.
+//   the default voxel needs no test: its weight is exactly 0, so wv = w = 0 is what the select would have chosen; 0 * 999 = 0 and
+//     0 * -1 = -0 are exact, the numerators are the observation and the new colour, the divisor is 1.  It is the only voxel with w <= 0.
+//   the fixed-point step: each of the three roundings multiplies the magnitude by at most 1 + 2^-24 (a denormal product w*s is off by
+//     at most 2^-150 instead, below everything here), so with g = (1 + 2^-24)^3 = 1 + d, d < 3.0000004 * 2^-24:
+//       |s'| <= (w |s| + T) g / (w + 1).
+//     For a bound B this maps |s| <= B to |s'| <= B as soon as (w B + T) g <= (w + 1) B, i.e. T g <= B (1 - w d).  B_W = T g / (1 - W d)
+//     satisfies that for every w <= W at once (1 - w d >= 1 - W d), and the first update (w = 0) gives |s'| = |o| < T <= B_W: by induction
+//     every voxel with weight <= W + 1 has |s| <= B_W.
+//   where 2^19 enters: W = 2^19 gives W d < 0.09376, B_W < 1.1035 T, and T <= 0.5 gives |s| < 0.552 < 1: TSDFVoxel::IsValid holds for every
+//     voxel of weight >= 1, the select would have passed w through.  Past 2^19 frames the bound keeps growing (it is void at w = 1 / d,
+//     5.6 million) and from w = 2^24 on, where w + 1 = w, the update is no mean at all: the host then goes back to the form with the
+//     select (as it does for T > 0.5, where one observation can itself be invalid from T >= 1 on, and after a sum-form batch, whose
+//     roundings this argument does not cover).  tests/test_kc_lean_cpu.py runs the operation sequence to weight 2^19 on adversarial
+//     streams (the worst |s| / T it finds is 1 - 2^-24: the mean does not leave the observations' range there) and checks that the colour means, convex combinations of values in [0, 1] under the
+//     same three monotone roundings, stay in [0, 1].
 // Without PLAIN (arbitrary uploaded data: NaN, infinities, denormals, fractional weights) the update is the reference's
 // two-branch form with four true divisions.
 // ---------------------------------------------------------------------------------------------
@@ -45,12 +66,12 @@ typedef unsigned int kc_v2u __attribute__((ext_vector_type(2)));
 // A plane row of a z-slice is still one 256-byte wave access.  Frames are applied in ascending order; the gathers of the
 // NEXT selected frame are issued before the current frame's updates (two record sets, the frame loop unrolled by two).
 // ---------------------------------------------------------------------------------------------
-template <bool PLAIN>
+template <bool PLAIN, bool LEAN = false>
 __device__ __forceinline__ void voxel_update(float& s, float& w, float& c0, float& c1, float& c2, float new_sdf, unsigned rgba, const float* s_c255) {
     const float n0 = s_c255[rgba & 0xffu], n1 = s_c255[(rgba >> 8) & 0xffu], n2 = s_c255[(rgba >> 16) & 0xffu];
     if (PLAIN) {
-        // TSDFVoxel::IsValid (TSDFVoxel.h:75-78) false -> weight 0 in the same formula (see the PLAIN comment above)
-        const float wv = (s >= 1 || w <= 0) ? 0.0f : w;
+        // TSDFVoxel::IsValid (TSDFVoxel.h:75-78) false -> weight 0 in the same formula (see the PLAIN comment above); LEAN: only w == 0 is invalid
+        const float wv = LEAN ? w : ((s >= 1 || w <= 0) ? 0.0f : w);
         const float wsum = wv + 1.0f;
         const float y = __builtin_amdgcn_rcpf(wsum);            // unrefined: div_int_rcp needs 1 ulp only
         const float ns = wv * s + 1.0f * new_sdf;
@@ -91,7 +112,7 @@ __device__ unsigned long long g_kc_trace[4096 * 4 * 8];
 #define KC_T(K) do { } while (0)
 #define KC_N(K, V) do { } while (0)
 #endif
-template <bool FAST, bool PLAIN, int ZT, bool SUMF = false>
+template <bool FAST, bool PLAIN, int ZT, bool SUMF = false, bool LEAN = false>
 __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAVES)) void k_integrate(BatchInv B, CamParams C, VolView V, const uint2* __restrict__ pimg, State* st,
                                                                             int n_frames, unsigned long long* __restrict__ upd_partial,
                                                                             unsigned long long* __restrict__ sel_partial, unsigned long long* __restrict__ chg_partial,
@@ -123,7 +144,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
     const float __attribute__((address_space(4)))* kargs =
         (const float __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr(); // BatchInv B = offset 0 of the kernarg segment
     (void)B;
-    unsigned upd = 0, sel = 0, chg = 0, nblk = 0;
+    unsigned upd = 0, sel = 0, chg = 0, nblk = 0;   // upd: per WAVE (a scalar count of hit ballots), the others per lane
 #ifndef KC_CHUNK_LOG2
 #define KC_CHUNK_LOG2 5
 #endif
@@ -216,11 +237,12 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                 for (int z = 0; z < ZT; ++z) {
                     const float d = __uint_as_float(rec[z].x); // off-image pixels carry d == 0 -> skipped like `continue`
                     const float new_sdf = d - zc[z];
-                    // Integrator.cpp:70,74 (d > 0 and |sdf| < truncation) as ONE compare and one divergent region: an absent
-                    // observation takes the place of an out-of-band one
-                    const float band = d > 0 ? fabsf(new_sdf) : C.trunc;
-                    const bool hit = band < C.trunc;
-                    upd += hit ? 1u : 0u;                              // per lane; summed over the wave at the end
+                    // Integrator.cpp:70,74 (d > 0 and |sdf| < truncation): two compares whose masks meet in scalar registers (& and not &&, as in
+                    // project_pixel) and one divergent region.  NaN and infinities fail the second compare, d <= 0 and -0 the first.
+                    const bool seen = d > 0, near = fabsf(new_sdf) < C.trunc, hit = seen & near;
+                    // the wave's hits, counted where the masks already are: control flow is wave-uniform here and every lane of the wave is live.
+                    // (The ballot of each compare IS its scalar mask; the ballot of their conjunction would be rebuilt from a per-lane 0 / 1.)
+                    upd += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(seen) & __builtin_amdgcn_ballot_w64(near));
                     if (SUMF) { // branch-free: an observation that misses adds zeros
                         ssum[z] += hit ? new_sdf : 0.0f;
                         const unsigned t = hit ? rec[z].y : 0u;           // byte 3 of a packed pixel is 1 (k_prepare_frames): the count
@@ -228,7 +250,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                         acc1n[z] += (t >> 8) & 0x00ff00ffu;
                     } else if (hit) {
                         changed |= 1u << z;
-                        voxel_update<kPlain>(s[z], w[z], c0[z], c1[z], c2[z], new_sdf, rec[z].y, s_c255);
+                        voxel_update<kPlain, kPlain && LEAN>(s[z], w[z], c0[z], c1[z], c2[z], new_sdf, rec[z].y, s_c255);
                     }
                 }
             };
@@ -332,7 +354,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
     if (lane == 0 && blockIdx.x < 4096) for (int k = 0; k < 8; ++k) g_kc_trace[((size_t)blockIdx.x * 4 + zg) * 8 + k] = kt_[k];
 #endif
     // per-workgroup counters into kPartialGrid slots
-    upd = wave_sum(upd); chg = wave_sum(chg);
+    chg = wave_sum(chg);                                      // (upd is the wave's total already)
     if (lane == 0) { s_cnt[zg][0] = upd; s_cnt[zg][1] = chg; }
     __syncthreads();
     if (tid == 0) {
@@ -385,7 +407,7 @@ bool vol_fusion_keeps_summaries(const op_volume* v) {
 
 void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int nf) {
     const VolView V = v->view();
-#define OP_KC(FASTPX, PLAINV, SUMFV) hipLaunchKernelGGL((k_integrate<FASTPX, PLAINV, (SUMFV ? KC_ZT_SUM : KC_ZT), SUMFV>), dim3(SUMFV ? kColGridSum : kColGrid), dim3(512 / (SUMFV ? KC_ZT_SUM : KC_ZT)), 0, v->stream, I, C, V, (const uint2*)v->pimg, \
+#define OP_KC(FASTPX, PLAINV, SUMFV, LEANV) hipLaunchKernelGGL((k_integrate<FASTPX, PLAINV, (SUMFV ? KC_ZT_SUM : KC_ZT), SUMFV, LEANV>), dim3(SUMFV ? kColGridSum : kColGrid), dim3(512 / (SUMFV ? KC_ZT_SUM : KC_ZT)), 0, v->stream, I, C, V, (const uint2*)v->pimg, \
                                                  v->state, nf, v->upd_partial, v->sel_partial, v->chg_partial, v->plain_from, rc_sum, rc_stamp)
     // The sum form tests TSDFVoxel::IsValid on the STORED voxel once per batch where the reference re-tests it before every frame (Integrator.cpp:74-87,
     // TSDFVoxel.h:75-78): the two agree to rounding only while no OBSERVATION can itself be invalid, i.e. truncation < 1 (an observed sdf is < truncation;
@@ -394,9 +416,14 @@ void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int n
     // the raycaster's summaries are kept current by this launch (vol_fusion_keeps_summaries: the host has then NOT advanced the content generation)
     unsigned* rc_sum = vol_fusion_keeps_summaries(v) ? v->rc_sum : nullptr;
     const unsigned rc_stamp = (unsigned)(v->content_gen & 0x3fffffffull);
-    if (sum_form) { if (C.fast_px) OP_KC(true, true, true); else OP_KC(false, true, true); }
-    else if (C.fast_px) { if (v->plain) OP_KC(true, true, false); else OP_KC(true, false, false); }
-    else { if (v->plain) OP_KC(false, true, false); else OP_KC(false, false, false); }
+    // LEAN (see voxel_update): what the volume holds was fused by the exact update with truncations <= 0.5 only, in at most 2^19 frames, this batch
+    // included (a replayed batch counts again: the bound is a sufficient one).  !(<=) so that a NaN truncation counts as too large.
+    if (sum_form || !(v->trunc <= 0.5f)) v->lean_ok = false;
+    v->lean_frames += (uint64_t)nf;
+    const bool lean = v->plain && v->lean_ok && v->lean_frames <= (1ull << 19);
+    if (sum_form) { if (C.fast_px) OP_KC(true, true, true, false); else OP_KC(false, true, true, false); }
+    else if (C.fast_px) { if (lean) OP_KC(true, true, false, true); else if (v->plain) OP_KC(true, true, false, false); else OP_KC(true, false, false, false); }
+    else { if (lean) OP_KC(false, true, false, true); else if (v->plain) OP_KC(false, true, false, false); else OP_KC(false, false, false, false); }
 #undef OP_KC
 }
 

@@ -965,7 +965,7 @@ int op_volume_clear(op_volume* v) {
     if (v->copy_stream) OP_HIP(hipStreamSynchronize(v->copy_stream));
     OP_HIP(hipStreamSynchronize(v->stream));
     v->log.clear(); // whatever was in flight (fused or poisoned) is wiped with the volume
-    v->plain = true; v->plain_from = 0;
+    v->plain = true; v->plain_from = 0; v->lean_ok = true; v->lean_frames = 0;
     for (auto& r : v->ring) r.busy_seq = 0;
     if (v->hstat) v->hstat[1] = 0;
     OP_HIP(hipMemcpy(&n, v->n_blocks, sizeof(n), hipMemcpyDeviceToHost));

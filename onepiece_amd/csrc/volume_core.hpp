@@ -475,6 +475,10 @@ struct op_volume {
     // true while every voxel was written by k_integrate only since create / clear (see k_integrate<., PLAIN>): any other
     // writer (upload, merge, sum-form unpack, resampling result, file) clears it and fusion takes the general update
     bool plain = true;
+    // k_integrate's LEAN update (integrate.hip, voxel_update): true while every fusion launch since create / clear was the exact update with a
+    // truncation <= 0.5, and the frames those launches held (launch_integrate keeps both)
+    bool lean_ok = true;
+    uint64_t lean_frames = 0;
     int select_mode = 0;         // OP_VOLUME_OPT_SELECT: OP_VOLUME_SELECT_AUTO, OP_VOLUME_SELECT_DIRECT, or the largest range (in super-blocks) a frame may vote with
     int update_mode = 0;         // OP_VOLUME_OPT_UPDATE: OP_VOLUME_UPDATE_EXACT (the reference's frame-by-frame running mean, bit for bit) or _SUM_FORM
     unsigned plain_from = 0;     // with !plain: pool slots below this bound may hold foreign data (general update); later blocks are k_integrate's own
