@@ -66,6 +66,13 @@ typedef unsigned int kc_v2u __attribute__((ext_vector_type(2)));
 // A plane row of a z-slice is still one 256-byte wave access.  Frames are applied in ascending order; the gathers of the
 // NEXT selected frame are issued before the current frame's updates (two record sets, the frame loop unrolled by two).
 // ---------------------------------------------------------------------------------------------
+// one voxel's five planes {sdf, weight, colour} of its block in the pool (kVox floats apart)
+__device__ __forceinline__ void voxel_load(const float* p, float& s, float& w, float& c0, float& c1, float& c2) {
+    s = p[0]; w = p[kVox]; c0 = p[2 * kVox]; c1 = p[3 * kVox]; c2 = p[4 * kVox];
+}
+__device__ __forceinline__ void voxel_store(float* p, float s, float w, float c0, float c1, float c2) {
+    p[0] = s; p[kVox] = w; p[2 * kVox] = c0; p[3 * kVox] = c1; p[4 * kVox] = c2;
+}
 template <bool PLAIN, bool LEAN = false>
 __device__ __forceinline__ void voxel_update(float& s, float& w, float& c0, float& c1, float& c2, float new_sdf, unsigned rgba, const float* s_c255) {
     const float n0 = s_c255[rgba & 0xffu], n1 = s_c255[(rgba >> 8) & 0xffu], n2 = s_c255[(rgba >> 16) & 0xffu];
@@ -118,11 +125,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                                                                             unsigned long long* __restrict__ sel_partial, unsigned long long* __restrict__ chg_partial,
                                                                             unsigned plain_from, unsigned* __restrict__ rc_sum, unsigned rc_stamp) {
     constexpr int kWaves = 8 / ZT;            // waves per workgroup = z-groups per block
-#ifdef KC_NO_SUMMARY // (A/B aid: the kernel without the raycaster's summaries)
-    constexpr bool kSummaries = false;
-#else
-    constexpr bool kSummaries = !SUMF;
-#endif
+    constexpr bool kSummaries = !SUMF;        // the raycaster's block summaries are restated by the exact update only
     __shared__ unsigned s_cnt[kWaves][2];
     __shared__ unsigned s_sign[2][kWaves];    // rc_sum: per wave, does its part of the block hold an observed sdf <= 0 (bit 0) / > 0 (bit 1) after the batch
     __shared__ float s_c255[256];             // (float)b / 255.0f for every byte (Integrator.cpp:78), correctly rounded once
@@ -145,46 +148,35 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
         (const float __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr(); // BatchInv B = offset 0 of the kernarg segment
     (void)B;
     unsigned upd = 0, sel = 0, chg = 0, nblk = 0;   // upd: per WAVE (a scalar count of hit ballots), the others per lane
-#ifndef KC_CHUNK_LOG2
-#define KC_CHUNK_LOG2 5
-#endif
     // XCD-aware order (workgroup b runs on XCD b % 8, each XCD has its own 4 MiB L2; blocks that gather the same pixels should meet in one L2)
     // and dynamic scheduling (blocks differ in work: 1..32 frames touch them; the workgroups of an XCD DRAW list positions from one counter,
-    // the next one before the current block is processed so that the atomic's round trip is hidden).  Two ways of dealing the batch's blocks
-    // to the eight draw counters:
-    //  * full batches (>= KC_STEAL_MIN_FRAMES frames): XCD x starts on the x-th contiguous eighth of the list (with -DKC_BANDS=1 on list x, see
-    //    kBands); the eighths hold the same number of blocks but not the same work, so a workgroup whose share is exhausted reads all eight
-    //    counters (one round trip) and goes on with the share that has the most left.
+    // the next one before the current block is processed so that the atomic's round trip is hidden).  Two ways of dealing the batch list to
+    // the eight draw counters:
+    //  * eighths + stealing, for full batches (>= KC_STEAL_MIN_FRAMES frames): share x is the x-th contiguous eighth of the list and XCD x
+    //    starts on it; the eighths hold the same number of blocks but not the same work, so a workgroup whose share is exhausted reads all
+    //    eight counters (one round trip) and goes on with the share that has the most left.
     //    Per 32-frame launch: eighths alone 689 us, with stealing 627-631 us;
-    //  * short batches: list 0, chunks of 32 blocks dealt round-robin (every XCD a sample of the whole list), no stealing: for ONE frame per
-    //    launch, where the kernel is HBM-bound and the work per block uniform, 79 us against 95 us with stealing (its last look costs a short
-    //    launch more than it can win).  Measured crossover (tools/prof_driver.bin batch=N under the tracer, stealing vs chunks): 8 frames
-    //    207 vs 194 us, 16: 360 vs 356, 24: 524 vs 527, 32: 677 vs 687.
+    //  * chunks, for short batches: share x is every eighth chunk of kChunk blocks (every XCD a sample of the whole list), no stealing: for
+    //    ONE frame per launch, where the kernel is HBM-bound and the work per block uniform, 79 us against 95 us with stealing (its last look
+    //    costs a short launch more than it can win).  Measured crossover (tools/prof_driver.bin batch=N under the tracer, stealing vs chunks):
+    //    8 frames 207 vs 194 us, 16: 360 vs 356, 24: 524 vs 527, 32: 677 vs 687.
+    // Either way a share is per0 list positions, position j of share x is list entry b below, and entries past the list's end are skipped.
     const bool eighths = n_frames >= KC_STEAL_MIN_FRAMES;
-    const bool lists = eighths && KC_BANDS != 0;              // one list per share
-    constexpr unsigned kChunk = 1u << KC_CHUNK_LOG2;
-    const unsigned n0 = st->n_list[0] < V.max_blocks ? st->n_list[0] : V.max_blocks;
-    const unsigned n_chunks = (n0 + kChunk - 1u) >> KC_CHUNK_LOG2;
-    const unsigned per0 = eighths ? (n0 + (unsigned)kKcShares - 1u) / (unsigned)kKcShares : ((n_chunks + (unsigned)kKcShares - 1u) / (unsigned)kKcShares) << KC_CHUNK_LOG2;
+    constexpr unsigned kChunkLog2 = 5u, kChunk = 1u << kChunkLog2;
+    const unsigned n0 = st->n_blist < V.max_blocks ? st->n_blist : V.max_blocks;
+    const unsigned n_chunks = (n0 + kChunk - 1u) >> kChunkLog2;
+    const unsigned per0 = eighths ? (n0 + (unsigned)kKcShares - 1u) / (unsigned)kKcShares : ((n_chunks + (unsigned)kKcShares - 1u) / (unsigned)kKcShares) << kChunkLog2;
     unsigned xcd = blockIdx.x % (unsigned)kKcShares;          // the share this workgroup draws from: its own first
     for (;;) {
     unsigned* ctr = &st->kc_next[xcd * 16u];
     if (tid == 0) s_next[0] = atomicAdd(ctr, 1u);
-    // positions j < per_xcd of share xcd; its blocks are list[j] (one list per share) or positions of list 0
-    unsigned per_xcd = per0, n = n0;
-    const int* list = V.blist;
-    if (lists) {
-        const unsigned nl = st->n_list[xcd];
-        per_xcd = n = nl < V.max_blocks ? nl : V.max_blocks;
-        list = V.blist + (size_t)xcd * V.max_blocks;
-    }
     __syncthreads();
     unsigned slot = 0u;
-    for (unsigned j = s_next[0]; j < per_xcd;) {
+    for (unsigned j = s_next[0]; j < per0;) {
         if (tid == 0) s_next[slot ^ 1u] = atomicAdd(ctr, 1u);
-        const unsigned b = lists ? j : (eighths ? xcd * per_xcd + j : (((j >> KC_CHUNK_LOG2) * (unsigned)kKcShares + xcd) << KC_CHUNK_LOG2) + (j & (kChunk - 1u)));
+        const unsigned b = eighths ? xcd * per0 + j : (((j >> kChunkLog2) * (unsigned)kKcShares + xcd) << kChunkLog2) + (j & (kChunk - 1u));
         KC_T(0);
-        const int tslot = b < n ? list[b] : -1;
+        const int tslot = b < n0 ? V.blist[b] : -1;
         const int idx = tslot >= 0 ? V.tvals[tslot] : -1; // idx < 0: pool overflow (reported through st->overflow)
         KC_N(6, 1);
         if (idx >= 0) {
@@ -196,7 +188,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
 #pragma unroll
             for (int z = 0; z < ZT; ++z) {
                 // (the sum form needs the stored voxel only after the frames: it is loaded there, and the registers are free until then)
-                if (!SUMF) { s[z] = vox[z * 64]; w[z] = vox[kVox + z * 64]; c0[z] = vox[2 * kVox + z * 64]; c1[z] = vox[3 * kVox + z * 64]; c2[z] = vox[4 * kVox + z * 64]; }
+                if (!SUMF) voxel_load(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
                 // GetGlobalPoint (VoxelCube.h:75-80): Point3(id) * CUBE_SIZE * VoxelResolution + offset
                 pz[z] = ((float)kz * 8.0f) * C.res + ((float)(zg * ZT + z) * C.res + half);
             }
@@ -280,7 +272,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
             if (SUMF) {
 #pragma unroll
                 for (int z = 0; z < ZT; ++z)
-                    if (acc1n[z] >> 16) { s[z] = vox[z * 64]; w[z] = vox[kVox + z * 64]; c0[z] = vox[2 * kVox + z * 64]; c1[z] = vox[3 * kVox + z * 64]; c2[z] = vox[4 * kVox + z * 64]; }
+                    if (acc1n[z] >> 16) voxel_load(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
 #pragma unroll
                 for (int z = 0; z < ZT; ++z) {
                     const unsigned cnt = acc1n[z] >> 16;
@@ -301,7 +293,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
             }
 #pragma unroll
             for (int z = 0; z < ZT; ++z)
-                if ((changed >> z) & 1u) { vox[z * 64] = s[z]; vox[kVox + z * 64] = w[z]; vox[2 * kVox + z * 64] = c0[z]; vox[3 * kVox + z * 64] = c1[z]; vox[4 * kVox + z * 64] = c2[z]; }
+                if ((changed >> z) & 1u) voxel_store(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
             chg += (unsigned)__popc(changed);
             // The raycaster's block summaries (raycast.hip: k_rc_neighbours drops blocks by them before loading a voxel) describe exactly what is in
             // registers here -- the block's 512 voxels after the batch: the kernel that changes a block restates its summary, so views between fusions
@@ -334,9 +326,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
         unsigned left = 0u;
         if (tid < kKcShares) {
             const unsigned c = __hip_atomic_load(&st->kc_next[(unsigned)tid * 16u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            unsigned len = per0;
-            if (lists) { const unsigned nl = st->n_list[tid]; len = nl < V.max_blocks ? nl : V.max_blocks; }
-            left = c < len ? len - c : 0u;
+            left = c < per0 ? per0 - c : 0u;
         }
         unsigned key = ((left < 0x7fffffu ? left : 0x7fffffu) << 8) | (unsigned)tid; // most left, ties to the higher share index (any fixed rule)
 #pragma unroll

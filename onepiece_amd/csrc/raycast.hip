@@ -358,11 +358,7 @@ __global__ __launch_bounds__(RC_WG, RC_MIN_WAVES) void k_rc_march(VolView V, RcV
         const unsigned flags = s_flags;
         if (!(flags & 1u) || (!(flags & 2u) && (s_ent[7] & 1))) continue;
         ++n_marched;
-#ifdef RC_STAGE_ONLY // (timing experiment only)
-        const int npix = s_sdf[tid] == 12345.0f ? s_ent[5] * s_ent[6] : 0;
-#else
         const int npix = s_ent[5] * s_ent[6];
-#endif
         if (tid == 0) { RC_COUNT(1, 1); RC_COUNT(2, npix); }
         const int bx8 = 8 * kx, by8 = 8 * ky, bz8 = 8 * kz, bu0 = s_ent[3], bv0 = s_ent[4], bw = s_ent[5];
         const float lo0 = ((float)bx8 + kDomLo) * W.res, lo1 = ((float)by8 + kDomLo) * W.res, lo2 = ((float)bz8 + kDomLo) * W.res, ext = kDomExt * W.res;
@@ -400,7 +396,6 @@ __global__ __launch_bounds__(RC_WG, RC_MIN_WAVES) void k_rc_march(VolView V, RcV
                     float sp = s_prev, tp = t_prev;
                     if (!prev_in) { // the previous lattice point belongs to another block (or there is none): one step upstream, normally still inside the tile
                         sp = __builtin_nanf("");
-#ifndef RC_NO_PREV // (timing experiment only: wrong results)
                         if (k > 0) {
                             tp = rc_t(W, k - 1);
                             const float x = o0 + tp * d0, y = o1 + tp * d1, z = o2 + tp * d2;
@@ -414,7 +409,6 @@ __global__ __launch_bounds__(RC_WG, RC_MIN_WAVES) void k_rc_march(VolView V, RcV
                                 if (rc_sample_global<false>(V, W, bc, x, y, z, &sv, nullptr)) sp = sv;
                             }
                         }
-#endif
                     }
                     if (sp > 0.0f) {
                         const float depth = tp + (t - tp) * (sp / (sp - acc));

@@ -9,7 +9,7 @@ namespace {
 
 __global__ void k_finish_select(VolView V, State* st) {
     for (unsigned k = blockIdx.x * blockDim.x + threadIdx.x; k < (unsigned)(kMaxBatch * kAccSlots * 8); k += gridDim.x * blockDim.x) (&st->acc[0][0][0])[k] = 0u; // as KC does
-    const unsigned n = st->n_list[0] < V.max_blocks ? st->n_list[0] : V.max_blocks; // a one-frame batch: list 0 only
+    const unsigned n = st->n_blist < V.max_blocks ? st->n_blist : V.max_blocks;
     const unsigned nr = st->n_rec < V.max_blocks ? st->n_rec : V.max_blocks;
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) V.bmask[V.blist[i]] = (bmask_t)0;
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < nr; i += gridDim.x * blockDim.x) V.sel_list[i] = V.tvals[V.sel_list[i]];
@@ -26,7 +26,7 @@ __global__ void k_mark_cubes(VolView V, State* st, const int* __restrict__ keys,
     const int slot = table_claim(V, st, x, y, z, &created);
     if (slot < 0) return;
     if (atomicOr(&V.bmask[slot], (bmask_t)1) == (bmask_t)0) { // a key listed twice is fused once
-        const unsigned pos = atomicAdd(&st->n_list[0], 1u);
+        const unsigned pos = atomicAdd(&st->n_blist, 1u);
         if (pos < V.max_blocks) V.blist[pos] = slot;
     }
 }
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_prepare_frames(KaFwd B, int f0, CamPara
     const int tid = threadIdx.x, f = f0 + (int)blockIdx.y; // frame of the batch
     if (blockIdx.x == 0 && f == 0 && tid == 0) {
         st->n_rec = 0; // new batch: empty lists
-        for (int b = 0; b < kBands; ++b) st->n_list[b] = 0;
+        st->n_blist = 0;
         st->cur_seq = seq;
         // Progress report for the host (host-mapped pinned memory, read without any synchronisation): this kernel starting
         // means every earlier batch has finished; unless the stream is poisoned by an overflow they all completed.  The host
@@ -320,10 +320,10 @@ __device__ __forceinline__ bool superblock_survives(const CamParams& C, const fl
 
 // Integrator::GetSDF (Integrator.cpp:8-35) probes of the 8 corner voxels {0,7,56,63,448,455,504,511} of the block at (bx, by, bz) for the frame
 // with inverse pose rows M and packed image img: all 8 projections first, then all 8 gathers in flight together, then the min.  True when the
-// block is selected (CubeHandler.cpp:176-190: min |sdf| < truncation).  pmax = the largest pixel index among the corners (-1: none on the image).
+// block is selected (CubeHandler.cpp:176-190: min |sdf| < truncation).
 template <bool FAST>
 __device__ __forceinline__ bool block_selected(const CamParams& C, const float* __restrict__ M, const uint2* __restrict__ img, float bx, float by, float bz,
-                                               float o_lo, float o_hi, int& pmax) {
+                                               float o_lo, float o_hi) {
     int pix[8];
     float zc[8];
 #pragma unroll
@@ -338,9 +338,8 @@ __device__ __forceinline__ bool block_selected(const CamParams& C, const float* 
         pix[corner] = project_pixel<FAST>(C, q0, q1c, q2c);
     }
     float dd[8];
-    pmax = pix[0];
 #pragma unroll
-    for (int corner = 0; corner < 8; ++corner) { dd[corner] = pix[corner] >= 0 ? __uint_as_float(img[(unsigned)pix[corner]].x) : 0.0f; pmax = max(pmax, pix[corner]); }
+    for (int corner = 0; corner < 8; ++corner) { dd[corner] = pix[corner] >= 0 ? __uint_as_float(img[(unsigned)pix[corner]].x) : 0.0f; }
     float min_sdf = FLT_MAX;
 #pragma unroll
     for (int corner = 0; corner < 8; ++corner) {
@@ -349,6 +348,22 @@ __device__ __forceinline__ bool block_selected(const CamParams& C, const float* 
         if (min_sdf > a) min_sdf = a;
     }
     return min_sdf < C.trunc;
+}
+
+// Workgroup of a grid (workgroups per frame, frames) -> frame f, slot within the frame, stride of the slots.  Consecutive workgroups land on
+// consecutive XCDs, each with its own 4 MiB L2, and a candidate's 8 corner probes gather from its frame's 2.4 MB packed image.
+// The batch is nf x 8 work units (a frame's chunks c with c % 8 == q); XCD x takes units [x nf, (x + 1) nf) in frame-major
+// order, i.e. exactly nf / 8 frames' worth whatever nf is, and walks them frame after frame (dispatch order ~ j), so that its L2 holds ONE
+// 2.4 MB image at a time.  (Whole frames per XCD -- frames x, x + 8, ... -- left some XCDs with two frames and others with one whenever
+// nf is not a multiple of 8: a 14-frame batch took as long as a 16-frame one.)
+__device__ __forceinline__ void select_workgroup(int& f, int& wslot, int& wstride) {
+    const int nf = (int)gridDim.y, id = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+    const int per_unit = (int)gridDim.x >> 3;        // workgroups per unit
+    const int x = id & 7, j = id >> 3;               // j = 0 .. nf * per_unit - 1 on this XCD
+    const int u = x * nf + j / per_unit;             // global unit
+    f = u >> 3;
+    wslot = (u & 7) + 8 * (j % per_unit);            // 0 .. grid.x - 1; slot 0 of a frame also publishes the frame's statistics
+    wstride = (int)gridDim.x;
 }
 
 #ifndef KB_MINWAVES
@@ -361,27 +376,11 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select(BatchInv B, CamPara
     __shared__ unsigned s_nsurv, s_nfirst, s_nrec, s_base[2];
     __shared__ unsigned s_surv[kSBPerWg];
     __shared__ int s_first[kSBPerWg * kSBVol];
-    __shared__ unsigned short s_fpos[kSBPerWg * kSBVol]; // band (3 bits) | rank within the workgroup's entries of that band << 3
-    __shared__ unsigned s_bcnt[kBands], s_bbase[kBands];
     __shared__ int s_rslot[kSBPerWg * kSBVol];
     __shared__ unsigned long long s_rcand[kSBPerWg * kSBVol];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // Workgroup -> (frame, slot within the frame).  Consecutive workgroups land on consecutive XCDs, each with its own 4 MiB
-    // L2, and a candidate's 8 corner probes gather from its frame's 2.4 MB packed image.
-    // The batch is nf x 8 work units (a frame's chunks c with c % 8 == q); XCD x takes units [x nf, (x + 1) nf) in frame-major
-    // order, i.e. exactly nf / 8 frames' worth whatever nf is, and walks them frame after frame (dispatch order ~ j), so that its L2 holds ONE
-    // 2.4 MB image at a time.  (Whole frames per XCD -- frames x, x + 8, ... -- left some XCDs with two frames and others with one whenever
-    // nf is not a multiple of 8: a 14-frame batch took as long as a 16-frame one.)
     int f, wslot, wstride;
-    {
-        const int nf = (int)gridDim.y, id = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-        const int per_unit = (int)gridDim.x >> 3;        // workgroups per unit
-        const int x = id & 7, j = id >> 3;               // j = 0 .. nf * per_unit - 1 on this XCD
-        const int u = x * nf + j / per_unit;             // global unit
-        f = u >> 3;
-        wslot = (u & 7) + 8 * (j % per_unit);            // 0 .. grid.x - 1; slot 0 of a frame also publishes the frame's statistics
-        wstride = (int)gridDim.x;
-    }
+    select_workgroup(f, wslot, wstride);
     const float* M = B.f[f].m;
     const uint2* img = pimg + (size_t)f * C.width * C.height;
     const int tw = tiles_w(C.width), th = tiles_h(C.height);
@@ -391,11 +390,7 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select(BatchInv B, CamPara
     if (tid == 0) {
         s_nsurv = 0u; s_nfirst = 0u; s_nrec = 0u;
     }
-    if (tid < kBands) s_bcnt[tid] = 0u;
     __syncthreads();
-    // full batches file a block under the image band (eighths of the image height) it is first seen in; see kBands
-    const bool bands = KC_BANDS != 0 && (int)gridDim.y >= KC_STEAL_MIN_FRAMES && record == 0;
-    const float band_scale = 8.0f / (float)(C.width * C.height);
     const int i0 = s_range[0], j0 = s_range[1], k0 = s_range[2];
     int ni = s_range[3], nj = s_range[4], nk = s_range[5];
     unsigned long long ncand = (unsigned long long)((long long)ni * nj * nk);
@@ -438,12 +433,11 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select(BatchInv B, CamPara
             const int sk = (int)(sb - q1 * nsk), sj = (int)(q1 - q2 * nsj), si = (int)q2;
             const int ci = si * kSB + (lane >> 4), cj = sj * kSB + ((lane >> 2) & 3), ck = sk * kSB + (lane & 3); // position in the range
             bool first = false, rec = false;
-            int pool_idx = -1, band = 0;
+            int pool_idx = -1;
             if (ci < ni && cj < nj && ck < nk) {
                 const int bi = i0 + ci, bj = j0 + cj, bk = k0 + ck;
                 const float bx = (float)bi * cube_res, by = (float)bj * cube_res, bz = (float)bk * cube_res;
-                int pmax; // the lowest on-image corner (largest pixel index): files the block under an image band below
-                if (block_selected<FAST>(C, M, img, bx, by, bz, o_lo, o_hi, pmax)) {
+                if (block_selected<FAST>(C, M, img, bx, by, bz, o_lo, o_hi)) {
                     if (!key_in_range(bi, bj, bk)) {
                         atomicOr(&st->overflow, 8u);
                     } else {
@@ -452,8 +446,6 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select(BatchInv B, CamPara
                         if (pool_idx >= 0) {
                             first = atomicOr(&V.bmask[pool_idx], fbit) == (bmask_t)0;
                             rec = record != 0;
-                            // the image row of the block's lowest on-image corner (pixel index / pixels per band; a heuristic, any band is correct)
-                            if (bands) band = min(kBands - 1, (int)((float)max(pmax, 0) * band_scale));
                         }
                     }
                 }
@@ -465,11 +457,7 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select(BatchInv B, CamPara
                 unsigned base = 0;
                 if (lane == 0) base = atomicAdd(&s_nfirst, (unsigned)__popcll(m_a));
                 base = __shfl(base, 0, 64);
-                if (first) {
-                    const unsigned k = base + __popcll(m_a & below);
-                    s_first[k] = pool_idx;
-                    s_fpos[k] = (unsigned short)((unsigned)band | ((bands ? atomicAdd(&s_bcnt[band], 1u) : k) << 3));
-                }
+                if (first) s_first[base + __popcll(m_a & below)] = pool_idx;
             }
             if (m_b) {
                 unsigned base = 0;
@@ -486,19 +474,15 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select(BatchInv B, CamPara
         __syncthreads();
         // ---- one global append per workgroup and list
         const unsigned nfirst = s_nfirst, nrec = s_nrec;
-        if (tid < kBands) { // one global append per list
-            const unsigned c = bands ? s_bcnt[tid] : (tid == 0 ? nfirst : 0u);
-            s_bbase[tid] = c ? atomicAdd(&st->n_list[tid], c) : 0u;
-        }
+        if (tid == 64) s_base[0] = nfirst ? atomicAdd(&st->n_blist, nfirst) : 0u; // (wave 1: the two appends' round trips overlap)
         if (tid == 0) {
             s_base[1] = nrec ? atomicAdd(&st->n_rec, nrec) : 0u;
             s_nsurv = 0u;
         }
         __syncthreads();
         for (unsigned k = (unsigned)tid; k < nfirst; k += 256u) {
-            const unsigned fp = s_fpos[k], b = fp & 7u;
-            const unsigned pos = s_bbase[b] + (fp >> 3);
-            if (pos < V.max_blocks) V.blist[(size_t)b * V.max_blocks + pos] = s_first[k];
+            const unsigned pos = s_base[0] + k;
+            if (pos < V.max_blocks) V.blist[pos] = s_first[k];
         }
         for (unsigned k = (unsigned)tid; k < nrec; k += 256u) {
             const unsigned pos = s_base[1] + k;
@@ -506,8 +490,7 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select(BatchInv B, CamPara
         }
         __syncthreads(); // the lists are reused by the next chunk
         if (tid == 0) { s_nfirst = 0u; s_nrec = 0u; }
-        if (tid < kBands) s_bcnt[tid] = 0u;
-        // (the next chunk's coarse test does not touch s_nfirst / s_nrec / s_bcnt; its __syncthreads orders the reset before their next use)
+        // (the next chunk's coarse test does not touch s_nfirst / s_nrec; its __syncthreads orders the reset before their next use)
     }
 }
 
@@ -549,16 +532,8 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select_vote(BatchInv B, Ca
     __shared__ unsigned s_vn[3], s_vsb[3][32]; // the survivors of three consecutive rounds (one barrier per round)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < 3) s_vn[tid] = 0u;
-    int f, wslot, wstride; // workgroup -> (frame, slot within the frame): whole frames per XCD, as in k_select
-    {
-        const int nf = (int)gridDim.y, id = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-        const int per_unit = (int)gridDim.x >> 3;
-        const int x = id & 7, j = id >> 3;
-        const int u = x * nf + j / per_unit;
-        f = u >> 3;
-        wslot = (u & 7) + 8 * (j % per_unit);
-        wstride = (int)gridDim.x;
-    }
+    int f, wslot, wstride;
+    select_workgroup(f, wslot, wstride);
     const float* M = B.f[f].m;
     const uint2* img = pimg + (size_t)f * C.width * C.height;
     const int tw = tiles_w(C.width), th = tiles_h(C.height);
@@ -641,8 +616,7 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select_vote(BatchInv B, Ca
             const int bi = oi + si * kSB + (lane >> 4), bj = oj + sj * kSB + ((lane >> 2) & 3), bk = ok + sk * kSB + (lane & 3);
             bool selected = false;
             if (bi >= i0 && bi < i0 + ni && bj >= j0 && bj < j0 + nj && bk >= k0 && bk < k0 + nk) { // a candidate of this frame
-                int pmax;
-                selected = block_selected<FAST>(C, M, img, (float)bi * cube_res, (float)bj * cube_res, (float)bk * cube_res, o_lo, o_hi, pmax);
+                selected = block_selected<FAST>(C, M, img, (float)bi * cube_res, (float)bj * cube_res, (float)bk * cube_res, o_lo, o_hi);
             }
             if (vote) { // the frame's word for this super-block
                 const unsigned long long word = __ballot(selected);
@@ -663,7 +637,7 @@ __global__ __launch_bounds__(256, KB_MINWAVES) void k_select_vote(BatchInv B, Ca
             }
             const unsigned long long got = __ballot(slot >= 0);
             unsigned base = 0;
-            if (lane == 0 && got) base = atomicAdd(&st->n_list[0], (unsigned)__popcll(got));
+            if (lane == 0 && got) base = atomicAdd(&st->n_blist, (unsigned)__popcll(got));
             base = __shfl(base, 0, 64);
             if (slot >= 0) {
                 const unsigned pos = base + (unsigned)__popcll(got & ((1ULL << lane) - 1ULL));
@@ -790,7 +764,7 @@ __global__ __launch_bounds__(64 * kMergeWords) void k_select_merge(VolView V, St
         if (tid == 0) {
             unsigned n = 0;
             for (int w = 0; w < kMergeWords; ++w) { s_wp[w] = n; n += s_wc[w]; }
-            s_base = atomicAdd(&st->n_list[0], n);
+            s_base = atomicAdd(&st->n_blist, n);
         }
         __syncthreads();
         if (slot >= 0) {
@@ -819,7 +793,7 @@ int launch_select(op_volume* v, const BatchInv& I, const CamParams& C, int nf, b
     const VolView V = v->view();
     if (cube_keys)
         hipLaunchKernelGGL(k_mark_cubes, dim3((n_cubes + 255u) / 256u), dim3(256), 0, v->stream, V, v->state, cube_keys, n_cubes);
-    else if (KB_VOTE && KC_BANDS == 0 && !record && nf >= (v->select_mode > 0 ? 2 : KB_VOTE_MIN_FRAMES) && v->select_mode != OP_VOLUME_SELECT_DIRECT) { // (an explicit limit: every batch of >= 2 frames) // several frames: they record their selections, one pass claims every block once
+    else if (KB_VOTE && !record && nf >= (v->select_mode > 0 ? 2 : KB_VOTE_MIN_FRAMES) && v->select_mode != OP_VOLUME_SELECT_DIRECT) { // (an explicit limit: every batch of >= 2 frames) // several frames: they record their selections, one pass claims every block once
         // the frames' voting words (64 MB): only a volume that takes this path ever has them (PrepareCubes / ComputeBounding volumes, short batches, the
         // many small sub-map volumes of a DenseSlam run do not)
         if (!v->sbits) OP_HIP(op::cached_malloc((void**)&v->sbits, (size_t)kMaxBatch * kVoteCap * sizeof(unsigned long long)));

@@ -134,7 +134,7 @@ int vol_grow(op_volume* v, unsigned long long want, unsigned n_valid) {
     bmask_t* bmask = nullptr;
     hipError_t e = op::cached_malloc((void**)&pool, sizeof(float) * kBlockFloats * (size_t)new_max);
     if (e == hipSuccess) e = op::cached_malloc((void**)&keys, sizeof(int) * 3 * (size_t)new_max);
-    if (e == hipSuccess) e = op::cached_malloc((void**)&blist, sizeof(int) * (size_t)(KC_BANDS ? kBands : 1) * (size_t)new_max);
+    if (e == hipSuccess) e = op::cached_malloc((void**)&blist, sizeof(int) * (size_t)new_max);
     if (e == hipSuccess) e = op::cached_malloc((void**)&sel_list, sizeof(int) * (size_t)new_max);
     if (e == hipSuccess) e = op::cached_malloc((void**)&sel_cand, sizeof(unsigned long long) * (size_t)new_max);
     if (e == hipSuccess) e = op::cached_malloc((void**)&tkeys, sizeof(unsigned long long) * (size_t)new_table);
@@ -852,7 +852,7 @@ int op_volume_create(const op_camera* cam, float voxel_res, float truncation, fl
     OP_HIP_C(op::cached_malloc((void**)&v->tkeys, sizeof(unsigned long long) * (size_t)v->table_size));
     OP_HIP_C(op::cached_malloc((void**)&v->tvals, sizeof(int) * (size_t)v->table_size));
     OP_HIP_C(op::cached_malloc((void**)&v->bmask, sizeof(bmask_t) * (size_t)v->table_size));
-    OP_HIP_C(op::cached_malloc((void**)&v->blist, sizeof(int) * (size_t)(KC_BANDS ? kBands : 1) * (size_t)v->max_blocks));
+    OP_HIP_C(op::cached_malloc((void**)&v->blist, sizeof(int) * (size_t)v->max_blocks));
     OP_HIP_C(op::cached_malloc((void**)&v->sel_partial, sizeof(unsigned long long) * kPartialGrid));
     OP_HIP_C(op::cached_malloc((void**)&v->keys, sizeof(int) * 3 * (size_t)v->max_blocks));
     OP_HIP_C(op::cached_malloc((void**)&v->pool, sizeof(float) * kBlockFloats * (size_t)v->max_blocks));

@@ -97,30 +97,14 @@ struct KaFwd { PoseFwd f[kKaFrames]; };            // the slice of a BatchFwd on
 struct BatchInv { PoseInv f[kMaxBatch]; };
 struct BatchPtrs { const void* depth[kMaxBatch]; const unsigned char* rgb[kMaxBatch]; }; // device images of each frame
 
-#ifndef KC_SHARES
-#define KC_SHARES 8
-#endif
-constexpr int kKcShares = KC_SHARES; // k_integrate: the batch list is dealt to this many draw counters (a multiple of 8: workgroup b draws from share b % kKcShares, on XCD b % 8)
-static_assert(kKcShares % 8 == 0 && kKcShares <= 256, "whole XCDs");
-// The batch's block list can be kept as kBands lists (-DKC_BANDS=1).  A FULL batch (>= KC_STEAL_MIN_FRAMES frames) then files a block under the
-// horizontal image band its first selecting frame sees it in (k_select), and k_integrate's XCD x starts on list x: the workgroups of one XCD -- one
-// 4 MiB L2 -- gather from one eighth of every packed frame of the batch instead of from all of them.  Measured (round 4, profiles/r04_ab_bands.txt,
-// 32-frame launches of the bench scene): L2 misses fall by 16 % (exact update: FETCH_SIZE 469 -> 393 MB x 2 per launch) to 20 % (sum form: 410 -> 327),
-// the launch takes the SAME time with the exact update (676 us both ways) and 5 % LONGER with the sum form (524 -> 551 us): the kernel is bound by
-// instruction issue, not by its L2 misses (which the 256 MB MALL serves), and lists of unequal length drain less evenly than equal shares of one
-// list.  Not the default.  Short batches use list 0 only in either build, dealt to the XCDs in chunks.
-#ifndef KC_BANDS
-#define KC_BANDS 0
-#endif
+constexpr int kKcShares = 8; // k_integrate: the batch list is dealt to this many draw counters (workgroup b draws from share b % 8 first, on XCD b % 8)
 #ifndef KC_STEAL_MIN_FRAMES
 #define KC_STEAL_MIN_FRAMES 24
 #endif
-constexpr int kBands = 8;
-static_assert(kBands == kKcShares, "one list per draw counter");
 constexpr int kKcTSlots = 256; // k_integrate's workgroup b reports its duration to slot b % 256 (atomics on one address serialise at ~100 ns each)
 struct State {
     // (the first 32 bytes are what the host's synchronous paths read: StateHead below)
-    unsigned n_batch;   // (unused since the batch list became kBands lists: n_list below)
+    unsigned pad0;
     unsigned overflow;  // bit0 pool full, bit1 table full, bit2 bbox too large, bit3 coordinate range
     unsigned n_rec;     // PrepareCubes record mode: entries in sel_list / sel_cand
     unsigned fail_seq;  // sequence number of the batch that first ran out of pool / table space (valid while overflow & 3)
@@ -143,11 +127,12 @@ struct State {
     unsigned acc[kMaxBatch][kAccSlots][8]; // kAccSlots sets per frame (workgroup x uses set x % kAccSlots): atomics on ONE
                                             // address serialise at ~100 ns each, 300 of them cost KA 35 us
     unsigned kc_next[kKcShares * 16]; // KC dynamic scheduling: next list position of each share of the batch list (one cache line each)
-    unsigned n_list[kBands];          // lengths of the batch's block lists (list b = blist + b * max_blocks); a short batch only fills list 0
+    unsigned n_blist;                 // length of the batch's block list (VolView::blist); may exceed max_blocks (appends past the end are dropped), readers clamp it
+    unsigned pad1[7];                 // (spare)
     int sel_rng[kMaxBatch][8];        // k_select_vote -> k_select_merge: first super-block (absolute) and extent in super-blocks of a frame's words ([3..5] = 0: none)
 };
 
-struct StateHead { unsigned n_batch, overflow, n_rec, fail_seq, cur_seq, pad[3]; }; // = the first 32 bytes of State
+struct StateHead { unsigned pad0, overflow, n_rec, fail_seq, cur_seq, pad[3]; }; // = the first 32 bytes of State
 static_assert(sizeof(StateHead) == 32 && offsetof(State, stat_frames) == 32, "StateHead mirrors the head of State");
 
 struct VolView {
@@ -159,7 +144,7 @@ struct VolView {
     unsigned max_blocks;
     unsigned* n_blocks;
     bmask_t* bmask;            // per TABLE slot: which frames of the current batch selected the block
-    int* blist;                // table slots touched by the current batch: kBands lists of max_blocks entries each (State::n_list)
+    int* blist;                // table slots touched by the current batch: max_blocks entries (State::n_blist of them in use)
     int* sel_list;             // record mode (PrepareCubes): table slot (translated to pool slot by k_finish_select) + candidate rank
     unsigned long long* sel_cand;
 };

@@ -1030,6 +1030,66 @@ def test_selection_with_frames_far_apart(oracle):
         _compare(oracle, ov, hv)
 
 
+def test_batch_list_edge_lengths(oracle):
+    """The batch's block list at the lengths where its arithmetic can go wrong, every batch one IntegrateSequence call into a fresh volume of a
+    40 x 30 pixel camera, keys, voxels and counters bit for bit the oracle's:
+    * batches of 1, 23, 24 and 32 frames -- either side of KC_STEAL_MIN_FRAMES (k_integrate deals the list in chunks below it, in eighths with
+      stealing from it on) -- with the selection modes "auto" (k_select for one frame, k_select_vote + k_select_merge for the others) and "direct"
+      (k_select's append for all of them);
+    * a 24-frame batch that sees one 2 x 2 pixel patch from one pose: a list of fewer than eight blocks, so a share is one position, most
+      shares are empty and the steal step finds nothing;
+    * a 2-frame batch whose list length is no multiple of 32: the last chunk is partly filled."""
+    import torch
+    dev = torch.device("cuda:0")
+    cam = small_camera(16)
+    w, h = cam[4], cam[5]
+    assert (w, h) == (40, 30)
+    poses = np.stack([S.room_pose(100 + k) for k in range(32)]).astype(np.float32)
+    rendered = [S.room_render(p, width=w, height=h, fx=cam[0], fy=cam[1], cx=cam[2], cy=cam[3]) for p in poses]
+    dn, cn = np.stack([r[0] for r in rendered]), np.stack([r[1] for r in rendered])
+
+    def check(ov, depth, rgb, pose, sel, upd, modes):
+        """one batch per mode into a fresh volume, against the oracle volume ov (which has fused exactly these frames)"""
+        n = len(pose)
+        dd, cc = torch.from_numpy(depth).to(dev), torch.from_numpy(rgb).to(dev)
+        for mode in modes:
+            _ov, hv = _mk(oracle, 0.01, cam=cam)
+            hv.SetSelectMode(mode)
+            hv.IntegrateSequence(dd, cc, pose)
+            st = hv.Stats()
+            print("batch of %d, mode %s: %s" % (n, mode, st))
+            assert st["launches"] == 1 and st["frames"] == n and st["blocks_selected"] == sel and st["voxels_updated"] == upd, (n, mode, st)
+            _compare(oracle, ov, hv)
+        return st
+
+    # batch sizes: the oracle fuses the 32 frames once, every batch is a prefix of them
+    ov, _ = _mk(oracle, 0.01, cam=cam)
+    sel = upd = 0
+    for k in range(32):
+        ns, _vis, nu = ov.integrate(dn[k], cn[k], poses[k])
+        sel += ns; upd += nu
+        if k + 1 in (1, 23, 24, 32):
+            check(ov, dn[:k + 1], cn[:k + 1], poses[:k + 1], sel, upd, ("auto", "direct"))
+        if k + 1 == 2:   # partly filled last chunk (two frames: "auto" claims directly, the explicit limit votes and merges)
+            keys, _vox = ov.export()
+            assert len(keys) > 32 and len(keys) % 32 != 0, len(keys)
+            check(ov, dn[:2], cn[:2], poses[:2], sel, upd, ("auto", 1 << 18))
+
+    # near-empty list: 24 frames with the colours above, all from the first pose, the depth zero except one patch
+    patch = np.zeros((24, h, w), np.float32)
+    patch[:, h // 2:h // 2 + 2, w // 2:w // 2 + 2] = 1.1
+    same = np.repeat(poses[:1], 24, axis=0)
+    ov, _ = _mk(oracle, 0.01, cam=cam)
+    sel = upd = 0
+    for k in range(24):
+        ns, _vis, nu = ov.integrate(patch[k], cn[k], same[k])
+        sel += ns; upd += nu
+    keys, _vox = ov.export()
+    assert 1 <= len(keys) < 8, len(keys)
+    st = check(ov, patch, cn[:24], same, sel, upd, ("auto", "direct"))
+    assert 1 <= st["blocks_selected"] / st["frames"] < 8, st
+
+
 def test_released_pools_are_kept_for_reuse_up_to_the_configured_limit():
     """A destroyed volume's block pool (2.7 GB at the default capacity) stays with the library for the next volume -- the reference's
     drivers make a CubeHandler per submap and per Transform -- until op_release_cached_memory, or not at all with the limit at 0
