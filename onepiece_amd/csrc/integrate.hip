@@ -79,15 +79,19 @@ __device__ __forceinline__ void voxel_update(float& s, float& w, float& c0, floa
     if (PLAIN) {
         // TSDFVoxel::IsValid (TSDFVoxel.h:75-78) false -> weight 0 in the same formula (see the PLAIN comment above); LEAN: only w == 0 is invalid
         const float wv = LEAN ? w : ((s >= 1 || w <= 0) ? 0.0f : w);
+        // the four products first, the weight sum after them: it can then be formed in the weight's own register (no copy of the weight is kept alive)
+        const float ps = wv * s, p0 = wv * c0, p1 = wv * c1, p2 = wv * c2;
         const float wsum = wv + 1.0f;
         const float y = __builtin_amdgcn_rcpf(wsum);            // unrefined: div_int_rcp needs 1 ulp only
-        const float ns = wv * s + 1.0f * new_sdf;
-        const float m0 = wv * c0 + 1.0f * n0, m1 = wv * c1 + 1.0f * n1, m2 = wv * c2 + 1.0f * n2;
+        const float ns = ps + 1.0f * new_sdf;
+        const float m0 = p0 + 1.0f * n0, m1 = p1 + 1.0f * n1, m2 = p2 + 1.0f * n2;
         float qs = div_int_rcp(ns, wsum, y), q0 = div_int_rcp(m0, wsum, y), q1 = div_int_rcp(m1, wsum, y), q2 = div_int_rcp(m2, wsum, y);
         // outside div_int_rcp's hypotheses (see the PLAIN comment above).  | and not ||: two compares whose masks meet in scalar registers,
         // no divergent region for the right-hand side.  A numerator of exactly 0 would pass through div_int_rcp unharmed (q0 = r = 0), but
         // telling it from a tiny one costs a third compare per update; it is as rare as a tiny one and the division gives the same 0.
-        const bool slow = (wsum > 0x1p19f) | !(fabsf(ns) >= 0x1p-60f);
+        // LEAN: the weight half cannot fire.  The host launches this form only while lean_frames <= 2^19, counted with the running batch included
+        // (launch_integrate), a voxel gains at most one per fused frame, so no weight sum formed here exceeds 2^19: only the numerator is tested.
+        const bool slow = LEAN ? !(fabsf(ns) >= 0x1p-60f) : ((wsum > 0x1p19f) | !(fabsf(ns) >= 0x1p-60f));
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(slow) != 0ull, 0)) {
             if (slow) { qs = ns / wsum; q0 = m0 / wsum; q1 = m1 / wsum; q2 = m2 / wsum; }
         }
@@ -147,7 +151,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
     const float __attribute__((address_space(4)))* kargs =
         (const float __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr(); // BatchInv B = offset 0 of the kernarg segment
     (void)B;
-    unsigned upd = 0, sel = 0, chg = 0, nblk = 0;   // upd: per WAVE (a scalar count of hit ballots), the others per lane
+    unsigned upd = 0, sel = 0, chg = 0, nblk = 0;   // upd and (exact update) chg: per WAVE (scalar counts of hit ballots), the others per lane
     // XCD-aware order (workgroup b runs on XCD b % 8, each XCD has its own 4 MiB L2; blocks that gather the same pixels should meet in one L2)
     // and dynamic scheduling (blocks differ in work: 1..32 frames touch them; the workgroups of an XCD DRAW list positions from one counter,
     // the next one before the current block is processed so that the atomic's round trip is hidden).  Two ways of dealing the batch list to
@@ -194,7 +198,13 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
             }
             const float px = ((float)kx * 8.0f) * C.res + ox;
             const float py = ((float)ky * 8.0f) * C.res + oy;
+            // voxels to write back.  Exact update: the hit masks are already in scalar registers, so one wave-uniform 64-bit mask per z collects
+            // them (no per-lane v_or per update); the stores run under it and its population count is the wave's share of voxels_written.
+            // Sum form: per lane, known only after the frames.
             unsigned changed = 0u;
+            unsigned long long changed_m[ZT];
+#pragma unroll
+            for (int z = 0; z < ZT; ++z) changed_m[z] = 0ull;
             // sum form: sdf sum, byte sums of colour channels 0 and 2 in the two halves of one word, of channel 1 in the low half of another whose
             // high half counts the observations (<= 64 frames x 255 < 2^16)
             float ssum[ZT];
@@ -234,15 +244,16 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                     const bool seen = d > 0, near = fabsf(new_sdf) < C.trunc, hit = seen & near;
                     // the wave's hits, counted where the masks already are: control flow is wave-uniform here and every lane of the wave is live.
                     // (The ballot of each compare IS its scalar mask; the ballot of their conjunction would be rebuilt from a per-lane 0 / 1.)
-                    upd += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(seen) & __builtin_amdgcn_ballot_w64(near));
+                    const unsigned long long hits = __builtin_amdgcn_ballot_w64(seen) & __builtin_amdgcn_ballot_w64(near);
+                    upd += (unsigned)__builtin_popcountll(hits);
                     if (SUMF) { // branch-free: an observation that misses adds zeros
                         ssum[z] += hit ? new_sdf : 0.0f;
                         const unsigned t = hit ? rec[z].y : 0u;           // byte 3 of a packed pixel is 1 (k_prepare_frames): the count
                         acc02[z] += t & 0x00ff00ffu;
                         acc1n[z] += (t >> 8) & 0x00ff00ffu;
-                    } else if (hit) {
-                        changed |= 1u << z;
-                        voxel_update<kPlain, kPlain && LEAN>(s[z], w[z], c0[z], c1[z], c2[z], new_sdf, rec[z].y, s_c255);
+                    } else {
+                        changed_m[z] |= hits;
+                        if (hit) voxel_update<kPlain, kPlain && LEAN>(s[z], w[z], c0[z], c1[z], c2[z], new_sdf, rec[z].y, s_c255);
                     }
                 }
             };
@@ -293,8 +304,12 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
             }
 #pragma unroll
             for (int z = 0; z < ZT; ++z)
-                if ((changed >> z) & 1u) voxel_store(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
-            chg += (unsigned)__popc(changed);
+                if (SUMF ? ((changed >> z) & 1u) != 0u : ((changed_m[z] >> lane) & 1ull) != 0ull) voxel_store(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
+            if (SUMF) chg += (unsigned)__popc(changed);
+            else {
+#pragma unroll
+                for (int z = 0; z < ZT; ++z) chg += (unsigned)__builtin_popcountll(changed_m[z]);
+            }
             // The raycaster's block summaries (raycast.hip: k_rc_neighbours drops blocks by them before loading a voxel) describe exactly what is in
             // registers here -- the block's 512 voxels after the batch: the kernel that changes a block restates its summary, so views between fusions
             // find every block they meet described instead of starting from nothing (the host does not invalidate the summaries for such a batch).
@@ -344,7 +359,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
     if (lane == 0 && blockIdx.x < 4096) for (int k = 0; k < 8; ++k) g_kc_trace[((size_t)blockIdx.x * 4 + zg) * 8 + k] = kt_[k];
 #endif
     // per-workgroup counters into kPartialGrid slots
-    chg = wave_sum(chg);                                      // (upd is the wave's total already)
+    if (SUMF) chg = wave_sum(chg);                            // (upd is the wave's total already, and so is the exact update's chg)
     if (lane == 0) { s_cnt[zg][0] = upd; s_cnt[zg][1] = chg; }
     __syncthreads();
     if (tid == 0) {

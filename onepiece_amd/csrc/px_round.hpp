@@ -77,6 +77,8 @@ struct PxAxis {
     int exact;
     float k;   // c + 0.5 rounded to fp32
     float hc;  // certificate of the fast path (px_certified): 0.5 - B, or -1 where the certificate may not be used
+    float kb;  // folded certificate (px_certified_folded): c + 0.5 + B2, the first fp32 at or above c + 0.5 + B
+    float h2;  // ... and its threshold B2 + B rounded up, or 2 where the certificate may not be used
 };
 
 // ---- certified fast path (project_pixel<true>, -DOP_PX_CERTIFIED=0 builds without it) --------------------------------------
@@ -102,6 +104,44 @@ OP_HD double px_cert_bound(double T, double absK) {
     const double S = T / (1.0 - u), Q = (S + absK) / (1.0 - dy);
     return (u * S + Q * (dy + u) + 0x1p-22) * (1.0 + 0x1p-40); // (the last factor covers the rounding of this double evaluation)
 }
+// ---- folded certificate (what project_pixel<true> uses; px_certified above stays as the two-sided statement of the same thing) ----------
+// The two-sided test costs v_fract, v_add -0.5 and a compare of the magnitude.  Shifting t' UP by a margin B2 >= B turns it into a
+// one-sided test, and the shift costs nothing when it is part of the FMA's constant:
+//     t'' = RN(nx * y + kb),   kb = an fp32 with B2 = kb - K >= B (exact in double: K = c + 0.5 and kb are close floats / half-integers),
+//     certified  <=>  fract(t'') > h2,   h2 >= B2 + B,   pixel u = trunc(t''), inside = (unsigned)u < extent.
+// Error, for -2 <= t'' <= T = extent + 1 (the sums whose pixel matters).  With s'' = nx y + kb (real, formed exactly inside the fma) the chain of
+// px_cert_bound applies with kb in K's place and NO |K' - K| term -- kb's rounding is not an error here, B2 is DEFINED as kb - K, whatever px_axis
+// had to round to get a float: s'' - B2 = nx y + K, t = a + K, so
+//     (t'' - B2) - t = (t'' - s'') + q (dq - ra),   |t'' - s''| <= 2^-24 |s''|,  |dq| <= dy = 2^-24 + 2^-39,  |ra| <= 2^-24.
+// Here |s''| <= |t''| / (1 - 2^-24), so s'' lies in [-L, S] with L = 2 / (1 - 2^-24), S = T / (1 - 2^-24) >= L, and q (1 + dq) = s'' - kb lies in
+// [-L - kb, S - kb]: |q| <= Qf = (max(|S - K|, |L + K|) + 1/4) / (1 - dy) for every kb in [K, K + 1/4] (px_axis refuses an axis whose B2 would exceed
+// 1/4).  px_cert_bound took |q| <= S + |K| over the whole window |t'| <= T instead; for a principal point near the middle of the image that is three
+// times what a sum in [-2, T] can have, and the far negative part of the window needs no such bound (last paragraph).  So
+//     |(t'' - B2) - t| < B := px_cert_bound_folded(T, K) = 2^-24 S + Qf (dy + 2^-24) + 2^-22,
+// the last term in reserve for denormal quotients (their RN is off by 2^-150 at most, not by a relative 2^-24).  For a certified t'' in [-2, T],
+// n = floor(t''), f = fract(t''):
+//  * n >= 0: f = t'' - n exactly.  t > t'' - B2 - B > n + h2 - B2 - B >= n, and t < t'' - B2 + B < n + 1 because B2 >= B: t lies in
+//    (n, n + 1), trunc(t) = n = trunc(t'').
+//  * -1 < t'' < 0 (v_cvt_i32_f32 gives 0; the reference's pixel 0 covers the reals (-1, 1)): v_fract returns RN(t'' + 1) clamped below 1, and
+//    RN(x) > h2 needs x > h2 (h2 is a float, RN is monotone): t'' + 1 > h2, t > t'' - B2 - B > -1 + h2 - B2 - B >= -1; and t < t'' - B2 + B
+//    <= t'' < 0: trunc(t) = 0.  (The downward shift, certified <=> fract < h2, fails exactly here: it would certify t'' = -1, fract 0,
+//    whose t lies in (-1, 0) -- pixel 0 -- while trunc(-1) = -1 says outside.  Upward, t'' = -1 and t'' = +-0 have fract 0: refused.)
+//  * -2 < t'' < -1 (t'' = -2 and -1 have fract 0 and are refused): f = t'' + 2 exactly, t lies in (-2, -1) as in the first case: trunc(t) = -1 =
+//    trunc(t''), outside on both paths.
+// Off the image, 2^23 > t'' > T or -2^23 < t'' < -2: with |q| <= (|s''| + |kb|) / (1 - dy) and extent, |K| < 2^20 the error is
+// |(t'' - B2) - t| < 2^-22 (|t''| + |K| + 1/4) + 2^-22 < 0.26 + 2^-22 |t''|.  t'' > extent + 1: t > t'' - 1/4 - 0.26 - 2^-22 t'' > extent (the left side
+// grows with t''): outside, and u = trunc(t'') >= extent + 1 says so.  t'' < -2: t < t'' + 0.26 + 2^-22 |t''| < -1: trunc(t) <= -1, and u <= -2.
+// |t''| >= 2^23 has fract 0, NaN has fract NaN (so has +-inf, whose v_cvt_i32_f32 saturates outside the image anyway), h2 = 2 exceeds every fract:
+// all refused.
+// Width of the accepted set per unit interval: 1 - h2 = 1 - 2B - (B2 - B) with 0 <= B2 - B < ulp(kb) (+ one ulp of h2's own rounding).  With the
+// bound of the two-sided form the fold would cost up to one ulp(K) of width (3e-5 at K ~ 320, a tenth of its 2B: 3.42 % -> 3.76 % of wave-
+// projections took the exact fallback on the bench frames); with B halved by the argument above the rate falls instead (profiles/kc_trim_ab.txt).
+OP_HD double px_cert_bound_folded(double T, double K) {
+    const double u = 0x1p-24, dy = u + 0x1p-39;
+    const double S = T / (1.0 - u), L = 2.0 / (1.0 - u);
+    const double Qf = (fmax(fabs(S - K), fabs(L + K)) + 0.25) / (1.0 - dy);
+    return (u * S + Qf * (dy + u) + 0x1p-22) * (1.0 + 0x1p-40); // (the last factor covers the rounding of this double evaluation)
+}
 
 OP_HD PxAxis px_axis(float c, int extent) {
     PxAxis s;
@@ -119,6 +159,17 @@ OP_HD PxAxis px_axis(float c, int extent) {
         if ((double)hc > 0.5 - B) hc = nextafterf(hc, 0.0f); // rounded down: never wider than derived
         s.hc = hc;
     }
+    s.kb = s.k;
+    s.h2 = 2.0f;
+    if (s.exact) {
+        const double B2min = px_cert_bound_folded((double)extent + 1.0, K);
+        float kb = (float)(K + B2min);
+        if ((double)kb < K + B2min) kb = nextafterf(kb, INFINITY);  // rounded up: B2 = kb - K >= B
+        const double B2 = (double)kb - K;                           // exact
+        float h2 = (float)(B2 + B2min);
+        if ((double)h2 < B2 + B2min) h2 = nextafterf(h2, INFINITY); // rounded up: never wider than derived
+        if (B2 <= 0.25) { s.kb = kb; s.h2 = h2; }
+    }
     return s;
 }
 
@@ -135,12 +186,16 @@ OP_HD float px_fract(float t) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_fractf(t); // v_fract_f32: t - floor(t) clamped below 1; NaN for NaN and +-inf
 #else
-    const float f = t - floorf(t);
-    return f < 1.0f ? f : 0x1.fffffep-1f;
+    const float f = t - floorf(t); // (inf - inf = NaN, as on the device)
+    return f >= 1.0f ? 0x1.fffffep-1f : f;
 #endif
 }
 OP_HD bool px_certified(float t, const PxAxis& s) {
     return fabsf(px_fract(t) - 0.5f) < s.hc; // distance of t to the nearest integer > 0.5 - hc >= B; false for NaN
+}
+// The folded certificate on t'' = fma(f*X, y, kb) (see above): true when trunc(t'') is the pixel px_pixel_sp gives, inside or outside.
+OP_HD bool px_certified_folded(float t2, const PxAxis& s) {
+    return px_fract(t2) > s.h2; // false for NaN
 }
 OP_HD bool px_pixel_dp(float a, float c, int extent, int& u) {
     u = px_round_dp(a, c);

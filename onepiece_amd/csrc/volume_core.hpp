@@ -246,8 +246,8 @@ static __device__ unsigned long long g_px_waves[2];
 #endif
 
 // Pixel index v * width + u of the projection, or -1 when it falls outside the image (Integrator.cpp:20-21,61-63).
-// FAST (px_axis exact on both axes), certified path (px_round.hpp px_cert_bound): t' = fma(f*X, y, c + 0.5) per axis, the pixel is
-// trunc(t') when t' is farther than B from every integer; a wave with any lane that is not (roughly 1 in 10^3..10^4 lane-axes, or |Z|
+// FAST (px_axis exact on both axes), certified path (px_round.hpp px_cert_bound, folded form): t'' = fma(f*X, y, c + 0.5 + B2) per axis, the
+// pixel is trunc(t'') when fract(t'') > h2, i.e. when the unshifted sum is farther than B from every integer; a wave with any lane that is not (roughly 1 in 10^3..10^4 lane-axes, or |Z|
 // outside the window, or NaN) runs the exact sequence for those lanes out of line.
 template <bool FAST>
 __device__ __forceinline__ int project_pixel(const CamParams& C, float X, float Y, float Z) {
@@ -259,11 +259,12 @@ __device__ __forceinline__ int project_pixel(const CamParams& C, float X, float 
         float y = __builtin_amdgcn_rcpf(Z);
         const float e = __builtin_fmaf(-Z, y, 1.0f);
         y = __builtin_fmaf(e, y, y);
-        const float tx = __builtin_fmaf(nx, y, C.ax.k), ty = __builtin_fmaf(ny, y, C.ay.k);
+        // the certificate's margin travels in the FMA's constant (kb = c + 0.5 + B2): one v_fract and one compare per axis certify the lane
+        const float tx = __builtin_fmaf(nx, y, C.ax.kb), ty = __builtin_fmaf(ny, y, C.ay.kb);
         // 2^-60 <= |Z| < 2^60: the biased exponent (bits 24..31 of the sign-less word shifted left once) in [67, 187)
         const bool win = (__float_as_uint(Z) << 1) - (67u << 24) < (120u << 24);
-        const bool cx = px_certified(tx, C.ax), cy = px_certified(ty, C.ay);
-        u = (int)tx; v = (int)ty; // v_cvt_i32_f32 truncates toward zero; a certified |t'| is below 2^23
+        const bool cx = px_certified_folded(tx, C.ax), cy = px_certified_folded(ty, C.ay);
+        u = (int)tx; v = (int)ty; // v_cvt_i32_f32 truncates toward zero; a certified |t''| is below 2^23
         // (one ballot per compare: each is the compare's own mask, and the ANDs stay scalar -- a ballot of the combined bool costs
         // a v_cndmask + v_cmp to rebuild the mask; a && chain becomes nested branches)
         const unsigned long long ok = __builtin_amdgcn_ballot_w64(win) & __builtin_amdgcn_ballot_w64(cx) & __builtin_amdgcn_ballot_w64(cy);
