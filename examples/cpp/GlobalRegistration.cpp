@@ -4,7 +4,7 @@
 // library's own public functions in the order registration::RansacRegistration calls them; parameters default to DenseSlam's (DenseSlam.h:49-68).
 //
 //   GlobalRegistration <source.ply> <target.ply> | --synthetic   [--path host|device] [--dump DIR] [--max-iteration 40000] [--voxel 0.05]
-//                      [--as-given] [--features-only] [--load-features DIR]
+//                      [--as-given] [--features-only] [--load-features DIR] [--knn 100] [--search-radius 0.25]
 //
 //   --synthetic       two views of an analytic room (a box with two spheres) rendered to depth and back-projected (op_points_from_depth through
 //                     PointCloud::LoadFromDepth); the source is the second view expressed in its own camera frame, so the transform that is
@@ -13,6 +13,7 @@
 //   --path            OP_RUNTIME_OPT_GLOBAL_REGISTRATION: host (default) or device
 //   --as-given        PLY clouds that carry normals are used as they are (no down-sampling)
 //   --features-only   stop after the features (no device is needed on the host path up to there)
+//   --knn, --search-radius   FPFH's neighbour count and radius (the radius is compared with squared distances); DenseSlam's 100 and 0.25
 //   --load-features   match with the features of an earlier --dump instead of the ones just computed
 //   --dump DIR        raw little-endian arrays (float32 / int32) and result.json with the sizes, the result and the time of every stage
 #include <chrono>
@@ -136,12 +137,14 @@ int main(int argc, char** argv) {
         else if (a == "--load-features" && i + 1 < argc) load_features = argv[++i];
         else if (a == "--max-iteration" && i + 1 < argc) r_para.max_iteration = std::atoi(argv[++i]);
         else if (a == "--voxel" && i + 1 < argc) r_para.voxel_len = static_cast<float>(std::atof(argv[++i]));
+        else if (a == "--knn" && i + 1 < argc) r_para.max_nn = std::atoi(argv[++i]);
+        else if (a == "--search-radius" && i + 1 < argc) r_para.search_radius = static_cast<float>(std::atof(argv[++i]));
         else if (a.compare(0, 2, "--") != 0) files.push_back(a);
         else { std::cout << "unknown argument " << a << std::endl; return 2; }
     }
-    if ((!synthetic && files.size() != 2) || (path != "host" && path != "device")) {
+    if ((!synthetic && files.size() != 2) || (path != "host" && path != "device") || r_para.max_nn < 1 || !(r_para.search_radius > 0)) {
         std::cout << "Usage: GlobalRegistration <source.ply> <target.ply> | --synthetic [--path host|device] [--dump DIR] [--max-iteration N] [--voxel L] [--as-given] "
-                     "[--features-only] [--load-features DIR]" << std::endl;
+                     "[--features-only] [--load-features DIR] [--knn K] [--search-radius R]" << std::endl;
         return 2;
     }
     if (op_runtime_set_option(OP_RUNTIME_OPT_GLOBAL_REGISTRATION, path == "device" ? 1 : 0) != OP_OK) { std::cout << op_last_error() << std::endl; return 3; }

@@ -34,15 +34,28 @@ void ParallelFor(size_t n, size_t grain, F f) {
     for (auto& x : th) x.join();
 }
 
-// neighbours of every point: squared distance strictly below r2, ascending (index breaks ties), at most max_n of them, the point itself first
+// THE CELL RULE (one formula, also in op_fpfh_compute of onepiece_amd/csrc/global_reg.hip): the cell of a coordinate p is
+// floor((double)p / c) with c = sqrt((double)r2) * (1 + 2^-20), in double.  Why two points that the float32 test d2 < r2 keeps are never two
+// cells apart on any axis: with D the true difference of the two floats on that axis, dx = fl(pj - pi) >= |D| (1 - 2^-24), fl(dx dx) >=
+// dx^2 (1 - 2^-24), and each of the two float additions of non-negative terms gives at least its larger term times (1 - 2^-24); so
+// D^2 <= d2 (1 - 2^-24)^-5 < r2 (1 + 6 * 2^-24), |D| < sqrt(r2) (1 + 2^-22) < c (1 - 2^-21).  The true quotients p / c of the two points
+// therefore differ by less than 1 - 2^-21.  A double quotient is off by at most 2^-53 |p / c|, which is below 2^-23 for every accepted index
+// (|p / c| < 1e9 < 2^30; sqrt and the product forming c add a few 2^-53 relative, far inside the 2^-21 margin), so the computed quotients
+// differ by less than 1 - 2^-21 + 2^-22 < 1 and their floors by at most 1.  A float quotient cannot give this: its own rounding, 2^-24 |p / c|,
+// reaches a whole cell at |p / c| = 2^24.  (Squares in the subnormal range are outside the argument: r2 and the coordinates are metres.)
+inline double NeighbourCellEdge(float r2) { return std::sqrt(static_cast<double>(r2)) * (1.0 + 1.0 / 1048576.0); }
+inline double NeighbourCell(float p, double edge) { return std::floor(static_cast<double>(p) / edge); }
+
+// neighbours of every point: squared distance strictly below r2, ascending (index breaks ties), at most max_n of them; the point itself is
+// among them at distance 0, first unless an exact duplicate has a lower index
 void RadiusNeighbours(const geometry::Point3List& pts, float r2, int max_n, std::vector<std::vector<int> >& out) {
     const size_t n = pts.size();
     out.assign(n, std::vector<int>());
     if (n == 0) return;
-    const float cell = std::sqrt(r2);
+    const double cell = NeighbourCellEdge(r2);
     std::unordered_map<geometry::Point3i, std::vector<int>, geometry::VoxelGridHasher> grid;
     auto cell_of = [cell](const geometry::Point3& p) {
-        return geometry::Point3i(static_cast<int>(std::floor(p(0) / cell)), static_cast<int>(std::floor(p(1) / cell)), static_cast<int>(std::floor(p(2) / cell)));
+        return geometry::Point3i(static_cast<int>(NeighbourCell(p(0), cell)), static_cast<int>(NeighbourCell(p(1), cell)), static_cast<int>(NeighbourCell(p(2), cell)));
     };
     for (size_t i = 0; i < n; ++i) grid[cell_of(pts[i])].push_back(static_cast<int>(i));
     ParallelFor(n, 256, [&](size_t lo, size_t hi) {
@@ -120,7 +133,10 @@ PairDescriptor ComputePairDescriptor(const geometry::Point3& ps, const geometry:
     result(3) = distance;
     result(1) = v.dot(nt);
     result(2) = u.dot(dir);
-    result(0) = static_cast<float>(std::atan2(w.dot(nt), u.dot(nt)));
+    // the atan2 operands as Eigen's (and the device's) sums form them, first product first and no leading +0: with a zero normal nt both are
+    // signed zeros, and atan2(+-0, -0) = +-pi where a sum started from +0 would always give atan2(+-0, +0) = +-0
+    const float y = (w(0) * nt(0) + w(1) * nt(1)) + w(2) * nt(2), x = (u(0) * nt(0) + u(1) * nt(1)) + u(2) * nt(2);
+    result(0) = static_cast<float>(std::atan2(y, x));
     return result;
 }
 

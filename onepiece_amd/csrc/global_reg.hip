@@ -4,6 +4,9 @@
 // separate multiply and add -- the library is built with -ffp-contract=off -- correctly rounded sqrt and divide), so that the class surface
 // can switch paths (OP_RUNTIME_OPT_GLOBAL_REGISTRATION) without changing a result.  The one exception is the atan2 of the first Darboux
 // angle: it is evaluated in double on the float operands and rounded once, where the host calls its libm's atan2f (see k_spfh).
+// What FPFH is pinned to, beyond the host path: exact radius neighbours (every point with float32 d2 < radius, by (d2, index)) followed by
+// the arithmetic of the reference's 3DFeature.cpp, stated independently in numpy by tests/global_registration_common.py (brute force, no
+// cells).  Not pinned: nanoflann's approximate radius search that the reference asks with 1024 checks, and the seeding of the RANSAC.
 //
 //   k_fpfh_neighbours   one wave per point: candidates of the 27 cells around the point, d2 < radius, exact top-knn by (d2, index)
 //   k_spfh              one wave per point: pair descriptor + three bins per neighbour, integer histogram in LDS
@@ -316,7 +319,9 @@ int op_fpfh_compute(const float* xyz, const float* normals, size_t n, int knn, f
     Scope s;
     OP_TRY(s.open(device));
     if (n == 0) return OP_OK;
-    // The cells are those of the host path: floor(p / sqrtf(radius)) per axis in float.  They are formed and sorted here, on the host, in
+    // The cells are those of the host path, the CELL RULE stated and argued at RadiusNeighbours of host/one_piece/src/GlobalRegistration.cpp:
+    // floor((double)p / c) per axis with c = sqrt((double)radius) * (1 + 2^-20), in double, so that two points with float32 d2 < radius are
+    // never two cells apart for any index accepted below (|p / c| < 1e9).  They are formed and sorted here, on the host, in
     // O(n log n) -- the cloud of a submap is a few thousand points; the candidate distances and the selection are the device's.
     std::vector<float> host_xyz;
     const float* hx = xyz;
@@ -325,13 +330,13 @@ int op_fpfh_compute(const float* xyz, const float* normals, size_t n, int knn, f
         OP_HIP(hipMemcpy(host_xyz.data(), xyz, n * 12, hipMemcpyDeviceToHost));
         hx = host_xyz.data();
     }
-    const float cell = std::sqrt(radius);
+    const double cell = std::sqrt((double)radius) * (1.0 + 1.0 / 1048576.0);
     std::vector<int> pcell(n * 3);
     long long lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     for (size_t i = 0; i < n; ++i)
         for (int a = 0; a < 3; ++a) {
-            const float f = std::floor(hx[3 * i + a] / cell);
-            if (!(std::fabs(f) < 1.0e9f)) return fail(OP_ERR_INVALID, "point %zu is not finite or too far from the origin for cells of %g", i, (double)cell);
+            const double f = std::floor((double)hx[3 * i + a] / cell);
+            if (!(std::fabs(f) < 1.0e9)) return fail(OP_ERR_INVALID, "point %zu is not finite or too far from the origin for cells of %g", i, cell);
             const int c = static_cast<int>(f);
             pcell[3 * i + a] = c;
             if (i == 0 || c < lo[a]) lo[a] = c;

@@ -316,7 +316,8 @@ def EstimateRigidTransformation(correspondence_set, device=0, finish="reference"
 def ComputeFPFHFeature(pcd, knn=100, radius=0.1, device=0, return_debug=False):
     """registration::ComputeFPFHFeature (Registration/3DFeature.cpp:86-130) on the GPU -> features [n,33] float32.
     `radius` is compared with SQUARED distances, as in the reference.  return_debug: also the neighbour lists
-    [n,knn] int32 (-1 padded, the point itself first) and the simplified histograms [n,33]."""
+    [n,knn] int32 (-1 padded, ascending by (squared distance, index): the point itself first unless an exact duplicate of it has
+    a lower index) and the simplified histograms [n,33]."""
     if not pcd.HasNormals():
         raise ValueError("ComputeFPFHFeature needs normals")
     n = len(pcd.points)

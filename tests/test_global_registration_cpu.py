@@ -118,3 +118,71 @@ def test_kernels_compile_for_gfx950_without_scratch(tmp_path):
     # device writes are vector stores and HIP atomics only: no scalar-unit instruction of the compiled code writes memory or touches the data cache
     scalar_writes = sorted(set(re.findall(r"^\s+(s_\w*(?:store|atomic|dcache)\w*)", asm, flags=re.M)))
     assert not scalar_writes, scalar_writes
+
+
+# ---- the host path against the independent statement of FPFH (exact radius neighbours + the arithmetic of 3DFeature.cpp) ------------------
+
+def _is_random(name):
+    return not (name.startswith("degenerate") or name == "adversarial")
+
+
+@pytest.mark.parametrize("name", G.CASE_NAMES)
+def test_host_path_against_the_reference(name, tmp_path):
+    """Neighbour lists equal to the brute-force search in order and count; SPFH / FPFH thirds 2 and 3 bit-identical to the float32 restatement;
+    third 1 by the one-bin rule.  The clumps run at every knn of CPU_CLUMP_KNN, everything else at DenseSlam's 100."""
+    p, n, knn, radius = G.case(name)
+    for k in (G.CPU_CLUMP_KNN if name.startswith("clump") else (knn,)):
+        got = G.path_features(str(tmp_path / ("knn%d" % k)), p, n, k, radius)
+        assert got["json"]["knn"] == k and np.array_equal(got["source_points"], p)
+        G.check_against_reference(G.case_reference(name, k), got, enforce_shares=name.startswith("room"))
+        G.check_list_properties(name, k, got)
+
+
+def test_the_reference_alone_stays_inside_the_caps():
+    """flagged <= 1 % and tainted <= 5 % of the room clouds' points depend on the input and the reference alone"""
+    for name in ("room source", "room target"):
+        ref = G.case_reference(name)
+        G.check_features(ref, ref, "source", enforce_shares=True)
+
+
+@pytest.mark.parametrize("name", G.CASE_NAMES)
+def test_float64_cross_check_of_the_restatement(name):
+    """spfh_reference's float32 bins against float64 bins wherever float64 is not within DELTA of a boundary.  Random inputs: at most 1 % of
+    the pairs are excluded.  Degenerate sets: exactly the constructed pairs are.  The adversarial cloud: every constructed pair is (duplicates
+    and the opposed normals on its lattice); its normals elsewhere are random, and what else is excluded stays under 1 % of the pairs."""
+    p, n, _knn, _radius = G.case(name)
+    nb = G.case_reference(name)["source_neighbours"]
+    excluded, share = G.float64_cross_check(p, n, nb, name)
+    pairs = max(int((nb[:, 1:] >= 0).sum()), 1)
+    if _is_random(name):
+        assert share <= 0.01, share
+    elif name == "adversarial":
+        constructed = G.adversarial_constructed(p, n, nb)
+        assert constructed.sum() > 1000 and not (constructed & ~excluded).any()
+        assert (excluded & ~constructed).sum() <= 0.01 * pairs, (excluded & ~constructed).sum()
+    else:
+        constructed = G.constructed_pairs(G.degenerate_sets()[name[len("degenerate: "):]][4], nb)
+        assert np.array_equal(excluded, constructed), (excluded.sum(), constructed.sum())
+
+
+def test_inputs_reach_what_they_are_built_for():
+    """the cell-edge clouds hold pairs on both sides of the radius; the far cloud's lists are neither empty nor cut; a clump's are cut; a
+    lower-indexed duplicate takes slot 0; d2 == radius is not a neighbour"""
+    for radius in G.CELL_EDGE_RADII:
+        p, _n, _knn, _r = G.case("cell edge %g" % radius)
+        a, b = p[0::9].astype(np.float32), p[1::9].astype(np.float32)      # the straddling pair of every group
+        d = b - a
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        assert (d2 < np.float32(radius)).any() and not (d2 < np.float32(radius)).all(), radius
+    m = (G.case_reference("far")["source_neighbours"] >= 0).sum(1)
+    print("far cloud: mean list length", m.mean())
+    assert 5 <= m.mean() <= 50
+    assert ((G.case_reference("clump 1025")["source_neighbours"] >= 0).sum(1) == 256).sum() >= 1025
+    nb = G.case_reference("degenerate: duplicates of earlier points")["source_neighbours"]
+    assert (nb[60:, 0] < 60).all() and (nb[:60, 0] == np.arange(60)).all()
+    nb = G.case_reference("degenerate: lattice with d2 == radius")["source_neighbours"]
+    assert (nb >= 0).sum(1).max() == 27 and (nb >= 0).sum(1).min() == 8                                     # 3^3 around an inner point, 2^3 at a corner
+    nb, p = G.case_reference("clump lattice")["source_neighbours"], G.case("clump lattice")[0]
+    rows = np.nonzero(nb[:, 100] >= 0)[0]
+    d, e = p[nb[rows, 99]] - p[rows], p[nb[rows, 100]] - p[rows]
+    assert len(rows) >= 513 and ((d * d).sum(1) == (e * e).sum(1)).any()                                                     # the cut at 100 falls inside a shell of tied d2

@@ -1,5 +1,6 @@
 """Global registration on the device against the host path (OP_RUNTIME_OPT_GLOBAL_REGISTRATION 0, run through examples/cpp/GlobalRegistration.bin)
-and, for the direct C-ABI entries, against the float32 numpy restatements of global_registration_common.py.
+and, for the direct C-ABI entries, against the float32 numpy restatements of global_registration_common.py; FPFH also against that module's
+independent statement (exact radius neighbours by brute force, then the arithmetic of the reference's 3DFeature.cpp).
 
 The one permitted difference is the first Darboux angle's bin for pairs that sit on a bin boundary (the host's atan2f is its libm's, the device
 rounds a double atan2 once): global_registration_common.check_features states the rule."""
@@ -178,3 +179,43 @@ def test_small_and_degenerate_sets_through_the_class_surface(plys, tmp_path):
         G.check_features(host, dev, "source", enforce_shares=False)
         if np.array_equal(host["source_fpfh"].view(np.uint32), dev["source_fpfh"].view(np.uint32)) and np.array_equal(host["target_fpfh"].view(np.uint32), dev["target_fpfh"].view(np.uint32)):
             _compare_tail(host, dev)
+
+
+# ---- the device path against the independent statement of FPFH ----------------------------------------------------------------------------
+
+def _device_dump(p, n, knn, radius):
+    fpfh, nb, spfh = R.ComputeFPFHFeature(R.PointCloud(p, n), knn=knn, radius=radius, return_debug=True)
+    return {"source_points": p, "source_normals": n, "source_neighbours": nb, "source_spfh": spfh, "source_fpfh": fpfh}
+
+
+@pytest.mark.parametrize("name", G.CASE_NAMES)
+def test_device_path_against_the_reference(name):
+    """The same clouds and the same assertions as the host path's test in test_global_registration_cpu.py: lists equal to the brute-force
+    search in order and count, thirds 2 and 3 bit-identical, third 1 by the one-bin rule.  The clumps at every knn of GPU_CLUMP_KNN."""
+    p, n, knn, radius = G.case(name)
+    for k in (G.GPU_CLUMP_KNN if name.startswith("clump") else (knn,)):
+        got = _device_dump(p, n, k, radius)
+        G.check_against_reference(G.case_reference(name, k), got, enforce_shares=name.startswith("room"))
+        G.check_list_properties(name, k, got)
+
+
+def test_device_memory_through_the_c_abi_equals_host_memory():
+    """op_fpfh_compute with OP_MEM_DEVICE inputs and outputs (torch tensors' data_ptr) against the OP_MEM_HOST call: bit for bit"""
+    import ctypes as C
+    import torch
+    from onepiece_amd import _lib as L
+    p, n, _knn, radius = G.case("cell edge 0.05")
+    knn = 65
+    want = _device_dump(p, n, knn, radius)
+    dp, dn = torch.from_numpy(p).cuda(), torch.from_numpy(n).cuda()
+    f = torch.full((len(p), 33), -7.0, dtype=torch.float32, device="cuda")
+    s = torch.full((len(p), 33), -7.0, dtype=torch.float32, device="cuda")
+    nb = torch.full((len(p), knn), -7, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    L.check(L.load().op_fpfh_compute(vp(dp), vp(dn), len(p), knn, float(radius), L.OP_MEM_DEVICE, 0, vp(f), vp(nb), vp(s)))
+    torch.cuda.synchronize()
+    assert np.array_equal(nb.cpu().numpy(), want["source_neighbours"])
+    assert np.array_equal(s.cpu().numpy().view(np.uint32), want["source_spfh"].view(np.uint32))
+    assert np.array_equal(f.cpu().numpy().view(np.uint32), want["source_fpfh"].view(np.uint32))
+    G.check_against_reference(G.with_knn(G.case_reference("cell edge 0.05"), knn), want)

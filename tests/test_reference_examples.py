@@ -660,8 +660,9 @@ def test_reference_dense_fusion_example_runs_on_the_gpu(hip, tmp_path):
     submap 2 against 0 by FPFH + RANSAC on the host, registration::RansacRegistration), the submap poses go through optimization::Optimizer::
     FastBA, every 8th frame is fused with its optimised pose (ConvertDepthTo32F + BilateralFilter + CubeHandler::IntegrateImage on the GPU),
     the mesh is extracted, simplified and written.  Checked: the example's own progress lines, one trajectory line per frame with rigid poses
-    that stay within centimetres of the synthetic ground truth, a mesh of the room.  (FPFH / RANSAC / FastBA are host code with no pinned
-    parity: the reference seeds its RANSAC from std::random_device.)"""
+    that stay within centimetres of the synthetic ground truth, a mesh of the room.  (FPFH is pinned elsewhere, by
+    tests/global_registration_common.py, to exact radius neighbours plus the arithmetic of the reference's 3DFeature.cpp; NOT pinned: nanoflann's
+    approximate radius search, the RANSAC, which the reference seeds from std::random_device, and FastBA.)"""
     exe = _example("DenseFusion")
     seq = str(tmp_path / "seq")
     n = 118
