@@ -137,6 +137,11 @@ class CubeHandler {
     // (example/MergeMultipleSubmaps.cpp:45-46, ImageIntegration.cpp:45) in one device call (op_volume_extract_mesh_processed): only the finished mesh
     // reaches the host.  Not in the reference.  What the device entry refuses takes the separate calls.
     void ExtractProcessedTriangleMesh(geometry::TriangleMesh& mesh, float grid_len, size_t min_points, bool compute_normals);
+    // the model seen from `pose` as an RGB-D frame in the format IntegrateImage and odometry::Odometry::DenseTracking take: rgb CV_8UC3, depth CV_32FC1 in
+    // metres (0 = no surface), both of the handler's camera's size (op_volume_render_frame: the raycast with colours, packed on the device).  Returns the
+    // number of pixels that see the model.  Not in the reference, which has no raycaster; the frame-to-model tracker that uses the same view without
+    // bringing it to the host is odometry::Odometry::DenseTrackingToModel.
+    size_t RenderFrame(const geometry::TransformationMatrix& pose, cv::Mat& rgb, cv::Mat& depth);
     void GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh);
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;

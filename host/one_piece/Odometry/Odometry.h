@@ -23,6 +23,7 @@
 struct op_tracker; // include/onepiece_hip.h
 
 namespace one_piece {
+namespace integration { class CubeHandler; }
 namespace odometry {
 
 class SparseTrackingResult { // Odometry.h:21-29 (the type only: DenseSlam-style code stores it)
@@ -40,6 +41,12 @@ class DenseTrackingResult { // Odometry.h:30-38
     geometry::PointCorrespondenceSet correspondence_set;       // (source xyz, target xyz), both read at the source pixel (Odometry.cpp:676-683)
     double rmse = 1e6;
     bool tracking_success;
+};
+
+class ModelTrackingResult : public DenseTrackingResult { // not in the reference: what Odometry::DenseTrackingToModel returns
+  public:
+    geometry::TransformationMatrix pose; // the tracked frame's camera pose: model_pose * T^-1, or model_pose when tracking_success is false
+    size_t model_pixels = 0;             // pixels of the model view that saw a surface
 };
 
 class Odometry {
@@ -75,6 +82,18 @@ class Odometry {
                               int term_type = 0);
     std::shared_ptr<DenseTrackingResult> DenseTrackingWait();
     size_t DenseTrackingPending() const { return inflight_.size() + ready_.size(); }
+
+    // ---- beyond the reference's surface: frame-to-MODEL tracking ---------------------------------------------------------------------------
+    // The KinectFusion loop (render, track, fuse), which the reference does not have: its DenseSlam tracks frame to frame.  The source frame is
+    // `model` rendered at `model_pose` (integration::CubeHandler::RenderFrame's view, made on the device and never brought to the host), the target
+    // is `frame` (its device copy when it has one); the result is DenseTracking's for that pair (T, rmse, tracking_success; the correspondence sets
+    // stay empty), plus the frame's camera pose model_pose * T^-1 -- model_pose itself when the track failed -- and the number of pixels of the
+    // model view that saw a surface (op_tracker_track_model).
+    std::shared_ptr<ModelTrackingResult> DenseTrackingToModel(integration::CubeHandler& model, const geometry::TransformationMatrix& model_pose,
+                                                              const geometry::RGBDFrame& frame, const geometry::TransformationMatrix& initial_T,
+                                                              int term_type = 0);
+    // measurement hook: the last DenseTrackingToModel call -- its model view on the device's clock and the whole call on the host's, in ms (op_tracker_model_times)
+    void LastModelTimes(double* render_ms, double* total_ms) const;
 
     void SetCamera(const camera::PinholeCamera& _camera) { camera = _camera; }
     void SetCameraPara(float _fx, float _fy, float _cx, float _cy, int _width, int _height, float depthScale, float* _distortion = nullptr) {

@@ -397,6 +397,19 @@ void CubeHandler::ExtractProcessedTriangleMesh(geometry::TriangleMesh& mesh, flo
     if (Failed(rc, "ExtractProcessedTriangleMesh")) return;
     std::cout << BLUE << "[ExtractTriangleMesh]::[INFO]::Finish Extracting Mesh, " << mesh.triangles.size() << " triangles after post-processing." << RESET << std::endl;
 }
+size_t CubeHandler::RenderFrame(const geometry::TransformationMatrix& pose, cv::Mat& rgb, cv::Mat& depth) {
+    Pending();
+    if (!Ensure()) return 0;
+    const op_camera pod = camera.Pod();
+    rgb.create(pod.height, pod.width, CV_8UC3);
+    depth.create(pod.height, pod.width, CV_32FC1);
+    float p[16];
+    bridge::RowMajor(pose, p);
+    uint64_t n = 0;
+    if (op_volume_render_frame(vol, &pod, p, rgb.data, reinterpret_cast<float*>(depth.data), OP_MEM_HOST, &n) != OP_OK) { Report("RenderFrame"); return 0; }
+    ReleaseBorrowed(); // (the call synchronised the volume)
+    return static_cast<size_t>(n);
+}
 void CubeHandler::GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh) {
     Pending();
     if (!vol) return;

@@ -1,5 +1,6 @@
 // Odometry.cpp -- odometry::Odometry::DenseTracking over op_tracker_dense_tracking.
 #include "Odometry/Odometry.h"
+#include "Integration/CubeHandler.h"
 
 #include "Bridge.h"
 #include "DeviceFrame.h"
@@ -157,6 +158,61 @@ std::shared_ptr<DenseTrackingResult> Odometry::DenseTracking(const cv::Mat& sour
 std::shared_ptr<DenseTrackingResult> Odometry::DenseTracking(geometry::RGBDFrame& source_frame, geometry::RGBDFrame& target_frame,
                                                              const geometry::TransformationMatrix& initial_T, int term_type) {
     return DenseTracking(source_frame.rgb, target_frame.rgb, source_frame.depth, target_frame.depth, initial_T, term_type);
+}
+
+std::shared_ptr<ModelTrackingResult> Odometry::DenseTrackingToModel(integration::CubeHandler& model, const geometry::TransformationMatrix& model_pose,
+                                                                    const geometry::RGBDFrame& frame, const geometry::TransformationMatrix& initial_T, int term_type) {
+    std::shared_ptr<ModelTrackingResult> result = std::make_shared<ModelTrackingResult>();
+    result->T = initial_T;
+    result->pose = model_pose;
+    result->tracking_success = false;
+    const int w = static_cast<int>(camera.GetWidth()), h = static_cast<int>(camera.GetHeight());
+    // the frame's device copy when a tracker or the volume has made one, its host images otherwise
+    const void *rgb = nullptr, *depth = nullptr;
+    int depth_fmt = 0, mem = OP_MEM_HOST;
+    std::shared_ptr<bridge::DeviceImages> dev = std::static_pointer_cast<bridge::DeviceImages>(frame.on_device);
+    if (dev && dev->width == w && dev->height == h && dev->device == bridge::Device()) {
+        rgb = dev->rgb; depth = dev->depth; depth_fmt = dev->depth_fmt; mem = OP_MEM_DEVICE;
+    } else {
+        const bool ok = frame.rgb.rows == h && frame.rgb.cols == w && frame.depth.rows == h && frame.depth.cols == w && frame.rgb.data && frame.depth.data &&
+                        frame.rgb.type() == CV_8UC3 && (frame.depth.type() == CV_16UC1 || frame.depth.type() == CV_32FC1) && frame.rgb.isContinuous() && frame.depth.isContinuous();
+        if (!ok) {
+            std::cout << RED << "[ERROR]::[DenseTrackingToModel]::the frame needs a continuous CV_8UC3 colour image and a CV_16UC1 / CV_32FC1 depth image of the camera's size ("
+                      << w << " x " << h << ")" << RESET << std::endl;
+            return result;
+        }
+        rgb = frame.rgb.data; depth = frame.depth.data; depth_fmt = bridge::DepthFormat(frame.depth);
+    }
+    if (static_cast<int>(iter_count_per_level.size()) != multi_scale_level) {
+        std::cout << RED << "[ERROR]::[DenseTrackingToModel]::iter_count_per_level does not have multi_scale_level entries" << RESET << std::endl;
+        return result;
+    }
+    op_volume* vol = model.Handle();
+    if (!vol) return result;
+    if (!tracker_ && bridge::Failed(op_tracker_create(bridge::Device(), &tracker_), "DenseTrackingToModel")) return result;
+    float T0[16], mp[16], pose[16];
+    bridge::RowMajor(initial_T, T0);
+    bridge::RowMajor(model_pose, mp);
+    std::vector<int32_t> iters(iter_count_per_level.begin(), iter_count_per_level.end());
+    const op_camera pod = camera.Pod();
+    op_track_result r;
+    uint64_t seen = 0;
+    if (bridge::Failed(op_tracker_track_model(tracker_, vol, &pod, multi_scale_level, iters.data(), mp, static_cast<const uint8_t*>(rgb), depth, depth_fmt, T0, term_type, mem, &r,
+                                              pose, &seen),
+                       "DenseTrackingToModel"))
+        return result;
+    result->T = bridge::FromRowMajor(r.T);
+    result->rmse = r.rmse;
+    result->tracking_success = r.tracking_success != 0;
+    result->pose = bridge::FromRowMajor(pose);
+    result->model_pixels = static_cast<size_t>(seen);
+    return result;
+}
+
+void Odometry::LastModelTimes(double* render_ms, double* total_ms) const {
+    if (render_ms) *render_ms = 0;
+    if (total_ms) *total_ms = 0;
+    if (tracker_) op_tracker_model_times(tracker_, render_ms, total_ms);
 }
 
 } // namespace odometry

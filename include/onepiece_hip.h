@@ -411,6 +411,16 @@ int op_volume_raycast(op_volume *v, const op_camera *cam, const float pose[16], 
  * of those earlier views' summaries dropped before loading (OP_VOLUME_OPT_RAYCAST_PRUNE), how many were loaded into LDS and how many of
  * the loaded ones were marched (the others held no zero crossing). */
 int op_volume_raycast_stats(op_volume *v, uint64_t *visible_blocks, uint64_t *dropped_unloaded, uint64_t *loaded_blocks, uint64_t *marched_blocks);
+/* The same view as an RGB-D FRAME, in the format op_volume_integrate and op_tracker_dense_tracking consume (NO reference counterpart either):
+ * op_volume_raycast with colours, then per pixel p
+ *   depth_out[p]     = the raycast depth in metres (0 = no hit), W*H floats;
+ *   rgb_out[3p + k]  = (uint8_t)min(max(c_k * 255.0f + 0.5f, 0.0f), 255.0f), c_k the raycast colour in stored channel order (product and sum
+ *                      rounded separately) -- 0 where there is no hit or the colour is not valid; W*H*3 bytes;
+ *   *n_valid         = the number of pixels with depth > 0 (may be NULL).
+ * cam == NULL: the volume's camera.  Like every accessor the call sees all frames integrated before it (the queue is flushed first); the kernels run on
+ * the volume's stream and the call returns when they are done.  The float colours never leave the device: a packing kernel (four pixels per lane, three
+ * dword stores) follows the raycaster's.  An empty volume or a view that sees nothing gives an all-zero frame and OP_OK. */
+int op_volume_render_frame(op_volume *v, const op_camera *cam, const float pose[16], uint8_t *rgb_out, float *depth_out, int mem, uint64_t *n_valid);
 
 /* Frame-sharded multi-GPU merge (the distributed form of CubeHandler::Merge; DESIGN.md "Multi-GPU").
  * All pointers are DEVICE pointers on the volume's device.
@@ -836,6 +846,22 @@ int op_tracker_dense_tracking_enqueue(op_tracker *t, const op_camera *cam, int n
                                       int term_type, int mem, int want_point_corr);
 int op_tracker_wait(op_tracker *t, op_track_result *result, int32_t *pixel_corr, float *point_corr,
                     size_t corr_cap);
+/* Frame-to-MODEL tracking (the KinectFusion loop: render, track, fuse; NO reference counterpart -- the reference's DenseSlam tracks frame to frame).
+ * The SOURCE frame is volume `v` rendered at camera-to-world `model_pose` with `cam` (op_volume_render_frame's definition), into a frame buffer the
+ * tracker owns: it never reaches the host.  The TARGET frame is the caller's (rgb, depth, depth_fmt, mem as in op_tracker_dense_tracking; the model
+ * view's depth is float metres whatever depth_fmt says).  `result` is exactly what op_tracker_dense_tracking returns for that source / target pair,
+ * in the tracker's current OP_TRACK_OPT_SUMS mode.  pose_out (may be NULL) = model_pose * T^-1 (DenseSlam.cpp:30's composition: op_mat4_inverse's
+ * arithmetic, float32 products) when result->tracking_success is set, else a copy of model_pose.  model_pixels (may be NULL) = the model view's
+ * pixels with depth > 0.  The frames queued on the volume are fused before the view is rendered; the volume's stream renders, the tracker's stream
+ * waits for it through an event.  An empty volume or a view that sees nothing is no error: the source frame is all zero, model_pixels = 0 and the
+ * result is the one op_tracker_dense_tracking gives for such a frame.  Volume and tracker must live on the same device. */
+int op_tracker_track_model(op_tracker *t, op_volume *v, const op_camera *cam, int n_levels,
+                           const int32_t *iters_per_level, const float model_pose[16], const uint8_t *rgb,
+                           const void *depth, int depth_fmt, const float init_T[16], int term_type, int mem,
+                           op_track_result *result, float pose_out[16], uint64_t *model_pixels);
+/* Measurement hook: the LAST op_tracker_track_model call of this tracker -- the time its model view took on the volume's stream (HIP events around the
+ * render; it includes fusion work the volume still had queued only in so far as the render had to flush it) and the whole call on the host's clock, in ms. */
+int op_tracker_model_times(op_tracker *t, double *render_ms, double *total_ms);
 /* Reads back an image prepared by the last op_tracker_dense_tracking call: frame 0 source / 1 target;
  * kind 0 colour, 1 depth, 2 colour_dx, 3 colour_dy, 4 depth_dx, 5 depth_dy (derivatives: target only). */
 int op_tracker_read_pyramid(op_tracker *t, int frame, int kind, int level, float *out, size_t cap);

@@ -146,6 +146,7 @@ SIGNATURES = {
     "op_volume_read_file": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "op_volume_raycast": (C.c_int, [_vp, C.POINTER(Camera), _fp, _fp, _fp, _fp, C.c_int]),
     "op_volume_raycast_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "op_volume_render_frame": (C.c_int, [_vp, C.POINTER(Camera), _fp, _vp, _fp, C.c_int, C.POINTER(C.c_uint64)]),
     "op_volume_keys_device": (C.c_int, [_vp, _vp, C.c_size_t, _szp]),
     "op_volume_pack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "op_volume_unpack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
@@ -207,6 +208,9 @@ SIGNATURES = {
     "op_tracker_dense_tracking_enqueue": (C.c_int, [_vp, C.POINTER(Camera), C.c_int, _ip, _vp, _vp, _vp, _vp, C.c_int, _fp, C.c_int,
                                                     C.c_int, C.c_int]),
     "op_tracker_wait": (C.c_int, [_vp, C.POINTER(TrackResult), _vp, _vp, C.c_size_t]),
+    "op_tracker_track_model": (C.c_int, [_vp, _vp, C.POINTER(Camera), C.c_int, _ip, _fp, _vp, _vp, C.c_int, _fp, C.c_int, C.c_int,
+                                         C.POINTER(TrackResult), _fp, C.POINTER(C.c_uint64)]),
+    "op_tracker_model_times": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "op_tracker_read_pyramid": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t]),
     "op_dense_track": (C.c_int, [C.POINTER(TrackLevel), C.c_int, _ip, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
                                  C.c_int, C.POINTER(TrackResult), _vp, _vp, C.c_size_t]),

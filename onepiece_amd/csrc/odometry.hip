@@ -21,9 +21,14 @@
 // NormalizeIntensity) on the device, and splits into _enqueue / op_tracker_wait so that several trackers
 // (one HIP stream each) keep independent frame pairs in flight; one call's ~100 launches are captured
 // into a hipGraph on first use and replayed afterwards.
+//
+// op_tracker_track_model is the same call with the SOURCE frame rendered from a TSDF volume on the device (model_frame.hpp; frame-to-model tracking).
 #include "odometry_core.hpp"
 #include "host_thread.hpp"
 #include "seq_sums.hpp"
+#include "model_frame.hpp"
+
+#include <chrono>
 
 using namespace op;
 using namespace opt;
@@ -480,6 +485,14 @@ struct op_tracker {
     hipGraphExec_t graph_exec = nullptr;
     unsigned long long graph_key[4] = {0, 0, 0, 0};
     int graph_ok = 1;                // cleared when capture/instantiate fails (then launches are issued directly)
+    // op_tracker_track_model: the model view that serves as the source frame (rendered on the volume's stream, never on the host), the count of its
+    // valid pixels, and the event this tracker's stream waits for before it reads them
+    unsigned char* model_rgb = nullptr;
+    float* model_depth = nullptr;
+    unsigned long long* model_count = nullptr;
+    size_t model_cap = 0;            // pixels
+    hipEvent_t model_begin = nullptr, model_ready = nullptr;
+    double model_render_ms = 0, model_total_ms = 0; // the last op_tracker_track_model call: its render on the volume's stream (between the two events), the whole call on the host's clock
 };
 
 namespace {
@@ -586,6 +599,9 @@ int op_tracker_destroy(op_tracker* t) {
     if (t->pair_host) (void)hipHostFree(t->pair_host);
     (void)hipFree(t->pair_t); (void)hipFree(t->pair_p); (void)hipFree(t->code); (void)hipFree(t->partials); (void)hipFree(t->wg_count); (void)hipFree(t->pix_out); (void)hipFree(t->pts_out);
     (void)hipFree(t->images); (void)hipFree(t->st); (void)hipFree(t->raw_rgb); (void)hipFree(t->raw_depth); (void)hipFree(t->pyr); (void)hipFree(t->norm_scales); (void)hipFree(t->prep_dev);
+    (void)hipFree(t->model_rgb); (void)hipFree(t->model_depth); (void)hipFree(t->model_count);
+    if (t->model_ready) (void)hipEventDestroy(t->model_ready);
+    if (t->model_begin) (void)hipEventDestroy(t->model_begin);
     if (t->prep_host) (void)hipHostFree(t->prep_host);
     if (t->graph_exec) (void)hipGraphExecDestroy(t->graph_exec);
     if (t->st_host) (void)hipHostFree(t->st_host);
@@ -820,7 +836,8 @@ static float* pyr_image(const op_tracker* t, int f, int k, int l) {
 
 static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n_levels, const int32_t* iters_per_level,
                                       const uint8_t* source_rgb, const uint8_t* target_rgb, const void* source_depth, const void* target_depth,
-                                      int depth_fmt, const float init_T[16], int term_type, int mem, int want_point_corr) {
+                                      int depth_fmt, const float init_T[16], int term_type, int mem, int want_point_corr, bool model_source) {
+    // model_source (op_tracker_track_model): the source frame is a model view in DEVICE memory whatever `mem` says, its depth float metres whatever depth_fmt says
     if (t->pending) return fail(OP_ERR_INVALID, "op_tracker_dense_tracking: an enqueued run has not been waited for");
     OP_TRY(check_iters("op_tracker_dense_tracking", n_levels, iters_per_level, term_type));
     if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "op_tracker_dense_tracking: bad depth_fmt %d", depth_fmt);
@@ -849,15 +866,16 @@ static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n
             OP_HIP(hipMalloc(&t->raw_depth, 2 * np * 4));
             t->raw_cap = np;
         }
-        OP_HIP(hipMemcpyAsync(t->raw_rgb, source_rgb, np * 3, hipMemcpyHostToDevice, t->stream));
+        if (!model_source) OP_HIP(hipMemcpyAsync(t->raw_rgb, source_rgb, np * 3, hipMemcpyHostToDevice, t->stream));
         OP_HIP(hipMemcpyAsync(t->raw_rgb + np * 3, target_rgb, np * 3, hipMemcpyHostToDevice, t->stream));
-        OP_HIP(hipMemcpyAsync(t->raw_depth, source_depth, np * dbytes, hipMemcpyHostToDevice, t->stream));
+        if (!model_source) OP_HIP(hipMemcpyAsync(t->raw_depth, source_depth, np * dbytes, hipMemcpyHostToDevice, t->stream));
         OP_HIP(hipMemcpyAsync(t->raw_depth + np * 4, target_depth, np * dbytes, hipMemcpyHostToDevice, t->stream));
         P.rgb[0] = t->raw_rgb; P.rgb[1] = t->raw_rgb + np * 3; P.depth[0] = t->raw_depth; P.depth[1] = t->raw_depth + np * 4;
+        if (model_source) { P.rgb[0] = source_rgb; P.depth[0] = source_depth; }
     } else {
         P.rgb[0] = source_rgb; P.rgb[1] = target_rgb; P.depth[0] = source_depth; P.depth[1] = target_depth;
     }
-    P.is_u16 = depth_fmt == OP_DEPTH_U16; P.depth_scale = cam->depth_scale; P.w = W; P.h = H;
+    P.is_u16 = depth_fmt == OP_DEPTH_U16 ? (model_source ? 2 : 3) : 0; P.depth_scale = cam->depth_scale; P.w = W; P.h = H;
     P.out[0] = pyr_image(t, 0, 0, 0); P.out[1] = pyr_image(t, 1, 0, 0); P.out[2] = pyr_image(t, 0, 1, 0); P.out[3] = pyr_image(t, 1, 1, 0);
 
     // level descriptors (Camera.h:38-42: intrinsics halved per level) + the NormalizeIntensity pass header
@@ -882,7 +900,7 @@ static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n
                                      ((unsigned long long)(unsigned)depth_fmt << 16) | (unsigned)t->lds_cap,
                                  0ull, (unsigned long long)(uintptr_t)t->pyr ^ ((unsigned long long)(uintptr_t)t->pair_p << 1)};
     for (int l = 0; l < n_levels; ++l) key[2] = key[2] * 1000003ull + (unsigned long long)(unsigned)iters_per_level[l] + 1ull;
-    const bool graph_path = t->graph_ok && mem == OP_MEM_DEVICE && !want_point_corr && t->sums == OP_TRACK_SUMS_FP64; // the validation mode synchronises every iteration: not capturable
+    const bool graph_path = t->graph_ok && mem == OP_MEM_DEVICE && !want_point_corr && t->sums == OP_TRACK_SUMS_FP64 && !model_source; // the validation mode synchronises every iteration: not capturable
     if (graph_path && t->graph_exec && std::memcmp(key, t->graph_key, sizeof(key)) == 0) {
         OP_HIP(hipGraphLaunch(t->graph_exec, t->stream));
         t->pending = true; t->pending_logs = false; t->pending_points = false;
@@ -977,14 +995,14 @@ static int dense_tracking_enqueue_now(op_tracker* t, const op_camera* cam, int n
     return rc;
 }
 
-int op_tracker_dense_tracking_enqueue(op_tracker* t, const op_camera* cam, int n_levels, const int32_t* iters_per_level,
+static int dense_tracking_enqueue_any(op_tracker* t, const op_camera* cam, int n_levels, const int32_t* iters_per_level,
                                       const uint8_t* source_rgb, const uint8_t* target_rgb, const void* source_depth, const void* target_depth,
-                                      int depth_fmt, const float init_T[16], int term_type, int mem, int want_point_corr) {
+                                      int depth_fmt, const float init_T[16], int term_type, int mem, int want_point_corr, bool model_source) {
     if (!t || !cam || !iters_per_level || !source_rgb || !target_rgb || !source_depth || !target_depth || !init_T)
         return fail(OP_ERR_INVALID, "op_tracker_dense_tracking: NULL argument");
     if (t->pending || t->worker.active) return fail(OP_ERR_INVALID, "op_tracker_dense_tracking: an enqueued run has not been waited for");
     if (t->sums == OP_TRACK_SUMS_FP64)
-        return dense_tracking_enqueue_now(t, cam, n_levels, iters_per_level, source_rgb, target_rgb, source_depth, target_depth, depth_fmt, init_T, term_type, mem, want_point_corr);
+        return dense_tracking_enqueue_now(t, cam, n_levels, iters_per_level, source_rgb, target_rgb, source_depth, target_depth, depth_fmt, init_T, term_type, mem, want_point_corr, model_source);
     // reference-order sums: the run synchronises with the host every iteration -- on the tracker's own host thread (the images must stay valid until op_tracker_wait, as for any enqueue)
     OP_TRY(check_iters("op_tracker_dense_tracking", n_levels, iters_per_level, term_type));
     const op_camera cam_copy = *cam;
@@ -992,8 +1010,14 @@ int op_tracker_dense_tracking_enqueue(op_tracker* t, const op_camera* cam, int n
     std::array<float, 16> T0;
     std::memcpy(T0.data(), init_T, sizeof(float) * 16);
     return t->worker.start("op_tracker_dense_tracking: could not start the tracker's host thread", [=] {
-        return dense_tracking_enqueue_now(t, &cam_copy, n_levels, iters.data(), source_rgb, target_rgb, source_depth, target_depth, depth_fmt, T0.data(), term_type, mem, want_point_corr);
+        return dense_tracking_enqueue_now(t, &cam_copy, n_levels, iters.data(), source_rgb, target_rgb, source_depth, target_depth, depth_fmt, T0.data(), term_type, mem, want_point_corr, model_source);
     });
+}
+
+int op_tracker_dense_tracking_enqueue(op_tracker* t, const op_camera* cam, int n_levels, const int32_t* iters_per_level,
+                                      const uint8_t* source_rgb, const uint8_t* target_rgb, const void* source_depth, const void* target_depth,
+                                      int depth_fmt, const float init_T[16], int term_type, int mem, int want_point_corr) {
+    return dense_tracking_enqueue_any(t, cam, n_levels, iters_per_level, source_rgb, target_rgb, source_depth, target_depth, depth_fmt, init_T, term_type, mem, want_point_corr, false);
 }
 
 int op_tracker_wait(op_tracker* t, op_track_result* result, int32_t* pixel_corr, float* point_corr, size_t corr_cap) {
@@ -1014,6 +1038,71 @@ int op_tracker_dense_tracking(op_tracker* t, const op_camera* cam, int n_levels,
     OP_TRY(op_tracker_dense_tracking_enqueue(t, cam, n_levels, iters_per_level, source_rgb, target_rgb, source_depth, target_depth, depth_fmt,
                                              init_T, term_type, mem, point_corr != nullptr));
     return op_tracker_wait(t, result, pixel_corr, point_corr, corr_cap);
+}
+
+// Frame-to-model tracking: the source frame is the volume rendered at model_pose (op_volume_render_frame's kernels, into buffers of the tracker's own),
+// the target is the caller's frame; the track itself is op_tracker_dense_tracking's, launch for launch (issued directly: the model view's pointers are not
+// part of a captured graph's key, and nothing here is captured).  The volume's stream renders, the tracker's stream tracks: an event orders the two.
+int op_tracker_track_model(op_tracker* t, op_volume* v, const op_camera* cam, int n_levels, const int32_t* iters_per_level, const float model_pose[16],
+                           const uint8_t* rgb, const void* depth, int depth_fmt, const float init_T[16], int term_type, int mem, op_track_result* result,
+                           float pose_out[16], uint64_t* model_pixels) {
+    if (!t || !v || !cam || !iters_per_level || !model_pose || !rgb || !depth || !init_T || !result) return fail(OP_ERR_INVALID, "op_tracker_track_model: NULL argument");
+    if (t->pending || t->worker.active) return fail(OP_ERR_INVALID, "op_tracker_track_model: an enqueued run has not been waited for");
+    if (op::volume_device(v) != t->device) return fail(OP_ERR_INVALID, "op_tracker_track_model: the volume lives on device %d, the tracker on device %d", op::volume_device(v), t->device);
+    // (what the track itself would refuse is refused before anything is rendered)
+    OP_TRY(check_iters("op_tracker_track_model", n_levels, iters_per_level, term_type));
+    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "op_tracker_track_model: bad depth_fmt %d", depth_fmt);
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_tracker_track_model: bad mem %d", mem);
+    const int W = cam->width, H = cam->height;
+    if (W < 4 || H < 4 || (size_t)W * H > (1u << 28) || (W >> (n_levels - 1)) < 3 || (H >> (n_levels - 1)) < 3)
+        return fail(OP_ERR_INVALID, "op_tracker_track_model: %dx%d with %d levels", W, H, n_levels);
+    OP_TRY(use_device(t->device));
+    const size_t np = (size_t)W * H;
+    if (np > t->model_cap) {
+        (void)hipFree(t->model_rgb); (void)hipFree(t->model_depth); t->model_rgb = nullptr; t->model_depth = nullptr; t->model_cap = 0;
+        OP_HIP(hipMalloc(&t->model_rgb, np * 3));
+        OP_HIP(hipMalloc(&t->model_depth, np * 4));
+        t->model_cap = np;
+    }
+    if (!t->model_count) OP_HIP(hipMalloc(&t->model_count, sizeof(unsigned long long)));
+    if (!t->model_ready) OP_HIP(hipEventCreate(&t->model_ready));
+    if (!t->model_begin) OP_HIP(hipEventCreate(&t->model_begin));
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    hipStream_t vs = op::volume_stream(v);
+    OP_HIP(hipEventRecord(t->model_begin, vs)); // (behind whatever fusion the volume's stream still holds: the render starts when that is done)
+    OP_TRY(op::volume_render_frame_enqueue(v, cam, model_pose, t->model_rgb, t->model_depth, t->model_count, nullptr));
+    OP_HIP(hipEventRecord(t->model_ready, vs));
+    OP_HIP(hipStreamWaitEvent(t->stream, t->model_ready, 0));
+    OP_TRY(dense_tracking_enqueue_any(t, cam, n_levels, iters_per_level, t->model_rgb, rgb, t->model_depth, depth, depth_fmt, init_T, term_type, mem, 0, true));
+    OP_TRY(op_tracker_wait(t, result, nullptr, nullptr, 0));
+    {
+        float ms = 0.0f; // (both events have completed: the track that waited for the second one has)
+        t->model_render_ms = hipEventElapsedTime(&ms, t->model_begin, t->model_ready) == hipSuccess ? (double)ms : 0.0;
+        t->model_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (model_pixels) {
+        unsigned long long n = 0;
+        OP_HIP(hipMemcpyAsync(&n, t->model_count, sizeof(n), hipMemcpyDeviceToHost, t->stream));
+        OP_HIP(hipStreamSynchronize(t->stream));
+        *model_pixels = n;
+    }
+    if (pose_out) {
+        // the model's pose composed with the track (camera pose = model_pose * T^-1, as DenseSlam.cpp:30 composes its poses); a failed track moves nothing
+        std::memcpy(pose_out, model_pose, sizeof(float) * 16);
+        if (result->tracking_success) {
+            float inv[16];
+            op_host::mat4_inverse(result->T, inv);
+            op_host::mat4_mul(model_pose, inv, pose_out);
+        }
+    }
+    return OP_OK;
+}
+
+int op_tracker_model_times(op_tracker* t, double* render_ms, double* total_ms) {
+    if (!t) return fail(OP_ERR_INVALID, "op_tracker_model_times: NULL tracker");
+    if (render_ms) *render_ms = t->model_render_ms;
+    if (total_ms) *total_ms = t->model_total_ms;
+    return OP_OK;
 }
 
 int op_tracker_read_pyramid(op_tracker* t, int frame, int kind, int level, float* out, size_t cap) {

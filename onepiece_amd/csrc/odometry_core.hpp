@@ -54,7 +54,8 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 struct PrepFrames {
     const unsigned char* rgb[2];
     const void* depth[2];
-    int is_u16;
+    int is_u16;         // bit f: depth[f] is 16-bit raw (divided by depth_scale), else float metres.  Both frames of a caller's pair share a format (0 or 3);
+                        // a model view (op_tracker_track_model's source) is always float
     float depth_scale;
     int w, h;
     float* out[4];      // src gray, tgt gray, src depth, tgt depth (level 0)

@@ -28,7 +28,7 @@ __device__ __forceinline__ float prep_raw(const PrepFrames& P, int z, int y, int
         return (float)(g & 255) / 255.0f;
     }
     const void* dp = z == 2 ? P.depth[0] : P.depth[1];
-    if (P.is_u16) {
+    if (P.is_u16 & (z == 2 ? 1 : 2)) { // (bit f: frame f's depth is 16-bit raw)
         const unsigned short d = static_cast<const unsigned short*>(dp)[k];
         return ((double)d > 0.5 * (double)P.depth_scale && (float)d < 4.0f * P.depth_scale) ? (float)d / P.depth_scale : __builtin_nanf("");
     }

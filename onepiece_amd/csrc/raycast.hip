@@ -34,6 +34,8 @@
 //   R2 k_rc_finish   per pixel: bits -> depth; normals / colours zeroed.
 //   R3 k_rc_shade    (when normals or colours are asked for) block-major again, over the blocks that hold hit points: the same LDS tile
 //                    serves the six gradient samples of every hit pixel; colours are gathered through the entry's neighbour slots.
+//   R4 k_rf_pack     (op_volume_render_frame / op_tracker_track_model only) the view as an RGB-D frame: the float colours to bytes, four pixels per lane,
+//                    and the count of pixels that were hit.
 // The result does not depend on the order blocks are processed in (tests compare it with the CPU restatement bit for bit).
 #include "volume_core.hpp"
 
@@ -532,18 +534,9 @@ __global__ __launch_bounds__(RC_WG, RC_SHADE_MIN_WAVES) void k_rc_shade(VolView 
 #define RC_MARCH_GRID 16384 // workgroups of k_rc_march, each taking every RC_MARCH_GRID-th visible block (4 x what is resident: evens out blocks of unequal cost)
 #endif
 
-} // namespace
-
-extern "C" {
-
-int op_volume_raycast(op_volume* v, const op_camera* cam, const float pose[16], float* depth_out, float* normals_out, float* colors_out, int mem) {
-    OP_VOL(v);
-    if (!pose || !depth_out) return fail(OP_ERR_INVALID, "null argument");
-    const op_camera c = cam ? *cam : v->cam;
-    OP_TRY(check_cam(&c));
-    OP_TRY(vol_check(v));
-    const size_t npx = (size_t)c.width * c.height;
-    // the visible-block list (one entry per pool block at most) and the hit-point bytes (one per pool slot; zero between calls)
+// ---- the host side of a view, shared by op_volume_raycast and the frame renderer -----------------------------------------------------------------
+// the visible-block list (one entry per pool block at most), the hit-point bytes (one per pool slot; zero between calls) and the call's counters
+int rc_reserve(op_volume* v) {
     if (v->rc_cap < v->max_blocks || !v->rc_list || !v->rc_hit || !v->rc_sum || !v->rc_order) {
         if (v->rc_list) op::cached_free(v->rc_list);
         if (v->rc_hit) op::cached_free(v->rc_hit);
@@ -560,22 +553,24 @@ int op_volume_raycast(op_volume* v, const op_camera* cam, const float pose[16], 
     }
     if (!v->rc_count) OP_HIP(op::cached_malloc((void**)&v->rc_count, sizeof(unsigned) * kRcCountWords)); // [0] the list's length, [16 + 16 s ...] shard s of the call's counters
     OP_HIP(hipMemsetAsync(v->rc_count, 0, sizeof(unsigned) * kRcCountWords, v->stream));
-    float *d_depth = depth_out, *d_nrm = normals_out, *d_col = colors_out;
-    // OP_MEM_HOST: device temporaries from the buffer cache; released on EVERY exit (a failed allocation or launch must not leave them in the cache's live set)
-    auto release_tmp = [&] {
-        if (mem != OP_MEM_HOST) return;
-        if (d_depth) op::cached_free(d_depth);
-        if (d_nrm) op::cached_free(d_nrm);
-        if (d_col) op::cached_free(d_col);
-        d_depth = d_nrm = d_col = nullptr;
-    };
-    if (mem == OP_MEM_HOST) {
-        d_depth = d_nrm = d_col = nullptr;
-        hipError_t ea = op::cached_malloc((void**)&d_depth, npx * 4);
-        if (ea == hipSuccess && normals_out) ea = op::cached_malloc((void**)&d_nrm, npx * 12);
-        if (ea == hipSuccess && colors_out) ea = op::cached_malloc((void**)&d_col, npx * 12);
-        if (ea != hipSuccess) { release_tmp(); return fail(OP_ERR_HIP, "raycast: no device memory for the output images: %s", hipGetErrorString(ea)); }
-    }
+    return OP_OK;
+}
+
+// k_rc_shade clears the hit bytes it consumes; a launch that failed may have left some set, and the next shading call assumes they are zero between calls:
+// drop the raycast buffers, the next call re-creates (and zeroes) them
+void rc_drop(op_volume* v) {
+    (void)hipStreamSynchronize(v->stream);
+    if (v->rc_list) op::cached_free(v->rc_list);
+    if (v->rc_hit) op::cached_free(v->rc_hit);
+    if (v->rc_sum) op::cached_free(v->rc_sum);
+    if (v->rc_order) op::cached_free(v->rc_order);
+    v->rc_list = nullptr; v->rc_hit = nullptr; v->rc_sum = nullptr; v->rc_order = nullptr; v->rc_cap = 0;
+}
+
+// The kernels of one view on the volume's stream, into DEVICE images (d_nrm, d_col may be null); does not wait for them.  false: the block summaries could
+// not be wiped (*e says why) and nothing but k_rc_visible was launched; true: *e = what the launches reported.
+bool rc_launch(op_volume* v, const op_camera& c, const float pose[16], float* d_depth, float* d_nrm, float* d_col, hipError_t* e) {
+    const size_t npx = (size_t)c.width * c.height;
     RcView W;
     float inv[16];
     op_host::mat4_inverse(pose, inv);
@@ -598,8 +593,8 @@ int op_volume_raycast(op_volume* v, const op_camera* cam, const float pose[16], 
     const bool shade = d_nrm || d_col;
     // summaries are stamped with the low 30 bits of the content generation; when those wrap, nothing older may survive
     if ((v->content_gen >> 30) != v->rc_sum_epoch) {
-        const hipError_t ew = hipMemsetAsync(v->rc_sum, 0, sizeof(unsigned) * (size_t)v->rc_cap, v->stream);
-        if (ew != hipSuccess) { release_tmp(); return fail(OP_ERR_HIP, "raycast: wiping the block summaries failed: %s", hipGetErrorString(ew)); }
+        *e = hipMemsetAsync(v->rc_sum, 0, sizeof(unsigned) * (size_t)v->rc_cap, v->stream);
+        if (*e != hipSuccess) return false;
         v->rc_sum_epoch = v->content_gen >> 30;
     }
     const unsigned stamp = (unsigned)(v->content_gen & 0x3fffffffull);
@@ -619,7 +614,163 @@ int op_volume_raycast(op_volume* v, const op_camera* cam, const float pose[16], 
                                           (const float*)d_depth, d_nrm, d_col)
     if (shade) { if (plain) OP_RC_SHADE(true); else OP_RC_SHADE(false); }
 #undef OP_RC_SHADE
-    hipError_t e = hipGetLastError();
+    *e = hipGetLastError();
+    return true;
+}
+
+// ---- the view as an RGB-D frame (op_volume_render_frame; the source frame of op_tracker_track_model) -------------------------------------------------
+// depth is the raycast depth itself (metres, 0 = no hit); the kernel turns the three float colours of a pixel into the bytes fusion and the tracker read,
+//   byte = (uint8_t)min(max(c * 255 + 0.5, 0), 255)   (product and sum rounded separately: the library is built without contraction),
+// and counts the pixels with depth > 0.  A lane owns FOUR pixels: three 16-byte colour loads and one 16-byte depth load in, three dword stores out (a
+// wave writes 768 contiguous bytes); the last group of an image whose pixel count is no multiple of 4 stores its 3, 6 or 9 bytes one by one.  ALIGNED = the
+// caller's rgb pointer admits dword stores and its depth pointer 16-byte loads (checked on the host); otherwise the same values go through scalar accesses.
+// The count: every lane adds up its own pixels over the grid-stride loop, one wave reduction, one 64-bit atomic per wave that saw a hit.
+__device__ __forceinline__ unsigned rf_byte(float c) {
+    const float s = c * 255.0f + 0.5f;
+    return (unsigned)(unsigned char)fminf(fmaxf(s, 0.0f), 255.0f);
+}
+template <bool ALIGNED>
+__global__ __launch_bounds__(256) void k_rf_pack(const float* __restrict__ depth, const float* __restrict__ col, unsigned char* __restrict__ rgb, size_t npx,
+                                                 unsigned long long* __restrict__ n_valid) {
+    const size_t n_groups = (npx + 3) / 4;
+    unsigned mine = 0;
+    for (size_t g = (size_t)blockIdx.x * 256u + threadIdx.x; g < n_groups; g += (size_t)gridDim.x * 256u) {
+        const size_t p0 = 4 * g;
+        if (ALIGNED && p0 + 4 <= npx) {
+            const float4 d = reinterpret_cast<const float4*>(depth)[g];
+            const float4 c0 = reinterpret_cast<const float4*>(col)[3 * g], c1 = reinterpret_cast<const float4*>(col)[3 * g + 1], c2 = reinterpret_cast<const float4*>(col)[3 * g + 2];
+            mine += (d.x > 0.0f ? 1u : 0u) + (d.y > 0.0f ? 1u : 0u) + (d.z > 0.0f ? 1u : 0u) + (d.w > 0.0f ? 1u : 0u);
+            unsigned* o = reinterpret_cast<unsigned*>(rgb) + 3 * g;
+            o[0] = rf_byte(c0.x) | (rf_byte(c0.y) << 8) | (rf_byte(c0.z) << 16) | (rf_byte(c0.w) << 24);
+            o[1] = rf_byte(c1.x) | (rf_byte(c1.y) << 8) | (rf_byte(c1.z) << 16) | (rf_byte(c1.w) << 24);
+            o[2] = rf_byte(c2.x) | (rf_byte(c2.y) << 8) | (rf_byte(c2.z) << 16) | (rf_byte(c2.w) << 24);
+        } else {
+            const size_t p1 = p0 + 4 < npx ? p0 + 4 : npx;
+            for (size_t p = p0; p < p1; ++p) {
+                mine += depth[p] > 0.0f ? 1u : 0u;
+                rgb[3 * p] = (unsigned char)rf_byte(col[3 * p]);
+                rgb[3 * p + 1] = (unsigned char)rf_byte(col[3 * p + 1]);
+                rgb[3 * p + 2] = (unsigned char)rf_byte(col[3 * p + 2]);
+            }
+        }
+    }
+    const unsigned total = wave_sum(mine); // (every lane of the workgroup gets here)
+    if ((threadIdx.x & 63) == 0 && total) atomicAdd(n_valid, (unsigned long long)total);
+}
+
+} // namespace
+
+namespace op {
+
+// One view of the volume as an RGB-D frame in DEVICE memory (rgb: 3 bytes per pixel, depth: float metres, n_valid: one 64-bit word), enqueued on the
+// volume's stream after everything integrated so far; does not wait for the kernels.  The float colours stay in a buffer of the volume's own.
+int volume_render_frame_enqueue(op_volume* v, const op_camera* cam, const float pose[16], unsigned char* d_rgb, float* d_depth, unsigned long long* d_n_valid,
+                                hipStream_t* stream) {
+    OP_VOL(v);
+    if (!pose || !d_rgb || !d_depth || !d_n_valid) return fail(OP_ERR_INVALID, "render frame: null argument");
+    const op_camera c = cam ? *cam : v->cam;
+    OP_TRY(check_cam(&c));
+    OP_TRY(vol_check(v)); // the frames queued by op_volume_integrate are fused first
+    const size_t npx = (size_t)c.width * c.height;
+    OP_TRY(rc_reserve(v));
+    if (v->rf_cap < npx) {
+        (void)hipStreamSynchronize(v->stream); // an earlier view may still be reading the old buffer
+        if (v->rf_col) op::cached_free(v->rf_col);
+        v->rf_col = nullptr; v->rf_cap = 0;
+        OP_HIP(op::cached_malloc((void**)&v->rf_col, npx * 12));
+        v->rf_cap = npx;
+    }
+    hipError_t e = hipSuccess;
+    if (!rc_launch(v, c, pose, d_depth, nullptr, v->rf_col, &e)) return fail(OP_ERR_HIP, "render frame: wiping the block summaries failed: %s", hipGetErrorString(e));
+    if (e == hipSuccess) e = hipMemsetAsync(d_n_valid, 0, sizeof(unsigned long long), v->stream);
+    if (e == hipSuccess) {
+        const bool aligned = (reinterpret_cast<uintptr_t>(d_rgb) & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_depth) & 15u) == 0;
+        const unsigned grid = (unsigned)std::min<size_t>(2048, ((npx + 3) / 4 + 255) / 256);
+        if (aligned) hipLaunchKernelGGL(k_rf_pack<true>, dim3(grid), dim3(256), 0, v->stream, (const float*)d_depth, (const float*)v->rf_col, d_rgb, npx, d_n_valid);
+        else hipLaunchKernelGGL(k_rf_pack<false>, dim3(grid), dim3(256), 0, v->stream, (const float*)d_depth, (const float*)v->rf_col, d_rgb, npx, d_n_valid);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        rc_drop(v);
+        return fail(OP_ERR_HIP, "render frame failed: %s", hipGetErrorString(e));
+    }
+    if (stream) *stream = v->stream;
+    return OP_OK;
+}
+
+int volume_device(const op_volume* v) { return v->device; }
+hipStream_t volume_stream(const op_volume* v) { return v->stream; }
+
+} // namespace op
+
+extern "C" {
+
+int op_volume_render_frame(op_volume* v, const op_camera* cam, const float pose[16], uint8_t* rgb_out, float* depth_out, int mem, uint64_t* n_valid) {
+    OP_VOL(v);
+    if (!pose || !rgb_out || !depth_out) return fail(OP_ERR_INVALID, "op_volume_render_frame: null argument");
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_render_frame: bad mem %d", mem);
+    const op_camera c = cam ? *cam : v->cam;
+    OP_TRY(check_cam(&c));
+    const size_t npx = (size_t)c.width * c.height;
+    if (!v->rf_count) OP_HIP(op::cached_malloc((void**)&v->rf_count, sizeof(unsigned long long)));
+    unsigned char* d_rgb = rgb_out;
+    float* d_depth = depth_out;
+    auto release_tmp = [&] { // OP_MEM_HOST: device temporaries from the buffer cache, released on every exit
+        if (mem != OP_MEM_HOST) return;
+        if (d_rgb) op::cached_free(d_rgb);
+        if (d_depth) op::cached_free(d_depth);
+        d_rgb = nullptr; d_depth = nullptr;
+    };
+    if (mem == OP_MEM_HOST) {
+        d_rgb = nullptr; d_depth = nullptr;
+        hipError_t ea = op::cached_malloc((void**)&d_rgb, npx * 3);
+        if (ea == hipSuccess) ea = op::cached_malloc((void**)&d_depth, npx * 4);
+        if (ea != hipSuccess) { release_tmp(); return fail(OP_ERR_HIP, "op_volume_render_frame: no device memory for the frame: %s", hipGetErrorString(ea)); }
+    }
+    const int rc = op::volume_render_frame_enqueue(v, &c, pose, d_rgb, d_depth, v->rf_count, nullptr);
+    if (rc != OP_OK) { (void)hipStreamSynchronize(v->stream); release_tmp(); return rc; }
+    hipError_t e = hipStreamSynchronize(v->stream);
+    unsigned long long n = 0;
+    if (e == hipSuccess && n_valid) e = hipMemcpy(&n, v->rf_count, sizeof(n), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && mem == OP_MEM_HOST) {
+        e = hipMemcpy(rgb_out, d_rgb, npx * 3, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(depth_out, d_depth, npx * 4, hipMemcpyDeviceToHost);
+    }
+    release_tmp();
+    if (e != hipSuccess) {
+        rc_drop(v);
+        return fail(OP_ERR_HIP, "op_volume_render_frame failed: %s", hipGetErrorString(e));
+    }
+    if (n_valid) *n_valid = n;
+    return OP_OK;
+}
+
+int op_volume_raycast(op_volume* v, const op_camera* cam, const float pose[16], float* depth_out, float* normals_out, float* colors_out, int mem) {
+    OP_VOL(v);
+    if (!pose || !depth_out) return fail(OP_ERR_INVALID, "null argument");
+    const op_camera c = cam ? *cam : v->cam;
+    OP_TRY(check_cam(&c));
+    OP_TRY(vol_check(v));
+    const size_t npx = (size_t)c.width * c.height;
+    OP_TRY(rc_reserve(v));
+    float *d_depth = depth_out, *d_nrm = normals_out, *d_col = colors_out;
+    // OP_MEM_HOST: device temporaries from the buffer cache; released on EVERY exit (a failed allocation or launch must not leave them in the cache's live set)
+    auto release_tmp = [&] {
+        if (mem != OP_MEM_HOST) return;
+        if (d_depth) op::cached_free(d_depth);
+        if (d_nrm) op::cached_free(d_nrm);
+        if (d_col) op::cached_free(d_col);
+        d_depth = d_nrm = d_col = nullptr;
+    };
+    if (mem == OP_MEM_HOST) {
+        d_depth = d_nrm = d_col = nullptr;
+        hipError_t ea = op::cached_malloc((void**)&d_depth, npx * 4);
+        if (ea == hipSuccess && normals_out) ea = op::cached_malloc((void**)&d_nrm, npx * 12);
+        if (ea == hipSuccess && colors_out) ea = op::cached_malloc((void**)&d_col, npx * 12);
+        if (ea != hipSuccess) { release_tmp(); return fail(OP_ERR_HIP, "raycast: no device memory for the output images: %s", hipGetErrorString(ea)); }
+    }
+    hipError_t e = hipSuccess;
+    if (!rc_launch(v, c, pose, d_depth, d_nrm, d_col, &e)) { release_tmp(); return fail(OP_ERR_HIP, "raycast: wiping the block summaries failed: %s", hipGetErrorString(e)); }
     if (e == hipSuccess) e = hipStreamSynchronize(v->stream);
 #ifdef RC_STATS
     {
@@ -635,14 +786,7 @@ int op_volume_raycast(op_volume* v, const op_camera* cam, const float pose[16], 
     }
     release_tmp();
     if (e != hipSuccess) {
-        // k_rc_shade clears the hit bytes it consumes; a launch that failed may have left some set, and the next shading call assumes they are zero between calls:
-        // drop the raycast buffers, the next call re-creates (and zeroes) them
-        (void)hipStreamSynchronize(v->stream);
-        if (v->rc_list) op::cached_free(v->rc_list);
-        if (v->rc_hit) op::cached_free(v->rc_hit);
-        if (v->rc_sum) op::cached_free(v->rc_sum);
-        if (v->rc_order) op::cached_free(v->rc_order);
-        v->rc_list = nullptr; v->rc_hit = nullptr; v->rc_sum = nullptr; v->rc_order = nullptr; v->rc_cap = 0;
+        rc_drop(v);
         return fail(OP_ERR_HIP, "raycast failed: %s", hipGetErrorString(e));
     }
     return OP_OK;

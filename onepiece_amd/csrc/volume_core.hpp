@@ -4,7 +4,7 @@
 //   select.hip      KA k_prepare_frames (ComputeBounding + frame packing), KB k_select / k_select_vote / k_select_merge (PrepareCubes)
 //   integrate.hip   KC k_integrate (Integrator::IntegrateImage)
 //   volume_ops.hip  GetCubeMap / SetCubeMap / Merge / sum-form pack + unpack / Transform / GetPointCloud / ExtractTriangleMesh / .map files
-//   raycast.hip     the raycaster
+//   raycast.hip     the raycaster, and its view packed as an RGB-D frame (model_frame.hpp: what the dense tracker takes from here)
 // Data layout in HBM: see volume.hip (and DESIGN.md section 2).
 #pragma once
 #include <cfloat>
@@ -477,6 +477,9 @@ struct op_volume {
     int rc_prune = 1;             // OP_VOLUME_OPT_RAYCAST_PRUNE
     uint64_t content_gen = 1;     // bumped by everything that can change a voxel or a pool slot's meaning without restating the summaries (clear, growth, every foreign writer, sum-form fusion; exact fusion only while no summaries exist)
     unsigned char* rc_hit = nullptr; // one byte per pool slot: the block holds hit points of the view being cast (zero between calls)
+    float* rf_col = nullptr;      // raycast.hip, the frame renderer: the float colours of the view being packed into bytes (rf_cap pixels) and the public entry's count of valid pixels
+    size_t rf_cap = 0;
+    unsigned long long* rf_count = nullptr;
     int* unpack_slots = nullptr; // table slots of the union keys between op_volume_unpack_sum_begin and its chunks
     size_t unpack_n = 0;
     uint64_t generation = 0, unpack_gen = 0; // bumped by whatever moves or drops table slots (growth, clear) or fuses frames; _chunk checks it

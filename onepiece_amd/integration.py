@@ -461,6 +461,27 @@ class CubeHandler:
         as_fp = lambda a: C.cast(C.c_void_p(int(a)), L._fp) if a else None
         L.check(self._lib.op_volume_raycast(self._h, C.byref(cam), _fp(pose), as_fp(depth_ptr), as_fp(normals_ptr), as_fp(colors_ptr), L.OP_MEM_DEVICE))
 
+    def RenderFrame(self, pose, camera=None):
+        """The model seen from `pose` as an RGB-D frame (op_volume_render_frame; no reference counterpart) -> (rgb [h,w,3] uint8,
+        depth [h,w] float32 metres, 0 = no hit, n_valid): the format IntegrateImage and Odometry.DenseTracking take."""
+        cam = camera if camera is not None else self.camera
+        pose = _f32(pose).reshape(16)
+        rgb = np.zeros((cam.height, cam.width, 3), np.uint8)
+        d = np.zeros((cam.height, cam.width), np.float32)
+        n = C.c_uint64(0)
+        L.check(self._lib.op_volume_render_frame(self._h, C.byref(cam), _fp(pose), C.c_void_p(rgb.ctypes.data), _fp(d), L.OP_MEM_HOST, C.byref(n)))
+        return rgb, d, int(n.value)
+
+    def RenderFrameDevice(self, pose, rgb_ptr, depth_ptr, camera=None):
+        """The same into buffers that stay in HBM: device addresses (e.g. torch tensor.data_ptr()) of a W*H*3 uint8 and a W*H float32 buffer on
+        the volume's device.  Returns the number of valid pixels, when the frame is complete."""
+        cam = camera if camera is not None else self.camera
+        pose = _f32(pose).reshape(16)
+        n = C.c_uint64(0)
+        L.check(self._lib.op_volume_render_frame(self._h, C.byref(cam), _fp(pose), C.c_void_p(int(rgb_ptr)), C.cast(C.c_void_p(int(depth_ptr)), L._fp),
+                                                 L.OP_MEM_DEVICE, C.byref(n)))
+        return int(n.value)
+
     def RaycastStats(self):
         """Measurement hook: what the last Raycast call did (op_volume_raycast_stats)."""
         v = [C.c_uint64(0) for _ in range(4)]

@@ -227,6 +227,37 @@ class Odometry:
                                   want_point_correspondences=want_correspondences and want_points)
         return self.Wait(want_correspondences, want_points)
 
+    def DenseTrackingToModel(self, model, model_pose, color, depth, initial_T=None, term_type=0):
+        """Frame-to-model tracking (op_tracker_track_model; no reference counterpart): the source frame is `model` (an
+        integration.CubeHandler) rendered at `model_pose` on the device, the target is (color, depth) -- numpy or CUDA torch tensors, as for
+        DenseTracking.  Returns the DenseTrackingResult of that pair with two more fields: `pose` = model_pose @ inv(T) in float32 when the
+        track succeeded (else model_pose), and `model_pixels`, the valid pixels of the model view."""
+        from .integration import _image_arg
+        pd, fd, md, k0 = _image_arg(depth, "depth")
+        pc, _, mc, k1 = _image_arg(color, "rgb")
+        if md != mc:
+            raise ValueError("colour and depth must share a memory space")
+        T0 = np.ascontiguousarray(np.eye(4) if initial_T is None else initial_T, np.float32).reshape(16)
+        mp = np.ascontiguousarray(model_pose, np.float32).reshape(16)
+        iters = np.asarray(self.iter_count_per_level, np.int32)
+        if len(iters) != self.multi_scale_level:
+            raise ValueError("iter_count_per_level must have multi_scale_level entries")
+        res = L.TrackResult()
+        pose = np.zeros(16, np.float32)
+        npx = C.c_uint64(0)
+        L.check(L.load().op_tracker_track_model(self._h, model._h, C.byref(self.camera), self.multi_scale_level, iters.ctypes.data_as(L._ip),
+                                                mp.ctypes.data_as(L._fp), pc, pd, fd, T0.ctypes.data_as(L._fp), int(term_type), md, C.byref(res),
+                                                pose.ctypes.data_as(L._fp), C.byref(npx)))
+        out = DenseTrackingResult()
+        out.T = np.array(res.T, np.float32).reshape(4, 4)
+        out.rmse = float(res.rmse)
+        out.tracking_success = bool(res.tracking_success)
+        out.iterations = int(res.iterations)
+        out.n_correspondences = int(res.n_correspondences)
+        out.pose = pose.reshape(4, 4)
+        out.model_pixels = int(npx.value)
+        return out
+
     def ReadPyramid(self, frame, kind, level):
         """Image prepared by the last DenseTracking call (frame 0 source / 1 target; kind index into
         (colour, depth, colour_dx, colour_dy, depth_dx, depth_dy))."""
