@@ -210,6 +210,14 @@ int op_debug_voxel_update(const float *s, const float *w, const float *c0, const
 /* Test hook (device): out[i] = v_rcp_f32(x[i]), the unrefined hardware reciprocal (csrc/integrate.hip voxel_update<true>:
  * y = __builtin_amdgcn_rcpf(wsum)).  Runs on device 0. */
 int op_debug_rcp(const float *x, long long n, float *out);
+/* Test hook (device): the fusion kernel's structured gather (csrc/volume_core.hpp gather2d: a buffer descriptor with stride = one image
+ * row and num_records = the rows does the row test and the address arithmetic) of n pixels uv = n x {u, v}, each in [-2^23, 2^23), from
+ * frame `frame` of a stack of n_frames packed images (images: n_frames x height x width records {depth bits, rgba}; width <= 2047).
+ * out: n x {depth bits, rgba}, {0, 0} for a pixel outside the image.  column_test = 1: gather2d as the kernel uses it; 0: the descriptor
+ * alone (vindex = v, voffset = u * 8) -- what the hardware's range check makes of the pair; every address base + v * stride + u * 8
+ * must then lie inside the stack.  Runs on device 0. */
+int op_debug_gather2d(const unsigned *images, int width, int height, int n_frames, int frame, int column_test, const int *uv,
+                      long long n, unsigned *out);
 /* geometry::Se3ToSE3 (Geometry/Geometry.cpp:9-13). */
 int op_se3_exp(const float x[6], float T[16]);
 

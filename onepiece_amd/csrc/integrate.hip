@@ -123,7 +123,9 @@ __device__ unsigned long long g_kc_trace[4096 * 4 * 8];
 #define KC_T(K) do { } while (0)
 #define KC_N(K, V) do { } while (0)
 #endif
-template <bool FAST, bool PLAIN, int ZT, bool SUMF = false, bool LEAN = false>
+// G2D: the frame's records are gathered through a structured descriptor (gather2d, volume_core.hpp) that does the row test and the address
+// arithmetic; the host launches it for certified cameras whose rows fit the stride field (launch_integrate), every other launch keeps the raw form.
+template <bool FAST, bool PLAIN, int ZT, bool SUMF = false, bool LEAN = false, bool G2D = false>
 __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAVES)) void k_integrate(BatchInv B, CamParams C, VolView V, const uint2* __restrict__ pimg, State* st,
                                                                             int n_frames, unsigned long long* __restrict__ upd_partial,
                                                                             unsigned long long* __restrict__ sel_partial, unsigned long long* __restrict__ chg_partial,
@@ -217,7 +219,9 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                 asm volatile("" : "+s"(fo));
                 const float __attribute__((address_space(4)))* M = kargs + fo * 12;
                 // (frame base in 32 bits: check_cam keeps kMaxBatch x npix x 8 below 2^32)
-                const __amdgpu_buffer_rsrc_t frame = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)pimg + (unsigned)fo * (npix * 8u)), 0, (int)(npix * 8u), 0x00020000);
+                const char* fbase = (const char*)pimg + (unsigned)fo * (npix * 8u);
+                const __amdgpu_buffer_rsrc_t frame = __builtin_amdgcn_make_buffer_rsrc((void*)fbase, 0, (int)(npix * 8u), 0x00020000);
+                const px_v4i frame2d = gather2d_rsrc(fbase, C.width, C.height);
                 const float a0 = M[0] * px + M[1] * py, a1 = M[4] * px + M[5] * py, a2 = M[8] * px + M[9] * py;
 #pragma unroll
                 for (int z = 0; z < ZT; ++z) {
@@ -225,8 +229,14 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                     const float q1 = (a1 + M[6] * pz[z]) + M[7] * 1.0f;
                     const float q2 = (a2 + M[10] * pz[z]) + M[11] * 1.0f;
                     zc[z] = q2;
-                    const int pix = project_pixel<FAST>(C, q0, q1, q2); // off-image: pixel -1 = an offset the buffer answers with zeros
-                    rec[z] = __builtin_amdgcn_raw_buffer_load_b64(frame, pix * 8, 0, 0);
+                    if (G2D) { // off-image: a row the descriptor answers with zeros
+                        int u, v;
+                        project_pixel_uv<FAST>(C, q0, q1, q2, u, v);
+                        rec[z] = gather2d(frame2d, u, v, C.width);
+                    } else {
+                        const int pix = project_pixel<FAST>(C, q0, q1, q2); // off-image: pixel -1 = an offset the buffer answers with zeros
+                        rec[z] = __builtin_amdgcn_raw_buffer_load_b64(frame, pix * 8, 0, 0);
+                    }
                 }
             };
             // PLAIN: every block of the volume was written by this kernel only.  Otherwise (the volume has seen an upload, a merge, a
@@ -394,6 +404,18 @@ __global__ void k_debug_rcp(const float* __restrict__ x, long long n, float* __r
     const long long i = blockIdx.x * 256ll + threadIdx.x;
     if (i < n) out[i] = __builtin_amdgcn_rcpf(x[i]);
 }
+// k_integrate's structured gather (volume_core.hpp gather2d) of n pixels (u, v) of one frame of a stack of packed images; column_test == 0: the
+// descriptor alone (vindex = v, voffset = u * 8), what the hardware's own range check makes of them
+__global__ void k_debug_gather2d(const uint2* __restrict__ img, int width, int height, int frame, int column_test, const int* __restrict__ uv, long long n,
+                                 uint2* __restrict__ out) {
+    const long long i = blockIdx.x * 256ll + threadIdx.x;
+    if (i >= n) return;
+    int fo = frame;
+    asm volatile("" : "+s"(fo));
+    const px_v4i rsrc = gather2d_rsrc(img + (size_t)fo * ((size_t)width * height), width, height);
+    const px_v2u r = column_test ? gather2d(rsrc, uv[2 * i], uv[2 * i + 1], width) : op_struct_buffer_load_b64(rsrc, uv[2 * i + 1], uv[2 * i] << 3, 0, 0);
+    out[i] = make_uint2(r.x, r.y);
+}
 
 // ---------------------------------------------------------------------------------------------
 // export / import / merge kernels
@@ -412,7 +434,8 @@ bool vol_fusion_keeps_summaries(const op_volume* v) {
 
 void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int nf) {
     const VolView V = v->view();
-#define OP_KC(FASTPX, PLAINV, SUMFV, LEANV) hipLaunchKernelGGL((k_integrate<FASTPX, PLAINV, (SUMFV ? KC_ZT_SUM : KC_ZT), SUMFV, LEANV>), dim3(SUMFV ? kColGridSum : kColGrid), dim3(512 / (SUMFV ? KC_ZT_SUM : KC_ZT)), 0, v->stream, I, C, V, (const uint2*)v->pimg, \
+#define OP_KC(FASTPX, PLAINV, SUMFV, LEANV) OP_KC6(FASTPX, PLAINV, SUMFV, LEANV, false)
+#define OP_KC6(FASTPX, PLAINV, SUMFV, LEANV, G2DV) hipLaunchKernelGGL((k_integrate<FASTPX, PLAINV, (SUMFV ? KC_ZT_SUM : KC_ZT), SUMFV, LEANV, G2DV>), dim3(SUMFV ? kColGridSum : kColGrid), dim3(512 / (SUMFV ? KC_ZT_SUM : KC_ZT)), 0, v->stream, I, C, V, (const uint2*)v->pimg, \
                                                  v->state, nf, v->upd_partial, v->sel_partial, v->chg_partial, v->plain_from, rc_sum, rc_stamp)
     // The sum form tests TSDFVoxel::IsValid on the STORED voxel once per batch where the reference re-tests it before every frame (Integrator.cpp:74-87,
     // TSDFVoxel.h:75-78): the two agree to rounding only while no OBSERVATION can itself be invalid, i.e. truncation < 1 (an observed sdf is < truncation;
@@ -426,10 +449,18 @@ void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int n
     if (sum_form || !(v->trunc <= 0.5f)) v->lean_ok = false;
     v->lean_frames += (uint64_t)nf;
     const bool lean = v->plain && v->lean_ok && v->lean_frames <= (1ull << 19);
-    if (sum_form) { if (C.fast_px) OP_KC(true, true, true, false); else OP_KC(false, true, true, false); }
+    // the structured gather: certified projection and rows that fit the descriptor's stride field (2047 pixels), else the raw form as before
+    if (C.fast_px && gather2d_fits(C.width)) {
+        if (sum_form) OP_KC6(true, true, true, false, true);
+        else if (lean) OP_KC6(true, true, false, true, true);
+        else if (v->plain) OP_KC6(true, true, false, false, true);
+        else OP_KC6(true, false, false, false, true);
+    }
+    else if (sum_form) { if (C.fast_px) OP_KC(true, true, true, false); else OP_KC(false, true, true, false); }
     else if (C.fast_px) { if (lean) OP_KC(true, true, false, true); else if (v->plain) OP_KC(true, true, false, false); else OP_KC(true, false, false, false); }
     else { if (lean) OP_KC(false, true, false, true); else if (v->plain) OP_KC(false, true, false, false); else OP_KC(false, false, false, false); }
 #undef OP_KC
+#undef OP_KC6
 }
 
 void kc_trace_dump(op_volume* v) {
@@ -501,6 +532,35 @@ int op_debug_rcp(const float* x, long long n, float* out) {
     }
     op::cached_free(d);
     if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_rcp failed: %s", hipGetErrorString(e));
+    return OP_OK;
+}
+
+int op_debug_gather2d(const unsigned* images, int width, int height, int n_frames, int frame, int column_test, const int* uv, long long n, unsigned* out) {
+    if (!images || !uv || !out) return fail(OP_ERR_INVALID, "null argument");
+    if (width <= 0 || !gather2d_fits(width) || height <= 0 || n_frames <= 0 || frame < 0 || frame >= n_frames || (long long)width * height * n_frames > (1ll << 24))
+        return fail(OP_ERR_INVALID, "op_debug_gather2d: rows of 1 .. %d pixels, a frame of the stack, at most 2^24 pixels in all", kGather2dMaxWidth);
+    if (n < 0 || n > (1ll << 24)) return fail(OP_ERR_INVALID, "n out of range [0, 2^24]");
+    for (long long i = 0; i < 2 * n; ++i) // what project_pixel_uv can return: a certified |t''| is below 2^23
+        if (uv[i] < -(1 << 23) || uv[i] >= (1 << 23)) return fail(OP_ERR_INVALID, "op_debug_gather2d: coordinates in [-2^23, 2^23)");
+    if (!column_test) // the descriptor alone: whatever the hardware checks, base + v * stride + u * 8 has to stay inside the stack
+        for (long long i = 0; i < n; ++i) {
+            const long long rec = ((long long)frame * height + uv[2 * i + 1]) * width + uv[2 * i];
+            if (rec < 0 || rec >= (long long)width * height * n_frames) return fail(OP_ERR_INVALID, "op_debug_gather2d: without the column test every address must lie in the stack");
+        }
+    OP_TRY(op::use_device(0));
+    if (n == 0) return OP_OK;
+    const size_t N = (size_t)n, img_bytes = (size_t)width * height * n_frames * 8;
+    char* d = nullptr;       // the images, then uv, then out
+    OP_HIP(op::cached_malloc((void**)&d, img_bytes + 16 * N));
+    hipError_t e = hipMemcpy(d, images, img_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + img_bytes, uv, 8 * N, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_debug_gather2d, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const uint2*)d, width, height, frame, column_test, (const int*)(d + img_bytes), n,
+                           (uint2*)(d + img_bytes + 8 * N));
+        e = hipMemcpy(out, d + img_bytes + 8 * N, 8 * N, hipMemcpyDeviceToHost);
+    }
+    op::cached_free(d);
+    if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_gather2d failed: %s", hipGetErrorString(e));
     return OP_OK;
 }
 

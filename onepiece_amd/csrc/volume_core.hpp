@@ -249,9 +249,11 @@ static __device__ unsigned long long g_px_waves[2];
 // FAST (px_axis exact on both axes), certified path (px_round.hpp px_cert_bound, folded form): t'' = fma(f*X, y, c + 0.5 + B2) per axis, the
 // pixel is trunc(t'') when fract(t'') > h2, i.e. when the unshifted sum is farther than B from every integer; a wave with any lane that is not (roughly 1 in 10^3..10^4 lane-axes, or |Z|
 // outside the window, or NaN) runs the exact sequence for those lanes out of line.
+// project_pixel_uv is that projection before the bounds test, for project_pixel below and for a caller that leaves the test to a buffer descriptor
+// (gather2d): a certified lane returns trunc(t'') per axis, unchecked (|t''| < 2^23; the axis is inside the image exactly when 0 <= u < extent),
+// every other lane the exact pixel of an axis inside the image and -1 for an axis outside it.
 template <bool FAST>
-__device__ __forceinline__ int project_pixel(const CamParams& C, float X, float Y, float Z) {
-    int u, v;
+__device__ __forceinline__ void project_pixel_uv(const CamParams& C, float X, float Y, float Z, int& u, int& v) {
     bool in_u, in_v;
     if (FAST && OP_PX_CERTIFIED) {
         OP_PX_COUNT(0);
@@ -277,12 +279,51 @@ __device__ __forceinline__ int project_pixel(const CamParams& C, float X, float 
                 v = in_v ? v : -1;
             }
         }
+    } else {
+        project_uv_exact<FAST>(C, X, Y, Z, u, v, in_u, in_v);
+        u = in_u ? u : -1;
+        v = in_v ? v : -1;
+    }
+}
+template <bool FAST>
+__device__ __forceinline__ int project_pixel(const CamParams& C, float X, float Y, float Z) {
+    int u, v;
+    bool in_u, in_v;
+    if (FAST && OP_PX_CERTIFIED) {
+        project_pixel_uv<true>(C, X, Y, Z, u, v);
         in_u = (unsigned)u < (unsigned)C.width;
         in_v = (unsigned)v < (unsigned)C.height;
     } else {
         project_uv_exact<FAST>(C, X, Y, Z, u, v, in_u, in_v);
     }
     return (in_u && in_v) ? (int)__umul24((unsigned)v, (unsigned)C.width) + u : -1; // both factors < 2^20: one full-rate 24-bit multiply
+}
+
+// The {depth, rgba} record of pixel (u, v) of one packed frame through a STRUCTURED buffer descriptor: stride = one image row, num_records = the
+// rows, read with idxen + offen (vindex = v, voffset = u * 8), so that the address unit forms base + v * stride + u * 8 and refuses v outside
+// [0, height) (zeros come back), where the raw form needs two compares, a multiply, an add-shift and a select per pixel.  gfx950's rule for
+// an untyped buffer_load with idxen, stride != 0 and swizzling off (tests/test_gather2d_gpu.py pins it): the index is compared, unsigned, with
+// num_records; the offset is NOT compared with the stride.  So the u axis keeps one compare and one select: a pixel outside on u reads row -1.
+// The stride field holds 14 bits: rows of up to kGather2dMaxWidth pixels; the host keeps wider images on the raw form (gather2d_fits).
+typedef unsigned int px_v2u __attribute__((ext_vector_type(2)));
+typedef int px_v4i __attribute__((ext_vector_type(4)));
+constexpr int kGather2dMaxWidth = 0x3fff / 8; // 2047
+__host__ __device__ inline bool gather2d_fits(int width) { return width <= kGather2dMaxWidth; }
+// (this compiler has no __builtin_amdgcn_struct_buffer_load_*: the intrinsic by its name; vmcnt is tracked for it like for the raw builtin)
+__device__ px_v2u op_struct_buffer_load_b64(px_v4i rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.load.v2i32");
+// frame = address of the frame's first record (wave-uniform).  Words 2, 3 and the stride half of word 1 do not depend on the frame: per frame
+// a caller pays the base's add, as for the raw descriptor, and one OR.
+__device__ __forceinline__ px_v4i gather2d_rsrc(const void* frame, int width, int height) {
+    const unsigned long long a = (unsigned long long)frame;
+    px_v4i r;
+    r.x = (int)(unsigned)a;
+    r.y = (int)(((unsigned)(a >> 32) & 0xffffu) | ((unsigned)width << 19)); // stride = width * 8 bytes in bits 16..29
+    r.z = height;
+    r.w = 0x00020000;
+    return r;
+}
+__device__ __forceinline__ px_v2u gather2d(px_v4i rsrc, int u, int v, int width) {
+    return op_struct_buffer_load_b64(rsrc, (unsigned)u < (unsigned)width ? v : -1, u << 3, 0, 0);
 }
 
 
