@@ -200,6 +200,9 @@ int op_debug_project_px(float a, float c, int fast);
  * IEEE division.  out: n x {u, v, u_plain, v_plain}; INT_MIN stands for "no int can hold it". */
 int op_debug_project_uv(float fx, float fy, float cx, float cy, const float *X, const float *Y, const float *Z,
                         size_t n, int device, int32_t *out);
+/* ... the same for an image of width x height pixels (op_debug_project_uv's is 640 x 480); {u, v} = {INT_MIN, INT_MIN} for a pixel outside it. */
+int op_debug_project_uv_image(float fx, float fy, float cx, float cy, int width, int height, const float *X, const float *Y,
+                              const float *Z, size_t n, int device, int32_t *out);
 /* Test hook (device): TSDFVoxel::operator+ with other = (new_sdf, 1, rgb / 255) (Integration/TSDFVoxel.h:24-39; Integrator.cpp:74-87)
  * for n stored voxels {s, w, c0, c1, c2} and observations {new_sdf, rgba}, lanes packed 64 to a wave in input order.
  * out_fast: the fusion kernel's update of a volume it alone has written (csrc/integrate.hip voxel_update<true>: one hardware
@@ -210,6 +213,9 @@ int op_debug_voxel_update(const float *s, const float *w, const float *c0, const
 /* Test hook (device): out[i] = v_rcp_f32(x[i]), the unrefined hardware reciprocal (csrc/integrate.hip voxel_update<true>:
  * y = __builtin_amdgcn_rcpf(wsum)).  Runs on device 0. */
 int op_debug_rcp(const float *x, long long n, float *out);
+/* Test hook (host): the bound on |1 - Z * v_rcp_f32(Z)| that the certified pixel projection's error bound assumes of the unrefined
+ * hardware reciprocal (csrc/px_round.hpp kPxRcpErr); tests/test_kc_diet_gpu.py holds op_debug_rcp to it over every significand. */
+double op_debug_px_rcp_err(void);
 /* Test hook (device): the fusion kernel's structured gather (csrc/volume_core.hpp gather2d: a buffer descriptor with stride = one image
  * row and num_records = the rows does the row test and the address arithmetic) of n pixels uv = n x {u, v}, each in [-2^23, 2^23), from
  * frame `frame` of a stack of n_frames packed images (images: n_frames x height x width records {depth bits, rgba}; width <= 2047).

@@ -47,6 +47,15 @@ typedef unsigned int kc_v2u __attribute__((ext_vector_type(2)));
 //     roundings this argument does not cover).  tests/test_kc_lean_cpu.py runs the operation sequence to weight 2^19 on adversarial
 //     streams (the worst |s| / T it finds is 1 - 2^-24: the mean does not leave the observations' range there) and checks that the colour means, convex combinations of values in [0, 1] under the
 //     same three monotone roundings, stay in [0, 1].
+//   the counters come from the weights (kWCount in k_integrate): under these hypotheses every update is wv = w, w' = RN(w + 1) with an integer
+//     w <= 2^19 + kMaxBatch - 1 < 2^24, so w' = w + 1 exactly, and the guard's division path (the `slow` lanes) replaces the four quotients only, never
+//     w.  A voxel's weight after the batch's frames minus its weight as loaded is therefore, exactly in float, the number of its updates in the
+//     batch: the sum of these differences over a block's voxels is the block's share of voxels_updated (kept per lane as an integer, folded with
+//     wave_sum at the kernel's end, as the sum form folds chg), a voxel was updated -- and has to be stored -- exactly when the two weights differ, and
+//     the population count of that compare is the wave's share of voxels_written.  So the lean frame loop carries no ballot of the hits, no
+//     s_bcnt1 / s_add for upd and no s_or for the store mask (2 + 2 + 2 scalar instructions per frame half).  Every other instantiation keeps them:
+//     there an invalid voxel restarts at weight 1 (wv = 0), and from T >= 1 on an update can leave the weight at 1, so the difference is not the count.
+//     tests/test_kc_counts_cpu.py runs the weight chain; tests/test_kc_diet_gpu.py holds both counters to the oracle's.
 // Without PLAIN (arbitrary uploaded data: NaN, infinities, denormals, fractional weights) the update is the reference's
 // two-branch form with four true divisions.
 // ---------------------------------------------------------------------------------------------
@@ -132,6 +141,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                                                                             unsigned plain_from, unsigned* __restrict__ rc_sum, unsigned rc_stamp) {
     constexpr int kWaves = 8 / ZT;            // waves per workgroup = z-groups per block
     constexpr bool kSummaries = !SUMF;        // the raycaster's block summaries are restated by the exact update only
+    constexpr bool kWCount = LEAN && !SUMF;   // voxels_updated, voxels_written and the store mask are read off the weights after the frames (LEAN paragraph above)
     __shared__ unsigned s_cnt[kWaves][2];
     __shared__ unsigned s_sign[2][kWaves];    // rc_sum: per wave, does its part of the block hold an observed sdf <= 0 (bit 0) / > 0 (bit 1) after the batch
     __shared__ float s_c255[256];             // (float)b / 255.0f for every byte (Integrator.cpp:78), correctly rounded once
@@ -153,7 +163,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
     const float __attribute__((address_space(4)))* kargs =
         (const float __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr(); // BatchInv B = offset 0 of the kernarg segment
     (void)B;
-    unsigned upd = 0, sel = 0, chg = 0, nblk = 0;   // upd and (exact update) chg: per WAVE (scalar counts of hit ballots), the others per lane
+    unsigned upd = 0, sel = 0, chg = 0, nblk = 0;   // upd and (exact update) chg: per WAVE (scalar counts of hit ballots), the others per lane; kWCount: upd per lane
     // XCD-aware order (workgroup b runs on XCD b % 8, each XCD has its own 4 MiB L2; blocks that gather the same pixels should meet in one L2)
     // and dynamic scheduling (blocks differ in work: 1..32 frames touch them; the workgroups of an XCD DRAW list positions from one counter,
     // the next one before the current block is processed so that the atomic's round trip is hidden).  Two ways of dealing the batch list to
@@ -200,6 +210,9 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
             }
             const float px = ((float)kx * 8.0f) * C.res + ox;
             const float py = ((float)ky * 8.0f) * C.res + oy;
+            float w0[ZT];                                  // kWCount: the weights as loaded (two registers; the flagship instantiation has them to spare)
+#pragma unroll
+            for (int z = 0; z < ZT; ++z) w0[z] = kWCount ? w[z] : 0.0f;
             // voxels to write back.  Exact update: the hit masks are already in scalar registers, so one wave-uniform 64-bit mask per z collects
             // them (no per-lane v_or per update); the stores run under it and its population count is the wave's share of voxels_written.
             // Sum form: per lane, known only after the frames.
@@ -252,6 +265,10 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                     // Integrator.cpp:70,74 (d > 0 and |sdf| < truncation): two compares whose masks meet in scalar registers (& and not &&, as in
                     // project_pixel) and one divergent region.  NaN and infinities fail the second compare, d <= 0 and -0 the first.
                     const bool seen = d > 0, near = fabsf(new_sdf) < C.trunc, hit = seen & near;
+                    if (kWCount) { // lean: no ballot, no count, no mask per update -- the weights carry all three (LEAN paragraph above)
+                        if (hit) voxel_update<true, true>(s[z], w[z], c0[z], c1[z], c2[z], new_sdf, rec[z].y, s_c255);
+                        continue;
+                    }
                     // the wave's hits, counted where the masks already are: control flow is wave-uniform here and every lane of the wave is live.
                     // (The ballot of each compare IS its scalar mask; the ballot of their conjunction would be rebuilt from a per-lane 0 / 1.)
                     const unsigned long long hits = __builtin_amdgcn_ballot_w64(seen) & __builtin_amdgcn_ballot_w64(near);
@@ -312,13 +329,23 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                     }
                 }
             }
+            if (kWCount) { // the weights' differences are the voxel's hits of the batch (exact: integers <= 2^19 + kMaxBatch), a changed weight is a voxel to store
 #pragma unroll
-            for (int z = 0; z < ZT; ++z)
-                if (SUMF ? ((changed >> z) & 1u) != 0u : ((changed_m[z] >> lane) & 1ull) != 0ull) voxel_store(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
-            if (SUMF) chg += (unsigned)__popc(changed);
-            else {
+                for (int z = 0; z < ZT; ++z) {
+                    const bool wrote = w[z] != w0[z];
+                    upd += (unsigned)(w[z] - w0[z]);       // (per lane)
+                    chg += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(wrote));
+                    if (wrote) voxel_store(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
+                }
+            } else {
 #pragma unroll
-                for (int z = 0; z < ZT; ++z) chg += (unsigned)__builtin_popcountll(changed_m[z]);
+                for (int z = 0; z < ZT; ++z)
+                    if (SUMF ? ((changed >> z) & 1u) != 0u : ((changed_m[z] >> lane) & 1ull) != 0ull) voxel_store(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
+                if (SUMF) chg += (unsigned)__popc(changed);
+                else {
+#pragma unroll
+                    for (int z = 0; z < ZT; ++z) chg += (unsigned)__builtin_popcountll(changed_m[z]);
+                }
             }
             // The raycaster's block summaries (raycast.hip: k_rc_neighbours drops blocks by them before loading a voxel) describe exactly what is in
             // registers here -- the block's 512 voxels after the batch: the kernel that changes a block restates its summary, so views between fusions
@@ -370,6 +397,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
 #endif
     // per-workgroup counters into kPartialGrid slots
     if (SUMF) chg = wave_sum(chg);                            // (upd is the wave's total already, and so is the exact update's chg)
+    if (kWCount) upd = wave_sum(upd);                         // (... except where it was kept per lane)
     if (lane == 0) { s_cnt[zg][0] = upd; s_cnt[zg][1] = chg; }
     __syncthreads();
     if (tid == 0) {
@@ -534,6 +562,8 @@ int op_debug_rcp(const float* x, long long n, float* out) {
     if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_rcp failed: %s", hipGetErrorString(e));
     return OP_OK;
 }
+
+double op_debug_px_rcp_err(void) { return kPxRcpErr; }
 
 int op_debug_gather2d(const unsigned* images, int width, int height, int n_frames, int frame, int column_test, const int* uv, long long n, unsigned* out) {
     if (!images || !uv || !out) return fail(OP_ERR_INVALID, "null argument");

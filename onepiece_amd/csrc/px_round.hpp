@@ -108,16 +108,29 @@ OP_HD double px_cert_bound(double T, double absK) {
 // The two-sided test costs v_fract, v_add -0.5 and a compare of the magnitude.  Shifting t' UP by a margin B2 >= B turns it into a
 // one-sided test, and the shift costs nothing when it is part of the FMA's constant:
 //     t'' = RN(nx * y + kb),   kb = an fp32 with B2 = kb - K >= B (exact in double: K = c + 0.5 and kb are close floats / half-integers),
+//     y = v_rcp_f32(z) as the hardware delivers it, NOT refined (one step: the two FMAs of the Newton step are gone from the fast path),
 //     certified  <=>  fract(t'') > h2,   h2 >= B2 + B,   pixel u = trunc(t''), inside = (unsigned)u < extent.
 // Error, for -2 <= t'' <= T = extent + 1 (the sums whose pixel matters).  With s'' = nx y + kb (real, formed exactly inside the fma) the chain of
 // px_cert_bound applies with kb in K's place and NO |K' - K| term -- kb's rounding is not an error here, B2 is DEFINED as kb - K, whatever px_axis
 // had to round to get a float: s'' - B2 = nx y + K, t = a + K, so
-//     (t'' - B2) - t = (t'' - s'') + q (dq - ra),   |t'' - s''| <= 2^-24 |s''|,  |dq| <= dy = 2^-24 + 2^-39,  |ra| <= 2^-24.
+//     (t'' - B2) - t = (t'' - s'') + q (dq - ra),   |t'' - s''| <= 2^-24 P,  |dq| <= dy,  |ra| <= 2^-24,
+// with P = the largest power of two <= T: t'' = RN(s'') is off by at most half an ulp of t'', and every float with |t''| <= T < 2 P has an ulp of at
+// most 2^-23 P (P >= 2 because T >= 2, so the sums in [-2, 0] are covered as well).  The relative form 2^-24 |s''| <= 2^-24 S of px_cert_bound charges
+// the top binade's half ulp at its upper end, a quarter more than any rounding there can be (3.8e-5 instead of 3.05e-5 at T = 641); with it the bound
+// was so slack that a reciprocal twice as far off as d_rcp still produced no wrong pixel, i.e. tests/test_px_unrefined_cpu.py could not see the
+// hypothesis the bound rests on.  The reciprocal:
+// the chain for the unrefined reciprocal is one step long: z y = 1 + d with |d| <= d_rcp = kPxRcpErr, so nx y = (nx / z)(z y) = q (1 + dq) with
+// dq = d: dy = d_rcp (the refined form had dy = 2^-24 + 2^-39; px_cert_bound above still states that one).  d_rcp is not taken on faith: over all 2^23
+// significands of [1, 2) and of [-2, -1), and 2^16 random ones in each of the binades 2^-60, 2^-1, 2^59, the device shows max |1 - z y| =
+// 9.1483642e-8 = 0.76742 * 2^-23 (at z = +-1.8744549; tests/test_kc_diet_gpu.py repeats the sweep against the constant), rounded up to the short
+// binary constant 2^-23 = 1.1920929e-7 -- which is also what an error of one ulp of y gives at most (|y - 1/z| <= ulp(y) <= 2^-24 for y in [1/2, 1),
+// times |z| < 2), the accuracy div_int_rcp (volume_core.hpp) relies on for integer divisors.  Inside the caller's window 2^-60 <= |z| < 2^60 neither
+// z nor y is denormal, and the significand sweep covers every binade.
 // Here |s''| <= |t''| / (1 - 2^-24), so s'' lies in [-L, S] with L = 2 / (1 - 2^-24), S = T / (1 - 2^-24) >= L, and q (1 + dq) = s'' - kb lies in
 // [-L - kb, S - kb]: |q| <= Qf = (max(|S - K|, |L + K|) + 1/4) / (1 - dy) for every kb in [K, K + 1/4] (px_axis refuses an axis whose B2 would exceed
 // 1/4).  px_cert_bound took |q| <= S + |K| over the whole window |t'| <= T instead; for a principal point near the middle of the image that is three
 // times what a sum in [-2, T] can have, and the far negative part of the window needs no such bound (last paragraph).  So
-//     |(t'' - B2) - t| < B := px_cert_bound_folded(T, K) = 2^-24 S + Qf (dy + 2^-24) + 2^-22,
+//     |(t'' - B2) - t| < B := px_cert_bound_folded(T, K) = 2^-24 P + Qf (dy + 2^-24) + 2^-22,
 // the last term in reserve for denormal quotients (their RN is off by 2^-150 at most, not by a relative 2^-24).  For a certified t'' in [-2, T],
 // n = floor(t''), f = fract(t''):
 //  * n >= 0: f = t'' - n exactly.  t > t'' - B2 - B > n + h2 - B2 - B >= n, and t < t'' - B2 + B < n + 1 because B2 >= B: t lies in
@@ -129,18 +142,25 @@ OP_HD double px_cert_bound(double T, double absK) {
 //  * -2 < t'' < -1 (t'' = -2 and -1 have fract 0 and are refused): f = t'' + 2 exactly, t lies in (-2, -1) as in the first case: trunc(t) = -1 =
 //    trunc(t''), outside on both paths.
 // Off the image, 2^23 > t'' > T or -2^23 < t'' < -2: with |q| <= (|s''| + |kb|) / (1 - dy) and extent, |K| < 2^20 the error is
-// |(t'' - B2) - t| < 2^-22 (|t''| + |K| + 1/4) + 2^-22 < 0.26 + 2^-22 |t''|.  t'' > extent + 1: t > t'' - 1/4 - 0.26 - 2^-22 t'' > extent (the left side
+// |(t'' - B2) - t| <= 2^-24 |s''| + 3 * 2^-24 |q| < 2^-22 (|t''| + |K| + 1/4) + 2^-22 < 0.26 + 2^-22 |t''|.  t'' > extent + 1: t > t'' - 1/4 - 0.26 - 2^-22 t'' > extent (the left side
 // grows with t''): outside, and u = trunc(t'') >= extent + 1 says so.  t'' < -2: t < t'' + 0.26 + 2^-22 |t''| < -1: trunc(t) <= -1, and u <= -2.
 // |t''| >= 2^23 has fract 0, NaN has fract NaN (so has +-inf, whose v_cvt_i32_f32 saturates outside the image anyway), h2 = 2 exceeds every fract:
 // all refused.
 // Width of the accepted set per unit interval: 1 - h2 = 1 - 2B - (B2 - B) with 0 <= B2 - B < ulp(kb) (+ one ulp of h2's own rounding).  With the
 // bound of the two-sided form the fold would cost up to one ulp(K) of width (3e-5 at K ~ 320, a tenth of its 2B: 3.42 % -> 3.76 % of wave-
 // projections took the exact fallback on the bench frames); with B halved by the argument above the rate falls instead (profiles/kc_trim_ab.txt).
+// The unrefined reciprocal widens B again, by Qf (d_rcp - 2^-24), and the half-ulp rounding term takes 2^-24 (S - P) back: for 640 pixels and a
+// principal point near the middle (Qf ~ 322, P = 512) B goes from 7.7e-5 to 8.8e-5 (9.6e-5 with the relative rounding term); the fallback share on
+// the bench frames is in profiles/kc_diet_ab.txt.
+constexpr double kPxRcpErr = 0x1p-23; // d_rcp: >= |1 - z * v_rcp_f32(z)| for every normal z whose reciprocal is normal (measured maximum 0.76742 * 2^-23, see above)
 OP_HD double px_cert_bound_folded(double T, double K) {
-    const double u = 0x1p-24, dy = u + 0x1p-39;
+    const double u = 0x1p-24, dy = kPxRcpErr;
     const double S = T / (1.0 - u), L = 2.0 / (1.0 - u);
     const double Qf = (fmax(fabs(S - K), fabs(L + K)) + 0.25) / (1.0 - dy);
-    return (u * S + Qf * (dy + u) + 0x1p-22) * (1.0 + 0x1p-40); // (the last factor covers the rounding of this double evaluation)
+    int e2;
+    frexp(T, &e2);
+    const double P = ldexp(1.0, e2 - 1);                       // the largest power of two <= T
+    return (u * P + Qf * (dy + u) + 0x1p-22) * (1.0 + 0x1p-40); // (the last factor covers the rounding of this double evaluation)
 }
 
 OP_HD PxAxis px_axis(float c, int extent) {

@@ -802,7 +802,13 @@ int op_debug_project_px(float a, float c, int fast) {
 }
 
 int op_debug_project_uv(float fx, float fy, float cx, float cy, const float* X, const float* Y, const float* Z, size_t n, int device, int32_t* out) {
+    return op_debug_project_uv_image(fx, fy, cx, cy, 640, 480, X, Y, Z, n, device, out);
+}
+
+int op_debug_project_uv_image(float fx, float fy, float cx, float cy, int width, int height, const float* X, const float* Y, const float* Z, size_t n, int device,
+                              int32_t* out) {
     if (!X || !Y || !Z || !out) return fail(OP_ERR_INVALID, "null argument");
+    if (width <= 0 || height <= 0 || width >= (1 << 20) || height >= (1 << 20)) return fail(OP_ERR_INVALID, "op_debug_project_uv_image: sides in [1, 2^20)");
     OP_TRY(op::use_device(device));
     if (n == 0) return OP_OK;
     float* d_in = nullptr;
@@ -814,7 +820,7 @@ int op_debug_project_uv(float fx, float fy, float cx, float cy, const float* X, 
     if (e == hipSuccess) e = hipMemcpy(d_in + 2 * n, Z, n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         CamParams C{};
-        C.fx = fx; C.fy = fy; C.cx = cx; C.cy = cy; C.width = 640; C.height = 480;
+        C.fx = fx; C.fy = fy; C.cx = cx; C.cy = cy; C.width = width; C.height = height;
         C.ax = px_axis(cx, C.width); C.ay = px_axis(cy, C.height);
         C.fast_px = C.ax.exact && C.ay.exact;
         hipLaunchKernelGGL(k_debug_project_uv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, C, (const float*)d_in,

@@ -258,9 +258,9 @@ __device__ __forceinline__ void project_pixel_uv(const CamParams& C, float X, fl
     if (FAST && OP_PX_CERTIFIED) {
         OP_PX_COUNT(0);
         const float nx = C.fx * X, ny = C.fy * Y;
-        float y = __builtin_amdgcn_rcpf(Z);
-        const float e = __builtin_fmaf(-Z, y, 1.0f);
-        y = __builtin_fmaf(e, y, y);
+        // the reciprocal as the hardware delivers it: the certificate needs a bound on |Z y - 1| only, and kPxRcpErr (px_round.hpp) is one for
+        // v_rcp_f32 without the Newton step (which the exact sequence below keeps: its quotients must be correctly rounded)
+        const float y = __builtin_amdgcn_rcpf(Z);
         // the certificate's margin travels in the FMA's constant (kb = c + 0.5 + B2): one v_fract and one compare per axis certify the lane
         const float tx = __builtin_fmaf(nx, y, C.ax.kb), ty = __builtin_fmaf(ny, y, C.ay.kb);
         // 2^-60 <= |Z| < 2^60: the biased exponent (bits 24..31 of the sign-less word shifted left once) in [67, 187)
