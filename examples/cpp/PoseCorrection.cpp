@@ -1,0 +1,230 @@
+// PoseCorrection.cpp -- using a corrected pose of a frame that is already fused.  N frames of the analytic room are fused, K of them at a perturbed
+// (drifted) pose; then the volume is repaired, either the only way there was before de-integration -- Clear() and fusing all N frames again at the
+// true poses -- or by moving the K frames: CubeHandler::ReintegrateImage(depth, rgb, drifted pose, true pose), about 2 K frame updates.
+//
+//   PoseCorrection --synthetic N STRIDE SEED [--perturb K] [--res 0.01] [--path refuse|reintegrate|split] [--runs R]
+//   --synthetic N STRIDE SEED  N frames of the analytic room of LiveFusion.cpp: frame k is step FIRST + k * STRIDE of a 1000-step orbit, SEED picks FIRST
+//   --perturb K                K of the N frames (evenly spread) are first fused 3 cm and about one degree off (default N / 10, at least 1)
+//   --res                      voxel size in metres
+//   --path                     refuse (default): Clear() + IntegrateImage of all N frames; reintegrate: ReintegrateImage of the K frames
+//                              split: DeintegrateImage of the K frames, then IntegrateImage of the K frames (the two kernels side by side under a profiler)
+//   --runs R                   R > 1: one untimed pass and R timed ones in this process (the volume cleared in between); the medians are printed
+// It prints one JSON line: the stage times (host clock, each stage waited for) and, against a second volume fused at the true poses, the number of
+// voxels whose weights differ and the largest |sdf| and |colour| differences over the others.  A re-fused volume is that volume bit for bit; a
+// re-integrated one has the same weights and differs by the float32 roundings of the inverse running mean (op_volume_deintegrate).
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "Geometry/Geometry.h"
+#include "Integration/CubeHandler.h"
+#include "onepiece_hip.h"
+using namespace one_piece;
+
+namespace {
+
+const double kPi = 3.14159265358979323846;
+const float kRoomHalf[3] = {2.6f, 1.4f, 2.6f};
+const float kSpheres[2][4] = {{1.2f, 0.7f, 1.6f, 0.55f}, {-1.4f, 0.5f, -1.1f, 0.7f}};
+
+// camera-to-world pose of orbit step i: radius 0.4 m, looking outward, a slow pitch
+geometry::TransformationMatrix RoomPose(long i) {
+    const double th = 2.0 * kPi * static_cast<double>(i % 1000) / 1000.0;
+    const long loop = i / 1000;
+    const double radius = 0.4 + 0.05 * static_cast<double>(loop % 8), pitch = 0.12 * std::sin(2.0 * th + 0.3 * static_cast<double>(loop));
+    const double cy = std::cos(th), sy = std::sin(th), cp = std::cos(pitch), sp = std::sin(pitch);
+    const double Ry[3][3] = {{cy, 0, sy}, {0, 1, 0}, {-sy, 0, cy}}, Rx[3][3] = {{1, 0, 0}, {0, cp, -sp}, {0, sp, cp}};
+    geometry::TransformationMatrix T = geometry::TransformationMatrix::Identity();
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) T(r, c) = static_cast<float>(Ry[r][0] * Rx[0][c] + Ry[r][1] * Rx[1][c] + Ry[r][2] * Rx[2][c]);
+    T(0, 3) = static_cast<float>(radius * sy);
+    T(1, 3) = static_cast<float>(0.15 * std::sin(3.0 * th));
+    T(2, 3) = static_cast<float>(radius * cy);
+    return T;
+}
+
+// a drifted estimate of `pose`: 3 cm and about a degree off, the direction depending on k
+geometry::TransformationMatrix Drifted(const geometry::TransformationMatrix& pose, long k) {
+    const double a = 0.015 + 0.002 * static_cast<double>(k % 3);
+    geometry::TransformationMatrix D = geometry::TransformationMatrix::Identity();
+    D(0, 0) = static_cast<float>(std::cos(a)); D(0, 2) = static_cast<float>(std::sin(a));
+    D(2, 0) = static_cast<float>(-std::sin(a)); D(2, 2) = static_cast<float>(std::cos(a));
+    D(0, 3) = 0.03f; D(1, 3) = k % 2 ? -0.015f : -0.02f; D(2, 3) = 0.025f;
+    return pose * D;
+}
+
+float Slab(float o, float d, float half) {
+    if (!(std::fabs(d) > 1e-9f)) return 1e9f;
+    return ((d > 0 ? half : -half) - o) / d;
+}
+
+// the room seen from `pose`: z-depth in metres (CV_32FC1) and a colour that depends on the surface point alone (CV_8UC3)
+void RoomRender(const geometry::TransformationMatrix& pose, const camera::PinholeCamera& cam, cv::Mat& depth, cv::Mat& rgb) {
+    const int w = static_cast<int>(cam.GetWidth()), h = static_cast<int>(cam.GetHeight());
+    depth.create(h, w, CV_32FC1);
+    rgb.create(h, w, CV_8UC3);
+    const float fx = cam.GetFx(), fy = cam.GetFy(), cx = cam.GetCx(), cy = cam.GetCy();
+    const float ox = pose(0, 3), oy = pose(1, 3), oz = pose(2, 3);
+    for (int v = 0; v < h; ++v)
+        for (int u = 0; u < w; ++u) {
+            const float a = (static_cast<float>(u) - cx) / fx, b = (static_cast<float>(v) - cy) / fy;
+            const float dx = pose(0, 0) * a + pose(0, 1) * b + pose(0, 2), dy = pose(1, 0) * a + pose(1, 1) * b + pose(1, 2), dz = pose(2, 0) * a + pose(2, 1) * b + pose(2, 2);
+            float t = std::fmin(std::fmin(Slab(ox, dx, kRoomHalf[0]), Slab(oy, dy, kRoomHalf[1])), Slab(oz, dz, kRoomHalf[2]));
+            const float dd = dx * dx + dy * dy + dz * dz;
+            for (int s = 0; s < 2; ++s) {
+                const float lx = ox - kSpheres[s][0], ly = oy - kSpheres[s][1], lz = oz - kSpheres[s][2];
+                const float bb = dx * lx + dy * ly + dz * lz, cc = lx * lx + ly * ly + lz * lz - kSpheres[s][3] * kSpheres[s][3];
+                const float disc = bb * bb - dd * cc;
+                if (disc > 0) {
+                    const float ts = (-bb - std::sqrt(disc)) / dd;
+                    if (ts > 0.05f && ts < t) t = ts;
+                }
+            }
+            const float hx = ox + t * dx, hy = oy + t * dy, hz = oz + t * dz;
+            const float r = 128.0f + 110.0f * std::sin(3.1f * hx + 0.7f * hy), g = 128.0f + 110.0f * std::sin(2.3f * hy + 1.9f * hz), bl = 128.0f + 110.0f * std::sin(2.7f * hz - 1.3f * hx);
+            depth.at<float>(v, u) = t;
+            unsigned char* px = rgb.data + 3 * (static_cast<size_t>(v) * w + u); // stored order B, G, R like cv::imread
+            px[0] = static_cast<unsigned char>(std::fmin(std::fmax(bl, 0.0f), 255.0f));
+            px[1] = static_cast<unsigned char>(std::fmin(std::fmax(g, 0.0f), 255.0f));
+            px[2] = static_cast<unsigned char>(std::fmin(std::fmax(r, 0.0f), 255.0f));
+        }
+}
+
+double Seconds(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); }
+
+struct Blocks {
+    std::vector<int32_t> keys;
+    std::vector<float> vox; // n x 512 x {sdf, weight, c0, c1, c2}
+    size_t n;
+};
+
+bool Download(integration::CubeHandler& h, Blocks* out) {
+    op_volume* v = h.Handle();
+    size_t n = 0, got = 0;
+    if (!v || op_volume_block_count(v, &n) != OP_OK) return false;
+    out->keys.resize(3 * n + 3);
+    out->vox.resize(n * 512 * 5 + 5);
+    if (n && op_volume_download(v, out->keys.data(), out->vox.data(), n, &got) != OP_OK) return false;
+    out->n = n ? got : 0;
+    return true;
+}
+
+} // namespace
+
+int main(int argc, char* argv[]) {
+    long synthetic[3] = {0, 1, 1}, perturb = -1, runs = 1;
+    bool is_synthetic = false, bad = false;
+    std::string path = "refuse";
+    float res = 0.01f;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--synthetic" && i + 3 < argc) { is_synthetic = true; for (int k = 0; k < 3; ++k) synthetic[k] = std::atol(argv[++i]); }
+        else if (a == "--perturb" && i + 1 < argc) perturb = std::atol(argv[++i]);
+        else if (a == "--res" && i + 1 < argc) res = static_cast<float>(std::atof(argv[++i]));
+        else if (a == "--path" && i + 1 < argc) path = argv[++i];
+        else if (a == "--runs" && i + 1 < argc) runs = std::atol(argv[++i]);
+        else bad = true;
+    }
+    const long n = synthetic[0], stride = synthetic[1];
+    if (perturb < 0) perturb = n / 10 > 0 ? n / 10 : 1;
+    if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || perturb < 1 || perturb > n || !(res > 0) || runs < 1 || (path != "refuse" && path != "reintegrate" && path != "split")) {
+        std::cout << "usage::PoseCorrection --synthetic N STRIDE SEED [--perturb K] [--res 0.01] [--path refuse|reintegrate|split] [--runs R]" << std::endl;
+        return bad || argc > 1 ? 2 : 0;
+    }
+    const long first = ((synthetic[2] + 999) % 1000) * 97 % 1000;
+
+    camera::PinholeCamera camera;
+    camera.SetCameraType(camera::CameraType::OPEN3D_DATASET);
+    std::vector<cv::Mat> depth(n), rgb(n);
+    std::vector<geometry::TransformationMatrix> truth(n), fused_at(n);
+    std::vector<char> moved(n, 0);
+    for (long k = 0; k < perturb; ++k) moved[(2 * k + 1) * n / (2 * perturb)] = 1; // K frames, evenly spread
+    for (long k = 0; k < n; ++k) {
+        truth[k] = RoomPose(first + k * stride);
+        RoomRender(truth[k], camera, depth[k], rgb[k]);
+        fused_at[k] = moved[k] ? Drifted(truth[k], k) : truth[k];
+    }
+
+    integration::CubeHandler volume(camera), reference(camera);
+    volume.SetVoxelResolution(res);
+    reference.SetVoxelResolution(res);
+    if (!volume.Handle()) return 1; // (no device: the class has said so)
+
+    // with --runs R > 1: one untimed pass, then R timed ones (the volume cleared in between); the medians are reported
+    std::vector<double> fuse_s, repair_s;
+    size_t blocks_drifted = 0;
+    std::chrono::steady_clock::time_point t0;
+    for (long pass = runs > 1 ? -1 : 0; pass < runs; ++pass) {
+        volume.Clear();
+        t0 = std::chrono::steady_clock::now();
+        for (long k = 0; k < n; ++k) volume.IntegrateImage(depth[k], rgb[k], fused_at[k]);
+        volume.Synchronize();
+        const double tf = Seconds(t0);
+        blocks_drifted = volume.GetCubeCount();
+        t0 = std::chrono::steady_clock::now();
+        if (path == "refuse") {
+            volume.Clear();
+            for (long k = 0; k < n; ++k) volume.IntegrateImage(depth[k], rgb[k], truth[k]);
+        } else if (path == "reintegrate") {
+            for (long k = 0; k < n; ++k)
+                if (moved[k]) volume.ReintegrateImage(depth[k], rgb[k], fused_at[k], truth[k]);
+        } else { // split: the K de-integrations in launches of their own, then the K frames through the ordinary integration of a volume that is no longer plain
+            for (long k = 0; k < n; ++k)
+                if (moved[k]) volume.DeintegrateImage(depth[k], rgb[k], fused_at[k]);
+            volume.Synchronize();
+            for (long k = 0; k < n; ++k)
+                if (moved[k]) volume.IntegrateImage(depth[k], rgb[k], truth[k]);
+        }
+        volume.Synchronize();
+        const double tr = Seconds(t0);
+        if (pass >= 0) { fuse_s.push_back(tf); repair_s.push_back(tr); }
+    }
+    std::sort(fuse_s.begin(), fuse_s.end());
+    std::sort(repair_s.begin(), repair_s.end());
+    const double t_fuse = fuse_s[fuse_s.size() / 2], t_repair = repair_s[repair_s.size() / 2];
+
+    t0 = std::chrono::steady_clock::now();
+    for (long k = 0; k < n; ++k) reference.IntegrateImage(depth[k], rgb[k], truth[k]);
+    reference.Synchronize();
+    const double t_reference = Seconds(t0);
+
+    Blocks got, want;
+    if (!Download(volume, &got) || !Download(reference, &want)) { std::cout << RED << "[ERROR]::cannot read the volumes back: " << op_last_error() << RESET << std::endl; return 1; }
+    std::map<std::vector<int32_t>, size_t> at;
+    for (size_t b = 0; b < got.n; ++b) at[std::vector<int32_t>(got.keys.begin() + 3 * b, got.keys.begin() + 3 * b + 3)] = b;
+    unsigned long long weight_mismatch = 0, missing_blocks = 0, extra_observed = 0;
+    double max_sdf = 0, max_col = 0;
+    std::vector<char> seen(got.n, 0);
+    for (size_t b = 0; b < want.n; ++b) {
+        std::map<std::vector<int32_t>, size_t>::const_iterator it = at.find(std::vector<int32_t>(want.keys.begin() + 3 * b, want.keys.begin() + 3 * b + 3));
+        if (it == at.end()) { ++missing_blocks; continue; }
+        seen[it->second] = 1;
+        const float* w = &want.vox[b * 2560];
+        const float* g = &got.vox[it->second * 2560];
+        for (int i = 0; i < 512; ++i) {
+            if (w[5 * i + 1] != g[5 * i + 1]) { ++weight_mismatch; continue; }
+            if (!(w[5 * i + 1] > 0)) continue;
+            max_sdf = std::fmax(max_sdf, std::fabs(static_cast<double>(w[5 * i]) - static_cast<double>(g[5 * i])));
+            for (int c = 2; c < 5; ++c) max_col = std::fmax(max_col, std::fabs(static_cast<double>(w[5 * i + c]) - static_cast<double>(g[5 * i + c])));
+        }
+    }
+    for (size_t b = 0; b < got.n; ++b) // blocks only the drifted frames selected: they remain, and must hold nothing
+        if (!seen[b])
+            for (int i = 0; i < 512; ++i)
+                if (got.vox[b * 2560 + 5 * i + 1] != 0.0f) ++extra_observed;
+    uint64_t dei[4] = {0, 0, 0, 0};
+    op_volume_deintegrate_stats(volume.Handle(), &dei[0], &dei[1], &dei[2], &dei[3]);
+    std::cout << "{\"frames\": " << n << ", \"stride\": " << stride << ", \"first\": " << first << ", \"perturbed\": " << perturb << ", \"res\": " << res << ", \"path\": \"" << path
+              << "\", \"runs\": " << runs << ", \"repair_ms_min_max\": [" << repair_s.front() * 1000.0 << ", " << repair_s.back() * 1000.0 << "]"
+              << ", \"ms\": {\"fuse_drifted\": " << t_fuse * 1000.0 << ", \"repair\": " << t_repair * 1000.0 << ", \"reference\": " << t_reference * 1000.0 << "}"
+              << ", \"blocks_drifted\": " << blocks_drifted << ", \"blocks\": " << got.n << ", \"blocks_reference\": " << want.n << ", \"missing_blocks\": " << missing_blocks
+              << ", \"weight_mismatches\": " << weight_mismatch + extra_observed << ", \"max_abs_sdf_diff\": " << max_sdf << ", \"max_abs_colour_diff\": " << max_col
+              << ", \"deintegrated\": {\"frames\": " << dei[0] << ", \"reverted\": " << dei[1] << ", \"reset\": " << dei[2] << ", \"skipped\": " << dei[3] << "}}" << std::endl;
+    return 0;
+}

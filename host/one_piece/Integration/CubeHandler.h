@@ -121,6 +121,13 @@ class CubeHandler {
     // on the volume's stream and the aligned image never leaves the device
     void IntegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& pose, const camera::PinholeCamera& rgb_camera,
                         const geometry::TransformationMatrix& color_to_depth = geometry::TransformationMatrix::Identity());
+    // EXTENSION (not in the reference): takes a frame that was fused at `pose` out of the volume again -- the steps of IntegrateImage (same selection,
+    // same pixel, same predicate) with TSDFVoxel::operator+ given an observation of weight -1; a voxel whose weight returns to 0 is the default voxel
+    // again (op_volume_deintegrate states the definition).  Queued like IntegrateImage, in call order with the integrations around it.
+    void DeintegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& pose);
+    // EXTENSION: DeintegrateImage(depth, rgb, old_pose) then IntegrateImage(depth, rgb, new_pose) on one uploaded copy of the images and in one launch
+    // (op_volume_reintegrate): what a corrected pose of an already fused frame is used for.
+    void ReintegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& old_pose, const geometry::TransformationMatrix& new_pose);
     CubeID GetCubeID(const geometry::Point3& point) const { return c_para.GetCubeID(point); }
     void AddCube(const CubeID& cube_id);
     // allocate the blocks the voxel centres of v_cube land in after trans: their eight trilinear neighbours / the voxel

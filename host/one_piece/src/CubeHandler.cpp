@@ -212,6 +212,24 @@ void CubeHandler::IntegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const
     static const bool verbose = std::getenv("ONEPIECE_HIP_VERBOSE") != nullptr;
     if (verbose) std::cout << GREEN << "[IntegrateImage]::[Info]::Image queued for integration." << RESET << std::endl;
 }
+void CubeHandler::DeintegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& pose) {
+    Pending();
+    if (!Ensure()) return;
+    Touch();
+    float p[16], pi[16];
+    bridge::RowMajor(pose, p);
+    bridge::RowMajor(pose.inverse(), pi); // as IntegrateImage forms it: the voxels project to the pixels the fused frame used
+    if (op_volume_deintegrate(vol, depth.data, bridge::DepthFormat(depth), rgb.data, OP_MEM_HOST, p, pi) != OP_OK) Report("DeintegrateImage");
+}
+void CubeHandler::ReintegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& old_pose, const geometry::TransformationMatrix& new_pose) {
+    Pending();
+    if (!Ensure()) return;
+    Touch();
+    float po[16], pn[16];
+    bridge::RowMajor(old_pose, po);
+    bridge::RowMajor(new_pose, pn);
+    if (op_volume_reintegrate(vol, depth.data, bridge::DepthFormat(depth), rgb.data, OP_MEM_HOST, po, pn) != OP_OK) Report("ReintegrateImage");
+}
 void CubeHandler::IntegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& pose, const camera::PinholeCamera& rgb_camera,
                                  const geometry::TransformationMatrix& color_to_depth) {
     Pending();

@@ -271,7 +271,8 @@ int op_volume_set_option(op_volume *v, int option, int value);
 /* How far the volume has got with the frames handed to op_volume_integrate / _sequence, WITHOUT waiting: frames accepted so far, and how many
  * of them belong to batches the device has reported complete (frames are queued up to 32 per launch and a launched batch may still be
  * replayed after a pool growth).  Device images of the first `frames_done` frames (OP_MEM_DEVICE, in call order) are
- * no longer read and may be released or overwritten; host images are only borrowed for the call anyway. */
+ * no longer read and may be released or overwritten; host images are only borrowed for the call anyway.  Every queue entry counts: a
+ * de-integration is one, a re-integration two. */
 int op_volume_progress(op_volume *v, uint64_t *frames_accepted, uint64_t *frames_done);
 int op_volume_clear(op_volume *v);                            /* CubeHandler.h:133-136 */
 int op_volume_sync(op_volume *v);
@@ -340,9 +341,47 @@ int op_volume_integrate_unaligned(op_volume *v, const void *depth, int depth_fmt
 int op_volume_integrate_unaligned_sequence(op_volume *v, const void *depth, size_t depth_stride_bytes, int depth_fmt, const uint8_t *color,
                                            size_t color_stride_bytes, int color_rows, int color_cols, const op_camera *color_cam,
                                            const float *color_to_depth, const float *poses, size_t n_frames);
+/* DE-INTEGRATION: take a fused frame out of the volume again (NO reference member; the arithmetic is the reference's own).  D(depth, rgb, pose)
+ * takes the steps of IntegrateImage(depth, rgb, pose) (Integrator.cpp:52-92): the frame is prepared and its blocks are selected as for a fused frame --
+ * neither depends on what the volume stores -- and a selected block the volume does not hold is ALLOCATED, all-default, exactly as integration would.
+ * Every voxel of a selected block is projected to the same pixel and tested by the same predicate (pixel inside, d > 0, |new_sdf| < truncation).  A voxel
+ * that passes holds (s, w, c); with the observation o = new_sdf and oc = byte / 255 per channel it receives TSDFVoxel::operator+ (TSDFVoxel.h:24-39)
+ * with an observation of weight -1, the inverse of the running mean:
+ *   1. applied iff TSDFVoxel::IsValid (!(s >= 1 || w <= 0)) and w >= 1; otherwise the voxel is left as it is and counted `skipped` (never observed,
+ *      invalid, or a fractional weight < 1 from an upload or a merge; the reference's `weight == 0 -> return other` would store weight -1: not reproduced);
+ *   2. rw = w + (-1) in float32;
+ *   3. rw == 0: the voxel becomes the default voxel {999, 0, -1, -1, -1}, the reference's default-constructed result (`reset`);
+ *   4. otherwise s' = (RN(w s) + RN(-1 o)) / rw, the same per colour channel, w' = rw (`reverted`): every product, sum and quotient rounded to float32.
+ * So a frame fused and de-integrated at the SAME pose leaves the weights exactly as they were, a voxel only that frame had seen default again, and sdf /
+ * colour within a few float32 roundings per operation of never having fused it (tests/test_deintegrate_cpu.py derives the bound).
+ * Queue entries -- integrations and de-integrations alike -- are applied to a voxel in call order; they share the queue and its batches of up to 32
+ * per launch, and a batch that holds a de-integration runs one kernel (k_update_signed) for all its entries.  After such a launch the volume keeps the
+ * general (reference-literal) update for the blocks that existed then, and the shorter exact forms of k_integrate's first frames are not used again
+ * until op_volume_clear; OP_VOLUME_UPDATE_SUM_FORM does not apply to such a launch (its entries take the exact forms); the raycaster's block summaries
+ * are invalidated.  Images: as for op_volume_integrate (OP_MEM_HOST copied before the call returns, OP_MEM_DEVICE valid until the next synchronising
+ * call).  Frames of a second colour camera are aligned first (op_align_color_to_depth). */
+int op_volume_deintegrate(op_volume *v, const void *depth, int depth_fmt, const uint8_t *rgb, int mem, const float pose[16],
+                          const float *pose_inv);
+/* Multi-frame form for device-resident frames, mirroring op_volume_integrate_sequence (TSDFVoxel.h:24-39 with weight -1 under the predicate of
+ * Integrator.cpp:52-92, as above): bit-identical to n_frames op_volume_deintegrate calls in order. */
+int op_volume_deintegrate_sequence(op_volume *v, const void *depth, size_t depth_stride_bytes, int depth_fmt, const uint8_t *rgb,
+                                   size_t rgb_stride_bytes, const float *poses, size_t n_frames);
+/* R(depth, rgb, old_pose, new_pose) = D(old_pose) then I(new_pose) (TSDFVoxel.h:24-39 with weights -1 and +1 under the predicate of
+ * Integrator.cpp:52-92, as above) as two entries of the queue on ONE uploaded copy of the images: a frame that was fused at old_pose moves to
+ * new_pose.  Both entries stay in one launch.  With old_pose == new_pose every weight is exactly unchanged. */
+int op_volume_reintegrate(op_volume *v, const void *depth, int depth_fmt, const uint8_t *rgb, int mem, const float old_pose[16],
+                          const float new_pose[16]);
+/* Multi-frame form for device-resident frames: D(old_poses + 16 f), I(new_poses + 16 f) for f = 0 .. n_frames - 1 in that order (definition above:
+ * TSDFVoxel.h:24-39, Integrator.cpp:52-92), 16 frames per launch. */
+int op_volume_reintegrate_sequence(op_volume *v, const void *depth, size_t depth_stride_bytes, int depth_fmt, const uint8_t *rgb,
+                                   size_t rgb_stride_bytes, const float *old_poses, const float *new_poses, size_t n_frames);
+/* Counters of the de-integrations since create/clear (synchronises): frames de-integrated, and of their voxels that passed the predicate of
+ * Integrator.cpp:52-92 those that were reverted (step 4 above), reset to the default voxel (step 3) and skipped (step 1; TSDFVoxel.h:24-39). */
+int op_volume_deintegrate_stats(op_volume *v, uint64_t *frames, uint64_t *reverted, uint64_t *reset, uint64_t *skipped);
 /* Counters since create/clear (synchronises): frames integrated, sum over frames of
  * len(cube_id_list), of voxels visited (512 x len) and of voxels that passed the update predicate
- * (Integrator.cpp:63,70,74). */
+ * (Integrator.cpp:63,70,74).  frames, blocks_selected and voxels_visited also count DE-INTEGRATED frames (they are prepared and selected like fused
+ * ones); voxels_updated counts integration updates only -- op_volume_deintegrate_stats has the rest. */
 int op_volume_stats(op_volume *v, uint64_t *frames, uint64_t *blocks_selected, uint64_t *voxels_visited,
                     uint64_t *voxels_updated);
 /* Launch-level counters since create/clear (synchronises; measurement hook, no reference counterpart):

@@ -132,6 +132,11 @@ SIGNATURES = {
     "op_volume_integrate": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, _fp]),
     "op_volume_integrate_sequence": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, _fp,
                                                C.c_size_t]),
+    "op_volume_deintegrate": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, _fp]),
+    "op_volume_deintegrate_sequence": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, _fp, C.c_size_t]),
+    "op_volume_reintegrate": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, _fp]),
+    "op_volume_reintegrate_sequence": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, _fp, _fp, C.c_size_t]),
+    "op_volume_deintegrate_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
     "op_volume_integrate_cubes": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, _fp, _vp, C.c_size_t]),
     "op_volume_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
     "op_volume_stats_launches": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),

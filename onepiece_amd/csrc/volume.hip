@@ -113,13 +113,14 @@ int vol_reset(op_volume* v) {
     OP_HIP(hipMemsetAsync(v->upd_partial, 0, sizeof(unsigned long long) * kPartialGrid, v->stream));
     OP_HIP(hipMemsetAsync(v->sel_partial, 0, sizeof(unsigned long long) * kPartialGrid, v->stream));
     OP_HIP(hipMemsetAsync(v->chg_partial, 0, sizeof(unsigned long long) * 2 * kPartialGrid, v->stream));
+    OP_HIP(hipMemsetAsync(v->dei_partial, 0, sizeof(unsigned long long) * (3 * kPartialGrid + 8), v->stream));
     OP_HIP(hipGetLastError());
     return OP_OK;
 }
 
 
 int vol_enqueue_batch(op_volume* v, const BatchFwd& F, const BatchInv& I, const BatchPtrs& Q, int nf, int depth_fmt, bool select_only, bool record,
-                      const int* cube_keys = nullptr, unsigned n_cubes = 0);
+                      const int* cube_keys = nullptr, unsigned n_cubes = 0, bmask_t sign = 0);
 
 // Grows the pool to new_max blocks (and the hash table to twice that), keeping the first n_valid blocks.  The stream
 // must be idle.  The new buffers are allocated before the old ones are released, so a failed allocation leaves the
@@ -229,7 +230,7 @@ int vol_recover(op_volume* v, unsigned* flags_out) {
         v->recovering = true;
         int rrc = OP_OK;
         for (auto& r : replay) {
-            rrc = vol_enqueue_batch(v, r.F, r.I, r.P, r.nf, r.fmt, false, false); // assigns a new sequence number
+            rrc = vol_enqueue_batch(v, r.F, r.I, r.P, r.nf, r.fmt, false, false, nullptr, 0, r.sign); // assigns a new sequence number; the batch keeps its signs
             ++v->n_replayed;
             if (rrc != OP_OK) break;
             if (r.ring_slot >= 0) v->ring[r.ring_slot].busy_seq = v->seq;
@@ -247,6 +248,12 @@ int vol_check(op_volume* v) {
     OP_HIP(hipStreamSynchronize(v->stream));
     unsigned of = 0;
     OP_TRY(vol_recover(v, &of));
+    if (v->dei_pending) { // every launch that held a de-integration has run: the blocks they may have changed are the ones that exist now (as after an upload or a merge)
+        unsigned n = 0;
+        OP_HIP(hipMemcpy(&n, v->n_blocks, sizeof(n), hipMemcpyDeviceToHost));
+        v->plain_from = n < v->max_blocks ? n : v->max_blocks;
+        v->dei_pending = false;
+    }
     if (of & 12u) { // report once, then clear: the offending frames selected nothing, everything else was fused
         const unsigned zero = 0;
         OP_HIP(hipMemcpy(&v->state->overflow, &zero, sizeof(zero), hipMemcpyHostToDevice));
@@ -330,8 +337,10 @@ int vol_ensure_frame_buffers(op_volume* v) {
 // select_only, KC.  No host synchronisation.
 // With cube_keys (device array of n_cubes ids, nf == 1): KB is replaced by k_mark_cubes -- the frame is fused into exactly
 // those cubes (op_volume_integrate_cubes); the caller has reserved the room and synchronises, so the batch is not logged.
+// sign: bit f set = entry f is a de-integration.  A batch with a non-zero sign mask takes k_update_signed (deintegrate.hip) in KC's place, and
+// the volume stops being plain and lean (until it is cleared): that kernel writes weights and means k_integrate's short forms do not cover.
 int vol_enqueue_batch(op_volume* v, const BatchFwd& F, const BatchInv& I, const BatchPtrs& Q, int nf, int depth_fmt, bool select_only, bool record,
-                      const int* cube_keys, unsigned n_cubes) {
+                      const int* cube_keys, unsigned n_cubes, bmask_t sign) {
     OP_TRY(vol_ensure_frame_buffers(v));
     // Look at the device's lagging progress report (no synchronisation): retire confirmed batches and, when the pool is
     // about to run full, grow it NOW -- between batches -- instead of paying for a replay later.
@@ -351,8 +360,8 @@ int vol_enqueue_batch(op_volume* v, const BatchFwd& F, const BatchInv& I, const 
     }
     const unsigned seq = (unsigned)(++v->seq);
     ++v->generation;
-    if (select_only || !vol_fusion_keeps_summaries(v)) ++v->content_gen; // (otherwise k_integrate restates the raycaster's summaries of what it changes)
-    if (!select_only && !cube_keys) v->log.push_back(op_volume::BatchRec{v->seq, F, I, Q, nf, depth_fmt, -1});
+    if (select_only || sign || !vol_fusion_keeps_summaries(v)) ++v->content_gen; // (otherwise k_integrate restates the raycaster's summaries of what it changes)
+    if (!select_only && !cube_keys) v->log.push_back(op_volume::BatchRec{v->seq, F, I, Q, nf, depth_fmt, -1, sign});
     const CamParams C = cam_params(v, depth_fmt);
     const bool sample = !select_only && v->prof_every > 0 && (v->prof_batch++ % (uint64_t)v->prof_every) == 0 &&
                         v->prof_events.size() < 4 * 65536;
@@ -366,6 +375,11 @@ int vol_enqueue_batch(op_volume* v, const BatchFwd& F, const BatchInv& I, const 
     OP_TRY(launch_select(v, I, C, nf, record, cube_keys, n_cubes));
     if (sample) OP_HIP(hipEventRecord(ev[2], v->stream));
     if (select_only) launch_finish_select(v);
+    else if (sign) {
+        v->plain = false; v->lean_ok = false;
+        v->plain_from = 0xffffffffu; v->dei_pending = true; // tightened to the block count by the next vol_check
+        launch_update_signed(v, I, C, nf, sign);
+    }
     else launch_integrate(v, I, C, nf);
     if (sample) {
         OP_HIP(hipEventRecord(ev[3], v->stream));
@@ -380,14 +394,16 @@ int vol_enqueue_batch(op_volume* v, const BatchFwd& F, const BatchInv& I, const 
 int vol_flush(op_volume* v) {
     if (v->pend_n == 0) return OP_OK;
     const int nf = v->pend_n, rs = v->ring_cur;
+    const bmask_t sign = v->pend_sign;
     v->pend_n = 0;
+    v->pend_sign = 0;
     v->ring_cur = -1;
     if (rs >= 0) { // the batch's kernels start when its host images have arrived
         OP_TRY(vol_ring_send(v, v->ring[rs]));
         OP_HIP(hipEventRecord(v->ring[rs].copied, v->copy_stream));
         OP_HIP(hipStreamWaitEvent(v->stream, v->ring[rs].copied, 0));
     }
-    OP_TRY(vol_enqueue_batch(v, v->pend_F, v->pend_I, v->pend_P, nf, v->pend_fmt, false, false));
+    OP_TRY(vol_enqueue_batch(v, v->pend_F, v->pend_I, v->pend_P, nf, v->pend_fmt, false, false, nullptr, 0, sign));
     if (rs >= 0) { v->ring[rs].busy_seq = v->seq; v->log.back().ring_slot = rs; }
     return OP_OK;
 }
@@ -868,6 +884,7 @@ int op_volume_create(const op_camera* cam, float voxel_res, float truncation, fl
     OP_HIP_C(op::cached_malloc((void**)&v->state, sizeof(State)));
     OP_HIP_C(op::cached_malloc((void**)&v->upd_partial, sizeof(unsigned long long) * kPartialGrid));
     OP_HIP_C(op::cached_malloc((void**)&v->chg_partial, sizeof(unsigned long long) * 2 * kPartialGrid));
+    OP_HIP_C(op::cached_malloc((void**)&v->dei_partial, sizeof(unsigned long long) * (3 * kPartialGrid + 8)));
     OP_HIP_C(op::cached_host_malloc((void**)&v->hstat, 2 * sizeof(unsigned)));
     v->hstat[0] = 0; v->hstat[1] = 0;
     OP_HIP_C(hipHostGetDevicePointer((void**)&v->hstat_dev, v->hstat, 0));
@@ -888,7 +905,7 @@ int op_volume_destroy(op_volume* v) {
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     for (auto e : v->prof_events) (void)hipEventDestroy(e);
     void* ptrs[] = {v->tkeys, v->tvals, v->keys, v->pool, v->n_blocks, v->bmask, v->blist, v->sel_list, v->sel_cand, v->state,
-                    v->partial, v->pimg, v->ptile, v->sbits, v->upd_partial, v->sel_partial, v->chg_partial, v->img_depth, v->img_rgb, v->unpack_slots, v->rc_list, v->rc_count, v->rc_hit, v->rc_sum, v->rc_order, v->rf_col, v->rf_count};
+                    v->partial, v->pimg, v->ptile, v->sbits, v->upd_partial, v->sel_partial, v->chg_partial, v->dei_partial, v->img_depth, v->img_rgb, v->unpack_slots, v->rc_list, v->rc_count, v->rc_hit, v->rc_sum, v->rc_order, v->rf_col, v->rf_count};
     for (void* p : ptrs)
         if (p) op::cached_free(p);
     if (v->copy_stream) (void)hipStreamSynchronize(v->copy_stream);
@@ -966,12 +983,13 @@ int op_volume_set_option(op_volume* v, int option, int value) {
 int op_volume_clear(op_volume* v) {
     OP_VOL(v);
     v->pend_n = 0; // queued frames would be wiped anyway
+    v->pend_sign = 0;
     v->ring_cur = -1;
     unsigned n = 0;
     if (v->copy_stream) OP_HIP(hipStreamSynchronize(v->copy_stream));
     OP_HIP(hipStreamSynchronize(v->stream));
     v->log.clear(); // whatever was in flight (fused or poisoned) is wiped with the volume
-    v->plain = true; v->plain_from = 0; v->lean_ok = true; v->lean_frames = 0;
+    v->plain = true; v->plain_from = 0; v->lean_ok = true; v->lean_frames = 0; v->dei_pending = false;
     for (auto& r : v->ring) r.busy_seq = 0;
     if (v->hstat) v->hstat[1] = 0;
     OP_HIP(hipMemcpy(&n, v->n_blocks, sizeof(n), hipMemcpyDeviceToHost));
@@ -1162,6 +1180,90 @@ int op_volume_integrate_sequence(op_volume* v, const void* depth, size_t depth_s
         ++v->frames_accepted;
         if (++v->pend_n == kMaxBatch) OP_TRY(vol_flush(v));
     }
+    return OP_OK;
+}
+
+} // extern "C"
+
+namespace {
+// The device comes first, as everywhere else: without one the new entries answer OP_ERR_NO_DEVICE whatever their arguments are.
+#define OP_VOL_DEV(v)                                                                             \
+    if (!(v)) { OP_TRY(op::use_device(0)); return fail(OP_ERR_INVALID, "null volume"); }          \
+    OP_HIP(hipSetDevice((v)->device))
+
+// One entry of the queue op_volume_integrate fills, with its sign; the images are on the device (or on their way there through the ring).
+int queue_entry(op_volume* v, const void* depth, const unsigned char* rgb, int depth_fmt, const float* pose, const float* pose_inv, bool negative) {
+    const int slot = v->pend_n;
+    frame_params(v, pose, pose_inv, &v->pend_F.f[slot], &v->pend_I.f[slot]);
+    v->pend_P.depth[slot] = depth;
+    v->pend_P.rgb[slot] = rgb;
+    v->pend_fmt = depth_fmt;
+    if (negative) v->pend_sign |= (bmask_t)1 << slot;
+    ++v->frames_accepted;
+    if (++v->pend_n == kMaxBatch) return vol_flush(v);
+    return OP_OK;
+}
+
+// A re-integration is two entries, D(old_pose) then I(new_pose), on ONE copy of the images.  They stay in one batch (a queue with a single free
+// place is launched first): the batch's ring slot then holds the images for both, and a replay of the batch finds them together.
+int queue_pair(op_volume* v, const void* depth, const unsigned char* rgb, int depth_fmt, int mem, const float* old_pose, const float* new_pose) {
+    if (v->pend_n > 0 && v->pend_fmt != depth_fmt) OP_TRY(vol_flush(v));
+    if (mem == OP_MEM_HOST) OP_TRY(vol_ring_alloc(v)); // (may launch what is queued: the queue position is only valid afterwards)
+    if (v->pend_n == kMaxBatch - 1) OP_TRY(vol_flush(v));
+    if (mem == OP_MEM_HOST) OP_TRY(vol_ring_stage(v, &depth, depth_fmt, &rgb, v->pend_n));
+    OP_TRY(queue_entry(v, depth, rgb, depth_fmt, old_pose, nullptr, true));
+    return queue_entry(v, depth, rgb, depth_fmt, new_pose, nullptr, false);
+}
+} // namespace
+
+extern "C" {
+
+int op_volume_deintegrate(op_volume* v, const void* depth, int depth_fmt, const uint8_t* rgb, int mem, const float pose[16], const float* pose_inv) {
+    OP_VOL_DEV(v);
+    if (!depth || !rgb || !pose) return fail(OP_ERR_INVALID, "null argument");
+    if (v->pend_n > 0 && v->pend_fmt != depth_fmt) OP_TRY(vol_flush(v));
+    const unsigned char* c = rgb;
+    if (mem == OP_MEM_HOST) {
+        OP_TRY(vol_ring_alloc(v));
+        OP_TRY(vol_ring_stage(v, &depth, depth_fmt, &c, v->pend_n));
+    }
+    return queue_entry(v, depth, c, depth_fmt, pose, pose_inv, true);
+}
+
+int op_volume_deintegrate_sequence(op_volume* v, const void* depth, size_t depth_stride_bytes, int depth_fmt, const uint8_t* rgb, size_t rgb_stride_bytes,
+                                   const float* poses, size_t n_frames) {
+    OP_VOL_DEV(v);
+    if (!depth || !rgb || !poses) return fail(OP_ERR_INVALID, "null argument");
+    if (v->pend_n > 0 && v->pend_fmt != depth_fmt) OP_TRY(vol_flush(v));
+    for (size_t f = 0; f < n_frames; ++f)
+        OP_TRY(queue_entry(v, (const char*)depth + f * depth_stride_bytes, rgb + f * rgb_stride_bytes, depth_fmt, poses + 16 * f, nullptr, true));
+    return OP_OK;
+}
+
+int op_volume_reintegrate(op_volume* v, const void* depth, int depth_fmt, const uint8_t* rgb, int mem, const float old_pose[16], const float new_pose[16]) {
+    OP_VOL_DEV(v);
+    if (!depth || !rgb || !old_pose || !new_pose) return fail(OP_ERR_INVALID, "null argument");
+    return queue_pair(v, depth, rgb, depth_fmt, mem, old_pose, new_pose);
+}
+
+int op_volume_reintegrate_sequence(op_volume* v, const void* depth, size_t depth_stride_bytes, int depth_fmt, const uint8_t* rgb, size_t rgb_stride_bytes,
+                                   const float* old_poses, const float* new_poses, size_t n_frames) {
+    OP_VOL_DEV(v);
+    if (!depth || !rgb || !old_poses || !new_poses) return fail(OP_ERR_INVALID, "null argument");
+    for (size_t f = 0; f < n_frames; ++f)
+        OP_TRY(queue_pair(v, (const char*)depth + f * depth_stride_bytes, rgb + f * rgb_stride_bytes, depth_fmt, OP_MEM_DEVICE, old_poses + 16 * f, new_poses + 16 * f));
+    return OP_OK;
+}
+
+int op_volume_deintegrate_stats(op_volume* v, uint64_t* frames, uint64_t* reverted, uint64_t* reset, uint64_t* skipped) {
+    OP_VOL_DEV(v);
+    OP_TRY(vol_check(v));
+    unsigned long long c[4];
+    OP_TRY(vol_deintegrate_counts(v, c));
+    if (frames) *frames = c[0];
+    if (reverted) *reverted = c[1];
+    if (reset) *reset = c[2];
+    if (skipped) *skipped = c[3];
     return OP_OK;
 }
 

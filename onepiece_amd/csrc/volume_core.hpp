@@ -3,6 +3,7 @@
 //   volume.hip      the host object: create / grow / replay, the staging ring, the integrate entry points (C-ABI), pool and table maintenance kernels
 //   select.hip      KA k_prepare_frames (ComputeBounding + frame packing), KB k_select / k_select_vote / k_select_merge (PrepareCubes)
 //   integrate.hip   KC k_integrate (Integrator::IntegrateImage)
+//   deintegrate.hip k_update_signed: KC's place in a batch that holds a de-integration (TSDFVoxel::operator+ with weight -1)
 //   volume_ops.hip  GetCubeMap / SetCubeMap / Merge / sum-form pack + unpack / Transform / GetPointCloud / ExtractTriangleMesh / .map files
 //   raycast.hip     the raycaster, and its view packed as an RGB-D frame (model_frame.hpp: what the dense tracker takes from here)
 // Data layout in HBM: see volume.hip (and DESIGN.md section 2).
@@ -493,7 +494,7 @@ struct op_volume {
     // Growth / replay.  Every launched batch is logged until it is confirmed complete; if a batch exhausts the pool or the
     // hash table the stream is poisoned on the device (nothing is fused from that batch on), and the host -- at its next
     // look -- grows the volume and replays the log from the failing batch.  No frame is lost or partially applied.
-    struct BatchRec { uint64_t seq; BatchFwd F; BatchInv I; BatchPtrs P; int nf, fmt, ring_slot; };
+    struct BatchRec { uint64_t seq; BatchFwd F; BatchInv I; BatchPtrs P; int nf, fmt, ring_slot; bmask_t sign = 0; }; // sign: bit f set = entry f is a de-integration
     std::deque<BatchRec> log;
     uint64_t seq = 0;            // sequence number of the last launched batch
     unsigned* hstat = nullptr;   // pinned + mapped: [0] = last batch known complete, [1] = n_blocks at that time
@@ -533,6 +534,12 @@ struct op_volume {
     BatchFwd pend_F;
     BatchInv pend_I;
     BatchPtrs pend_P;
+    bmask_t pend_sign = 0;       // bit f: queue entry f is a de-integration (op_volume_deintegrate*, the first half of op_volume_reintegrate*)
+    // De-integration (deintegrate.hip).  A launch that holds one takes k_update_signed; from then on the volume is neither plain nor lean until it is
+    // cleared.  The blocks such a launch may have changed are known once it has run: until the next synchronising look (vol_check) plain_from covers
+    // every slot (dei_pending), then it is the block count, as after an upload or a merge.
+    bool dei_pending = false;
+    unsigned long long* dei_partial = nullptr; // 3 x kPartialGrid slots k_update_signed's workgroups add to (reverted, reset, skipped) + [3 x kPartialGrid] de-integrated frames
     // Aligned-colour ring of op_volume_integrate_unaligned (align_color.hip): kUaSlots images of the volume camera's size, written by k_align_color on
     // `stream`; for host frames also the device copies of their depth images (ua_depth, allocated with the first one) and two staging buffers for
     // the colour image the kernel reads.  ua_frame[s] = ordinal (frames_accepted) of the frame slot s was last given to: the slot is free once that
@@ -586,6 +593,9 @@ void kb_trace_dump(op_volume* v);            // -DKB_TRACE builds only
 void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int nf);
 bool vol_fusion_keeps_summaries(const op_volume* v); // integrate.hip: this batch's k_integrate restates the raycaster's summaries of the blocks it changes
 void kc_trace_dump(op_volume* v);            // -DKC_TRACE builds only
+// deintegrate.hip: k_update_signed, KC's place in a batch whose sign mask is not zero
+void launch_update_signed(op_volume* v, const BatchInv& I, const CamParams& C, int nf, bmask_t sign);
+int vol_deintegrate_counts(op_volume* v, unsigned long long out[4]); // frames, reverted, reset, skipped since create / clear (the stream is idle)
 // volume_ops.hip: the count and emit passes of k_mesh into device buffers (op_volume_extract_mesh; mesh_cluster.hip simplifies the soup in place)
 int vol_mesh_soup(op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, bool emit, size_t cap_vertices, float** d_pts_out,
                   float** d_col_out, size_t* n_vertices);

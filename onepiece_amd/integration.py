@@ -206,6 +206,66 @@ class CubeHandler:
         if len(self._alive) > 4096:
             self.Synchronize()
 
+    # -- de-integration (extension; op_volume_deintegrate* / op_volume_reintegrate*: TSDFVoxel::operator+ with weight -1 under IntegrateImage's predicate)
+    def _image_pair(self, depth, rgb):
+        pd, fmt, mem, k1 = _image_arg(depth, "depth")
+        pr, _f, mem2, k2 = _image_arg(rgb, "rgb")
+        if mem != mem2:
+            raise ValueError("depth and rgb must both be host arrays or both be device tensors")
+        return pd, fmt, pr, mem, (k1, k2)
+
+    def _keep(self, mem, keep):
+        if mem == L.OP_MEM_DEVICE:
+            self._alive.append(keep)
+            if len(self._alive) > 4096:
+                self.Synchronize()
+
+    def DeintegrateImage(self, depth, rgb, pose, pose_inv=None):
+        """Takes a frame that was fused at `pose` out again (the steps of IntegrateImage with an observation of weight -1; a voxel whose
+        weight returns to 0 is the default voxel again).  Asynchronous, in call order with the integrations around it."""
+        pd, fmt, pr, mem, keep = self._image_pair(depth, rgb)
+        pose = _f32(pose).reshape(16)
+        pinv = _f32(pose_inv).reshape(16) if pose_inv is not None else None
+        L.check(self._lib.op_volume_deintegrate(self._h, pd, fmt, pr, mem, _fp(pose), _fp(pinv) if pinv is not None else None))
+        self._keep(mem, keep)
+
+    def ReintegrateImage(self, depth, rgb, old_pose, new_pose):
+        """DeintegrateImage(depth, rgb, old_pose) then IntegrateImage(depth, rgb, new_pose) on one uploaded copy of the images, in one launch."""
+        pd, fmt, pr, mem, keep = self._image_pair(depth, rgb)
+        old, new = _f32(old_pose).reshape(16), _f32(new_pose).reshape(16)
+        L.check(self._lib.op_volume_reintegrate(self._h, pd, fmt, pr, mem, _fp(old), _fp(new)))
+        self._keep(mem, keep)
+
+    def _sequence_args(self, depth, rgb):
+        pd, fmt, pr, mem, keep = self._image_pair(depth, rgb)
+        if mem != L.OP_MEM_DEVICE:
+            raise ValueError("the sequence forms need device-resident frames")
+        npx = self.camera.width * self.camera.height
+        return pd, npx * (2 if fmt == L.OP_DEPTH_U16 else 4), fmt, pr, npx * 3, keep
+
+    def DeintegrateSequence(self, depth, rgb, poses):
+        """n device-resident frames (torch tensors [n,h,w] / [n,h,w,3]); identical to n DeintegrateImage calls in order."""
+        n = depth.shape[0]
+        pd, ds, fmt, pr, rs, keep = self._sequence_args(depth, rgb)
+        poses = _f32(poses).reshape(n, 16)
+        L.check(self._lib.op_volume_deintegrate_sequence(self._h, pd, ds, fmt, pr, rs, _fp(poses), n))
+        self._keep(L.OP_MEM_DEVICE, keep)
+
+    def ReintegrateSequence(self, depth, rgb, old_poses, new_poses):
+        """n device-resident frames moved from old_poses[f] to new_poses[f]; identical to n ReintegrateImage calls in order (16 frames per launch)."""
+        n = depth.shape[0]
+        pd, ds, fmt, pr, rs, keep = self._sequence_args(depth, rgb)
+        old, new = _f32(old_poses).reshape(n, 16), _f32(new_poses).reshape(n, 16)
+        L.check(self._lib.op_volume_reintegrate_sequence(self._h, pd, ds, fmt, pr, rs, _fp(old), _fp(new), n))
+        self._keep(L.OP_MEM_DEVICE, keep)
+
+    def DeintegrateStats(self):
+        """De-integrations since create / Clear (synchronises): frames, and of their voxels that passed the update predicate those reverted,
+        reset to the default voxel and skipped (op_volume_deintegrate_stats)."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        L.check(self._lib.op_volume_deintegrate_stats(self._h, *[C.byref(x) for x in v]))
+        return {"frames": v[0].value, "reverted": v[1].value, "reset": v[2].value, "skipped": v[3].value}
+
     def IntegrateImageUnaligned(self, depth, rgb, pose, rgb_camera, color_to_depth=None, pose_inv=None):
         """Extension: IntegrateImage(depth, tool::AlignColorToDepth(rgb, depth, rgb_camera, this camera, color_to_depth), pose) for a colour image
         from a second camera ([hc, wc, 3], any size) -- the ScanNet flow (example/GenerateModelFromScannet.cpp, Tool/IO.cpp:9-58).  The alignment

@@ -1,0 +1,334 @@
+"""De-integration and re-integration on the device (csrc/deintegrate.hip k_update_signed, op_volume_deintegrate* / op_volume_reintegrate*) against
+the oracle plus the numpy restatement of the definition (tests/deintegrate_common.py): block keys, every voxel bit for bit, and the counters.
+
+Shapes: the room at 37 x 29 and 64 x 48 into 4 cm voxels, 33 frames (launches of 32 + 1) and 70 (32 + 32 + 6), truncations 0.1 (lean until the
+first de-integration), 0.6 (plain) and 1.5 (an observation can itself be an invalid voxel)."""
+import numpy as np
+import pytest
+
+import deintegrate_common as D
+from onepiece_amd import integration as I
+
+pytestmark = pytest.mark.gpu
+
+CAMS = {"37x29": D.CAM_37, "64x48": D.CAM_64}
+TRUNCS = (0.1, 0.6, 1.5)
+_cache = {}
+
+
+def _frames(shape, n=70):
+    key = ("frames", shape)
+    if key not in _cache:
+        _cache[key] = D.frames(CAMS[shape], 70)
+    return _cache[key][:n]
+
+
+def _device(shape):
+    """the 70 frames as device tensors (depth [70,h,w], rgb [70,h,w,3])"""
+    import torch
+    key = ("device", shape)
+    if key not in _cache:
+        fr = _frames(shape)
+        dev = torch.device("cuda:0")
+        _cache[key] = (torch.from_numpy(np.stack([f[0] for f in fr])).to(dev).contiguous(), torch.from_numpy(np.stack([f[1] for f in fr])).to(dev).contiguous())
+        torch.cuda.synchronize()
+    return _cache[key]
+
+
+def _poses(shape, lo, hi):
+    return np.stack([f[2] for f in _frames(shape)[lo:hi]])
+
+
+def _handler(shape, trunc, max_blocks=1 << 14):
+    hcam = I.PinholeCamera()
+    hcam.fx, hcam.fy, hcam.cx, hcam.cy, hcam.width, hcam.height, hcam.depth_scale = CAMS[shape]
+    hv = I.CubeHandler(hcam, device=0, max_blocks=max_blocks)
+    hv.SetVoxelResolution(D.RES)
+    hv.SetTruncation(trunc)
+    return hv
+
+
+def _expected(oracle, key, build):
+    """an expected run, computed once: (keys, voxels, de-integration counts, entries, selected, updated, model)"""
+    if key not in _cache:
+        m = build()
+        k, v = m.export()
+        v.setflags(write=False)
+        _cache[key] = (k, v, dict(m.counts), m.entries, m.selected, m.updated, m)
+    return _cache[key]
+
+
+def _check(hv, exp, what=""):
+    ok, ox, counts, entries, selected, updated, _m = exp
+    hk, hx = hv.GetCubeMap()
+    assert hk.shape == ok.shape and np.array_equal(hk, ok), "block keys differ " + what
+    diff = (hx.view(np.uint32) != ox.view(np.uint32)).any(axis=-1)
+    assert not diff.any(), "%d voxels differ %s" % (int(diff.sum()), what)
+    got = hv.DeintegrateStats()
+    print("%s blocks %d, de-integration counters %s (restatement %s)" % (what, len(hk), got, counts))
+    assert got == counts
+    st = hv.Stats()
+    assert (st["frames"], st["blocks_selected"], st["voxels_visited"], st["voxels_updated"]) == (entries, selected, 512 * selected, updated)
+
+
+def _scenario_a(oracle, shape, trunc):
+    """fuse 33, de-integrate frames 10..20"""
+    def build():
+        m = D.Model(oracle, CAMS[shape], trunc)
+        for f in _frames(shape, 33):
+            m.integrate(f)
+        for f in _frames(shape, 33)[10:21]:
+            m.deintegrate(f)
+        return m
+    return _expected(oracle, ("a", shape, trunc), build)
+
+
+@pytest.mark.parametrize("trunc", TRUNCS)
+@pytest.mark.parametrize("shape", list(CAMS))
+def test_a_single_calls_with_host_images(oracle, shape, trunc):
+    exp = _scenario_a(oracle, shape, trunc)
+    assert exp[2]["reverted"] > 10000 and exp[2]["reset"] > 100
+    hv = _handler(shape, trunc)
+    fr = _frames(shape, 33)
+    for f in fr:
+        hv.IntegrateImage(*f)
+    for f in fr[10:21]:
+        hv.DeintegrateImage(*f)
+    _check(hv, exp, "(a) %s trunc %g:" % (shape, trunc))
+
+
+@pytest.mark.parametrize("trunc", TRUNCS)
+@pytest.mark.parametrize("shape", list(CAMS))
+def test_b_sequence_of_device_frames_gives_the_same_bits(oracle, shape, trunc):
+    exp = _scenario_a(oracle, shape, trunc)
+    depth, rgb = _device(shape)
+    hv = _handler(shape, trunc)
+    hv.IntegrateSequence(depth[:33], rgb[:33], _poses(shape, 0, 33))
+    hv.DeintegrateSequence(depth[10:21], rgb[10:21], _poses(shape, 10, 21))
+    _check(hv, exp, "(b) %s trunc %g:" % (shape, trunc))
+    assert hv.Stats()["launches"] == 2                      # 32 fused, then the 33rd frame with the 11 de-integrations in ONE signed launch
+
+
+@pytest.mark.parametrize("trunc", (0.1, 0.6))
+@pytest.mark.parametrize("shape", list(CAMS))
+def test_c_one_frame_fused_and_deintegrated_is_an_all_default_volume(oracle, shape, trunc):
+    f = _frames(shape)[12]
+    hv = _handler(shape, trunc)
+    hv.IntegrateImage(*f)
+    n0, upd = hv.BlockCount(), hv.Stats()["voxels_updated"]
+    assert hv.Raycast(f[2])[0].any()
+    hv.DeintegrateImage(*f)
+    keys, vox = hv.GetCubeMap()
+    assert len(keys) == n0 == hv.BlockCount() and D.is_default(vox).all()
+    assert hv.DeintegrateStats() == {"frames": 1, "reverted": 0, "reset": upd, "skipped": 0}
+    assert not hv.Raycast(f[2])[0].any(), "a raycast sees nothing"
+
+
+@pytest.mark.parametrize("trunc", TRUNCS)
+def test_d_integration_and_deintegration_queued_into_one_launch_apply_in_call_order(oracle, trunc):
+    shape = "37x29"
+    fr = _frames(shape)
+
+    def build():
+        m = D.Model(oracle, CAMS[shape], trunc)
+        return m.integrate(fr[3]).integrate(fr[4]).deintegrate(fr[3]).deintegrate(fr[4]).deintegrate(fr[4]).integrate(fr[5]).deintegrate(fr[5])
+    exp = _expected(oracle, ("d", trunc), build)
+    hv = _handler(shape, trunc)
+    hv.IntegrateImage(*fr[3]); hv.IntegrateImage(*fr[4])    # nothing is launched before the first accessor
+    hv.DeintegrateImage(*fr[3]); hv.DeintegrateImage(*fr[4]); hv.DeintegrateImage(*fr[4])
+    hv.IntegrateImage(*fr[5]); hv.DeintegrateImage(*fr[5])
+    _check(hv, exp, "(d) trunc %g:" % trunc)
+    assert hv.Stats()["launches"] == 1
+    if trunc < 1:
+        assert D.is_default(hv.GetCubeMap()[1]).all()
+    assert exp[2]["skipped"] > 0                            # the second de-integration of frame 4 finds nothing to take out
+
+
+@pytest.mark.parametrize("shape,trunc,n", [("37x29", 0.6, 16), ("37x29", 0.6, 17), ("64x48", 0.1, 17), ("37x29", 1.5, 16)])
+def test_e_reintegrate_sequence_is_d_i_d_i_in_that_order(oracle, shape, trunc, n):
+    fr = _frames(shape, 33)
+    moved = range(8, 8 + n)
+    old = {k: D.perturbed(fr[k][2], k) for k in moved}
+
+    def build():
+        m = D.Model(oracle, CAMS[shape], trunc)
+        for k, f in enumerate(fr):
+            m.integrate((f[0], f[1], old.get(k, f[2])))
+        for k in moved:
+            m.reintegrate((fr[k][0], fr[k][1], old[k]), fr[k][2])
+        return m
+    exp = _expected(oracle, ("e", shape, trunc, n), build)
+    depth, rgb = _device(shape)
+    poses = np.stack([old.get(k, fr[k][2]) for k in range(33)])
+    hv = _handler(shape, trunc)
+    hv.IntegrateSequence(depth[:33], rgb[:33], poses)
+    assert hv.Stats()["launches"] == 2                      # (flushes: the queue is empty)
+    hv.ReintegrateSequence(depth[8:8 + n], rgb[8:8 + n], poses[8:8 + n], _poses(shape, 8, 8 + n))
+    _check(hv, exp, "(e) %s trunc %g, %d frames:" % (shape, trunc, n))
+    assert hv.Stats()["launches"] == (3 if n == 16 else 4)  # 16 pairs fill one 32-entry launch, the 17th spills into a second
+
+
+def test_e_reintegrating_at_the_same_pose_leaves_the_weights_exactly_unchanged(oracle):
+    shape, trunc = "64x48", 0.6
+    depth, rgb = _device(shape)
+    hv = _handler(shape, trunc)
+    hv.IntegrateSequence(depth[:33], rgb[:33], _poses(shape, 0, 33))
+    k0, v0 = hv.GetCubeMap()
+    hv.ReintegrateSequence(depth[5:21], rgb[5:21], _poses(shape, 5, 21), _poses(shape, 5, 21))
+    k1, v1 = hv.GetCubeMap()
+    assert np.array_equal(k0, k1) and np.array_equal(v0[..., 1].view(np.uint32), v1[..., 1].view(np.uint32))
+    st = hv.DeintegrateStats()
+    assert st["frames"] == 16 and st["skipped"] == 0 and st["reverted"] + st["reset"] > 100000
+    seen = v0[..., 1] > 0
+    assert np.abs(v1[..., 0][seen] - v0[..., 0][seen]).max() <= 1e-4 * trunc  # (the bits: test (e) above)
+
+
+@pytest.mark.parametrize("trunc", TRUNCS)
+def test_f_deintegrating_a_frame_that_was_never_fused_allocates_its_selection_and_changes_nothing(oracle, trunc):
+    shape = "64x48"
+    f = _frames(shape)[20]
+    exp = _expected(oracle, ("f", trunc), lambda: D.Model(oracle, CAMS[shape], trunc).deintegrate(f))
+    hv = _handler(shape, trunc)
+    hv.DeintegrateImage(*f)
+    _check(hv, exp, "(f) trunc %g:" % trunc)
+    keys, vox = hv.GetCubeMap()
+    st = hv.DeintegrateStats()
+    assert len(keys) > 50 and D.is_default(vox).all()
+    assert st["reverted"] == 0 and st["reset"] == 0 and st["skipped"] == exp[6].last["hits"] > 1000
+
+
+def test_g_uploaded_fractional_weights_and_invalid_voxels_follow_the_skip_rules(oracle):
+    shape, trunc = "37x29", 1.5
+    f = _frames(shape)[7]
+    m = D.Model(oracle, CAMS[shape], trunc)
+    bk, bv = m.observation(f)
+    rng = np.random.default_rng(11)
+    vox = np.broadcast_to(D.DEFAULT_VOXEL, bv.shape).copy()
+    kind = rng.integers(0, 6, bv.shape[:2])                 # per voxel: default, w 0.5, w 1.5, invalid (sdf >= 1, w > 0), w 1, w 4
+    vox[..., 0] = np.where(kind == 3, 1.25, rng.uniform(-0.9, 0.9, kind.shape)).astype(np.float32)
+    vox[..., 1] = np.choose(kind, [0.0, 0.5, 1.5, 2.0, 1.0, 4.0]).astype(np.float32)
+    vox[..., 2:] = rng.random(bv.shape[:2] + (3,)).astype(np.float32)
+    vox[kind == 0] = D.DEFAULT_VOXEL
+    ek, ev, cnt = D.apply_deintegrate(bk, vox, bk, bv)
+    hit = bv[..., 1] == 1
+    assert cnt["skipped"] == int((hit & np.isin(kind, (0, 1, 3))).sum()) > 1000
+    assert cnt["reset"] == int((hit & (kind == 4)).sum()) > 300 and cnt["reverted"] == int((hit & np.isin(kind, (2, 5))).sum()) > 1000
+    hv = _handler(shape, trunc)
+    hv.AddCubes(bk, vox)
+    hv.DeintegrateImage(*f)
+    hk, hx = hv.GetCubeMap()
+    assert np.array_equal(hk, ek) and np.array_equal(hx.view(np.uint32), ev.view(np.uint32))
+    assert hv.DeintegrateStats() == {"frames": 1, "reverted": cnt["reverted"], "reset": cnt["reset"], "skipped": cnt["skipped"]}
+
+
+def _changed(before, after):
+    """voxels whose bits differ between two states (None: the empty volume) = what a launch between them stores"""
+    ka, xa = after
+    row = {} if before is None else {tuple(k): i for i, k in enumerate(before[0].tolist())}
+    dflt = D.DEFAULT_VOXEL.view(np.uint32)
+    n = 0
+    for i, k in enumerate(ka.tolist()):
+        j = row.get(tuple(k))
+        n += int((xa[i].view(np.uint32) != (before[1][j].view(np.uint32) if j is not None else dflt)).any(axis=-1).sum())
+    return n
+
+
+@pytest.mark.parametrize("shape,trunc", [("37x29", 0.1), ("64x48", 0.1), ("64x48", 0.6), ("37x29", 1.5)])
+def test_h_fusion_continues_after_a_deintegration_and_clear_brings_the_lean_form_back(oracle, shape, trunc):
+    fr = _frames(shape, 70)
+
+    def build():
+        m = D.Model(oracle, CAMS[shape], trunc)
+        for f in fr[:33]:
+            m.integrate(f)
+        for f in fr[10:15]:
+            m.deintegrate(f)
+        for f in fr[33:]:
+            m.integrate(f)                                  # the oracle, loaded with the expected state, goes on integrating
+        return m
+    exp = _expected(oracle, ("h", shape, trunc), build)
+
+    def build_plain():
+        m = D.Model(oracle, CAMS[shape], trunc)
+        for f in fr[:32]:
+            m.integrate(f)
+        m.snap32 = m.export()
+        return m.integrate(fr[32])
+    plain = _expected(oracle, ("h33", shape, trunc), build_plain)
+    depth, rgb = _device(shape)
+    hv = _handler(shape, trunc)
+    hv.IntegrateSequence(depth[:33], rgb[:33], _poses(shape, 0, 33))
+    hv.DeintegrateSequence(depth[10:15], rgb[10:15], _poses(shape, 10, 15))
+    hv.IntegrateSequence(depth[33:], rgb[33:], _poses(shape, 33, 70))
+    _check(hv, exp, "(h) %s trunc %g:" % (shape, trunc))
+    hv.Clear()
+    assert hv.DeintegrateStats() == {"frames": 0, "reverted": 0, "reset": 0, "skipped": 0}
+    hv.IntegrateSequence(depth[:33], rgb[:33], _poses(shape, 0, 33))
+    _check(hv, plain, "(h) after Clear, %s trunc %g:" % (shape, trunc))
+    written = _changed(None, plain[6].snap32) + _changed(plain[6].snap32, (plain[0], plain[1]))
+    assert hv.Stats()["voxels_written"] == written and hv.Stats()["launches"] == 2
+
+
+def _scenario_one_launch(oracle, shape, trunc):
+    """20 integrations and 11 de-integrations, 31 entries: one signed launch when nothing flushes in between"""
+    def build():
+        m = D.Model(oracle, CAMS[shape], trunc)
+        for f in _frames(shape)[:20]:
+            m.integrate(f)
+        for f in _frames(shape)[5:16]:
+            m.deintegrate(f)
+        return m
+    return _expected(oracle, ("one", shape, trunc), build)
+
+
+def _one_launch(hv, shape):
+    depth, rgb = _device(shape)
+    hv.IntegrateSequence(depth[:20], rgb[:20], _poses(shape, 0, 20))
+    hv.DeintegrateSequence(depth[5:16], rgb[5:16], _poses(shape, 5, 16))
+
+
+@pytest.mark.parametrize("trunc", (0.1, 1.5))
+def test_i_a_pool_that_has_to_grow_inside_a_signed_launch_is_replayed_with_its_signs(oracle, trunc):
+    shape = "64x48"
+    exp = _scenario_one_launch(oracle, shape, trunc)
+    assert len(exp[0]) > 64
+    hv = _handler(shape, trunc, max_blocks=64)
+    _one_launch(hv, shape)
+    _check(hv, exp, "(i) trunc %g:" % trunc)
+    g = hv.GrowthStats()
+    assert g["grows"] >= 1 and g["replayed_batches"] >= 1 and hv.Stats()["launches"] == 1
+
+
+@pytest.mark.parametrize("trunc", (0.1, 0.6))
+def test_j_with_the_sum_form_option_a_launch_that_holds_a_deintegration_is_still_exact(oracle, trunc):
+    shape = "64x48"
+    exp = _scenario_one_launch(oracle, shape, trunc)
+    hv = _handler(shape, trunc)
+    hv.SetUpdateMode("sum_form")
+    _one_launch(hv, shape)
+    _check(hv, exp, "(j) trunc %g:" % trunc)
+
+
+@pytest.mark.parametrize("shape,trunc", [("64x48", 0.1), ("37x29", 0.6)])
+def test_k_raycast_after_a_deintegration(oracle, shape, trunc):
+    exp = _scenario_a(oracle, shape, trunc)
+    fr = _frames(shape, 33)
+    views = [fr[15][2], fr[2][2], fr[28][2]]
+    hv = _handler(shape, trunc)
+    for f in fr:
+        hv.IntegrateImage(*f)
+    for p in views:
+        hv.Raycast(p)                                       # the raycaster's block summaries exist now
+    assert hv.RaycastStats()["loaded_blocks"] > 0
+    for f in fr[10:21]:
+        hv.DeintegrateImage(*f)
+    for p in views:
+        hv.SetRaycastPrune(True)
+        on = hv.Raycast(p)                                  # the first view after the change finds no summaries; the views after it prune by what it learnt
+        again = hv.Raycast(p)
+        hv.SetRaycastPrune(False)
+        off = hv.Raycast(p)
+        od, _on, _oc = exp[6].vol.raycast(p)
+        for a, b, c in zip(on, again, off):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.array_equal(a.view(np.uint32), c.view(np.uint32))
+        assert np.array_equal(on[0].view(np.uint32), od.view(np.uint32)) and (od > 0).sum() > 100
