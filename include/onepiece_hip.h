@@ -355,7 +355,7 @@ int op_volume_integrate_unaligned_sequence(op_volume *v, const void *depth, size
  * So a frame fused and de-integrated at the SAME pose leaves the weights exactly as they were, a voxel only that frame had seen default again, and sdf /
  * colour within a few float32 roundings per operation of never having fused it (tests/test_deintegrate_cpu.py derives the bound).
  * Queue entries -- integrations and de-integrations alike -- are applied to a voxel in call order; they share the queue and its batches of up to 32
- * per launch, and a batch that holds a de-integration runs one kernel (k_update_signed) for all its entries.  After such a launch the volume keeps the
+ * per launch, and a batch that holds a de-integration runs one kernel (k_integrate's SIGNED form) for all its entries.  After such a launch the volume keeps the
  * general (reference-literal) update for the blocks that existed then, and the shorter exact forms of k_integrate's first frames are not used again
  * until op_volume_clear; OP_VOLUME_UPDATE_SUM_FORM does not apply to such a launch (its entries take the exact forms); the raycaster's block summaries
  * are invalidated.  Images: as for op_volume_integrate (OP_MEM_HOST copied before the call returns, OP_MEM_DEVICE valid until the next synchronising

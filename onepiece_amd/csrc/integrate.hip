@@ -118,6 +118,39 @@ __device__ __forceinline__ void voxel_update(float& s, float& w, float& c0, floa
     }
 }
 
+// De-integration (op_volume_deintegrate* / op_volume_reintegrate*, include/onepiece_hip.h).  A de-integrated frame takes the steps of
+// Integrator::IntegrateImage (Integration/Integrator.cpp:52-92) -- k_prepare_frames and k_select* have packed it and selected (and allocated) its
+// blocks exactly as for a fused frame, because neither depends on what the volume stores -- and every voxel that passes the update predicate
+// (pixel inside, d > 0, |new_sdf| < truncation) receives TSDFVoxel::operator+ (TSDFVoxel.h:24-39) with an observation of weight -1: the inverse of
+// the running mean.  For the stored voxel (s, w, c), the observation o = new_sdf and oc = byte / 255 per channel:
+//   1. applied iff TSDFVoxel::IsValid (!(s >= 1 || w <= 0), TSDFVoxel.h:75-78) and w >= 1; otherwise the voxel stays as it is (`skipped`):
+//      an unobserved or invalid voxel, a fractional weight below 1 from an upload or a merge.  (The reference's `weight == 0 -> return other`
+//      would store a weight of -1; that is not reproduced.)
+//   2. rw = w + (-1);
+//   3. rw == 0: the voxel becomes the default voxel {999, 0, -1, -1, -1} -- the reference's default-constructed `result` (`reset`);
+//   4. otherwise s' = (w * s + (-1) * o) / rw, the same per colour channel, w' = rw (`reverted`): every product, sum and quotient rounded to
+//      float32, plain IEEE divisions (weights need not be integers here), no contraction (-ffp-contract=off).
+// A fused (positive) entry of a batch that holds a de-integration takes voxel_update<false>: the PLAIN and LEAN hypotheses do not survive a weight of -1.
+// voxel_revert is steps 1-4.  Every lane of the wave calls it, `hit` = its voxel passes the update predicate, and gets back step 1's verdict (`can`)
+// and step 3's (`zero`): the kernel counts the three outcomes from the scalar masks of these compares, as it counts the hits of a fused frame.
+__device__ __forceinline__ void voxel_revert(bool hit, float& s, float& w, float& c0, float& c1, float& c2, float new_sdf, unsigned rgba, const float* s_c255, bool& can,
+                                             bool& zero) {
+    can = hit & !(s >= 1 || w <= 0) & (w >= 1);
+    const float rw = w + (-1.0f);
+    zero = rw == 0;
+    if (!can) return;
+    const float n0 = s_c255[rgba & 0xffu], n1 = s_c255[(rgba >> 8) & 0xffu], n2 = s_c255[(rgba >> 16) & 0xffu];
+    if (zero) {
+        s = 999.0f; w = 0.0f; c0 = -1.0f; c1 = -1.0f; c2 = -1.0f;
+    } else {
+        s = (w * s + (-1.0f) * new_sdf) / rw;
+        c0 = (w * c0 + (-1.0f) * n0) / rw;
+        c1 = (w * c1 + (-1.0f) * n1) / rw;
+        c2 = (w * c2 + (-1.0f) * n2) / rw;
+        w = rw;
+    }
+}
+
 // SUMF (opt-in, OP_VOLUME_UPDATE_SUM_FORM): the frames of the batch are not applied one by one.  Per voxel the kernel keeps the NUMBER of in-band
 // observations of the batch, the sum of their sdf values and the sums of their colour bytes (exact integers), and forms the weighted mean with the
 // stored voxel ONCE per batch: s' = (w s + sum sdf) / (w + n), c' = (w c + sum bytes / 255) / (w + n), w' = w + n -- TSDFVoxel::operator+
@@ -134,15 +167,17 @@ __device__ unsigned long long g_kc_trace[4096 * 4 * 8];
 #endif
 // G2D: the frame's records are gathered through a structured descriptor (gather2d, volume_core.hpp) that does the row test and the address
 // arithmetic; the host launches it for certified cameras whose rows fit the stride field (launch_integrate), every other launch keeps the raw form.
-template <bool FAST, bool PLAIN, int ZT, bool SUMF = false, bool LEAN = false, bool G2D = false>
-__global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAVES)) void k_integrate(BatchInv B, CamParams C, VolView V, const uint2* __restrict__ pimg, State* st,
+template <bool FAST, bool PLAIN, int ZT, bool SUMF = false, bool LEAN = false, bool G2D = false, bool SIGNED = false>
+__global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : SIGNED ? KC_SIGNED_MIN_WAVES : KC_COL_MIN_WAVES)) void k_integrate(BatchInv B, CamParams C, VolView V, const uint2* __restrict__ pimg, State* st,
                                                                             int n_frames, unsigned long long* __restrict__ upd_partial,
                                                                             unsigned long long* __restrict__ sel_partial, unsigned long long* __restrict__ chg_partial,
-                                                                            unsigned plain_from, unsigned* __restrict__ rc_sum, unsigned rc_stamp) {
+                                                                            unsigned plain_from, unsigned* __restrict__ rc_sum, unsigned rc_stamp, bmask_t sign,
+                                                                            unsigned long long* __restrict__ dei_partial) {
+    static_assert(!SIGNED || !(PLAIN || SUMF || LEAN), "the PLAIN and LEAN hypotheses do not survive a weight of -1");
     constexpr int kWaves = 8 / ZT;            // waves per workgroup = z-groups per block
-    constexpr bool kSummaries = !SUMF;        // the raycaster's block summaries are restated by the exact update only
+    constexpr bool kSummaries = !SUMF && !SIGNED; // the raycaster's block summaries are restated by the exact update of fused frames only (the host invalidates them otherwise)
     constexpr bool kWCount = LEAN && !SUMF;   // voxels_updated, voxels_written and the store mask are read off the weights after the frames (LEAN paragraph above)
-    __shared__ unsigned s_cnt[kWaves][2];
+    __shared__ unsigned s_cnt[kWaves][SIGNED ? 5 : 2];
     __shared__ unsigned s_sign[2][kWaves];    // rc_sum: per wave, does its part of the block hold an observed sdf <= 0 (bit 0) / > 0 (bit 1) after the batch
     __shared__ float s_c255[256];             // (float)b / 255.0f for every byte (Integrator.cpp:78), correctly rounded once
     __shared__ unsigned s_next[2];
@@ -164,6 +199,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
         (const float __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr(); // BatchInv B = offset 0 of the kernarg segment
     (void)B;
     unsigned upd = 0, sel = 0, chg = 0, nblk = 0;   // upd and (exact update) chg: per WAVE (scalar counts of hit ballots), the others per lane; kWCount: upd per lane
+    unsigned neg_hit = 0, neg_can = 0, rst = 0;     // SIGNED, per wave: the voxels de-integrated entries hit, those voxel_revert was applied to, those it reset
     // XCD-aware order (workgroup b runs on XCD b % 8, each XCD has its own 4 MiB L2; blocks that gather the same pixels should meet in one L2)
     // and dynamic scheduling (blocks differ in work: 1..32 frames touch them; the workgroups of an XCD DRAW list positions from one counter,
     // the next one before the current block is processed so that the atomic's round trip is hidden).  Two ways of dealing the batch list to
@@ -256,7 +292,8 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
             // sum-form unpack or a file): the blocks that existed then (pool slots below plain_from) hold arbitrary data and take the
             // general update; blocks allocated since are this kernel's own and keep the fast one.  Uniform per block.
             const bool plain_block = PLAIN || (unsigned)idx >= plain_from;
-            auto apply = [&](const kc_v2u (&rec)[ZT], const float (&zc)[ZT], auto plain_c) {
+            // SIGNED: `negative` is the entry's bit of the batch's sign mask (wave-uniform) -- a de-integration
+            auto apply = [&](const kc_v2u (&rec)[ZT], const float (&zc)[ZT], auto plain_c, bool negative) {
                 constexpr bool kPlain = decltype(plain_c)::value;
 #pragma unroll
                 for (int z = 0; z < ZT; ++z) {
@@ -265,6 +302,18 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                     // Integrator.cpp:70,74 (d > 0 and |sdf| < truncation): two compares whose masks meet in scalar registers (& and not &&, as in
                     // project_pixel) and one divergent region.  NaN and infinities fail the second compare, d <= 0 and -0 the first.
                     const bool seen = d > 0, near = fabsf(new_sdf) < C.trunc, hit = seen & near;
+                    if constexpr (SIGNED) {
+                        if (negative) { // the same predicate, the inverse update; its outcomes counted where the masks are, like the hits below
+                            bool can, zero;
+                            voxel_revert(hit, s[z], w[z], c0[z], c1[z], c2[z], new_sdf, rec[z].y, s_c255, can, zero);
+                            const unsigned long long m_can = __builtin_amdgcn_ballot_w64(can);
+                            neg_hit += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(seen) & __builtin_amdgcn_ballot_w64(near));
+                            neg_can += (unsigned)__builtin_popcountll(m_can);
+                            rst += (unsigned)__builtin_popcountll(m_can & __builtin_amdgcn_ballot_w64(zero));
+                            changed_m[z] |= m_can;
+                            continue;
+                        }
+                    }
                     if (kWCount) { // lean: no ballot, no count, no mask per update -- the weights carry all three (LEAN paragraph above)
                         if (hit) voxel_update<true, true>(s[z], w[z], c0[z], c1[z], c2[z], new_sdf, rec[z].y, s_c255);
                         continue;
@@ -286,6 +335,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
             };
             kc_v2u recA[ZT], recB[ZT];
             float zcA[ZT], zcB[ZT];
+            bool negA = false, negB = false;               // SIGNED: each record set's own sign, read where its entry is projected
 #ifdef KC_TRACE
             { float keep_ = px + py + pz[0]; if (!SUMF) keep_ += s[0]; asm volatile("" :: "v"(keep_)); KC_T(1); } // (the block's metadata and voxels have arrived)
 #endif
@@ -294,18 +344,27 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
                 if (!m) return;
                 int f = mask_ctz(m); m &= m - 1u;
                 project(f, recA, zcA);
+                if constexpr (SIGNED) negA = ((sign >> f) & 1u) != 0u;
                 for (;;) {
                     const bool more1 = m != 0u;
-                    if (more1) { f = mask_ctz(m); m &= m - 1u; project(f, recB, zcB); }
-                    apply(recA, zcA, plain_c);
+                    if (more1) {
+                        f = mask_ctz(m); m &= m - 1u; project(f, recB, zcB);
+                        if constexpr (SIGNED) negB = ((sign >> f) & 1u) != 0u;
+                    }
+                    apply(recA, zcA, plain_c, negA);
                     if (!more1) break;
                     const bool more2 = m != 0u;
-                    if (more2) { f = mask_ctz(m); m &= m - 1u; project(f, recA, zcA); }
-                    apply(recB, zcB, plain_c);
+                    if (more2) {
+                        f = mask_ctz(m); m &= m - 1u; project(f, recA, zcA);
+                        if constexpr (SIGNED) negA = ((sign >> f) & 1u) != 0u;
+                    }
+                    apply(recB, zcB, plain_c, negB);
                     if (!more2) break;
                 }
             };
-            if (SUMF || PLAIN || plain_block) frames(std::true_type{}); else frames(std::false_type{});
+            // SIGNED: the general update for every block, whatever plain_from says
+            if constexpr (SIGNED) frames(std::false_type{});
+            else if (SUMF || PLAIN || plain_block) frames(std::true_type{}); else frames(std::false_type{});
             KC_T(2); KC_N(7, mask_popc(mask));
             if (SUMF) {
 #pragma unroll
@@ -399,11 +458,21 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : KC_COL_MIN_WAV
     if (SUMF) chg = wave_sum(chg);                            // (upd is the wave's total already, and so is the exact update's chg)
     if (kWCount) upd = wave_sum(upd);                         // (... except where it was kept per lane)
     if (lane == 0) { s_cnt[zg][0] = upd; s_cnt[zg][1] = chg; }
+    if constexpr (SIGNED) if (lane == 0) { s_cnt[zg][2] = neg_can - rst; s_cnt[zg][3] = rst; s_cnt[zg][4] = neg_hit - neg_can; } // reverted, reset, skipped
     __syncthreads();
     if (tid == 0) {
         unsigned t = 0, c = 0;
         for (int k = 0; k < kWaves; ++k) { t += s_cnt[k][0]; c += s_cnt[k][1]; }
         const unsigned slot_c = blockIdx.x % (unsigned)kPartialGrid;
+        if constexpr (SIGNED) {
+            unsigned d[3] = {0, 0, 0};
+            for (int k = 0; k < kWaves; ++k)
+                for (int q = 0; q < 3; ++q) d[q] += s_cnt[k][2 + q];
+            atomicAdd(&dei_partial[kDeiReverted + slot_c], (unsigned long long)d[0]);
+            atomicAdd(&dei_partial[kDeiReset + slot_c], (unsigned long long)d[1]);
+            atomicAdd(&dei_partial[kDeiSkipped + slot_c], (unsigned long long)d[2]);
+            if (blockIdx.x == 0) dei_partial[kDeiFrames] += (unsigned long long)mask_popc(sign);
+        }
         atomicAdd(&upd_partial[slot_c], (unsigned long long)t);
         atomicAdd(&sel_partial[slot_c], (unsigned long long)sel);
         atomicAdd(&chg_partial[slot_c], (unsigned long long)c);
@@ -460,35 +529,43 @@ bool vol_fusion_keeps_summaries(const op_volume* v) {
     return !sum_form && v->rc_sum != nullptr && v->rc_cap >= v->max_blocks && (v->content_gen >> 30) == v->rc_sum_epoch;
 }
 
-void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int nf) {
-    const VolView V = v->view();
-#define OP_KC(FASTPX, PLAINV, SUMFV, LEANV) OP_KC6(FASTPX, PLAINV, SUMFV, LEANV, false)
-#define OP_KC6(FASTPX, PLAINV, SUMFV, LEANV, G2DV) hipLaunchKernelGGL((k_integrate<FASTPX, PLAINV, (SUMFV ? KC_ZT_SUM : KC_ZT), SUMFV, LEANV, G2DV>), dim3(SUMFV ? kColGridSum : kColGrid), dim3(512 / (SUMFV ? KC_ZT_SUM : KC_ZT)), 0, v->stream, I, C, V, (const uint2*)v->pimg, \
-                                                 v->state, nf, v->upd_partial, v->sel_partial, v->chg_partial, v->plain_from, rc_sum, rc_stamp)
+// k_integrate's instantiations: every update form with every gather form, and no other
+enum { kUpdSum, kUpdLean, kUpdPlain, kUpdGeneral, kUpdSigned };  // SUMF / PLAIN + LEAN / PLAIN / neither / SIGNED
+enum { kGatExact, kGatFastRaw, kGatFast2d };                     // the exact projection with the raw gather; the certified one with the raw and with the structured gather
+template <int UPD, int GAT>
+void launch_kc(op_volume* v, const BatchInv& I, const CamParams& C, int nf, bmask_t sign, unsigned* rc_sum) {
+    constexpr bool kSum = UPD == kUpdSum, kSigned = UPD == kUpdSigned;
+    constexpr int kZt = kSum ? KC_ZT_SUM : KC_ZT;
+    hipLaunchKernelGGL((k_integrate<GAT != kGatExact, (UPD <= kUpdPlain), kZt, kSum, UPD == kUpdLean, GAT == kGatFast2d, kSigned>),
+                       dim3(kSum ? kColGridSum : kSigned ? kSignedGrid : kColGrid), dim3(512 / kZt), 0, v->stream, I, C, v->view(), (const uint2*)v->pimg, v->state, nf,
+                       v->upd_partial, v->sel_partial, v->chg_partial, v->plain_from, rc_sum, (unsigned)(v->content_gen & 0x3fffffffull), sign, v->dei_partial);
+}
+
+void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int nf, bmask_t sign) {
     // The sum form tests TSDFVoxel::IsValid on the STORED voxel once per batch where the reference re-tests it before every frame (Integrator.cpp:74-87,
     // TSDFVoxel.h:75-78): the two agree to rounding only while no OBSERVATION can itself be invalid, i.e. truncation < 1 (an observed sdf is < truncation;
     // a stored voxel of any origin gets the test).  With truncation >= 1 the exact update runs, whatever the option says.
-    const bool sum_form = v->update_mode == OP_VOLUME_UPDATE_SUM_FORM && v->trunc < 1.0f;
+    // A batch that holds a de-integration (sign != 0) is exact whatever the option says, and the host has invalidated the summaries (vol_enqueue_batch).
+    const bool sum_form = !sign && v->update_mode == OP_VOLUME_UPDATE_SUM_FORM && v->trunc < 1.0f;
     // the raycaster's summaries are kept current by this launch (vol_fusion_keeps_summaries: the host has then NOT advanced the content generation)
-    unsigned* rc_sum = vol_fusion_keeps_summaries(v) ? v->rc_sum : nullptr;
-    const unsigned rc_stamp = (unsigned)(v->content_gen & 0x3fffffffull);
+    unsigned* rc_sum = !sign && vol_fusion_keeps_summaries(v) ? v->rc_sum : nullptr;
     // LEAN (see voxel_update): what the volume holds was fused by the exact update with truncations <= 0.5 only, in at most 2^19 frames, this batch
     // included (a replayed batch counts again: the bound is a sufficient one).  !(<=) so that a NaN truncation counts as too large.
+    // (A signed launch: vol_enqueue_batch has ended plain and lean_ok until the volume is cleared.)
     if (sum_form || !(v->trunc <= 0.5f)) v->lean_ok = false;
     v->lean_frames += (uint64_t)nf;
     const bool lean = v->plain && v->lean_ok && v->lean_frames <= (1ull << 19);
-    // the structured gather: certified projection and rows that fit the descriptor's stride field (2047 pixels), else the raw form as before
-    if (C.fast_px && gather2d_fits(C.width)) {
-        if (sum_form) OP_KC6(true, true, true, false, true);
-        else if (lean) OP_KC6(true, true, false, true, true);
-        else if (v->plain) OP_KC6(true, true, false, false, true);
-        else OP_KC6(true, false, false, false, true);
-    }
-    else if (sum_form) { if (C.fast_px) OP_KC(true, true, true, false); else OP_KC(false, true, true, false); }
-    else if (C.fast_px) { if (lean) OP_KC(true, true, false, true); else if (v->plain) OP_KC(true, true, false, false); else OP_KC(true, false, false, false); }
-    else { if (lean) OP_KC(false, true, false, true); else if (v->plain) OP_KC(false, true, false, false); else OP_KC(false, false, false, false); }
-#undef OP_KC
-#undef OP_KC6
+    const int upd = sign ? kUpdSigned : sum_form ? kUpdSum : lean ? kUpdLean : v->plain ? kUpdPlain : kUpdGeneral;
+    // the structured gather: certified projection and rows that fit the descriptor's stride field (2047 pixels), else the raw form
+    const int gat = !C.fast_px ? kGatExact : gather2d_fits(C.width) ? kGatFast2d : kGatFastRaw;
+    typedef void (*launch_fn)(op_volume*, const BatchInv&, const CamParams&, int, bmask_t, unsigned*);
+    static const launch_fn table[5][3] = {
+        {launch_kc<kUpdSum, kGatExact>, launch_kc<kUpdSum, kGatFastRaw>, launch_kc<kUpdSum, kGatFast2d>},
+        {launch_kc<kUpdLean, kGatExact>, launch_kc<kUpdLean, kGatFastRaw>, launch_kc<kUpdLean, kGatFast2d>},
+        {launch_kc<kUpdPlain, kGatExact>, launch_kc<kUpdPlain, kGatFastRaw>, launch_kc<kUpdPlain, kGatFast2d>},
+        {launch_kc<kUpdGeneral, kGatExact>, launch_kc<kUpdGeneral, kGatFastRaw>, launch_kc<kUpdGeneral, kGatFast2d>},
+        {launch_kc<kUpdSigned, kGatExact>, launch_kc<kUpdSigned, kGatFastRaw>, launch_kc<kUpdSigned, kGatFast2d>}};
+    table[upd][gat](v, I, C, nf, sign, rc_sum);
 }
 
 void kc_trace_dump(op_volume* v) {

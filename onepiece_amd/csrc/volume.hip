@@ -337,8 +337,8 @@ int vol_ensure_frame_buffers(op_volume* v) {
 // select_only, KC.  No host synchronisation.
 // With cube_keys (device array of n_cubes ids, nf == 1): KB is replaced by k_mark_cubes -- the frame is fused into exactly
 // those cubes (op_volume_integrate_cubes); the caller has reserved the room and synchronises, so the batch is not logged.
-// sign: bit f set = entry f is a de-integration.  A batch with a non-zero sign mask takes k_update_signed (deintegrate.hip) in KC's place, and
-// the volume stops being plain and lean (until it is cleared): that kernel writes weights and means k_integrate's short forms do not cover.
+// sign: bit f set = entry f is a de-integration.  A batch with a non-zero sign mask takes k_integrate's SIGNED form, and
+// the volume stops being plain and lean (until it is cleared): that form writes weights and means k_integrate's short forms do not cover.
 int vol_enqueue_batch(op_volume* v, const BatchFwd& F, const BatchInv& I, const BatchPtrs& Q, int nf, int depth_fmt, bool select_only, bool record,
                       const int* cube_keys, unsigned n_cubes, bmask_t sign) {
     OP_TRY(vol_ensure_frame_buffers(v));
@@ -375,12 +375,13 @@ int vol_enqueue_batch(op_volume* v, const BatchFwd& F, const BatchInv& I, const 
     OP_TRY(launch_select(v, I, C, nf, record, cube_keys, n_cubes));
     if (sample) OP_HIP(hipEventRecord(ev[2], v->stream));
     if (select_only) launch_finish_select(v);
-    else if (sign) {
-        v->plain = false; v->lean_ok = false;
-        v->plain_from = 0xffffffffu; v->dei_pending = true; // tightened to the block count by the next vol_check
-        launch_update_signed(v, I, C, nf, sign);
+    else {
+        if (sign) {
+            v->plain = false; v->lean_ok = false;
+            v->plain_from = 0xffffffffu; v->dei_pending = true; // tightened to the block count by the next vol_check
+        }
+        launch_integrate(v, I, C, nf, sign);
     }
-    else launch_integrate(v, I, C, nf);
     if (sample) {
         OP_HIP(hipEventRecord(ev[3], v->stream));
         for (auto e : ev) v->prof_events.push_back(e);
@@ -1258,12 +1259,14 @@ int op_volume_reintegrate_sequence(op_volume* v, const void* depth, size_t depth
 int op_volume_deintegrate_stats(op_volume* v, uint64_t* frames, uint64_t* reverted, uint64_t* reset, uint64_t* skipped) {
     OP_VOL_DEV(v);
     OP_TRY(vol_check(v));
-    unsigned long long c[4];
-    OP_TRY(vol_deintegrate_counts(v, c));
-    if (frames) *frames = c[0];
-    if (reverted) *reverted = c[1];
-    if (reset) *reset = c[2];
-    if (skipped) *skipped = c[3];
+    std::vector<unsigned long long> part((size_t)kDeiFrames + 1);
+    OP_HIP(hipMemcpy(part.data(), v->dei_partial, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    unsigned long long c[3] = {0, 0, 0};
+    for (int i = 0; i < kPartialGrid; ++i) { c[0] += part[kDeiReverted + i]; c[1] += part[kDeiReset + i]; c[2] += part[kDeiSkipped + i]; }
+    if (frames) *frames = part[kDeiFrames];
+    if (reverted) *reverted = c[0];
+    if (reset) *reset = c[1];
+    if (skipped) *skipped = c[2];
     return OP_OK;
 }
 

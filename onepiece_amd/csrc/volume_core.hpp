@@ -2,8 +2,7 @@
 // the hash-table device helpers, the host object op_volume and the host-side functions / kernel launchers that cross translation units.
 //   volume.hip      the host object: create / grow / replay, the staging ring, the integrate entry points (C-ABI), pool and table maintenance kernels
 //   select.hip      KA k_prepare_frames (ComputeBounding + frame packing), KB k_select / k_select_vote / k_select_merge (PrepareCubes)
-//   integrate.hip   KC k_integrate (Integrator::IntegrateImage)
-//   deintegrate.hip k_update_signed: KC's place in a batch that holds a de-integration (TSDFVoxel::operator+ with weight -1)
+//   integrate.hip   KC k_integrate (Integrator::IntegrateImage; its SIGNED instantiations: a batch that holds a de-integration, TSDFVoxel::operator+ with weight -1)
 //   volume_ops.hip  GetCubeMap / SetCubeMap / Merge / sum-form pack + unpack / Transform / GetPointCloud / ExtractTriangleMesh / .map files
 //   raycast.hip     the raycaster, and its view packed as an RGB-D frame (model_frame.hpp: what the dense tracker takes from here)
 // Data layout in HBM: see volume.hip (and DESIGN.md section 2).
@@ -81,8 +80,17 @@ constexpr int kColGrid = KC_COL_GRID;
 constexpr int kColGridSum = 256 * KC_SUM_MIN_WAVES * 4 / (8 / KC_ZT_SUM);
 static_assert(kColGridSum % 8 == 0, "one drawing workgroup per XCD slab at least");
 static_assert(kColGrid % 8 == 0, "one drawing workgroup per XCD slab at least");
+// the SIGNED instantiations (a batch that holds a de-integration): the four true divisions of an update need registers -- 65 / 65 / 69 VGPRs,
+// which fit the 72 of seven waves per SIMD without scratch (eight would spill).  Per launch of 20 de-integrations, alternating in one visit
+// (profiles/one_kc_kernel_times.json): 4 waves (a grid of 1024) 1033-1048 us, 5 waves 905-914 us, 7 waves 781-794 us.
+#ifndef KC_SIGNED_MIN_WAVES
+#define KC_SIGNED_MIN_WAVES 7
+#endif
+constexpr int kSignedGrid = 256 * KC_SIGNED_MIN_WAVES * 4 / (8 / KC_ZT);
+static_assert(kSignedGrid % 8 == 0, "one drawing workgroup per XCD slab at least");
 constexpr int kPartialGrid = 1024; // slots of the counter arrays k_integrate's workgroups add to (workgroup b -> slot b % 1024).  Not more: the host reads
                                    // them with small pageable copies, and a 16 KB device-to-host copy takes the runtime's pinned-staging path (milliseconds)
+constexpr int kDeiReverted = 0, kDeiReset = kPartialGrid, kDeiSkipped = 2 * kPartialGrid, kDeiFrames = 3 * kPartialGrid; // the slots of op_volume::dei_partial
 constexpr int kCoordLimit = 1 << 20; // |block coordinate| < 2^20 (40 km at 4 cm blocks)
 
 struct CamParams {
@@ -535,11 +543,11 @@ struct op_volume {
     BatchInv pend_I;
     BatchPtrs pend_P;
     bmask_t pend_sign = 0;       // bit f: queue entry f is a de-integration (op_volume_deintegrate*, the first half of op_volume_reintegrate*)
-    // De-integration (deintegrate.hip).  A launch that holds one takes k_update_signed; from then on the volume is neither plain nor lean until it is
+    // De-integration.  A launch that holds one takes k_integrate's SIGNED form; from then on the volume is neither plain nor lean until it is
     // cleared.  The blocks such a launch may have changed are known once it has run: until the next synchronising look (vol_check) plain_from covers
     // every slot (dei_pending), then it is the block count, as after an upload or a merge.
     bool dei_pending = false;
-    unsigned long long* dei_partial = nullptr; // 3 x kPartialGrid slots k_update_signed's workgroups add to (reverted, reset, skipped) + [3 x kPartialGrid] de-integrated frames
+    unsigned long long* dei_partial = nullptr; // 3 x kPartialGrid slots the SIGNED k_integrate's workgroups add to (reverted, reset, skipped) + [3 x kPartialGrid] de-integrated frames
     // Aligned-colour ring of op_volume_integrate_unaligned (align_color.hip): kUaSlots images of the volume camera's size, written by k_align_color on
     // `stream`; for host frames also the device copies of their depth images (ua_depth, allocated with the first one) and two staging buffers for
     // the colour image the kernel reads.  ua_frame[s] = ordinal (frames_accepted) of the frame slot s was last given to: the slot is free once that
@@ -589,13 +597,10 @@ void launch_prepare_frames(op_volume* v, const BatchFwd& F, int nf, const CamPar
 int launch_select(op_volume* v, const BatchInv& I, const CamParams& C, int nf, bool record, const int* cube_keys, unsigned n_cubes); // (may allocate the voting words: can fail)
 void launch_finish_select(op_volume* v);
 void kb_trace_dump(op_volume* v);            // -DKB_TRACE builds only
-// integrate.hip: KC
-void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int nf);
+// integrate.hip: KC (sign: bit f set = entry f of the batch is a de-integration)
+void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int nf, bmask_t sign);
 bool vol_fusion_keeps_summaries(const op_volume* v); // integrate.hip: this batch's k_integrate restates the raycaster's summaries of the blocks it changes
 void kc_trace_dump(op_volume* v);            // -DKC_TRACE builds only
-// deintegrate.hip: k_update_signed, KC's place in a batch whose sign mask is not zero
-void launch_update_signed(op_volume* v, const BatchInv& I, const CamParams& C, int nf, bmask_t sign);
-int vol_deintegrate_counts(op_volume* v, unsigned long long out[4]); // frames, reverted, reset, skipped since create / clear (the stream is idle)
 // volume_ops.hip: the count and emit passes of k_mesh into device buffers (op_volume_extract_mesh; mesh_cluster.hip simplifies the soup in place)
 int vol_mesh_soup(op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, bool emit, size_t cap_vertices, float** d_pts_out,
                   float** d_col_out, size_t* n_vertices);

@@ -1,8 +1,13 @@
-"""De-integration and re-integration on the device (csrc/deintegrate.hip k_update_signed, op_volume_deintegrate* / op_volume_reintegrate*) against
+"""De-integration and re-integration on the device (csrc/integrate.hip, k_integrate's SIGNED instantiations; op_volume_deintegrate* / op_volume_reintegrate*) against
 the oracle plus the numpy restatement of the definition (tests/deintegrate_common.py): block keys, every voxel bit for bit, and the counters.
 
 Shapes: the room at 37 x 29 and 64 x 48 into 4 cm voxels, 33 frames (launches of 32 + 1) and 70 (32 + 32 + 6), truncations 0.1 (lean until the
-first de-integration), 0.6 (plain) and 1.5 (an observation can itself be an invalid voxel)."""
+first de-integration), 0.6 (plain) and 1.5 (an observation can itself be an invalid voxel).  Both cameras take the certified projection with the
+structured gather; test_l holds the other two forms of the signed kernel (the raw gather, the exact projection) to the same restatement."""
+import os
+import subprocess
+import tempfile
+
 import numpy as np
 import pytest
 
@@ -12,6 +17,10 @@ from onepiece_amd import integration as I
 pytestmark = pytest.mark.gpu
 
 CAMS = {"37x29": D.CAM_37, "64x48": D.CAM_64}
+# test_l's cameras.  "raw gather": the 2048x2 camera of tests/test_gather2d_edges_gpu.py, certified on both axes, its rows one pixel wider than the
+# structured descriptor's stride field holds (2047).  "exact projection": a principal point on a half-integer has no certified rounding on that axis.
+FORM_CAMS = {"raw gather": (1600.0, 50.0, 1023.75, 0.75, 2048, 2, 1000.0), "exact projection": (30.0, 30.0, 18.5, 14.25, 37, 29, 1000.0)}
+ALL_CAMS = dict(CAMS, **FORM_CAMS)
 TRUNCS = (0.1, 0.6, 1.5)
 _cache = {}
 
@@ -19,7 +28,7 @@ _cache = {}
 def _frames(shape, n=70):
     key = ("frames", shape)
     if key not in _cache:
-        _cache[key] = D.frames(CAMS[shape], 70)
+        _cache[key] = D.frames(ALL_CAMS[shape], 70)
     return _cache[key][:n]
 
 
@@ -41,7 +50,7 @@ def _poses(shape, lo, hi):
 
 def _handler(shape, trunc, max_blocks=1 << 14):
     hcam = I.PinholeCamera()
-    hcam.fx, hcam.fy, hcam.cx, hcam.cy, hcam.width, hcam.height, hcam.depth_scale = CAMS[shape]
+    hcam.fx, hcam.fy, hcam.cx, hcam.cy, hcam.width, hcam.height, hcam.depth_scale = ALL_CAMS[shape]
     hv = I.CubeHandler(hcam, device=0, max_blocks=max_blocks)
     hv.SetVoxelResolution(D.RES)
     hv.SetTruncation(trunc)
@@ -332,3 +341,48 @@ def test_k_raycast_after_a_deintegration(oracle, shape, trunc):
         for a, b, c in zip(on, again, off):
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.array_equal(a.view(np.uint32), c.view(np.uint32))
         assert np.array_equal(on[0].view(np.uint32), od.view(np.uint32)) and (od > 0).sum() > 100
+
+
+def _px_axes_exact(camt):
+    """(x, y): does px_axis (csrc/px_round.hpp, what cam_params asks) certify the fast pixel rounding on that axis of the camera -- on the CPU"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = ('#include <cstdio>\n#include "px_round.hpp"\n'
+           'int main() { printf("%%d %%d\\n", (int)px_axis(%.9gf, %d).exact, (int)px_axis(%.9gf, %d).exact); return 0; }\n' % (camt[2], camt[4], camt[3], camt[5]))
+    with tempfile.TemporaryDirectory() as td:
+        cpp, exe = os.path.join(td, "t.cpp"), os.path.join(td, "t")
+        open(cpp, "w").write(src)
+        subprocess.check_call(["g++", "-O1", "-ffp-contract=off", "-I", os.path.join(root, "onepiece_amd", "csrc"), cpp, "-o", exe])
+        x, y = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()
+    return bool(int(x)), bool(int(y))
+
+
+@pytest.mark.parametrize("trunc", (0.1, 1.5))
+@pytest.mark.parametrize("form", list(FORM_CAMS))
+def test_l_the_raw_gather_and_the_exact_projection_of_the_signed_kernel(oracle, form, trunc):
+    """fuse 33, de-integrate frames 10..20, re-integrate 16 of the others at moved poses in one sequence call: keys, every voxel bit, all counters"""
+    camt = FORM_CAMS[form]
+    if form == "raw gather":        # certified, and too wide for the structured gather
+        assert _px_axes_exact(camt) == (True, True) and camt[4] > 2047
+    else:                           # not certified on x: were it, the launch would be the fast form the tests above cover
+        assert _px_axes_exact(camt) == (False, True)
+    fr = _frames(form, 33)
+    moved = list(range(2, 10)) + list(range(21, 29))
+    new = {k: D.perturbed(fr[k][2], k) for k in moved}
+
+    def build():
+        m = D.Model(oracle, camt, trunc)
+        for f in fr:
+            m.integrate(f)
+        for f in fr[10:21]:
+            m.deintegrate(f)
+        for k in moved:
+            m.reintegrate(fr[k], new[k])
+        return m
+    exp = _expected(oracle, ("l", form, trunc), build)
+    assert exp[2]["frames"] == 27 and exp[2]["reverted"] > 0 and exp[2]["reset"] > 0 and exp[5] > 0
+    depth, rgb = _device(form)
+    hv = _handler(form, trunc)
+    hv.IntegrateSequence(depth[:33], rgb[:33], _poses(form, 0, 33))
+    hv.DeintegrateSequence(depth[10:21], rgb[10:21], _poses(form, 10, 21))
+    hv.ReintegrateSequence(depth[moved].contiguous(), rgb[moved].contiguous(), np.stack([fr[k][2] for k in moved]), np.stack([new[k] for k in moved]))
+    _check(hv, exp, "(l) %s trunc %g:" % (form, trunc))

@@ -6,7 +6,14 @@
 Used when volume.hip was split into one translation unit per kernel family (round 5): every kernel of the old file must come out
 of its new file instruction for instruction.  Function names are compared with the anonymous-namespace and namespace qualifiers
 removed (shared types moved from an anonymous namespace to `opv`); labels, comments and directives are dropped, branch targets are
-replaced by their distance in instructions."""
+replaced by their distance in instructions.
+
+A kernel template that has gained ONE trailing template parameter (k_integrate's SIGNED) is matched too: an old instantiation without
+a namesake in the new files is compared with the new one that carries its arguments plus one more, the false / zero one where several
+do (the parameter's default).  Of a kernel that differs the differing lines are printed, and whether they differ in immediate operands
+only (an explicit kernel argument more moves the implicit ones behind it).  Every kernel is listed with the registers and the scratch
+its metadata states: (VGPRs, SGPRs, scratch bytes)."""
+import difflib
 import re
 import sys
 
@@ -33,6 +40,20 @@ def kernels(path):
     return out
 
 
+def resources(path):
+    """mangled name -> (vgpr_count, sgpr_count, private_segment_fixed_size) of the file's kernel metadata"""
+    out, cur = {}, {}
+    for line in open(path):
+        m = re.match(r"^\s+(?:- )?\.(name|vgpr_count|sgpr_count|private_segment_fixed_size):\s+(\S+)", line)
+        if not m:
+            continue
+        cur[m.group(1)] = m.group(2)
+        if len(cur) == 4:  # (the four keys of one kernel's entry, in the alphabetical order the compiler writes them)
+            out[cur["name"]] = (int(cur["vgpr_count"]), int(cur["sgpr_count"]), int(cur["private_segment_fixed_size"]))
+            cur = {}
+    return out
+
+
 def normalise(body):
     labels, n = {}, 0
     for kind, s in body:
@@ -52,32 +73,55 @@ def normalise(body):
 
 def key(mangled):
     # drop namespace qualifiers of the function and of its parameter types: compare by kernel name + template arguments
-    m = re.search(r"(k_[a-z_0-9]+?)(I[A-Za-z0-9_]+?E)?(Ev|E)", mangled)
     k = re.search(r"\d+(k_[a-z_]+)", mangled).group(1)
     t = re.search(r"\d+k_[a-z_]+(I(?:L[bij][0-9]+E)+E)?", mangled).group(1) or ""
     return k + t
 
 
+def load(paths):
+    out = {}
+    for p in paths:
+        res = resources(p)
+        for n, b in kernels(p).items():
+            out[key(n)] = (p.split("/")[-1], normalise(b), res.get(n))
+    return out
+
+
+def one_more_argument(k, new):
+    """the new kernel that carries k's template arguments and one more (its default: false / zero where there is a choice)"""
+    if not k.endswith("E") or "I" not in k:
+        return None
+    c = sorted(n for n in new if re.fullmatch(re.escape(k[:-1]) + r"L[bij][0-9]+EE", n))
+    zero = [n for n in c if re.search(r"L[bij]0EE$", n)]
+    return (zero or c or [None])[0]
+
+
+def immediates(s):
+    return re.sub(r"(?<![\w.])(?:0x[0-9a-f]+|\d+)\b", "#", s)
+
+
 def main():
     sep = sys.argv.index("--")
-    old = {}
-    for p in sys.argv[1:sep]:
-        for n, b in kernels(p).items():
-            old[key(n)] = normalise(b)
-    new = {}
-    for p in sys.argv[sep + 1:]:
-        for n, b in kernels(p).items():
-            new[key(n)] = (p, normalise(b))
-    bad = 0
+    old, new = load(sys.argv[1:sep]), load(sys.argv[sep + 1:])
+    bad, matched = 0, set()
     for k in sorted(old):
-        if k not in new:
-            print("%-44s MISSING in the new files" % k); bad += 1; continue
-        p, b = new[k]
-        same = b == old[k]
-        print("%-44s %6d instructions  %s  (%s)" % (k, len(old[k]), "identical" if same else "DIFFERENT (%d)" % len(b), p.split("/")[-1]))
-        bad += not same
-    for k in sorted(set(new) - set(old)):
-        print("%-44s only in the new files (%s)" % (k, new[k][0].split("/")[-1]))
+        _p0, b0, r0 = old[k]
+        k1 = k if k in new else one_more_argument(k, new)
+        if k1 is None:
+            print("%-44s MISSING in the new files, was %s" % (k, r0)); bad += 1; continue
+        matched.add(k1)
+        p, b, r = new[k1]
+        same = b == b0
+        imm = not same and len(b) == len(b0) and all(immediates(x) == immediates(y) for x, y in zip(b0, b))
+        verdict = "identical" if same else "identical but for immediates" if imm else "DIFFERENT (%d)" % len(b)
+        print("%-44s %6d instructions  %s  %s  (%s%s)" % (k, len(b0), verdict, r, p, "" if k1 == k else " as " + k1))
+        if not same:
+            for d in difflib.unified_diff(b0, b, "old", "new", n=0, lineterm=""):
+                if not d.startswith(("---", "+++")):
+                    print("    " + d)
+        bad += not (same or imm)
+    for k in sorted(set(new) - matched):
+        print("%-44s only in the new files  %s  (%s)" % (k, new[k][2], new[k][0]))
     return 1 if bad else 0
 
 
