@@ -9,12 +9,18 @@
 //   --path                     refuse (default): Clear() + IntegrateImage of all N frames; reintegrate: ReintegrateImage of the K frames
 //                              split: DeintegrateImage of the K frames, then IntegrateImage of the K frames (the two kernels side by side under a profiler)
 //   --runs R                   R > 1: one untimed pass and R timed ones in this process (the volume cleared in between); the medians are printed
+//   --collect none|device|roundtrip   after the repair (--path defaults to reintegrate then) the blocks it emptied are freed: device = CubeHandler::CollectGarbage(),
+//                              roundtrip = what there was before it (download, filter on the host, Clear(), upload), none = they stay.  The JSON gains
+//                              "collect": block counts before and after, the collection's time (median over the runs) and the times of one ExtractTriangleMesh, one
+//                              RenderFrame and one WriteToFile over the volume as it is then
+//   --dump FILE                with --collect: the final volume as (key, block) records sorted by key (device and roundtrip write equal files)
 // It prints one JSON line: the stage times (host clock, each stage waited for) and, against a second volume fused at the true poses, the number of
 // voxels whose weights differ and the largest |sdf| and |colour| differences over the others.  A re-fused volume is that volume bit for bit; a
 // re-integrated one has the same weights and differs by the float32 roundings of the inverse running mean (op_volume_deintegrate).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -23,6 +29,7 @@
 #include <vector>
 
 #include "Geometry/Geometry.h"
+#include "Geometry/TriangleMesh.h"
 #include "Integration/CubeHandler.h"
 #include "onepiece_hip.h"
 using namespace one_piece;
@@ -115,26 +122,66 @@ bool Download(integration::CubeHandler& h, Blocks* out) {
     return true;
 }
 
+// The route there was before CubeHandler::CollectGarbage: the whole pool to the host, the blocks without a voxel of weight > 0 taken out there,
+// Clear(), and the rest uploaded again.
+bool CollectByRoundTrip(integration::CubeHandler& h) {
+    Blocks all;
+    if (!Download(h, &all)) return false;
+    size_t kept = 0;
+    for (size_t b = 0; b < all.n; ++b) {
+        bool observed = false;
+        for (int i = 0; i < 512 && !observed; ++i) observed = all.vox[b * 2560 + 5 * i + 1] > 0.0f;
+        if (!observed) continue;
+        if (kept != b) {
+            std::copy(all.keys.begin() + 3 * b, all.keys.begin() + 3 * b + 3, all.keys.begin() + 3 * kept);
+            std::copy(all.vox.begin() + b * 2560, all.vox.begin() + (b + 1) * 2560, all.vox.begin() + kept * 2560);
+        }
+        ++kept;
+    }
+    h.Clear();
+    return kept == 0 || op_volume_upload(h.Handle(), all.keys.data(), all.vox.data(), kept) == OP_OK;
+}
+
+// (key, block) records sorted by key: equal files = equal volumes as sets of blocks
+bool Dump(integration::CubeHandler& h, const std::string& file) {
+    Blocks all;
+    if (!Download(h, &all)) return false;
+    std::vector<size_t> order(all.n);
+    for (size_t b = 0; b < all.n; ++b) order[b] = b;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return std::lexicographical_compare(all.keys.begin() + 3 * a, all.keys.begin() + 3 * a + 3, all.keys.begin() + 3 * b, all.keys.begin() + 3 * b + 3); });
+    FILE* f = fopen(file.c_str(), "wb");
+    if (!f) return false;
+    for (size_t i = 0; i < all.n; ++i) {
+        fwrite(&all.keys[3 * order[i]], sizeof(int32_t), 3, f);
+        fwrite(&all.vox[order[i] * 2560], sizeof(float), 2560, f);
+    }
+    return fclose(f) == 0;
+}
+
 } // namespace
 
 int main(int argc, char* argv[]) {
     long synthetic[3] = {0, 1, 1}, perturb = -1, runs = 1;
-    bool is_synthetic = false, bad = false;
-    std::string path = "refuse";
+    bool is_synthetic = false, bad = false, path_given = false;
+    std::string path = "refuse", collect, dump;
     float res = 0.01f;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--synthetic" && i + 3 < argc) { is_synthetic = true; for (int k = 0; k < 3; ++k) synthetic[k] = std::atol(argv[++i]); }
         else if (a == "--perturb" && i + 1 < argc) perturb = std::atol(argv[++i]);
         else if (a == "--res" && i + 1 < argc) res = static_cast<float>(std::atof(argv[++i]));
-        else if (a == "--path" && i + 1 < argc) path = argv[++i];
+        else if (a == "--path" && i + 1 < argc) { path = argv[++i]; path_given = true; }
         else if (a == "--runs" && i + 1 < argc) runs = std::atol(argv[++i]);
+        else if (a == "--collect" && i + 1 < argc) collect = argv[++i];
+        else if (a == "--dump" && i + 1 < argc) dump = argv[++i];
         else bad = true;
     }
+    if (!collect.empty() && !path_given) path = "reintegrate"; // a re-fused volume has nothing to collect
     const long n = synthetic[0], stride = synthetic[1];
     if (perturb < 0) perturb = n / 10 > 0 ? n / 10 : 1;
-    if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || perturb < 1 || perturb > n || !(res > 0) || runs < 1 || (path != "refuse" && path != "reintegrate" && path != "split")) {
-        std::cout << "usage::PoseCorrection --synthetic N STRIDE SEED [--perturb K] [--res 0.01] [--path refuse|reintegrate|split] [--runs R]" << std::endl;
+    if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || perturb < 1 || perturb > n || !(res > 0) || runs < 1 || (path != "refuse" && path != "reintegrate" && path != "split") ||
+        (!collect.empty() && collect != "none" && collect != "device" && collect != "roundtrip")) {
+        std::cout << "usage::PoseCorrection --synthetic N STRIDE SEED [--perturb K] [--res 0.01] [--path refuse|reintegrate|split] [--runs R] [--collect none|device|roundtrip] [--dump FILE]" << std::endl;
         return bad || argc > 1 ? 2 : 0;
     }
     const long first = ((synthetic[2] + 999) % 1000) * 97 % 1000;
@@ -157,8 +204,8 @@ int main(int argc, char* argv[]) {
     if (!volume.Handle()) return 1; // (no device: the class has said so)
 
     // with --runs R > 1: one untimed pass, then R timed ones (the volume cleared in between); the medians are reported
-    std::vector<double> fuse_s, repair_s;
-    size_t blocks_drifted = 0;
+    std::vector<double> fuse_s, repair_s, collect_s;
+    size_t blocks_drifted = 0, blocks_repaired = 0;
     std::chrono::steady_clock::time_point t0;
     for (long pass = runs > 1 ? -1 : 0; pass < runs; ++pass) {
         volume.Clear();
@@ -183,11 +230,44 @@ int main(int argc, char* argv[]) {
         }
         volume.Synchronize();
         const double tr = Seconds(t0);
-        if (pass >= 0) { fuse_s.push_back(tf); repair_s.push_back(tr); }
+        double tc = 0;
+        if (!collect.empty()) { // the blocks the repair emptied: freed on the device, or by the route there was before (download, filter, Clear, upload)
+            blocks_repaired = volume.GetCubeCount();
+            t0 = std::chrono::steady_clock::now();
+            if (collect == "device") volume.CollectGarbage();
+            else if (collect == "roundtrip" && !CollectByRoundTrip(volume)) { std::cout << RED << "[ERROR]::round trip failed: " << op_last_error() << RESET << std::endl; return 1; }
+            volume.Synchronize();
+            tc = Seconds(t0);
+        }
+        if (pass >= 0) { fuse_s.push_back(tf); repair_s.push_back(tr); collect_s.push_back(tc); }
     }
     std::sort(fuse_s.begin(), fuse_s.end());
     std::sort(repair_s.begin(), repair_s.end());
-    const double t_fuse = fuse_s[fuse_s.size() / 2], t_repair = repair_s[repair_s.size() / 2];
+    std::sort(collect_s.begin(), collect_s.end());
+    const double t_fuse = fuse_s[fuse_s.size() / 2], t_repair = repair_s[repair_s.size() / 2], t_collect = collect_s[collect_s.size() / 2];
+
+    // one pass of three consumers over the volume as the collection left it (with --collect none: over the volume with its empty blocks)
+    double t_mesh = 0, t_render = 0, t_write = 0;
+    size_t blocks_collected = 0, triangles = 0, rendered = 0;
+    if (!collect.empty()) {
+        blocks_collected = volume.GetCubeCount();
+        t0 = std::chrono::steady_clock::now();
+        geometry::TriangleMesh mesh;
+        volume.ExtractTriangleMesh(mesh);
+        t_mesh = Seconds(t0);
+        triangles = mesh.GetTriangleSize();
+        t0 = std::chrono::steady_clock::now();
+        cv::Mat view_rgb, view_depth;
+        rendered = volume.RenderFrame(truth[n / 2], view_rgb, view_depth);
+        t_render = Seconds(t0);
+        const char* tmp = std::getenv("TMPDIR");
+        const std::string map_file = std::string(tmp ? tmp : "/tmp") + "/pose_correction_" + std::to_string(static_cast<long>(std::chrono::steady_clock::now().time_since_epoch().count())) + ".map";
+        t0 = std::chrono::steady_clock::now();
+        volume.WriteToFile(map_file);
+        t_write = Seconds(t0);
+        std::remove(map_file.c_str());
+        if (!dump.empty() && !Dump(volume, dump)) { std::cout << RED << "[ERROR]::cannot write " << dump << RESET << std::endl; return 1; }
+    }
 
     t0 = std::chrono::steady_clock::now();
     for (long k = 0; k < n; ++k) reference.IntegrateImage(depth[k], rgb[k], truth[k]);
@@ -225,6 +305,14 @@ int main(int argc, char* argv[]) {
               << ", \"ms\": {\"fuse_drifted\": " << t_fuse * 1000.0 << ", \"repair\": " << t_repair * 1000.0 << ", \"reference\": " << t_reference * 1000.0 << "}"
               << ", \"blocks_drifted\": " << blocks_drifted << ", \"blocks\": " << got.n << ", \"blocks_reference\": " << want.n << ", \"missing_blocks\": " << missing_blocks
               << ", \"weight_mismatches\": " << weight_mismatch + extra_observed << ", \"max_abs_sdf_diff\": " << max_sdf << ", \"max_abs_colour_diff\": " << max_col
-              << ", \"deintegrated\": {\"frames\": " << dei[0] << ", \"reverted\": " << dei[1] << ", \"reset\": " << dei[2] << ", \"skipped\": " << dei[3] << "}}" << std::endl;
+              << ", \"deintegrated\": {\"frames\": " << dei[0] << ", \"reverted\": " << dei[1] << ", \"reset\": " << dei[2] << ", \"skipped\": " << dei[3] << "}";
+    if (!collect.empty()) {
+        const op_volume_collect_stats& cs = volume.CollectStats();
+        std::cout << ", \"collect\": {\"route\": \"" << collect << "\", \"blocks_before\": " << blocks_repaired << ", \"blocks_after\": " << blocks_collected << ", \"ms\": " << t_collect * 1000.0
+                  << ", \"ms_min_max\": [" << collect_s.front() * 1000.0 << ", " << collect_s.back() * 1000.0 << "], \"removed_unobserved\": " << cs.removed_unobserved
+                  << ", \"blocks_moved\": " << cs.blocks_moved << ", \"after_ms\": {\"extract_triangle_mesh\": " << t_mesh * 1000.0 << ", \"render_frame\": " << t_render * 1000.0
+                  << ", \"write_to_file\": " << t_write * 1000.0 << "}, \"triangles\": " << triangles << ", \"rendered_pixels\": " << rendered << "}";
+    }
+    std::cout << "}" << std::endl;
     return 0;
 }

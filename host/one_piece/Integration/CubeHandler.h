@@ -128,6 +128,15 @@ class CubeHandler {
     // EXTENSION: DeintegrateImage(depth, rgb, old_pose) then IntegrateImage(depth, rgb, new_pose) on one uploaded copy of the images and in one launch
     // (op_volume_reintegrate): what a corrected pose of an already fused frame is used for.
     void ReintegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& old_pose, const geometry::TransformationMatrix& new_pose);
+    // CollectGarbage(): declared by the reference (CubeHandler.h:357) and defined nowhere in it.  Here it frees every block that holds no voxel of
+    // weight > 0 -- what a de-integration leaves behind, what PrepareCubes selected and nothing updated -- on the device, compacting the pool in
+    // place (op_volume_collect_garbage states the definition).  EXTENSIONS: CollectGarbage(min_weight) also drops the blocks whose largest weight is
+    // below min_weight (depth-edge noise fewer than min_weight frames supported); CropToCubes(lo, hi) drops the blocks whose id lies outside
+    // [lo, hi] (inclusive, per axis) or that hold no observed voxel.  CollectStats(): what the last of these calls did.
+    void CollectGarbage();
+    void CollectGarbage(float min_weight);
+    void CropToCubes(const CubeID& lo, const CubeID& hi);
+    op_volume_collect_stats CollectStats() const; // (kept by the device volume: the class gains no data member, its layout is the one earlier builds were compiled against)
     CubeID GetCubeID(const geometry::Point3& point) const { return c_para.GetCubeID(point); }
     void AddCube(const CubeID& cube_id);
     // allocate the blocks the voxel centres of v_cube land in after trans: their eight trilinear neighbours / the voxel
@@ -189,6 +198,7 @@ class CubeHandler {
     static void Report(const char* where);
     void AddTransformedCubes(const VoxelCube& v_cube, const geometry::TransformationMatrix& trans, bool nearest);
     mutable op_volume* vol = nullptr;
+    void Collect(float min_weight, const int32_t* lo, const int32_t* hi, const char* where);
     // device images of frames that were fused in place (RGBDFrame::on_device): held until the volume is known to be done with them
     mutable std::deque<std::pair<unsigned long long, std::shared_ptr<void> > > borrowed_; // (position among the volume's accepted frames, images)
     void ReleaseBorrowed() const { borrowed_.clear(); } // call only right after a synchronising C-ABI call

@@ -118,6 +118,24 @@ void CubeHandler::Clear() {
     Touch();
     if (vol && op_volume_clear(vol) != OP_OK) Report("Clear");
 }
+void CubeHandler::Collect(float min_weight, const int32_t* lo, const int32_t* hi, const char* where) {
+    Pending();
+    if (!vol) return; // no device volume yet: nothing is allocated
+    Touch();
+    if (op_volume_collect_garbage(vol, min_weight, lo, hi, nullptr) != OP_OK) Report(where);
+    else ReleaseBorrowed(); // op_volume_collect_garbage synchronises
+}
+op_volume_collect_stats CubeHandler::CollectStats() const {
+    op_volume_collect_stats st = {0, 0, 0, 0, 0};
+    if (vol && op_volume_collect_last_stats(vol, &st) != OP_OK) Report("CollectStats");
+    return st;
+}
+void CubeHandler::CollectGarbage() { Collect(0.0f, nullptr, nullptr, "CollectGarbage"); }
+void CubeHandler::CollectGarbage(float min_weight) { Collect(min_weight, nullptr, nullptr, "CollectGarbage"); }
+void CubeHandler::CropToCubes(const CubeID& lo, const CubeID& hi) {
+    const int32_t l[3] = {lo(0), lo(1), lo(2)}, h[3] = {hi(0), hi(1), hi(2)};
+    Collect(0.0f, l, h, "CropToCubes");
+}
 bool CubeHandler::HasCube(const CubeID& cube_id) const {
     Pending();
     if (!vol) return false;

@@ -378,6 +378,33 @@ int op_volume_reintegrate_sequence(op_volume *v, const void *depth, size_t depth
 /* Counters of the de-integrations since create/clear (synchronises): frames de-integrated, and of their voxels that passed the predicate of
  * Integrator.cpp:52-92 those that were reverted (step 4 above), reset to the default voxel (step 3) and skipped (step 1; TSDFVoxel.h:24-39). */
 int op_volume_deintegrate_stats(op_volume *v, uint64_t *frames, uint64_t *reverted, uint64_t *reset, uint64_t *skipped);
+
+/* CubeHandler::CollectGarbage (declared at Integration/CubeHandler.h:357, never defined by the reference; no reference counterpart for the box and
+ * the weight bound): frees the blocks no frame supports any more -- what a de-integration leaves behind, what PrepareCubes selected and nothing
+ * ever updated -- and, on request, the blocks outside a box of block ids or below a weight.  THE DEFINITION:
+ *   - Like every accessor the call first sees all frames accepted before it (flush, synchronise, grow + replay); n = the blocks then.
+ *   - inside(b): true when box_lo and box_hi are both NULL; otherwise box_lo[a] <= CubeID(b)[a] <= box_hi[a] on every axis a, inclusive, in block
+ *     ids.  Exactly one of them NULL -> OP_ERR_INVALID.  box_lo[a] > box_hi[a] on an axis is legal and empties the volume.
+ *   - observed(b): some voxel of b has w > 0 && w >= min_weight (one float comparison pair per voxel; a NaN or negative weight, which only
+ *     foreign data can hold, counts as unobserved -- what TSDFVoxel::IsValid, TSDFVoxel.h:75-78, makes of it).  min_weight must be finite and
+ *     >= 0, otherwise OP_ERR_INVALID; 0 is pure garbage collection.
+ *   - b is kept iff inside(b) && observed(b).  A dropped block counts in removed_outside if it is not inside, otherwise in removed_unobserved.
+ *   - Pool order afterwards (what op_volume_download returns), m = blocks kept: a kept block in a slot < m stays where it is.  The dropped slots
+ *     below m, h_0 < h_1 < ..., are exactly as many as the kept slots at or above m, t_0 < t_1 < ...; block t_j (its five planes and its key)
+ *     moves to slot h_j, in place -- sources and destinations are disjoint.  blocks_moved is that count.
+ *   - Slots [m, n) hold default voxels again, as op_volume_clear leaves them, and are handed out as fresh; the block count is m; the hash table
+ *     is cleared and re-entered from the m keys (no tombstones).
+ *   - Pending op_volume_unpack_sum_begin slots and the raycaster's block summaries are invalidated.  Whether the volume takes the plain or the
+ *     lean update is unchanged (a kept block holds what it held, a freed slot the default voxel); foreign data only ever moves to a lower slot.
+ *   - The cumulative counters (op_volume_stats, op_volume_deintegrate_stats) count events and do not change.
+ *   - An empty volume, or nothing to drop: OP_OK, stats {n, n, 0, 0, 0}, and nothing runs beyond the classification and its count.
+ * Runs on the volume's stream and returns when it is done.  Without a device: OP_ERR_NO_DEVICE. */
+typedef struct { uint64_t blocks_before, blocks_kept, removed_outside, removed_unobserved, blocks_moved; } op_volume_collect_stats;
+int op_volume_collect_garbage(op_volume *v, float min_weight, const int32_t box_lo[3], const int32_t box_hi[3],
+                              op_volume_collect_stats *stats /* may be NULL */);
+/* What the last op_volume_collect_garbage of this volume did (CubeHandler::CollectStats; no reference counterpart): zeros before the first
+ * one and after a refused one.  Does not synchronise. */
+int op_volume_collect_last_stats(op_volume *v, op_volume_collect_stats *stats);
 /* Counters since create/clear (synchronises): frames integrated, sum over frames of
  * len(cube_id_list), of voxels visited (512 x len) and of voxels that passed the update predicate
  * (Integrator.cpp:63,70,74).  frames, blocks_selected and voxels_visited also count DE-INTEGRATED frames (they are prepared and selected like fused

@@ -35,6 +35,11 @@ class MergeStats(C.Structure):
                 ("wire_bytes_sent", C.c_uint64), ("wire_bytes_received", C.c_uint64)]
 
 
+class CollectStats(C.Structure):
+    """op_volume_collect_stats of op_volume_collect_garbage."""
+    _fields_ = [(k, C.c_uint64) for k in ("blocks_before", "blocks_kept", "removed_outside", "removed_unobserved", "blocks_moved")]
+
+
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("last_T", C.c_float * 16), ("rmse", C.c_double),
                 ("n_inliers", C.c_uint64), ("iterations", C.c_int32)]
@@ -137,6 +142,8 @@ SIGNATURES = {
     "op_volume_reintegrate": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, _fp]),
     "op_volume_reintegrate_sequence": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, _fp, _fp, C.c_size_t]),
     "op_volume_deintegrate_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
+    "op_volume_collect_garbage": (C.c_int, [_vp, C.c_float, _ip, _ip, C.POINTER(CollectStats)]),
+    "op_volume_collect_last_stats": (C.c_int, [_vp, C.POINTER(CollectStats)]),
     "op_volume_integrate_cubes": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, _fp, _vp, C.c_size_t]),
     "op_volume_stats": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
     "op_volume_stats_launches": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),

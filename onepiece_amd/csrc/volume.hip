@@ -104,6 +104,15 @@ void vol_mark_foreign(op_volume* v, unsigned long long bound) {
     if (b > v->plain_from) v->plain_from = b;
 }
 
+// The pool and table maintenance kernels for volume_gc.hip (a kernel is launched from the translation unit that defines it).
+void vol_launch_fill_pool(op_volume* v, size_t first_block, size_t n_blocks) {
+    if (n_blocks) hipLaunchKernelGGL(k_fill_pool, dim3(4096), dim3(256), 0, v->stream, v->pool, first_block, n_blocks);
+}
+void vol_launch_rehash(op_volume* v, unsigned n_valid) {
+    hipLaunchKernelGGL(k_clear_table, dim3(1024), dim3(256), 0, v->stream, v->tkeys, v->tvals, (size_t)v->table_size);
+    if (n_valid) hipLaunchKernelGGL(k_rehash, dim3((n_valid + 255) / 256), dim3(256), 0, v->stream, v->tkeys, v->tvals, v->table_size - 1, (const int*)v->keys, n_valid);
+}
+
 int vol_reset(op_volume* v) {
     ++v->generation; ++v->content_gen;
     hipLaunchKernelGGL(k_clear_table, dim3(1024), dim3(256), 0, v->stream, v->tkeys, v->tvals, (size_t)v->table_size);

@@ -547,6 +547,7 @@ struct op_volume {
     // cleared.  The blocks such a launch may have changed are known once it has run: until the next synchronising look (vol_check) plain_from covers
     // every slot (dei_pending), then it is the block count, as after an upload or a merge.
     bool dei_pending = false;
+    op_volume_collect_stats last_collect{};    // what the last op_volume_collect_garbage did (op_volume_collect_last_stats); zeros before the first one
     unsigned long long* dei_partial = nullptr; // 3 x kPartialGrid slots the SIGNED k_integrate's workgroups add to (reverted, reset, skipped) + [3 x kPartialGrid] de-integrated frames
     // Aligned-colour ring of op_volume_integrate_unaligned (align_color.hip): kUaSlots images of the volume camera's size, written by k_align_color on
     // `stream`; for host frames also the device copies of their depth images (ua_depth, allocated with the first one) and two staging buffers for
@@ -585,6 +586,8 @@ int vol_reset(op_volume* v);
 int vol_reserve(op_volume* v, unsigned long long need);
 int vol_block_count(op_volume* v, unsigned* n);
 void vol_mark_foreign(op_volume* v, unsigned long long bound);
+void vol_launch_fill_pool(op_volume* v, size_t first_block, size_t n_blocks); // k_fill_pool over pool slots [first_block, first_block + n_blocks), on the volume's stream
+void vol_launch_rehash(op_volume* v, unsigned n_valid);                       // k_clear_table, then k_rehash of keys[0, n_valid), on the volume's stream
 int check_cam(const op_camera* cam);
 void vol_retire(op_volume* v);               // retires the log entries of batches the device has reported complete; never blocks
 void frame_params(const op_volume* v, const float pose[16], const float* pose_inv, PoseFwd* fwd, PoseInv* inv);

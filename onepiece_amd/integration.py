@@ -266,6 +266,19 @@ class CubeHandler:
         L.check(self._lib.op_volume_deintegrate_stats(self._h, *[C.byref(x) for x in v]))
         return {"frames": v[0].value, "reverted": v[1].value, "reset": v[2].value, "skipped": v[3].value}
 
+    def CollectGarbage(self, min_weight=0.0, box=None):
+        """CubeHandler::CollectGarbage (declared at CubeHandler.h:357, defined nowhere in the reference; op_volume_collect_garbage): drops every
+        block without a voxel of weight > 0 and >= min_weight and, with box = (lo, hi) in block ids (inclusive), every block outside it; the pool
+        is compacted in place on the device.  Synchronises.  -> {"blocks_before", "blocks_kept", "removed_outside", "removed_unobserved",
+        "blocks_moved"}."""
+        st = L.CollectStats()
+        lo = hi = None
+        if box is not None:
+            lo, hi = (np.ascontiguousarray(b, np.int32).reshape(3) for b in box)
+        L.check(self._lib.op_volume_collect_garbage(self._h, float(min_weight), None if lo is None else _ip(lo), None if hi is None else _ip(hi), C.byref(st)))
+        self._alive = []
+        return {k: int(getattr(st, k)) for k, _t in L.CollectStats._fields_}
+
     def IntegrateImageUnaligned(self, depth, rgb, pose, rgb_camera, color_to_depth=None, pose_inv=None):
         """Extension: IntegrateImage(depth, tool::AlignColorToDepth(rgb, depth, rgb_camera, this camera, color_to_depth), pose) for a colour image
         from a second camera ([hc, wc, 3], any size) -- the ScanNet flow (example/GenerateModelFromScannet.cpp, Tool/IO.cpp:9-58).  The alignment
