@@ -158,6 +158,19 @@ class CubeHandler {
     // number of pixels that see the model.  Not in the reference, which has no raycaster; the frame-to-model tracker that uses the same view without
     // bringing it to the host is odometry::Odometry::DenseTrackingToModel.
     size_t RenderFrame(const geometry::TransformationMatrix& pose, cv::Mat& rgb, cv::Mat& depth);
+    // EXTENSIONS (not in the reference, which can only be read whole): what the model holds at the caller's points, one batch per device call
+    // (op_volume_sample states the definitions).  The points are taken through T first (an exact identity is not applied).  status[i] holds the
+    // OP_SAMPLE_* bits of point i.
+    //   SampleVoxels     the raycaster's strict trilinear sample (valid iff all eight voxels around the point are observed; otherwise the default
+    //                    voxel), or with reference_interpolation VoxelCube::ReadVoxelInterpolate as Transform evaluates it
+    //   SampleGradients  the central difference of the trilinear sdf at +-res/2 per axis, unnormalised (divided by the voxel resolution it
+    //                    approximates the gradient of the field; normalised it is the raycaster's normal); zero where a sample is missing
+    //   DistanceToModel  the statistics of |sdf| over the points of a cloud placed at `pose`: how far the cloud lies from the model
+    void SampleVoxels(const geometry::Point3List& points, std::vector<TSDFVoxel>& voxels, std::vector<uint8_t>& status, bool reference_interpolation = false,
+                      const geometry::TransformationMatrix& T = geometry::TransformationMatrix::Identity());
+    void SampleGradients(const geometry::Point3List& points, geometry::Point3List& gradients, std::vector<uint8_t>& status,
+                         const geometry::TransformationMatrix& T = geometry::TransformationMatrix::Identity());
+    op_volume_sample_stats DistanceToModel(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& pose = geometry::TransformationMatrix::Identity());
     void GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh);
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;

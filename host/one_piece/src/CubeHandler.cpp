@@ -446,6 +446,59 @@ size_t CubeHandler::RenderFrame(const geometry::TransformationMatrix& pose, cv::
     ReleaseBorrowed(); // (the call synchronised the volume)
     return static_cast<size_t>(n);
 }
+namespace {
+// the row-major T op_volume_sample takes, or nullptr for an exact identity (which is not applied: the points are sampled as they are given)
+const float* SampleTransform(const geometry::TransformationMatrix& T, float out[16]) {
+    bridge::RowMajor(T, out);
+    bool identity = true;
+    for (int k = 0; k < 16; ++k) identity = identity && out[k] == ((k % 5 == 0) ? 1.0f : 0.0f);
+    return identity ? nullptr : out;
+}
+} // namespace
+void CubeHandler::SampleVoxels(const geometry::Point3List& points, std::vector<TSDFVoxel>& voxels, std::vector<uint8_t>& status, bool reference_interpolation,
+                               const geometry::TransformationMatrix& T) {
+    Pending();
+    const size_t n = points.size();
+    voxels.assign(n, TSDFVoxel());
+    status.assign(n, static_cast<uint8_t>(OP_SAMPLE_INVALID));
+    if (n == 0 || !Ensure()) return;
+    float t[16];
+    const float* tp = SampleTransform(T, t);
+    std::vector<float> flat(5 * n);
+    if (op_volume_sample(vol, bridge::Floats(points), n, OP_MEM_HOST, tp, reference_interpolation ? OP_SAMPLE_REFERENCE : OP_SAMPLE_TRILINEAR, flat.data(), nullptr,
+                         status.data(), nullptr) != OP_OK) { Report("SampleVoxels"); return; }
+    ReleaseBorrowed(); // (the call synchronised the volume)
+    for (size_t i = 0; i < n; ++i) {
+        voxels[i].sdf = flat[5 * i]; voxels[i].weight = flat[5 * i + 1];
+        voxels[i].color = geometry::Point3(flat[5 * i + 2], flat[5 * i + 3], flat[5 * i + 4]);
+    }
+}
+void CubeHandler::SampleGradients(const geometry::Point3List& points, geometry::Point3List& gradients, std::vector<uint8_t>& status, const geometry::TransformationMatrix& T) {
+    Pending();
+    const size_t n = points.size();
+    gradients.assign(n, geometry::Point3(0, 0, 0));
+    status.assign(n, static_cast<uint8_t>(OP_SAMPLE_INVALID | OP_SAMPLE_NO_GRADIENT));
+    if (n == 0 || !Ensure()) return;
+    float t[16];
+    const float* tp = SampleTransform(T, t);
+    if (op_volume_sample(vol, bridge::Floats(points), n, OP_MEM_HOST, tp, OP_SAMPLE_TRILINEAR, nullptr, bridge::Floats(gradients), status.data(), nullptr) != OP_OK) {
+        Report("SampleGradients");
+        return;
+    }
+    ReleaseBorrowed();
+}
+op_volume_sample_stats CubeHandler::DistanceToModel(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& pose) {
+    Pending();
+    op_volume_sample_stats st = {0, 0, 0, 0, 0.0, 0.0, 0.0f};
+    const size_t n = pcd.points.size();
+    st.queries = n;
+    if (n == 0 || !Ensure()) return st;
+    float t[16];
+    const float* tp = SampleTransform(pose, t);
+    if (op_volume_sample(vol, bridge::Floats(pcd.points), n, OP_MEM_HOST, tp, OP_SAMPLE_TRILINEAR, nullptr, nullptr, nullptr, &st) != OP_OK) { Report("DistanceToModel"); return st; }
+    ReleaseBorrowed();
+    return st;
+}
 void CubeHandler::GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh) {
     Pending();
     if (!vol) return;

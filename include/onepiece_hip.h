@@ -502,6 +502,42 @@ int op_volume_raycast_stats(op_volume *v, uint64_t *visible_blocks, uint64_t *dr
  * dword stores) follows the raycaster's.  An empty volume or a view that sees nothing gives an all-zero frame and OP_OK. */
 int op_volume_render_frame(op_volume *v, const op_camera *cam, const float pose[16], uint8_t *rgb_out, float *depth_out, int mem, uint64_t *n_valid);
 
+/* What the model holds at the caller's points: a batch of n queries, one lane each (csrc/volume_sample.hip; NO reference counterpart for the entry --
+ * the two definitions are the ones this library already evaluates, made callable).  Every operation below is float32 and rounded separately;
+ * nothing is contracted.
+ *   query point  with T (16 floats, row-major, host memory): q_r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 * 1 per row r, p = q.xyz / q.w -- the order
+ *                TransformPoints takes (k_prepare_frames); without T (NULL): p is the given point.
+ *   OP_SAMPLE_TRILINEAR (the raycaster's rule, op_volume_raycast above): inv = 1.0f / res, g_a = p_a * inv - 0.5f, base voxel i = floor(g),
+ *                f = g - floor(g); taps i + (k & 1, (k >> 1) & 1, (k >> 2) & 1), k = 0..7, of weight (wx * wy) * wz with w_a = f_a where the tap's
+ *                bit is set and 1.0f - f_a where it is not; each of the five planes accumulates acc += w * t in tap order from 0.  The sample is
+ *                VALID iff all eight taps lie in held blocks and have weight > 0 (a NaN or negative weight is unobserved).  Valid: voxels gets the
+ *                five sums {sdf, weight, c0, c1, c2}.  Invalid: the default voxel {999, 0, -1, -1, -1} and OP_SAMPLE_INVALID in the status.
+ *   gradient     (OP_SAMPLE_TRILINEAR only) h = 0.5f * res, d_a = s(p + h e_a) - s(p - h e_a): six more trilinear sdf samples, k_rc_shade's
+ *                difference, unnormalised (d / res approximates the gradient of the sdf; the raycaster's normal is d divided by
+ *                sqrt(d0 d0 + (d1 d1 + d2 d2))).  If any of the six samples is invalid -- a sample whose g is out of range, below, is -- the
+ *                gradient is (0, 0, 0) and the status carries OP_SAMPLE_NO_GRADIENT.  The bit is only ever set when gradients are asked for.
+ *   OP_SAMPLE_REFERENCE (VoxelCube::ReadVoxelInterpolate, VoxelCube.cpp:6-50, as CubeHandler::Transform evaluates it): half = res / 2,
+ *                n = p - half, p0 = floor(n / res), weights (n - (float)p0 * res) / res; the eight taps p0 + (k & 1, (k >> 1) & 1, (k >> 2) & 1)
+ *                are fetched (a block that is not held gives the default voxel) and go through the seven lerp stages in the reference's order;
+ *                the resulting voxel is written as it comes, and the status carries OP_SAMPLE_INVALID iff its weight is 0.
+ *   OP_SAMPLE_OUT_OF_RANGE  a coordinate of g (of n / res in the reference mode) is NaN or of magnitude >= 8388600: decided by an explicit
+ *                test before any conversion to int (inside the bound every tap's block id is a legal one).  Implies OP_SAMPLE_INVALID, and
+ *                OP_SAMPLE_NO_GRADIENT where gradients are asked for: the default voxel and a zero gradient.
+ *   stats        queries = n; valid, gradients, out_of_range = the queries without OP_SAMPLE_INVALID, those with a gradient (0 unless gradients
+ *                are asked for), those out of range; sum_abs_sdf / sum_sq_sdf = the sums over valid samples of (double)|s| and (double)s * (double)s,
+ *                max_abs_sdf the largest |s| among them (0 without one).  Every workgroup reduces its lanes and writes one row; the host adds the
+ *                rows in index order in double: repeatable for a given n, no floating-point atomics.
+ * mem says where xyz (n x 3), voxels (n x 5), gradients (n x 3) and status (n bytes) live; T and stats are host memory.  The device buffers need
+ * the alignment of their element type only.  Like every accessor the call sees all frames accepted before it (the queue is flushed first); the kernel
+ * runs on the volume's stream and the call returns when it is done.  The volume is only read.  n == 0: OP_OK and zero stats.  OP_ERR_INVALID: a
+ * NULL volume, a NULL xyz with n > 0, every output (voxels, gradients, status, stats) NULL, a bad mem or mode, gradients with OP_SAMPLE_REFERENCE. */
+enum { OP_SAMPLE_TRILINEAR = 0, OP_SAMPLE_REFERENCE = 1 };
+enum { OP_SAMPLE_INVALID = 1, OP_SAMPLE_NO_GRADIENT = 2, OP_SAMPLE_OUT_OF_RANGE = 4 }; /* status bits */
+typedef struct { uint64_t queries, valid, gradients, out_of_range; double sum_abs_sdf, sum_sq_sdf; float max_abs_sdf; } op_volume_sample_stats;
+int op_volume_sample(op_volume *v, const float *xyz, size_t n, int mem, const float *T /* NULL or 16, row-major */, int mode,
+                     float *voxels /* n x 5 {sdf, weight, c0, c1, c2} or NULL */, float *gradients /* n x 3 or NULL */,
+                     uint8_t *status /* n or NULL */, op_volume_sample_stats *stats /* host, or NULL */);
+
 /* Frame-sharded multi-GPU merge (the distributed form of CubeHandler::Merge; DESIGN.md "Multi-GPU").
  * All pointers are DEVICE pointers on the volume's device.
  *   keys_device : copy this volume's block keys (n x 3 int32) into d_keys.

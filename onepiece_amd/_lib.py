@@ -40,6 +40,12 @@ class CollectStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("blocks_before", "blocks_kept", "removed_outside", "removed_unobserved", "blocks_moved")]
 
 
+class SampleStats(C.Structure):
+    """op_volume_sample_stats of op_volume_sample."""
+    _fields_ = [(k, C.c_uint64) for k in ("queries", "valid", "gradients", "out_of_range")] + \
+               [("sum_abs_sdf", C.c_double), ("sum_sq_sdf", C.c_double), ("max_abs_sdf", C.c_float)]
+
+
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("last_T", C.c_float * 16), ("rmse", C.c_double),
                 ("n_inliers", C.c_uint64), ("iterations", C.c_int32)]
@@ -64,6 +70,8 @@ OP_DEPTH_F32, OP_DEPTH_U16 = 0, 1
 OP_VOLUME_OPT_UPDATE, OP_VOLUME_UPDATE_EXACT, OP_VOLUME_UPDATE_SUM_FORM = 0, 0, 1
 OP_VOLUME_OPT_SELECT, OP_VOLUME_SELECT_AUTO, OP_VOLUME_SELECT_DIRECT = 1, 0, -1
 OP_VOLUME_OPT_RAYCAST_PRUNE = 2
+OP_SAMPLE_TRILINEAR, OP_SAMPLE_REFERENCE = 0, 1
+OP_SAMPLE_INVALID, OP_SAMPLE_NO_GRADIENT, OP_SAMPLE_OUT_OF_RANGE = 1, 2, 4
 OP_RUNTIME_OPT_MERGE_ALGORITHM, OP_RUNTIME_OPT_MERGE_SLICE_BLOCKS, OP_RUNTIME_OPT_MERGE_FORCE_SINGLE_RANK, OP_RUNTIME_OPT_TRACKER_GRAPH, OP_RUNTIME_OPT_COPY_THREADS, OP_RUNTIME_OPT_CACHE_DEVICE_BYTES, OP_RUNTIME_OPT_MERGE_FAULT, OP_RUNTIME_OPT_ICP_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_BATCH_SUMS, OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT, OP_RUNTIME_OPT_GLOBAL_REGISTRATION = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE = 12
 OP_RUNTIME_OPT_MESH_CLUSTERING = 13
@@ -162,6 +170,7 @@ SIGNATURES = {
     "op_volume_raycast": (C.c_int, [_vp, C.POINTER(Camera), _fp, _fp, _fp, _fp, C.c_int]),
     "op_volume_raycast_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "op_volume_render_frame": (C.c_int, [_vp, C.POINTER(Camera), _fp, _vp, _fp, C.c_int, C.POINTER(C.c_uint64)]),
+    "op_volume_sample": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp, C.c_int, _vp, _vp, _vp, C.POINTER(SampleStats)]),
     "op_volume_keys_device": (C.c_int, [_vp, _vp, C.c_size_t, _szp]),
     "op_volume_pack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "op_volume_unpack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

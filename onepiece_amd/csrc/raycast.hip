@@ -38,6 +38,7 @@
 //                    and the count of pixels that were hit.
 // The result does not depend on the order blocks are processed in (tests compare it with the CPU restatement bit for bit).
 #include "volume_core.hpp"
+#include "trilinear_sample.hpp"
 
 namespace {
 
@@ -67,40 +68,8 @@ struct RcView {
 // ---- the definition's arithmetic, shared by the LDS march and the global-memory gathers (same operations, same order) ----------
 __device__ __forceinline__ float rc_t(const RcView& W, int k) { return W.near_d + (float)k * W.res; }
 
-struct RcCell { int i0, i1, i2; float f0, f1, f2; };
-__device__ __forceinline__ RcCell rc_cell(const RcView& W, float x, float y, float z) {
-    const float g0 = x * W.inv_res - 0.5f, g1 = y * W.inv_res - 0.5f, g2 = z * W.inv_res - 0.5f;
-    const float b0 = floorf(g0), b1 = floorf(g1), b2 = floorf(g2);
-    return RcCell{(int)b0, (int)b1, (int)b2, g0 - b0, g1 - b1, g2 - b2};
-}
-__device__ __forceinline__ float rc_weight(const RcCell& c, int k) {
-    const float wx = (k & 1) ? c.f0 : 1.0f - c.f0, wy = (k & 2) ? c.f1 : 1.0f - c.f1, wz = (k & 4) ? c.f2 : 1.0f - c.f2;
-    return (wx * wy) * wz;
-}
-
-struct BlockCache { int cx, cy, cz, idx; };
-
-// trilinear sample through the hash (the march's rare previous-sample lookups and k_rc_finish): false = not all 8 voxels observed
-template <bool COL>
-__device__ bool rc_sample_global(const VolView& V, const RcView& W, BlockCache& bc, float x, float y, float z, float* sdf, float* col) {
-    const RcCell c = rc_cell(W, x, y, z);
-    float acc = 0, a0 = 0, a1 = 0, a2 = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int px = c.i0 + (k & 1), py = c.i1 + ((k >> 1) & 1), pz = c.i2 + ((k >> 2) & 1);
-        const int bx = px >> 3, by = py >> 3, bz = pz >> 3;
-        if (!(bx == bc.cx && by == bc.cy && bz == bc.cz)) { bc.cx = bx; bc.cy = by; bc.cz = bz; bc.idx = table_find(V, bx, by, bz); }
-        if (bc.idx < 0) return false;
-        const float* t = V.pool + (size_t)bc.idx * kBlockFloats + ((px - bx * 8) + (py - by * 8) * 8 + (pz - bz * 8) * 64);
-        if (!(t[kVox] > 0)) return false;
-        const float w = rc_weight(c, k);
-        acc += w * t[0];
-        if (COL) { a0 += w * t[2 * kVox]; a1 += w * t[3 * kVox]; a2 += w * t[4 * kVox]; } // colour planes only at the hit
-    }
-    *sdf = acc;
-    if (COL) { col[0] = a0; col[1] = a1; col[2] = a2; }
-    return true;
-}
+// rc_cell, rc_weight and rc_sample_global (the cell arithmetic, its tap weights, the gather through the hash): trilinear_sample.hpp, shared with the
+// point queries of volume_sample.hip
 
 // ---- R0 ------------------------------------------------------------------------------------------------------------------------
 // The sample domain of block (kx, ky, kz) -- the points whose base voxel lies in it -- is the block shifted by half a voxel:

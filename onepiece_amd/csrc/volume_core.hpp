@@ -5,6 +5,7 @@
 //   integrate.hip   KC k_integrate (Integrator::IntegrateImage; its SIGNED instantiations: a batch that holds a de-integration, TSDFVoxel::operator+ with weight -1)
 //   volume_ops.hip  GetCubeMap / SetCubeMap / Merge / sum-form pack + unpack / Transform / GetPointCloud / ExtractTriangleMesh / .map files
 //   raycast.hip     the raycaster, and its view packed as an RGB-D frame (model_frame.hpp: what the dense tracker takes from here)
+//   volume_gc.hip   CollectGarbage;  volume_sample.hip  the point queries (op_volume_sample), over trilinear_sample.hpp and voxel_interp.hpp
 // Data layout in HBM: see volume.hip (and DESIGN.md section 2).
 #pragma once
 #include <cfloat>

@@ -6,6 +6,7 @@
 //   CubeHandler::ExtractTriangleMesh / GenerateMeshByCube + MarchingCube   Integration/CubeHandler.cpp:9-114, MarchingCube.cpp:8-74
 //   CubeHandler::WriteToFile / ReadFromFile / ReadFromFileFloat            Integration/CubeHandler.h:40-128
 #include "volume_core.hpp"
+#include "voxel_interp.hpp"
 
 namespace {
 
@@ -115,36 +116,8 @@ __global__ __launch_bounds__(512) void k_unpack_sum(float* __restrict__ pool, co
 // GetPointCloud (CubeHandler.cpp:45-69)
 // ---------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ Vox5 default_voxel() { return Vox5{999.0f, 0.0f, -1.0f, -1.0f, -1.0f}; }
-
-// cube_map.find(GetCubeID(p)) + GetVoxel(GetVoxelID(p)) (VoxelCube.h:63-67,81-86); default voxel if absent
-__device__ Vox5 fetch_voxel(const VolView& S, int px, int py, int pz) {
-    const int cx = px >> 3, cy = py >> 3, cz = pz >> 3; // floor((p + 0.0) / 8)
-    const int idx = table_find(S, cx, cy, cz);
-    if (idx < 0) return default_voxel();
-    const int vid = (px - cx * 8) + (py - cy * 8) * 8 + (pz - cz * 8) * 64;
-    const float* t = S.pool + (size_t)idx * kBlockFloats + vid;
-    return Vox5{t[0], t[kVox], t[2 * kVox], t[3 * kVox], t[4 * kVox]};
-}
-// TSDFVoxel::operator*(float) (TSDFVoxel.h:56-67)
-__device__ __forceinline__ Vox5 vox_scale(const Vox5& a, float wgt) {
-    if (wgt == 0 || a.w == 0) return default_voxel();
-    return Vox5{a.s * wgt, a.w * wgt, a.c0 * wgt, a.c1 * wgt, a.c2 * wgt};
-}
-// TSDFVoxel::add (TSDFVoxel.h:40-51)
-__device__ __forceinline__ Vox5 vox_add_direct(const Vox5& a, const Vox5& b) {
-    if (a.w == 0) return b;
-    if (b.w == 0) return a;
-    return Vox5{a.s + b.s, a.w + b.w, a.c0 + b.c0, a.c1 + b.c1, a.c2 + b.c2};
-}
-// one stage of ReadVoxelInterpolate (VoxelCube.cpp:17-20):
-// ((a * (1 - t)).add(b * t)) / ((1 - t) * (a.weight != 0) + t * (b.weight != 0))
-__device__ __forceinline__ Vox5 interp_stage(const Vox5& a, const Vox5& b, float t) {
-    if (!(a.w != 0 || b.w != 0)) return default_voxel();
-    const Vox5 sum = vox_add_direct(vox_scale(a, 1 - t), vox_scale(b, t));
-    const float d = (1 - t) * (float)(a.w != 0) + t * (float)(b.w != 0);
-    return vox_scale(sum, 1 / d); // operator/(w) = operator*(1 / w) (TSDFVoxel.h:68-71)
-}
+// the voxel fetch and the stages of ReadVoxelInterpolate (fetch_voxel, vox_scale, vox_add_direct, interp_stage): voxel_interp.hpp (shared with the
+// point queries of volume_sample.hip)
 
 // workgroup-wide minimum / maximum of an int (512 threads = 8 waves), result in every thread
 __device__ __forceinline__ void wg_min_max(int v_lo, int v_hi, int* s_red, int* out_lo, int* out_hi) {

@@ -555,6 +555,46 @@ class CubeHandler:
                                                  L.OP_MEM_DEVICE, C.byref(n)))
         return int(n.value)
 
+    # -- point queries (extension; op_volume_sample: the raycaster's trilinear rule or ReadVoxelInterpolate at the caller's points)
+    _SAMPLE_MODES = {"trilinear": L.OP_SAMPLE_TRILINEAR, "reference": L.OP_SAMPLE_REFERENCE}
+
+    @staticmethod
+    def _sample_stats(st):
+        return {k: (int if t is C.c_uint64 else float)(getattr(st, k)) for k, t in L.SampleStats._fields_}
+
+    def Sample(self, points, T=None, mode="trilinear", gradients=False, stats=False):
+        """What the model holds at `points` ([n,3] float32, host): mode "trilinear" is the raycaster's strict trilinear sample (valid iff all
+        eight taps are observed), "reference" is VoxelCube::ReadVoxelInterpolate as Transform evaluates it.  T: a 4x4 applied to the points first.
+        -> (voxels [n,5] {sdf, weight, c0, c1, c2}, status [n] uint8 of OP_SAMPLE_* bits[, gradients [n,3]: the unnormalised central difference
+        of the trilinear sdf at +-res/2][, stats dict]).  Synchronises; the volume is only read."""
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        n = len(pts)
+        vox, status = np.empty((n, 5), np.float32), np.empty(n, np.uint8)
+        grad = np.empty((n, 3), np.float32) if gradients else None
+        st = L.SampleStats() if stats else None
+        Tm = _f32(T).reshape(16) if T is not None else None
+        L.check(self._lib.op_volume_sample(self._h, C.c_void_p(pts.ctypes.data), n, L.OP_MEM_HOST, _fp(Tm) if Tm is not None else None,
+                                           self._SAMPLE_MODES[mode], C.c_void_p(vox.ctypes.data), C.c_void_p(grad.ctypes.data) if gradients else None,
+                                           C.c_void_p(status.ctypes.data), C.byref(st) if stats else None))
+        self._alive = []
+        out = (vox, status)
+        if gradients:
+            out += (grad,)
+        if stats:
+            out += (self._sample_stats(st),)
+        return out
+
+    def SampleDevice(self, points_ptr, n, voxels_ptr=0, status_ptr=0, gradients_ptr=0, T=None, mode="trilinear", stats=False):
+        """The same with buffers that stay in HBM: device addresses (e.g. torch tensor.data_ptr()) of n x 3 float32 points and of the n x 5 float32,
+        n uint8 and n x 3 float32 outputs on the volume's device; 0 = not wanted.  Returns the stats dict (or None) when the outputs are complete."""
+        st = L.SampleStats() if stats else None
+        Tm = _f32(T).reshape(16) if T is not None else None
+        ptr = lambda a: C.c_void_p(int(a)) if a else None
+        L.check(self._lib.op_volume_sample(self._h, ptr(points_ptr), int(n), L.OP_MEM_DEVICE, _fp(Tm) if Tm is not None else None, self._SAMPLE_MODES[mode],
+                                           ptr(voxels_ptr), ptr(gradients_ptr), ptr(status_ptr), C.byref(st) if stats else None))
+        self._alive = []
+        return self._sample_stats(st) if stats else None
+
     def RaycastStats(self):
         """Measurement hook: what the last Raycast call did (op_volume_raycast_stats)."""
         v = [C.c_uint64(0) for _ in range(4)]
