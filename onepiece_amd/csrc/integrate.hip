@@ -1,6 +1,7 @@
 // integrate.hip -- KC k_integrate: Integrator::IntegrateImage (Integration/Integrator.cpp:36-94) + TSDFVoxel::operator+ (TSDFVoxel.h:24-39) for all frames
 // of a batch (volume_core.hpp lists the translation units).  file:line citations are relative to /root/reference/src.
 #include "volume_core.hpp"
+#include "kc_lanes.hpp"
 
 namespace {
 
@@ -192,9 +193,10 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : SIGNED ? KC_SI
     if (!SUMF) for (int k = tid; k < 256; k += blockDim.x) s_c255[k] = (float)k / 255.0f;
     const unsigned npix = (unsigned)(C.width * C.height);
     const float half = C.res / 2;
-    // VoxelCentroidOffSet (VoxelCube.h:48-61): x*res + half with x = lane & 7, y = lane >> 3
-    const float ox = (float)(lane & 7) * C.res + half;
-    const float oy = (float)(lane >> 3) * C.res + half;
+    // VoxelCentroidOffSet (VoxelCube.h:48-61): x*res + half, with the voxel (x, y, z) of this lane's slot 0 from the lane map (kc_lanes.hpp)
+    const int lx = kc_lanes::vx<ZT>(zg, 0, lane), ly = kc_lanes::vy<ZT>(zg, 0, lane), lz = kc_lanes::vz<ZT>(zg, 0, lane);
+    const float ox = (float)lx * C.res + half;
+    const float oy = (float)ly * C.res + half;
     const float __attribute__((address_space(4)))* kargs =
         (const float __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr(); // BatchInv B = offset 0 of the kernarg segment
     (void)B;
@@ -235,14 +237,14 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : SIGNED ? KC_SI
             const bmask_t mask = V.bmask[tslot];
             if (zg == 0) { sel += mask_popc(mask); ++nblk; }
             const int kx = V.keys[3 * idx], ky = V.keys[3 * idx + 1], kz = V.keys[3 * idx + 2];
-            float* vox = V.pool + (size_t)idx * kBlockFloats + (zg * ZT) * 64 + lane;
+            float* vox = V.pool + (size_t)idx * kBlockFloats + (lx + 8 * ly + 64 * lz);
             float s[ZT], w[ZT], c0[ZT], c1[ZT], c2[ZT], pz[ZT];
 #pragma unroll
             for (int z = 0; z < ZT; ++z) {
                 // (the sum form needs the stored voxel only after the frames: it is loaded there, and the registers are free until then)
-                if (!SUMF) voxel_load(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
+                if (!SUMF) voxel_load(vox + z * kc_lanes::kSlotStride, s[z], w[z], c0[z], c1[z], c2[z]);
                 // GetGlobalPoint (VoxelCube.h:75-80): Point3(id) * CUBE_SIZE * VoxelResolution + offset
-                pz[z] = ((float)kz * 8.0f) * C.res + ((float)(zg * ZT + z) * C.res + half);
+                pz[z] = ((float)kz * 8.0f) * C.res + ((float)(lz + z * kc_lanes::kBZ) * C.res + half);
             }
             const float px = ((float)kx * 8.0f) * C.res + ox;
             const float py = ((float)ky * 8.0f) * C.res + oy;
@@ -369,7 +371,7 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : SIGNED ? KC_SI
             if (SUMF) {
 #pragma unroll
                 for (int z = 0; z < ZT; ++z)
-                    if (acc1n[z] >> 16) voxel_load(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
+                    if (acc1n[z] >> 16) voxel_load(vox + z * kc_lanes::kSlotStride, s[z], w[z], c0[z], c1[z], c2[z]);
 #pragma unroll
                 for (int z = 0; z < ZT; ++z) {
                     const unsigned cnt = acc1n[z] >> 16;
@@ -394,12 +396,12 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : SIGNED ? KC_SI
                     const bool wrote = w[z] != w0[z];
                     upd += (unsigned)(w[z] - w0[z]);       // (per lane)
                     chg += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(wrote));
-                    if (wrote) voxel_store(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
+                    if (wrote) voxel_store(vox + z * kc_lanes::kSlotStride, s[z], w[z], c0[z], c1[z], c2[z]);
                 }
             } else {
 #pragma unroll
                 for (int z = 0; z < ZT; ++z)
-                    if (SUMF ? ((changed >> z) & 1u) != 0u : ((changed_m[z] >> lane) & 1ull) != 0ull) voxel_store(vox + z * 64, s[z], w[z], c0[z], c1[z], c2[z]);
+                    if (SUMF ? ((changed >> z) & 1u) != 0u : ((changed_m[z] >> lane) & 1ull) != 0ull) voxel_store(vox + z * kc_lanes::kSlotStride, s[z], w[z], c0[z], c1[z], c2[z]);
                 if (SUMF) chg += (unsigned)__popc(changed);
                 else {
 #pragma unroll
