@@ -216,6 +216,10 @@ int op_debug_rcp(const float *x, long long n, float *out);
 /* Test hook (host): the bound on |1 - Z * v_rcp_f32(Z)| that the certified pixel projection's error bound assumes of the unrefined
  * hardware reciprocal (csrc/px_round.hpp kPxRcpErr); tests/test_kc_diet_gpu.py holds op_debug_rcp to it over every significand. */
 double op_debug_px_rcp_err(void);
+/* Test hook (host): what k_prepare_frames is told about a frame of this camera at this pose (csrc/ka_cert.hpp): rect = {j_lo, j_hi, i_lo,
+ * i_hi} and z = {z_lo, z_hi}, the pixels and depths certified to lie inside the frame's own frustum (j_lo > j_hi: no certificate), and
+ * quot = whether the three-operation quotients by fx, fy and (for 16-bit depth) depth_scale are in use. */
+int op_debug_ka_certificate(const op_camera *cam, const float pose[16], float far_dist, float near_dist, int32_t rect[4], float z[2], int32_t quot[3]);
 /* Test hook (device): the fusion kernel's structured gather (csrc/volume_core.hpp gather2d: a buffer descriptor with stride = one image
  * row and num_records = the rows does the row test and the address arithmetic) of n pixels uv = n x {u, v}, each in [-2^23, 2^23), from
  * frame `frame` of a stack of n_frames packed images (images: n_frames x height x width records {depth bits, rgba}; width <= 2047).

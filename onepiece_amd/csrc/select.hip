@@ -41,9 +41,27 @@ __global__ void k_mark_cubes(VolView V, State* st, const int* __restrict__ keys,
 // One bounding partial per workgroup (no atomics): [max x,y,z, min x,y,z, inside, pad].
 // ---------------------------------------------------------------------------------------------
 
+// KAFAST (ka_cert.hpp): the host has certified, per frame, a pixel rectangle and a depth interval inside which a back-projected point lies in
+// the frustum by more than every rounding of the chain below, and that the quotients by fx and fy are the three-operation ones.  A certified
+// pixel forms x, y with ka_div_const and the first three rows of the pose product as before, and is inside: no fourth row, no division by it,
+// no planes.  The decision is per lane, not per wave: a wave whose valid lanes are all certified branches over the full sequence (execz); a mixed
+// wave executes both bodies, each under its lanes' mask, and the full sequence's ballot on q3 != 1 then sees the uncertified lanes only --
+// harmless, a lane with q3 == 1 gets q / 1 == q whether or not its wave divides.
+#ifdef KA_TRACE // development builds only: [0] wave passes over a pixel slot with a valid lane, [1] those of them with ANY uncertified lane
+                // (they run the full sequence for those lanes; not "waves that ran the full sequence only")
+__device__ unsigned long long g_ka_waves[2];
+#define KA_COUNT(K) do { if (__lane_id() == (unsigned)__builtin_ctzll(__builtin_amdgcn_read_exec())) atomicAdd(&g_ka_waves[K], 1ull); } while (0)
+#else
+#define KA_COUNT(K) do { } while (0)
+#endif
+
+struct KaNoArgs {}; // the form without certificates takes nothing on top of the common arguments
+template <bool KAFAST>
 __global__ __launch_bounds__(256) void k_prepare_frames(KaFwd B, int f0, CamParams C, BatchPtrs Q, uint2* __restrict__ pimg, float2* __restrict__ ptile,
                                                         float* __restrict__ partial, State* st, unsigned seq,
-                                                        const unsigned* __restrict__ n_blocks, unsigned* __restrict__ hstat) {
+                                                        const unsigned* __restrict__ n_blocks, unsigned* __restrict__ hstat,
+                                                        typename std::conditional<KAFAST, KaArgs, KaNoArgs>::type KA) {
+    const KaArgs* const K = KAFAST ? reinterpret_cast<const KaArgs*>(&KA) : nullptr;
     __shared__ float s_red[4][6];
     __shared__ unsigned s_cnt[4];
     __shared__ float s_tile[4][4][2];
@@ -96,7 +114,12 @@ __global__ __launch_bounds__(256) void k_prepare_frames(KaFwd B, int f0, CamPara
         if (wide) {
             if (C.depth_u16) {
                 const ushort4 d = *reinterpret_cast<const ushort4*>((const unsigned short*)dptr + pix0);
-                zz[0] = (float)d.x / C.depth_scale; zz[1] = (float)d.y / C.depth_scale; zz[2] = (float)d.z / C.depth_scale; zz[3] = (float)d.w / C.depth_scale;
+                if (KAFAST && K->use_d) { // 0 .. 65535 lie in the quotient's window (launch_prepare_frames)
+                    zz[0] = ka_div_const((float)d.x, C.depth_scale, K->yd); zz[1] = ka_div_const((float)d.y, C.depth_scale, K->yd);
+                    zz[2] = ka_div_const((float)d.z, C.depth_scale, K->yd); zz[3] = ka_div_const((float)d.w, C.depth_scale, K->yd);
+                } else {
+                    zz[0] = (float)d.x / C.depth_scale; zz[1] = (float)d.y / C.depth_scale; zz[2] = (float)d.z / C.depth_scale; zz[3] = (float)d.w / C.depth_scale;
+                }
             } else {
                 const float4 d = *reinterpret_cast<const float4*>((const float*)dptr + pix0);
                 zz[0] = d.x; zz[1] = d.y; zz[2] = d.z; zz[3] = d.w;
@@ -112,10 +135,21 @@ __global__ __launch_bounds__(256) void k_prepare_frames(KaFwd B, int f0, CamPara
         } else {
             for (int e = 0; e < nv; ++e) {
                 const int pix = pix0 + e;
-                zz[e] = C.depth_u16 ? (float)((const unsigned short*)dptr)[pix] / C.depth_scale : ((const float*)dptr)[pix];
+                if (KAFAST && C.depth_u16 && K->use_d) zz[e] = ka_div_const((float)((const unsigned short*)dptr)[pix], C.depth_scale, K->yd);
+                else zz[e] = C.depth_u16 ? (float)((const unsigned short*)dptr)[pix] / C.depth_scale : ((const float*)dptr)[pix];
                 if (cptr) cc[e] = (unsigned)cptr[3 * (size_t)pix] | ((unsigned)cptr[3 * (size_t)pix + 1] << 8) | ((unsigned)cptr[3 * (size_t)pix + 2] << 16);
                 out[pix] = make_uint2(__float_as_uint(zz[e]), cc[e] | 0x01000000u);
             }
+        }
+        // KAFAST: the thread's row and first column against the frame's certified rectangle (pixel e: 0 <= cj + e <= cw)
+        bool crow = false;
+        int cj = 0, cw = -1;
+        float cz_lo = 0.0f, cz_hi = 0.0f;
+        if (KAFAST) {
+            const KaCert& T = K->c[blockIdx.y];
+            crow = row >= T.i_lo && row <= T.i_hi;
+            cj = col0 - T.j_lo; cw = T.j_hi - T.j_lo;
+            cz_lo = T.z_lo; cz_hi = T.z_hi;
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -124,6 +158,22 @@ __global__ __launch_bounds__(256) void k_prepare_frames(KaFwd B, int f0, CamPara
             if (!(z > 0)) continue;
             tmin = fminf(tmin, z); tmax = fmaxf(tmax, z);
             const int i = row, j = col0 + e;
+            if (KAFAST) { // a certified pixel is finished here; the others (and every pixel without KAFAST) take the reference's whole sequence below
+                KA_COUNT(0);
+                if (crow & ((unsigned)(cj + e) <= (unsigned)cw) & (z >= cz_lo) & (z <= cz_hi)) {
+                    const float x = ka_div_const(((float)j - C.cx) * z, C.fx, K->yx);
+                    const float y = ka_div_const(((float)i - C.cy) * z, C.fy, K->yy);
+                    const float* M = P.pose;
+                    const float p0 = ((M[0] * x + M[1] * y) + M[2] * z) + M[3] * 1.0f;
+                    const float p1 = ((M[4] * x + M[5] * y) + M[6] * z) + M[7] * 1.0f;
+                    const float p2 = ((M[8] * x + M[9] * y) + M[10] * z) + M[11] * 1.0f;
+                    ++inside;
+                    mx0 = p0 > mx0 ? p0 : mx0; mx1 = p1 > mx1 ? p1 : mx1; mx2 = p2 > mx2 ? p2 : mx2;
+                    mn0 = p0 < mn0 ? p0 : mn0; mn1 = p1 < mn1 ? p1 : mn1; mn2 = p2 < mn2 ? p2 : mn2;
+                    continue;
+                }
+                KA_COUNT(1);
+            }
             const float x = ((float)j - C.cx) * z / C.fx; // PointCloud.cpp:90-93
             const float y = ((float)i - C.cy) * z / C.fy;
             const float* M = P.pose;                       // Geometry.cpp:19-27
@@ -780,12 +830,34 @@ namespace opv {
 
 void launch_prepare_frames(op_volume* v, const BatchFwd& F, int nf, const CamParams& C, const BatchPtrs& Q, unsigned seq) {
     const int g1 = ka_grid(C.width, C.height);
+    // the camera's three quotients (ka_quot: a few dozen trial divisions each), redone only when a constant changes
+    static thread_local struct { float fx, fy, ds; KaCam cam; bool set; } memo;
+    if (!memo.set || memo.fx != C.fx || memo.fy != C.fy || memo.ds != C.depth_scale) {
+        memo.fx = C.fx; memo.fy = C.fy; memo.ds = C.depth_scale; memo.cam = ka_cam(C.fx, C.fy, C.depth_scale); memo.set = true;
+    }
+    const KaCam& QC = memo.cam;
     for (int f0 = 0; f0 < nf; f0 += kKaFrames) {
         KaFwd A;
         const int na = nf - f0 < kKaFrames ? nf - f0 : kKaFrames;
         std::memcpy(A.f, F.f + f0, sizeof(PoseFwd) * (size_t)na);
-        hipLaunchKernelGGL(k_prepare_frames, dim3(g1, na), dim3(256), 0, v->stream, A, f0, C, Q, v->pimg, v->ptile, v->partial, v->state, seq,
-                           (const unsigned*)v->n_blocks, v->hstat_dev);
+        // the certified form when at least one frame of the launch has a certificate (a camera whose quotient flags are false has none)
+        KaArgs K;
+        bool any = false;
+        for (int k = 0; k < kKaFrames; ++k) {
+            K.c[k] = k < na ? ka_certificate(A.f[k].pose, A.f[k].planes, C.fx, C.fy, C.cx, C.cy, C.width, C.height, QC) : KaCert{0, -1, 0, -1, 1.0f, 0.0f};
+            any = any || K.c[k].j_lo <= K.c[k].j_hi;
+        }
+#ifdef KA_TRACE
+        any = true; // the trace build counts every frame's wave passes, those of a launch without a certificate included
+#endif
+        K.yx = QC.qx.y; K.yy = QC.qy.y; K.yd = QC.qd.y;
+        K.use_d = C.depth_u16 && QC.qd.ok && QC.qd.lo <= 0 && QC.qd.hi >= 15; // the numerators 0 .. 65535
+        if (any)
+            hipLaunchKernelGGL(k_prepare_frames<true>, dim3(g1, na), dim3(256), 0, v->stream, A, f0, C, Q, v->pimg, v->ptile, v->partial, v->state, seq,
+                               (const unsigned*)v->n_blocks, v->hstat_dev, K);
+        else
+            hipLaunchKernelGGL(k_prepare_frames<false>, dim3(g1, na), dim3(256), 0, v->stream, A, f0, C, Q, v->pimg, v->ptile, v->partial, v->state, seq,
+                               (const unsigned*)v->n_blocks, v->hstat_dev, KaNoArgs{});
     }
 }
 
@@ -837,6 +909,22 @@ void kb_trace_dump(op_volume* v) {
 #else
     (void)v;
 #endif
+#ifdef KA_TRACE
+    unsigned long long w[2] = {0, 0};
+    if (hipSetDevice(v->device) == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpyFromSymbol(w, HIP_SYMBOL(g_ka_waves), sizeof(w)) == hipSuccess)
+        fprintf(stderr, "KA_TRACE k_prepare_frames<true>: %llu wave passes over a pixel slot with a valid lane, %llu of them through the full sequence (%.3f %%)\n", w[0], w[1],
+                w[0] ? 100.0 * (double)w[1] / (double)w[0] : 0.0);
+#endif
 }
 
 } // namespace opv
+
+#ifdef KA_TRACE
+// development builds only (no declaration in onepiece_hip.h): the two counters of KA_COUNT since the last reset
+extern "C" __attribute__((visibility("default"))) int op_debug_ka_trace(unsigned long long out[2], int reset) {
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ka_waves), 16) != hipSuccess) return -1;
+    const unsigned long long zero[2] = {0, 0};
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_ka_waves), zero, 16) != hipSuccess) return -1;
+    return 0;
+}
+#endif

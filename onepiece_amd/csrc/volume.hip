@@ -788,6 +788,20 @@ int op_frustum_planes(const op_camera* cam, const float pose[16], float far_dist
     return OP_OK;
 }
 
+int op_debug_ka_certificate(const op_camera* cam, const float pose[16], float far_dist, float near_dist, int32_t rect[4], float z[2], int32_t quot[3]) {
+    OP_TRY(check_cam(cam));
+    if (!pose || !rect || !z || !quot) return fail(OP_ERR_INVALID, "null argument");
+    op_host::CameraPOD c{cam->fx, cam->fy, cam->cx, cam->cy, cam->width, cam->height, cam->depth_scale};
+    float planes[24];
+    op_host::frustum_planes(c, pose, far_dist, near_dist, planes);
+    const KaCam Q = ka_cam(cam->fx, cam->fy, cam->depth_scale);
+    const KaCert T = ka_certificate(pose, planes, cam->fx, cam->fy, cam->cx, cam->cy, cam->width, cam->height, Q);
+    rect[0] = T.j_lo; rect[1] = T.j_hi; rect[2] = T.i_lo; rect[3] = T.i_hi;
+    z[0] = T.z_lo; z[1] = T.z_hi;
+    quot[0] = Q.qx.ok; quot[1] = Q.qy.ok; quot[2] = Q.qd.ok && Q.qd.lo <= 0 && Q.qd.hi >= 15;
+    return OP_OK;
+}
+
 int op_frustum_from_camera(const op_camera* cam, const float pose[16], float far_dist, float near_dist, float planes[24], float corners[24]) {
     OP_TRY(check_cam(cam));
     if (!pose || !planes) return fail(OP_ERR_INVALID, "null argument");

@@ -26,6 +26,7 @@
 #include <type_traits>
 #include "host_math.hpp"
 #include "px_round.hpp"
+#include "ka_cert.hpp"
 
 namespace opv {
 
@@ -104,6 +105,10 @@ struct PoseFwd { float pose[16]; float planes[24]; }; // planes: top, left, righ
 struct PoseInv { float m[12]; };                      // rows 0..2 of pose^-1
 struct BatchFwd { PoseFwd f[kMaxBatch]; };
 struct KaFwd { PoseFwd f[kKaFrames]; };            // the slice of a BatchFwd one KA launch gets
+// ... and what its certified form (k_prepare_frames<true>, ka_cert.hpp) gets on top: the frames' in-frustum certificates, the reciprocals of
+// fx, fy, depth_scale and whether 16-bit depths take the short quotient.  With KaFwd, CamParams and BatchPtrs about 3.7 KB of kernel arguments.
+struct KaArgs { KaCert c[kKaFrames]; float yx, yy, yd; int use_d; };
+static_assert(sizeof(KaArgs) == 24 * kKaFrames + 16, "six words per frame");
 struct BatchInv { PoseInv f[kMaxBatch]; };
 struct BatchPtrs { const void* depth[kMaxBatch]; const unsigned char* rgb[kMaxBatch]; }; // device images of each frame
 

@@ -10,7 +10,8 @@ replaced by their distance in instructions.
 
 A kernel template that has gained ONE trailing template parameter (k_integrate's SIGNED) is matched too: an old instantiation without
 a namesake in the new files is compared with the new one that carries its arguments plus one more, the false / zero one where several
-do (the parameter's default).  Of a kernel that differs the differing lines are printed, and whether they differ in immediate operands
+do (the parameter's default); so is a kernel that was no template and has become one with a single parameter (k_prepare_frames' KAFAST).
+Of a kernel that differs the differing lines are printed, and whether they differ in immediate operands
 only (an explicit kernel argument more moves the implicit ones behind it).  Every kernel is listed with the registers and the scratch
 its metadata states: (VGPRs, SGPRs, scratch bytes)."""
 import difflib
@@ -89,9 +90,12 @@ def load(paths):
 
 def one_more_argument(k, new):
     """the new kernel that carries k's template arguments and one more (its default: false / zero where there is a choice)"""
-    if not k.endswith("E") or "I" not in k:
-        return None
-    c = sorted(n for n in new if re.fullmatch(re.escape(k[:-1]) + r"L[bij][0-9]+EE", n))
+    if not re.search(r"I(?:L[bij][0-9]+E)+E$", k):
+        # no mangled template-argument group behind the name (key() appends it): a kernel that was no template and has become one with a
+        # single parameter (k_prepare_frames' KAFAST)
+        c = sorted(n for n in new if re.fullmatch(re.escape(k) + r"IL[bij][0-9]+EE", n))
+    else:
+        c = sorted(n for n in new if re.fullmatch(re.escape(k[:-1]) + r"L[bij][0-9]+EE", n))
     zero = [n for n in c if re.search(r"L[bij]0EE$", n)]
     return (zero or c or [None])[0]
 
