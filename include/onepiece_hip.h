@@ -228,6 +228,18 @@ int op_debug_ka_certificate(const op_camera *cam, const float pose[16], float fa
  * must then lie inside the stack.  Runs on device 0. */
 int op_debug_gather2d(const unsigned *images, int width, int height, int n_frames, int frame, int column_test, const int *uv,
                       long long n, unsigned *out);
+/* Test hook (host): the rows of one tile of the sequential-sum kernels (csrc/seq_sums.hip kSeqRows); the tests derive their sizes from it. */
+int op_debug_seq_tile_rows(void);
+/* Test hook (device): the in-order float32 sums of the reference-order modes (csrc/seq_sums.hip k_seq_sums) over rows the caller makes up.
+ * layout 0 / 1 / 2 = one row {J[6], r} per item / two such rows per item / two values per item, summed as they are (7, 14, 2 floats per
+ * item; 42, 42, 2 sums).  All n_uploaded items of the host array `rows` go to the device, the first n_items <= n_uploaded <= 2^24 of them
+ * are summed through the production object (SeqSums::run, one workgroup on a stream of its own); rows may be NULL only when both counts
+ * are 0.  out: the sums, then n_items as an unsigned word.  OP_ERR_NO_DEVICE where the device cannot run the kernel.  Runs on device 0. */
+int op_debug_seq_sums(int layout, const float *rows, unsigned n_uploaded, unsigned n_items, float *out);
+/* Test hook (device): k problems of that layout, 1 <= k <= 32, in ONE launch of k_seq_sums_many, a workgroup each (what a meeting of
+ * reference-order contexts launches).  rows[i]: host array of n_items[i] <= 2^24 items, may be NULL when n_items[i] is 0.
+ * out: k x {the sums, n_items[i]}.  Runs on device 0. */
+int op_debug_seq_sums_many(int layout, const float *const *rows, const unsigned *n_items, int k, float *out);
 /* geometry::Se3ToSE3 (Geometry/Geometry.cpp:9-13). */
 int op_se3_exp(const float x[6], float T[16]);
 

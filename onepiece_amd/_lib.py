@@ -125,6 +125,9 @@ SIGNATURES = {
     "op_debug_px_rcp_err": (C.c_double, []),
     "op_debug_ka_certificate": (C.c_int, [C.POINTER(Camera), _fp, C.c_float, C.c_float, _vp, _fp, _vp]),
     "op_debug_gather2d": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, _vp]),
+    "op_debug_seq_tile_rows": (C.c_int, []),
+    "op_debug_seq_sums": (C.c_int, [C.c_int, _vp, C.c_uint, C.c_uint, _vp]),
+    "op_debug_seq_sums_many": (C.c_int, [C.c_int, _vp, _vp, C.c_int, _vp]),
     "op_volume_create": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_int, C.c_uint64, C.POINTER(_vp)]),
     "op_volume_destroy": (C.c_int, [_vp]),

@@ -266,3 +266,77 @@ hipError_t SeqSums::run(SeqLayout layout, const float* rows, const unsigned* n_r
     if (e == hipSuccess) e = hipMemcpyAsync(host, out, (seq_nacc(layout) + 1) * sizeof(float), hipMemcpyDeviceToHost, stream);
     return e == hipSuccess ? hipStreamSynchronize(stream) : e;
 }
+
+// ---- test hooks: the kernel on rows the caller makes up (see op_debug_seq_sums) -------------------------------------------------------------------------------------
+namespace {
+constexpr unsigned kSeqDebugMaxItems = 1u << 24;
+constexpr size_t seq_item_floats(int layout) { return layout == kSeqOneRow ? 7 : layout == kSeqTwoRows ? 14 : 2; }
+} // namespace
+
+extern "C" {
+
+int op_debug_seq_tile_rows(void) { return kSeqRows; }
+
+int op_debug_seq_sums(int layout, const float* rows, unsigned n_uploaded, unsigned n_items, float* out) {
+    if (layout < kSeqOneRow || layout > kSeqTwoValues) return op::fail(OP_ERR_INVALID, "op_debug_seq_sums: layout must be 0, 1 or 2");
+    if (!out || (!rows && n_uploaded)) return op::fail(OP_ERR_INVALID, "null argument");
+    if (n_items > n_uploaded || n_uploaded > kSeqDebugMaxItems) return op::fail(OP_ERR_INVALID, "op_debug_seq_sums: n_items <= n_uploaded <= 2^24");
+    OP_TRY(op::use_device(0));
+    if (!seq_device_ok(0)) return op::fail(OP_ERR_NO_DEVICE, "op_debug_seq_sums: the device cannot run k_seq_sums (dynamic LDS)");
+    const SeqLayout l = (SeqLayout)layout;
+    const size_t bytes = (size_t)n_uploaded * seq_item_floats(layout) * sizeof(float);
+    float* d = nullptr;      // all n_uploaded items; stays null without any: the kernel may not touch the rows of an empty problem
+    hipStream_t s = nullptr;
+    SeqSums sums;
+    hipError_t e = bytes ? op::cached_malloc((void**)&d, bytes) : hipSuccess;
+    if (e == hipSuccess && bytes) e = hipMemcpy(d, rows, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = op::cached_stream(&s);
+    if (e == hipSuccess) e = sums.reserve(0, false);
+    if (e == hipSuccess) e = sums.run(l, d, &n_items, s, nullptr);
+    if (e == hipSuccess) std::memcpy(out, sums.host, (seq_nacc(l) + 1) * sizeof(float));
+    if (s) { (void)hipStreamSynchronize(s); op::release_stream(s, 0); }
+    sums.release(0);
+    op::cached_free(d);
+    if (e != hipSuccess) return op::fail(OP_ERR_HIP, "op_debug_seq_sums failed: %s", hipGetErrorString(e));
+    return OP_OK;
+}
+
+int op_debug_seq_sums_many(int layout, const float* const* rows, const unsigned* n_items, int k, float* out) {
+    if (layout < kSeqOneRow || layout > kSeqTwoValues) return op::fail(OP_ERR_INVALID, "op_debug_seq_sums_many: layout must be 0, 1 or 2");
+    if (k < 1 || k > kSeqBatchMax) return op::fail(OP_ERR_INVALID, "op_debug_seq_sums_many: 1 <= k <= %d", kSeqBatchMax);
+    if (!rows || !n_items || !out) return op::fail(OP_ERR_INVALID, "null argument");
+    const size_t nf = seq_item_floats(layout), words = (size_t)seq_nacc((SeqLayout)layout) + 1;
+    size_t start[kSeqBatchMax], total = 0; // every problem's rows begin on a 256-byte boundary of one buffer
+    for (int i = 0; i < k; ++i) {
+        if (n_items[i] > kSeqDebugMaxItems || (!rows[i] && n_items[i])) return op::fail(OP_ERR_INVALID, "op_debug_seq_sums_many: problem %d: null rows or more than 2^24 items", i);
+        start[i] = total;
+        total += ((size_t)n_items[i] * nf + 63) / 64 * 64;
+    }
+    OP_TRY(op::use_device(0));
+    if (!seq_device_ok(0)) return op::fail(OP_ERR_NO_DEVICE, "op_debug_seq_sums_many: the device cannot run k_seq_sums_many (dynamic LDS)");
+    float* d_rows = nullptr;
+    float* d_out = nullptr;  // k x 64 words
+    unsigned* d_n = nullptr;
+    hipStream_t s = nullptr;
+    hipError_t e = total ? op::cached_malloc((void**)&d_rows, total * sizeof(float)) : hipSuccess;
+    if (e == hipSuccess) e = op::cached_malloc((void**)&d_out, (size_t)k * 64 * sizeof(float));
+    if (e == hipSuccess) e = op::cached_malloc((void**)&d_n, (size_t)k * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemcpy(d_n, n_items, (size_t)k * sizeof(unsigned), hipMemcpyHostToDevice);
+    SeqBatchTable t{};
+    for (int i = 0; i < k && e == hipSuccess; ++i) {
+        if (n_items[i]) e = hipMemcpy(d_rows + start[i], rows[i], (size_t)n_items[i] * nf * sizeof(float), hipMemcpyHostToDevice);
+        t.rows[i] = n_items[i] ? d_rows + start[i] : nullptr; t.n_pix[i] = d_n + i; t.out[i] = d_out + (size_t)i * 64;
+    }
+    if (e == hipSuccess) e = op::cached_stream(&s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kSeqKernels[layout].many, dim3((unsigned)k), dim3(kSeqThreads), kSeqKernels[layout].lds, s, t); // as SeqRendezvous::flush_locked does
+        e = hipGetLastError();
+    }
+    for (int i = 0; i < k && e == hipSuccess; ++i) e = hipMemcpyAsync(out + (size_t)i * words, d_out + (size_t)i * 64, words * sizeof(float), hipMemcpyDeviceToHost, s);
+    if (s) { const hipError_t es = hipStreamSynchronize(s); if (e == hipSuccess) e = es; op::release_stream(s, 0); }
+    op::cached_free(d_rows); op::cached_free(d_out); op::cached_free(d_n);
+    if (e != hipSuccess) return op::fail(OP_ERR_HIP, "op_debug_seq_sums_many failed: %s", hipGetErrorString(e));
+    return OP_OK;
+}
+
+} // extern "C"

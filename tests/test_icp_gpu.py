@@ -777,6 +777,32 @@ def test_run_many_where_the_reference_order_contexts_meet_gives_every_context_th
             lib.op_icp_destroy(h)
 
 
+def test_run_many_with_more_reference_order_contexts_than_one_launch_holds_gives_every_context_the_result_it_gets_alone(hip):
+    """34 reference-order contexts (one of them with an empty source) and two fp64-mode ones in one op_icp_run_many call: a k_seq_sums_many launch holds 32
+    problems (seq_sums.hpp kSeqBatchMax), so a round's batch fills and is launched before everybody has arrived, and the late arrivals are served with the
+    early ones of the next round or by the waiters' safety valve.  Who sums with whom must not matter: two repetitions, every entry bit-equal to op_icp_run
+    on the same context alone."""
+    import ctypes as C
+    from onepiece_amd import _lib as L
+    lib = L.load()
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    ctxs = []
+    try:
+        ctxs, alone, T0s, modes = _meeting_contexts(lib, L, 800, n_ref=34, n_fp64=2)
+        K = len(ctxs)
+        assert K == 36 and sum(m == L.OP_ICP_SUMS_REFERENCE_F32 for m in modes) == 34 and alone[1].n_inliers == 0
+        assert all(alone[k].n_inliers > 5000 and alone[k].iterations == 10 for k in range(K) if k != 1)
+        arr = (C.c_void_p * K)(*[c.value for c in ctxs])
+        for rep in range(2):
+            many = (L.IcpResult * K)()
+            L.check(lib.op_icp_run_many(arr, K, 1, fp(T0s), 10, C.cast(many, C.c_void_p)))
+            for k in range(K):
+                assert _same_result(many[k], alone[k]), (rep, k)
+    finally:
+        for h in ctxs:
+            lib.op_icp_destroy(h)
+
+
 def test_two_run_many_calls_at_the_same_time_each_give_their_sequential_results(hip):
     """Two op_icp_run_many calls of ten reference-order contexts (+ two fp64-mode ones) each, from two threads at the same time on one device: what the
     other call does must not change a result -- both bit-equal to op_icp_run on every context alone."""
