@@ -33,6 +33,7 @@
 #include "Integration/Integrator.h"
 #include "Integration/MarchingCube.h"
 #include "Integration/VoxelCube.h"
+#include "Registration/RegistrationResult.h"
 
 #define TRUNCATED_DISTANCES 1.0
 
@@ -171,6 +172,19 @@ class CubeHandler {
     void SampleGradients(const geometry::Point3List& points, geometry::Point3List& gradients, std::vector<uint8_t>& status,
                          const geometry::TransformationMatrix& T = geometry::TransformationMatrix::Identity());
     op_volume_sample_stats DistanceToModel(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& pose = geometry::TransformationMatrix::Identity());
+    // EXTENSIONS (not in the reference, which registers clouds against clouds by a kd-tree ICP): where a cloud or a depth frame belongs in the
+    // model, by point-to-plane Gauss-Newton against the field itself -- the trilinear sdf is the residual, its normalised gradient the normal
+    // (op_volume_register_points states the definition).  Returned like registration::PointToPlane's result: T (cloud to model / the refined
+    // camera-to-world pose) and rmse at T; the correspondence sets stay empty (there are no pairs).  params == nullptr: the defaults (30 iterations,
+    // max_distance = the truncation, min_step 1e-5, min_points 6); details (status, counts, iterations) go to *details when it is given.
+    //   RegistrationSystem  one evaluation at T: sums[28] = the upper triangle of JtJ row by row, Jtr, the sum of s^2; counts[4] = used, invalid,
+    //                       no_gradient, too_far.  false when the call failed.
+    std::shared_ptr<registration::RegistrationResult> RegisterPointCloud(const geometry::PointCloud& pcd,
+                                                                         const geometry::TransformationMatrix& init = geometry::TransformationMatrix::Identity(),
+                                                                         const op_volume_register_params* params = nullptr, op_volume_register_result* details = nullptr);
+    std::shared_ptr<registration::RegistrationResult> RegisterDepth(const cv::Mat& depth, const geometry::TransformationMatrix& init_pose, int pixel_stride = 1,
+                                                                    const op_volume_register_params* params = nullptr, op_volume_register_result* details = nullptr);
+    bool RegistrationSystem(const geometry::Point3List& points, const geometry::TransformationMatrix& T, float max_distance, double sums[28], uint64_t counts[4]);
     void GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh);
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;

@@ -487,6 +487,70 @@ void CubeHandler::SampleGradients(const geometry::Point3List& points, geometry::
     }
     ReleaseBorrowed();
 }
+namespace {
+std::shared_ptr<registration::RegistrationResult> RegistrationOutcome(const op_volume_register_result& r) {
+    registration::RegistrationResult result;
+    for (int i = 0; i < 4; ++i)
+        for (int k = 0; k < 4; ++k) result.T(i, k) = r.T[4 * i + k];
+    result.rmse = r.rmse;
+    return std::make_shared<registration::RegistrationResult>(std::move(result));
+}
+op_volume_register_result RegistrationNotRun(const geometry::TransformationMatrix& init) {
+    op_volume_register_result r = op_volume_register_result();
+    bridge::RowMajor(init, r.T);
+    r.status = OP_REGISTER_TOO_FEW_POINTS;
+    return r;
+}
+} // namespace
+std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterPointCloud(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& init,
+                                                                                  const op_volume_register_params* params, op_volume_register_result* details) {
+    Pending();
+    op_volume_register_result r = RegistrationNotRun(init);
+    if (Ensure()) {
+        float t[16];
+        bridge::RowMajor(init, t);
+        if (op_volume_register_points(vol, bridge::Floats(pcd.points), pcd.points.size(), OP_MEM_HOST, t, params, &r) != OP_OK) {
+            Report("RegisterPointCloud");
+            r = RegistrationNotRun(init);
+        } else {
+            ReleaseBorrowed(); // (the call synchronised the volume)
+        }
+    }
+    if (details) *details = r;
+    return RegistrationOutcome(r);
+}
+std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterDepth(const cv::Mat& depth, const geometry::TransformationMatrix& init_pose, int pixel_stride,
+                                                                             const op_volume_register_params* params, op_volume_register_result* details) {
+    Pending();
+    op_volume_register_result r = RegistrationNotRun(init_pose);
+    if (Ensure()) {
+        float t[16];
+        bridge::RowMajor(init_pose, t);
+        const op_camera pod = camera.Pod();
+        if (op_volume_register_depth(vol, &pod, depth.data, bridge::DepthFormat(depth), OP_MEM_HOST, pixel_stride, t, params, &r) != OP_OK) {
+            Report("RegisterDepth");
+            r = RegistrationNotRun(init_pose);
+        } else {
+            ReleaseBorrowed();
+        }
+    }
+    if (details) *details = r;
+    return RegistrationOutcome(r);
+}
+bool CubeHandler::RegistrationSystem(const geometry::Point3List& points, const geometry::TransformationMatrix& T, float max_distance, double sums[28], uint64_t counts[4]) {
+    Pending();
+    for (int k = 0; k < 28; ++k) sums[k] = 0.0;
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    if (!Ensure()) return false;
+    float t[16];
+    bridge::RowMajor(T, t);
+    if (op_volume_register_system(vol, bridge::Floats(points), points.size(), OP_MEM_HOST, t, max_distance, sums, counts, nullptr) != OP_OK) {
+        Report("RegistrationSystem");
+        return false;
+    }
+    ReleaseBorrowed();
+    return true;
+}
 op_volume_sample_stats CubeHandler::DistanceToModel(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& pose) {
     Pending();
     op_volume_sample_stats st = {0, 0, 0, 0, 0.0, 0.0, 0.0f};

@@ -554,6 +554,61 @@ int op_volume_sample(op_volume *v, const float *xyz, size_t n, int mem, const fl
                      float *voxels /* n x 5 {sdf, weight, c0, c1, c2} or NULL */, float *gradients /* n x 3 or NULL */,
                      uint8_t *status /* n or NULL */, op_volume_sample_stats *stats /* host, or NULL */);
 
+/* Where a cloud or a depth frame belongs in the model: point-to-plane registration against the FIELD (csrc/volume_register.hip; NO reference
+ * counterpart -- the reference registers clouds against clouds by a kd-tree ICP).  At a point the trilinear sdf is the residual and the normalised
+ * central difference the plane normal; no target cloud, no normals, no neighbour search.  Every per-point operation below is float32 and rounded
+ * separately; nothing is contracted.  For point x_i and a row-major T (16 floats, host memory):
+ *   1. p = T x in TransformPoints' order with the divide by q.w: exactly op_volume_sample's "query point".
+ *   2. s and the status bits are OP_SAMPLE_TRILINEAR's at p (sdf only); d is its gradient (six more samples at +-h, h = 0.5f * res, unnormalised;
+ *      NO_GRADIENT if any of the six is invalid).  OUT_OF_RANGE is decided by the same explicit compare and implies INVALID.
+ *   3. l2 = d0 d0 + (d1 d1 + d2 d2) (the raycaster's normal rule).
+ *   4. The point is USED iff INVALID is not set, NO_GRADIENT is not set, l2 > 0, and fabsf(s) <= max_distance (false for NaN; max_distance <= 0:
+ *      no gate; metres, as the volume stores sdf).
+ *   5. n_a = d_a / sqrtf(l2).
+ *   6. The row is j = (n0, n1, n2, p1 n2 - p2 n1, p2 n0 - p0 n2, p0 n1 - p1 n0): registration::PointToPlane's row (ICP.cpp:121-136) with the
+ *      transformed point in place of the transformed source point and the field's normal in place of the target's.
+ *   7. A used point contributes 28 terms, an unused one nothing: sums[0..20] += (double)(j_a j_b) for a <= b, row by row (the product is float32,
+ *      then widened, as ICP does); sums[21..26] += (double)(s j_a); sums[27] += (double)s * (double)s.
+ *   8. counts = {used, invalid, no_gradient, too_far}: every rejected point is counted once, under the first reason in this order -- invalid:
+ *      INVALID is set; no_gradient: NO_GRADIENT is set or l2 > 0 does not hold, on an otherwise valid sample; too_far: gated by max_distance alone.
+ *   9. The sums are taken in double.  Every wave reduces its 64 points' 32 slots (the 28 sums, the 4 counts as doubles) per trip of the grid-stride
+ *      loop and adds the trips in order; a workgroup adds its four waves in order and writes one row; a second kernel adds the rows (at most 1024)
+ *      in index order -- row r, r + 32, ... per row lane, then the 32 row lanes in order.  The order is fixed for a given n: two calls give the
+ *      same bits.  No floating-point atomics.
+ * op_volume_register_system evaluates this once: sums[28], counts[4] (host; counts may be NULL) and optionally rows: n x 8 floats in `mem`,
+ * {j[6], s, 1.0f} for a used point and eight zeros for an unused one.  The sums are the same bits with and without rows.
+ * op_volume_register_points runs Gauss-Newton on the host around it:
+ *   T = init_T; for each of at most max_iterations iterations: evaluate the system at T; used < min_points -> stop, OP_REGISTER_TOO_FEW_POINTS;
+ *   x = op_ldlt_solve6(JTJ, JTr) (JTJ.ldlt().solve(-JTr), JTJ the symmetric 6 x 6 of sums[0..20], JTr = sums[21..26]); a non-finite component of
+ *   x -> stop, OP_REGISTER_SINGULAR; T <- op_se3_exp(x) T, the 4 x 4 product in float32, each element ((a0 b0 + a1 b1) + a2 b2) + a3 b3;
+ *   iterations counts the updates; last_step = sqrt(sum (double)x_a^2); sum (double)x_a^2 < (double)min_step * (double)min_step -> stop,
+ *   OP_REGISTER_CONVERGED; after max_iterations updates: OP_REGISTER_MAX_ITERATIONS.
+ *   After the loop the system is evaluated at the returned T: used, invalid, no_gradient, too_far and rmse = sqrt(sums[27] / used) (0 when used
+ *   is 0) describe the pose that is returned; first_used / first_rmse are the same at init_T.  max_iterations == 0: T = init_T, one evaluation,
+ *   OP_REGISTER_TOO_FEW_POINTS if used < min_points and OP_REGISTER_MAX_ITERATIONS otherwise.
+ *   Defaults (params == NULL, op_volume_register_default_params): max_iterations 30 (ICPParameter's), max_distance = the volume's truncation,
+ *   min_step 1e-5, min_points 6.  A host cloud is uploaded once; every iteration runs on the volume's stream and brings back one folded row.
+ * op_volume_register_depth back-projects the depth image once on the device by op_points_from_depth's definition (PointCloud::LoadFromDepth), keeping
+ * every pixel_stride-th pixel in both directions (rows 0, stride, ...; columns likewise) in row-major order and skipping pixels without depth, into
+ * a buffer the volume owns, then runs the same loop with init_pose (camera to world) as init_T: its result is, bit for bit, op_volume_register_points
+ * on those points.  cam == NULL: the volume's camera.
+ * Like every accessor the calls see all frames accepted before them (the queue is flushed first) and only read the volume.  The argument checks
+ * run before any device use; OP_ERR_INVALID: a NULL volume, result, sums, T / init_T / init_pose or depth, a NULL xyz with n > 0, a bad mem or
+ * depth format, pixel_stride < 1, max_iterations < 0.  n == 0 or an empty volume is no error: zero sums, used = 0, OP_REGISTER_TOO_FEW_POINTS
+ * (with min_points > 0), T = init_T. */
+typedef struct { int max_iterations; float max_distance, min_step; int min_points; } op_volume_register_params;
+typedef struct { float T[16]; int iterations, status; uint64_t used, invalid, no_gradient, too_far, first_used;
+                 double rmse, first_rmse, last_step; } op_volume_register_result;
+enum { OP_REGISTER_CONVERGED = 0, OP_REGISTER_MAX_ITERATIONS = 1, OP_REGISTER_TOO_FEW_POINTS = 2, OP_REGISTER_SINGULAR = 3 };
+int op_volume_register_default_params(op_volume *v, op_volume_register_params *p);
+int op_volume_register_system(op_volume *v, const float *xyz, size_t n, int mem, const float T[16], float max_distance,
+                              double sums[28], uint64_t counts[4], float *rows /* n x 8 in `mem`, or NULL */);
+int op_volume_register_points(op_volume *v, const float *xyz, size_t n, int mem, const float init_T[16],
+                              const op_volume_register_params *params /* NULL: defaults */, op_volume_register_result *result);
+int op_volume_register_depth(op_volume *v, const op_camera *cam /* NULL: the volume's */, const void *depth, int depth_fmt, int mem,
+                             int pixel_stride, const float init_pose[16], const op_volume_register_params *params,
+                             op_volume_register_result *result);
+
 /* Frame-sharded multi-GPU merge (the distributed form of CubeHandler::Merge; DESIGN.md "Multi-GPU").
  * All pointers are DEVICE pointers on the volume's device.
  *   keys_device : copy this volume's block keys (n x 3 int32) into d_keys.

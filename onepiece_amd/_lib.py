@@ -46,6 +46,18 @@ class SampleStats(C.Structure):
                [("sum_abs_sdf", C.c_double), ("sum_sq_sdf", C.c_double), ("max_abs_sdf", C.c_float)]
 
 
+class RegisterParams(C.Structure):
+    """op_volume_register_params of op_volume_register_points / _depth."""
+    _fields_ = [("max_iterations", C.c_int32), ("max_distance", C.c_float), ("min_step", C.c_float), ("min_points", C.c_int32)]
+
+
+class RegisterResult(C.Structure):
+    """op_volume_register_result of op_volume_register_points / _depth."""
+    _fields_ = [("T", C.c_float * 16), ("iterations", C.c_int32), ("status", C.c_int32)] + \
+               [(k, C.c_uint64) for k in ("used", "invalid", "no_gradient", "too_far", "first_used")] + \
+               [(k, C.c_double) for k in ("rmse", "first_rmse", "last_step")]
+
+
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("last_T", C.c_float * 16), ("rmse", C.c_double),
                 ("n_inliers", C.c_uint64), ("iterations", C.c_int32)]
@@ -72,6 +84,7 @@ OP_VOLUME_OPT_SELECT, OP_VOLUME_SELECT_AUTO, OP_VOLUME_SELECT_DIRECT = 1, 0, -1
 OP_VOLUME_OPT_RAYCAST_PRUNE = 2
 OP_SAMPLE_TRILINEAR, OP_SAMPLE_REFERENCE = 0, 1
 OP_SAMPLE_INVALID, OP_SAMPLE_NO_GRADIENT, OP_SAMPLE_OUT_OF_RANGE = 1, 2, 4
+OP_REGISTER_CONVERGED, OP_REGISTER_MAX_ITERATIONS, OP_REGISTER_TOO_FEW_POINTS, OP_REGISTER_SINGULAR = 0, 1, 2, 3
 OP_RUNTIME_OPT_MERGE_ALGORITHM, OP_RUNTIME_OPT_MERGE_SLICE_BLOCKS, OP_RUNTIME_OPT_MERGE_FORCE_SINGLE_RANK, OP_RUNTIME_OPT_TRACKER_GRAPH, OP_RUNTIME_OPT_COPY_THREADS, OP_RUNTIME_OPT_CACHE_DEVICE_BYTES, OP_RUNTIME_OPT_MERGE_FAULT, OP_RUNTIME_OPT_ICP_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_DEFAULT_SUMS, OP_RUNTIME_OPT_TRACKER_BATCH_SUMS, OP_RUNTIME_OPT_ICP_MANY_IN_FLIGHT, OP_RUNTIME_OPT_GLOBAL_REGISTRATION = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE = 12
 OP_RUNTIME_OPT_MESH_CLUSTERING = 13
@@ -175,6 +188,10 @@ SIGNATURES = {
     "op_volume_raycast_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "op_volume_render_frame": (C.c_int, [_vp, C.POINTER(Camera), _fp, _vp, _fp, C.c_int, C.POINTER(C.c_uint64)]),
     "op_volume_sample": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp, C.c_int, _vp, _vp, _vp, C.POINTER(SampleStats)]),
+    "op_volume_register_default_params": (C.c_int, [_vp, C.POINTER(RegisterParams)]),
+    "op_volume_register_system": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp, C.c_float, C.POINTER(C.c_double), _u64p, _vp]),
+    "op_volume_register_points": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp, C.POINTER(RegisterParams), C.POINTER(RegisterResult)]),
+    "op_volume_register_depth": (C.c_int, [_vp, C.POINTER(Camera), _vp, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(RegisterParams), C.POINTER(RegisterResult)]),
     "op_volume_keys_device": (C.c_int, [_vp, _vp, C.c_size_t, _szp]),
     "op_volume_pack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "op_volume_unpack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

@@ -1,7 +1,8 @@
 // trilinear_sample.hpp -- the raycaster's strict trilinear sample (include/onepiece_hip.h, op_volume_raycast: "sample"), shared by the raycaster
-// (raycast.hip: the LDS march, its rare previous-sample lookups, the shading pass) and the point queries (volume_sample.hip: OP_SAMPLE_TRILINEAR
-// and its gradient).  One copy of the arithmetic: same operations, same order, every product and sum rounded separately.
-// `View` is whatever carries inv_res = 1.0f / res (the raycaster's RcView, the point queries' SampleView).
+// (raycast.hip: the LDS march, its rare previous-sample lookups, the shading pass), the point queries (volume_sample.hip: OP_SAMPLE_TRILINEAR
+// and its gradient) and the registration against the field (volume_register.hip: residual and normal).  One copy of the arithmetic: same
+// operations, same order, every product and sum rounded separately.
+// `View` is whatever carries inv_res = 1.0f / res (the raycaster's RcView, the point queries' SampleView, the registration's RegView).
 #pragma once
 #include "volume_core.hpp"
 
@@ -22,6 +23,13 @@ __device__ __forceinline__ float rc_weight(const RcCell& c, int k) {
 }
 
 struct BlockCache { int cx, cy, cz, idx; }; // a lane's last block: id -> pool slot (< 0: absent)
+
+// the point queries' range rule (volume_sample.hip, volume_register.hip): decided before any conversion to int
+constexpr float kSampleLimit = 8388600.0f; // |g| below this: floor(g) and floor(g) + 1 convert exactly and their block ids lie inside kCoordLimit
+static_assert((8388600 + 1) / 8 < kCoordLimit, "taps -8388600 .. 8388601: every block id of an in-range sample is a legal one");
+__device__ __forceinline__ bool sample_in_range(float g0, float g1, float g2) { // false for NaN
+    return fabsf(g0) < kSampleLimit && fabsf(g1) < kSampleLimit && fabsf(g2) < kSampleLimit;
+}
 
 // trilinear sample through the hash (the march's rare previous-sample lookups, k_rc_finish, the point queries): false = not all 8 voxels observed
 // (a tap in no held block, or of weight <= 0 or NaN)

@@ -536,6 +536,8 @@ struct op_volume {
     float* rf_col = nullptr;      // raycast.hip, the frame renderer: the float colours of the view being packed into bytes (rf_cap pixels) and the public entry's count of valid pixels
     size_t rf_cap = 0;
     unsigned long long* rf_count = nullptr;
+    float* reg_pts = nullptr;     // volume_register.hip: the back-projected points of the depth frame being registered (reg_cap points)
+    size_t reg_cap = 0;
     int* unpack_slots = nullptr; // table slots of the union keys between op_volume_unpack_sum_begin and its chunks
     size_t unpack_n = 0;
     uint64_t generation = 0, unpack_gen = 0; // bumped by whatever moves or drops table slots (growth, clear) or fuses frames; _chunk checks it

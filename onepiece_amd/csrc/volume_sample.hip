@@ -10,7 +10,7 @@
 // call's statistics in registers; a workgroup reduces them (wave shuffles, then LDS) into ONE row and the host adds the rows in index order -- no
 // floating-point atomics, the sums are repeatable for a given n.
 // Not built: re-ordering the queries by block on the device, a block-major LDS-tile form, a nearest-voxel mode,
-// projection onto the surface, registration against the field.
+// projection onto the surface.  (Registration against the field is volume_register.hip.)
 #include "volume_core.hpp"
 #include "trilinear_sample.hpp"
 #include "voxel_interp.hpp"
@@ -19,8 +19,6 @@ namespace {
 
 constexpr int kSampleWg = 256;
 constexpr unsigned kSampleMaxGrid = 1024; // rows of statistics the host adds: 4 workgroups per CU
-constexpr float kSampleLimit = 8388600.0f; // |g| below this: floor(g) and floor(g) + 1 convert exactly and their block ids lie inside kCoordLimit
-static_assert((8388600 + 1) / 8 < kCoordLimit, "taps -8388600 .. 8388601: every block id of an in-range sample is a legal one");
 
 struct SampleRow { unsigned long long valid, gradients, out_of_range; double sum_abs, sum_sq; float max_abs; unsigned pad; };
 static_assert(sizeof(SampleRow) == 48, "six 8-byte words");
@@ -38,10 +36,6 @@ struct SampleArgs {
     unsigned char* status;
     SampleRow* rows;
 };
-
-__device__ __forceinline__ bool sample_in_range(float g0, float g1, float g2) { // false for NaN
-    return fabsf(g0) < kSampleLimit && fabsf(g1) < kSampleLimit && fabsf(g2) < kSampleLimit;
-}
 
 // the five planes of the trilinear sample of cell c (rc_sample_global with the weight plane accumulated as well): false = not all 8 voxels observed
 __device__ bool sample_voxel5(const VolView& V, const RcCell& c, BlockCache& bc, Vox5* out) {

@@ -595,6 +595,61 @@ class CubeHandler:
         self._alive = []
         return self._sample_stats(st) if stats else None
 
+    # -- registration against the field (extension; op_volume_register_*: the trilinear sdf is the residual, its normalised gradient the normal)
+    REGISTER_STATUS = ("converged", "max_iterations", "too_few_points", "singular")
+
+    def _register_params(self, max_iterations, max_distance, min_step, min_points):
+        p = L.RegisterParams()
+        L.check(self._lib.op_volume_register_default_params(self._h, C.byref(p)))
+        for k, val in (("max_iterations", max_iterations), ("max_distance", max_distance), ("min_step", min_step), ("min_points", min_points)):
+            if val is not None:
+                setattr(p, k, val)
+        return p
+
+    @staticmethod
+    def _register_result(r):
+        out = {k: getattr(r, k) for k, _t in L.RegisterResult._fields_ if k != "T"}
+        out["T"] = np.array(r.T, np.float32).reshape(4, 4)
+        out["status_name"] = CubeHandler.REGISTER_STATUS[r.status]
+        return out
+
+    def RegistrationSystem(self, points, T, max_distance, rows=False):
+        """The point-to-plane system of `points` ([n,3] float32, host) at the 4x4 `T` against the model (op_volume_register_system)
+        -> (sums [28] float64: the upper triangle of JtJ row by row, Jtr, sum of s^2; counts dict[, rows [n,8]: j[6], s, used])."""
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        n = len(pts)
+        Tm = _f32(T).reshape(16)
+        sums, counts = np.zeros(28, np.float64), np.zeros(4, np.uint64)
+        out = np.empty((n, 8), np.float32) if rows else None
+        L.check(self._lib.op_volume_register_system(self._h, C.c_void_p(pts.ctypes.data), n, L.OP_MEM_HOST, _fp(Tm), float(max_distance),
+                                                    sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(L._u64p),
+                                                    C.c_void_p(out.ctypes.data) if rows else None))
+        self._alive = []
+        cd = dict(zip(("used", "invalid", "no_gradient", "too_far"), (int(c) for c in counts)))
+        return (sums, cd, out) if rows else (sums, cd)
+
+    def RegisterPoints(self, points, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None):
+        """Gauss-Newton registration of `points` ([n,3] float32, host) against the model from `init_T` (default identity) -> dict of
+        op_volume_register_result's fields (T [4,4]: points to model).  None = the default (30 iterations, the truncation, 1e-5, 6)."""
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        T0 = _f32(np.eye(4) if init_T is None else init_T).reshape(16)
+        p, r = self._register_params(max_iterations, max_distance, min_step, min_points), L.RegisterResult()
+        L.check(self._lib.op_volume_register_points(self._h, C.c_void_p(pts.ctypes.data), len(pts), L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(r)))
+        self._alive = []
+        return self._register_result(r)
+
+    def RegisterDepth(self, depth, init_pose, pixel_stride=1, camera=None, max_iterations=None, max_distance=None, min_step=None, min_points=None):
+        """The same for a depth image (numpy or CUDA torch tensor) back-projected on the device (every pixel_stride-th pixel in both directions)
+        from `init_pose` (camera to world) -> the result dict, T the refined pose."""
+        pd, fmt, mem, keep = _image_arg(depth, "depth")
+        pose = _f32(init_pose).reshape(16)
+        p, r = self._register_params(max_iterations, max_distance, min_step, min_points), L.RegisterResult()
+        L.check(self._lib.op_volume_register_depth(self._h, C.byref(camera) if camera is not None else None, pd, fmt, mem, int(pixel_stride), _fp(pose),
+                                                   C.byref(p), C.byref(r)))
+        del keep
+        self._alive = []
+        return self._register_result(r)
+
     def RaycastStats(self):
         """Measurement hook: what the last Raycast call did (op_volume_raycast_stats)."""
         v = [C.c_uint64(0) for _ in range(4)]
