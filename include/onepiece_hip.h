@@ -119,6 +119,10 @@ int op_runtime_hw_queues(int *requested);
  *                                         that example/GetLabelUsingKDTree.cpp writes.  1: they forward to op_nn_index_query / op_nn_index_transfer_labels (the same
  *                                         indices and distance bits), and fall back to the host loop for input the device entry refuses (OP_ERR_INVALID, OP_ERR_CAPACITY).
  *                                         Read through op_runtime_get_option like the five options above.
+ *   OP_RUNTIME_OPT_ALLOC_FAULT            TEST HOOK: k > 0 makes the k-th request to the library's buffer cache from now (device or pinned, process-wide) fail as if the
+ *                                         device were out of memory -- a host-side error return, before HIP or the cache is touched; once it has fired the option is 0
+ *                                         again (default; op_runtime_get_option reads it).  tests/test_scoped_buffers_gpu.py: every entry returns OP_ERR_HIP and leaves
+ *                                         nothing behind in the cache's live set (op_debug_cache_live)
  * op_runtime_set_rccl_library(path): the RCCL to bind at the first merge instead of "librccl.so.1" (a site build; the test suite names a
  *   host-memory double that runs several ranks on one device); NULL = the system's.  Fails once RCCL has been bound. */
 #define OP_RUNTIME_OPT_MERGE_ALGORITHM 0
@@ -138,10 +142,11 @@ int op_runtime_hw_queues(int *requested);
 #define OP_RUNTIME_OPT_MESH_POSTPROCESS 14
 #define OP_RUNTIME_OPT_COLOR_ALIGNMENT 15
 #define OP_RUNTIME_OPT_NEAREST_BATCH 16
+#define OP_RUNTIME_OPT_ALLOC_FAULT 17
 #define OP_MERGE_OWNER_EXCHANGE 0
 #define OP_MERGE_DENSE_REDUCE 1
 int op_runtime_set_option(int option, long long value);
-int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, OP_RUNTIME_OPT_MESH_CLUSTERING, OP_RUNTIME_OPT_MESH_POSTPROCESS, OP_RUNTIME_OPT_COLOR_ALIGNMENT and OP_RUNTIME_OPT_NEAREST_BATCH: the others are read inside the library */
+int op_runtime_get_option(int option, long long *value); /* OP_RUNTIME_OPT_GLOBAL_REGISTRATION, OP_RUNTIME_OPT_POINT_CLOUD_DOWNSAMPLE, OP_RUNTIME_OPT_MESH_CLUSTERING, OP_RUNTIME_OPT_MESH_POSTPROCESS, OP_RUNTIME_OPT_COLOR_ALIGNMENT, OP_RUNTIME_OPT_NEAREST_BATCH and OP_RUNTIME_OPT_ALLOC_FAULT: the others are read inside the library */
 int op_runtime_set_rccl_library(const char *path);
 /* Images that are used more than once -- a frame is tracked against twice and fused once (example/DenseFusion/DenseSlam.cpp:24-33,
  * DenseFusion.cpp:86-96) -- can be brought to the device ONCE and then handed to op_tracker_dense_tracking(_enqueue) /
@@ -230,6 +235,8 @@ int op_debug_gather2d(const unsigned *images, int width, int height, int n_frame
                       long long n, unsigned *out);
 /* Test hook (host): the rows of one tile of the sequential-sum kernels (csrc/seq_sums.hip kSeqRows); the tests derive their sizes from it. */
 int op_debug_seq_tile_rows(void);
+/* TEST HOOK: how many buffers of `device` the buffer cache has handed out and not got back (device memory, pinned host memory; either pointer may be NULL) */
+int op_debug_cache_live(int device, uint64_t *device_buffers, uint64_t *pinned_buffers);
 /* Test hook (device): the in-order float32 sums of the reference-order modes (csrc/seq_sums.hip k_seq_sums) over rows the caller makes up.
  * layout 0 / 1 / 2 = one row {J[6], r} per item / two such rows per item / two values per item, summed as they are (7, 14, 2 floats per
  * item; 42, 42, 2 sums).  All n_uploaded items of the host array `rows` go to the device, the first n_items <= n_uploaded <= 2^24 of them

@@ -91,6 +91,7 @@ OP_RUNTIME_OPT_MESH_CLUSTERING = 13
 OP_RUNTIME_OPT_MESH_POSTPROCESS = 14
 OP_RUNTIME_OPT_COLOR_ALIGNMENT = 15
 OP_RUNTIME_OPT_NEAREST_BATCH = 16
+OP_RUNTIME_OPT_ALLOC_FAULT = 17   # TEST HOOK: the k-th request to the buffer cache from now fails
 OP_MERGE_OWNER_EXCHANGE, OP_MERGE_DENSE_REDUCE = 0, 1
 OP_MEM_HOST, OP_MEM_DEVICE = 0, 1
 OP_ICP_POINT_TO_POINT, OP_ICP_POINT_TO_PLANE = 0, 1
@@ -99,7 +100,7 @@ OP_ICP_TIES_LOWEST_INDEX, OP_ICP_TIES_REFERENCE = 0, 1
 OP_ICP_FINISH_REFERENCE, OP_ICP_FINISH_FP64 = 0, 1
 OP_ICP_SUMS_FP64, OP_ICP_SUMS_REFERENCE_F32 = 0, 1
 OP_OK, OP_ERR_INVALID = 0, 1
-OP_ERR_NO_DEVICE, OP_ERR_CAPACITY, OP_ERR_MISMATCH, OP_ERR_NO_NORMALS = 2, 3, 4, 5
+OP_ERR_NO_DEVICE, OP_ERR_CAPACITY, OP_ERR_MISMATCH, OP_ERR_NO_NORMALS, OP_ERR_HIP = 2, 3, 4, 5, 6
 
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -139,6 +140,7 @@ SIGNATURES = {
     "op_debug_ka_certificate": (C.c_int, [C.POINTER(Camera), _fp, C.c_float, C.c_float, _vp, _fp, _vp]),
     "op_debug_gather2d": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, _vp]),
     "op_debug_seq_tile_rows": (C.c_int, []),
+    "op_debug_cache_live": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "op_debug_seq_sums": (C.c_int, [C.c_int, _vp, C.c_uint, C.c_uint, _vp]),
     "op_debug_seq_sums_many": (C.c_int, [C.c_int, _vp, _vp, C.c_int, _vp]),
     "op_volume_create": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_float, C.c_float,

@@ -36,6 +36,7 @@ struct RuntimeOptions {
     std::atomic<int> color_alignment{0};               // OP_RUNTIME_OPT_COLOR_ALIGNMENT: read by the class surface likewise; 1 = tool::AlignColorToDepth runs on the device
     std::atomic<int> nearest_batch{0};                 // OP_RUNTIME_OPT_NEAREST_BATCH: read by the class surface likewise; 1 = KDTree<3>::NearestBatch and tool::TransferLabels run on the device
     std::atomic<long long> merge_fault{0};             // TEST HOOK (OP_RUNTIME_OPT_MERGE_FAULT): stage * 1024 + rank + 1 -- that rank's allocation of that merge stage "fails"; 0 = off
+    std::atomic<long long> alloc_fault{0};             // TEST HOOK (OP_RUNTIME_OPT_ALLOC_FAULT): k > 0 -- the k-th cache_alloc from now "fails" with hipErrorOutOfMemory, then the option is 0 again
     std::atomic<long long> cache_device_bytes{32ll << 30}; // released device buffers kept for reuse, per device (buffer cache below); 0 = keep none
 };
 RuntimeOptions& runtime_options();
@@ -114,6 +115,12 @@ inline BufferCache& buffer_cache() { static BufferCache c; return c; }
 
 inline hipError_t cache_alloc(void** out, size_t bytes, bool host) {
     *out = nullptr;
+    {   // TEST HOOK (RuntimeOptions::alloc_fault): a host-side error return, before HIP or the cache is touched
+        std::atomic<long long>& fault = runtime_options().alloc_fault;
+        long long k = fault.load();
+        while (k > 0 && !fault.compare_exchange_weak(k, k - 1)) {}
+        if (k == 1) return hipErrorOutOfMemory;
+    }
     if (!bytes) bytes = 1;
     int device = 0;
     hipError_t e = hipGetDevice(&device);
@@ -231,29 +238,35 @@ inline void release_cached_memory() {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
 }
 
-// device buffers of one call: inputs in OP_MEM_HOST are copied in, OP_MEM_DEVICE inputs are used in place; everything allocated here goes back
-// to the buffer cache when the call ends
+// The buffers of one call.  RULE: a per-call buffer lives in a Scope bound to the stream that uses it.  The destructor synchronises that stream
+// (ignoring the result) and only then hands the buffers back to the buffer cache, so every exit -- an OP_TRY / OP_HIP return after a launch
+// included -- returns idle memory.  open() takes a cached stream of the Scope's own and releases it again; bind() borrows the stream of a
+// volume or an ICP context, or the null stream (nullptr), and never releases it.  A Scope that is neither opened nor bound may own only buffers
+// that no kernel touches.  Inputs in OP_MEM_HOST are copied in, OP_MEM_DEVICE inputs are used in place.  Ownership does not move: a callee whose
+// buffers the caller consumes takes the caller's Scope& and allocates into it.
 struct Scope {
     std::vector<void*> owned;
     hipStream_t stream = nullptr;
     int device = 0;
+    bool bound = false, own_stream = false;
+    Scope() = default;
+    Scope(const Scope&) = delete;
+    Scope& operator=(const Scope&) = delete;
     ~Scope() {
-        if (stream) { (void)hipStreamSynchronize(stream); op::release_stream(stream, device); }
+        if (bound) (void)hipStreamSynchronize(stream);
+        if (own_stream) op::release_stream(stream, device);
         for (void* p : owned) op::cached_free(p);
     }
     int open(int dev) {
         OP_TRY(op::use_device(dev));
         device = dev;
         OP_HIP(op::cached_stream(&stream));
+        bound = own_stream = true;
         return OP_OK;
     }
-    template <class T> int alloc(T** out, size_t count) {
-        void* p = nullptr;
-        OP_HIP(op::cached_malloc(&p, count * sizeof(T)));
-        owned.push_back(p);
-        *out = static_cast<T*>(p);
-        return OP_OK;
-    }
+    void bind(hipStream_t borrowed) { stream = borrowed; bound = true; } // the device of that stream is current
+    template <class T> int alloc(T** out, size_t count) { return take(out, count, false); }
+    template <class T> int pinned(T** out, size_t count) { return take(out, count, true); } // host memory, pinned and mapped
     template <class T> int input(const T* src, size_t count, int mem, const T** out) {
         if (mem == OP_MEM_DEVICE) { *out = src; return OP_OK; }
         T* d = nullptr;
@@ -270,6 +283,14 @@ struct Scope {
     template <class T> int output(T* dst, const T* d_src, size_t count, int mem) {
         if (count) OP_HIP(hipMemcpyAsync(dst, d_src, count * sizeof(T), mem == OP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
         OP_HIP(hipStreamSynchronize(stream));
+        return OP_OK;
+    }
+private:
+    template <class T> int take(T** out, size_t count, bool host) {
+        void* p = nullptr;
+        OP_HIP(op::cache_alloc(&p, count * sizeof(T), host));
+        owned.push_back(p);
+        *out = static_cast<T*>(p);
         return OP_OK;
     }
 };

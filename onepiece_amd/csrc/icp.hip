@@ -568,28 +568,21 @@ static int pair_sums_run(int mode, const float* a, size_t na_floats, const float
                          size_t n, int mem, int device, double out[kNSums]) {
     OP_TRY(op::use_device(device));
     const int n_wg = 256;
-    float *d_a = nullptr, *d_b = nullptr, *d_n = nullptr;
-    int* d_i = nullptr;
+    op::Scope s; // (everything here runs on the null stream)
+    s.bind(nullptr);
+    const float *d_a = nullptr, *d_b = nullptr, *d_n = nullptr;
+    const int32_t* d_i = nullptr;
     double *d_part = nullptr, *d_out = nullptr;
-    hipError_t e = hipSuccess;
-    auto up = [&](const void* src, size_t bytes, void** dst) {
-        if (e != hipSuccess || !src || !bytes) return;
-        if (mem == OP_MEM_DEVICE) { *dst = const_cast<void*>(src); return; }
-        e = op::cached_malloc(dst, bytes);
-        if (e == hipSuccess) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    };
-    up(a, na_floats * 4, (void**)&d_a); up(b, nb_floats * 4, (void**)&d_b); up(nrm, nb_floats * 4, (void**)&d_n); up(inliers, n * 8, (void**)&d_i);
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_part, (size_t)n_wg * kNSums * sizeof(double));
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_out, kNSums * sizeof(double));
-    if (e == hipSuccess) {
-        if (mode == 1) hipLaunchKernelGGL(k_pair_sums<1>, dim3(n_wg), dim3(kIterThreads), 0, nullptr, (const float*)d_a, (const float*)d_b, (const float*)d_n, (const int*)d_i, n, d_part);
-        else hipLaunchKernelGGL(k_pair_sums<0>, dim3(n_wg), dim3(kIterThreads), 0, nullptr, (const float*)d_a, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr, n, d_part);
-        hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(1024), 0, nullptr, (const double*)d_part, n_wg, d_out);
-        e = hipMemcpy(out, d_out, kNSums * sizeof(double), hipMemcpyDeviceToHost);
-    }
-    if (mem != OP_MEM_DEVICE) { op::cached_free(d_a); op::cached_free(d_b); op::cached_free(d_n); op::cached_free(d_i); }
-    op::cached_free(d_part); op::cached_free(d_out);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "pair sums failed: %s", hipGetErrorString(e));
+    if (a && na_floats) OP_TRY(s.input(a, na_floats, mem, &d_a));
+    if (b && nb_floats) OP_TRY(s.input(b, nb_floats, mem, &d_b));
+    if (nrm && nb_floats) OP_TRY(s.input(nrm, nb_floats, mem, &d_n));
+    if (inliers && n) OP_TRY(s.input(inliers, n * 2, mem, &d_i));
+    OP_TRY(s.alloc(&d_part, (size_t)n_wg * kNSums));
+    OP_TRY(s.alloc(&d_out, kNSums));
+    if (mode == 1) hipLaunchKernelGGL(k_pair_sums<1>, dim3(n_wg), dim3(kIterThreads), 0, nullptr, d_a, d_b, d_n, (const int*)d_i, n, d_part);
+    else hipLaunchKernelGGL(k_pair_sums<0>, dim3(n_wg), dim3(kIterThreads), 0, nullptr, d_a, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr, n, d_part);
+    hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(1024), 0, nullptr, (const double*)d_part, n_wg, d_out);
+    OP_HIP(hipMemcpy(out, d_out, kNSums * sizeof(double), hipMemcpyDeviceToHost));
     return OP_OK;
 }
 

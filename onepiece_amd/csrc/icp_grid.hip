@@ -297,30 +297,28 @@ __global__ __launch_bounds__(256) void k_depth_scatter(const void* __restrict__ 
 
 namespace opi {
 
-int device_exclusive_scan(const unsigned* d_count, size_t n, unsigned* d_start, hipStream_t stream, unsigned* total_out) {
-    const size_t nwg = (n + kScanWg - 1) / kScanWg;
-    unsigned* d_tot = nullptr;
-    OP_HIP(op::cached_malloc((void**)&d_tot, (nwg + 1) * sizeof(unsigned)));
-    hipLaunchKernelGGL(k_scan_totals, dim3((unsigned)nwg), dim3(256), 0, stream, d_count, n, d_tot);
-    hipLaunchKernelGGL(k_scan_of_totals, dim3(1), dim3(1024), 0, stream, d_tot, nwg);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nwg), dim3(256), 0, stream, d_count, n, (const unsigned*)d_tot, d_start);
-    hipError_t e = hipStreamSynchronize(stream);
-    if (e == hipSuccess && total_out) {
-        unsigned last_start = 0, last_count = 0;
-        e = hipMemcpy(&last_start, d_start + (n - 1), 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&last_count, d_count + (n - 1), 4, hipMemcpyDeviceToHost);
-        *total_out = last_start + last_count;
-    }
-    op::cached_free(d_tot);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "scan failed: %s", hipGetErrorString(e));
-    return OP_OK;
-}
-
 void scan_launch(const unsigned* d_count, size_t n, unsigned* d_tot, unsigned* d_start, hipStream_t stream) {
     const size_t nwg = (n + kScanWg - 1) / kScanWg;
     hipLaunchKernelGGL(k_scan_totals, dim3((unsigned)nwg), dim3(256), 0, stream, d_count, n, d_tot);
     hipLaunchKernelGGL(k_scan_of_totals, dim3(1), dim3(1024), 0, stream, d_tot, nwg);
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nwg), dim3(256), 0, stream, d_count, n, (const unsigned*)d_tot, d_start);
+}
+
+int device_exclusive_scan(const unsigned* d_count, size_t n, unsigned* d_start, hipStream_t stream, unsigned* total_out) {
+    const size_t nwg = (n + kScanWg - 1) / kScanWg;
+    op::Scope s;
+    s.bind(stream);
+    unsigned* d_tot = nullptr;
+    OP_TRY(s.alloc(&d_tot, nwg + 1));
+    scan_launch(d_count, n, d_tot, d_start, stream);
+    OP_HIP(hipStreamSynchronize(stream));
+    if (total_out) {
+        unsigned last_start = 0, last_count = 0;
+        OP_HIP(hipMemcpy(&last_start, d_start + (n - 1), 4, hipMemcpyDeviceToHost));
+        OP_HIP(hipMemcpy(&last_count, d_count + (n - 1), 4, hipMemcpyDeviceToHost));
+        *total_out = last_start + last_count;
+    }
+    return OP_OK;
 }
 
 } // namespace opi
@@ -336,6 +334,34 @@ extern "C" {
 //   a filled volume (uniform test clouds):        occupied cells ~ box volume / cell^3    -> cell = cbrt(volume * per_cell / m)
 // (a box that is flat along one or two axes falls back to the area / the length it has).  The cell is never finer than 2^-12 of the
 // largest coordinate magnitude: cell_coord works in float32, and below that a cell's width approaches the rounding of (p - origin) * inv_cell.
+// the two per-call temporaries of icp_create, each in a Scope bound to the context's stream that ends before the caller can drop the context
+static int target_box(op_icp* c, unsigned box[6]) { // encoded max xyz, min xyz of the target
+    op::Scope s;
+    s.bind(c->stream);
+    unsigned* d_box = nullptr;
+    OP_TRY(s.alloc(&d_box, 6));
+    const unsigned init[6] = {0u, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    OP_HIP(hipMemcpy(d_box, init, sizeof(init), hipMemcpyHostToDevice));
+    if (c->m) hipLaunchKernelGGL(k_bbox, dim3(128), dim3(256), 0, c->stream, (const float*)c->tgt_orig, c->m, d_box);
+    OP_HIP(hipStreamSynchronize(c->stream));
+    OP_HIP(hipMemcpy(box, d_box, 6 * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return OP_OK;
+}
+static int sort_target_into_cells(op_icp* c, size_t n_tab) { // c->cell_start and c->tgt from c->tgt_orig
+    op::Scope s;
+    s.bind(c->stream);
+    const size_t m = c->m;
+    unsigned* d_count = nullptr;
+    OP_TRY(s.alloc(&d_count, n_tab));
+    OP_HIP(hipMemsetAsync(d_count, 0, n_tab * sizeof(unsigned), c->stream));
+    if (m) hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->tgt_orig, m, c->grid, d_count);
+    OP_TRY(device_exclusive_scan(d_count, n_tab, c->cell_start, c->stream, nullptr));
+    if (m) hipLaunchKernelGGL(k_cell_scatter, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->tgt_orig, m,
+                              c->grid, (const unsigned*)c->cell_start, d_count, c->tgt);
+    OP_HIP(hipStreamSynchronize(c->stream));
+    return OP_OK;
+}
+
 static int icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, double threshold, double extent_divisor, double per_cell, int mem, int device,
                       op_icp** out) {
     if (!out) return fail(OP_ERR_INVALID, "null out");
@@ -372,15 +398,9 @@ static int icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, 
         }
     }
     // bounding box -> grid
-    unsigned* d_box = nullptr;
-    OP_HIP_C(op::cached_malloc((void**)&d_box, 6 * sizeof(unsigned)));
-    unsigned init[6] = {0u, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-    OP_HIP_C(hipMemcpy(d_box, init, sizeof(init), hipMemcpyHostToDevice));
-    if (m) hipLaunchKernelGGL(k_bbox, dim3(128), dim3(256), 0, c->stream, (const float*)c->tgt_orig, m, d_box);
-    OP_HIP_C(hipStreamSynchronize(c->stream));
     unsigned box[6];
-    OP_HIP_C(hipMemcpy(box, d_box, sizeof(box), hipMemcpyDeviceToHost));
-    op::cached_free(d_box);
+    int rc = target_box(c, box);
+    if (rc != OP_OK) return bail(rc);
     float mx[3], mn[3];
     for (int k = 0; k < 3; ++k) { mx[k] = dec_f(box[k]); mn[k] = dec_f(box[3 + k]); }
     if (!m || !(mx[0] >= mn[0])) { for (int k = 0; k < 3; ++k) { mx[k] = 0; mn[k] = 0; } }
@@ -425,19 +445,8 @@ static int icp_create(const float* tgt_xyz, const float* tgt_normals, size_t m, 
     // run of x-adjacent cells is [cell_start[first], cell_start[last + 1]) and one 16-byte load sees both ends
     const size_t n_tab = c->ncell + 4;
     OP_HIP_C(op::cached_malloc((void**)&c->cell_start, n_tab * sizeof(unsigned)));
-    unsigned* d_count = nullptr;
-    OP_HIP_C(op::cached_malloc((void**)&d_count, n_tab * sizeof(unsigned)));
-    auto drop = [&]() { op::cached_free(d_count); };
-    hipError_t e = hipMemsetAsync(d_count, 0, n_tab * sizeof(unsigned), c->stream);
-    if (e != hipSuccess) { drop(); return bail(fail(OP_ERR_HIP, "grid build failed: %s", hipGetErrorString(e))); }
-    if (m) hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->tgt_orig, m, c->grid, d_count);
-    int rc = device_exclusive_scan(d_count, n_tab, c->cell_start, c->stream, nullptr);
-    if (rc != OP_OK) { drop(); return bail(rc); }
-    if (m) hipLaunchKernelGGL(k_cell_scatter, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->tgt_orig, m,
-                              c->grid, (const unsigned*)c->cell_start, d_count, c->tgt);
-    e = hipStreamSynchronize(c->stream);
-    drop();
-    if (e != hipSuccess) return bail(fail(OP_ERR_HIP, "grid build failed: %s", hipGetErrorString(e)));
+    rc = sort_target_into_cells(c, n_tab);
+    if (rc != OP_OK) return bail(rc);
     OP_HIP_C(op::cached_malloc((void**)&c->sync, (kGroups + 1) * sizeof(unsigned)));
     OP_HIP_C(hipMemset(c->sync, 0, (kGroups + 1) * sizeof(unsigned)));
     OP_HIP_C(op::cached_malloc((void**)&c->result, kNSums * sizeof(double)));
@@ -556,52 +565,30 @@ static int points_from_images(const op_camera* cam, const void* depth, int depth
     if (cam->width <= 0 || cam->height <= 0) return fail(OP_ERR_INVALID, "invalid camera");
     OP_TRY(op::use_device(device));
     const size_t npix = (size_t)cam->width * cam->height;
-    const size_t dbytes = npix * (depth_fmt == OP_DEPTH_U16 ? 2 : 4);
-    void* d_depth = nullptr;
+    const bool u16 = depth_fmt == OP_DEPTH_U16;
+    op::Scope s; // (everything here runs on the null stream)
+    s.bind(nullptr);
+    const unsigned char *dsrc = nullptr, *rsrc = nullptr;
+    OP_TRY(s.input((const unsigned char*)depth, npix * (u16 ? 2 : 4), mem, &dsrc));
     unsigned *d_count = nullptr, *d_start = nullptr;
-    float *d_xyz = nullptr, *d_col = nullptr;
-    unsigned char* d_rgb = nullptr;
-    const unsigned char* rsrc = rgb;
-    int rc = OP_OK;
-    hipError_t e = hipSuccess;
-    const void* dsrc = depth;
-    if (mem == OP_MEM_HOST) {
-        e = op::cached_malloc(&d_depth, dbytes);
-        if (e == hipSuccess) e = hipMemcpy(d_depth, depth, dbytes, hipMemcpyHostToDevice);
-        dsrc = d_depth;
-    }
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_count, npix * 4);
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_start, npix * 4);
-    if (e == hipSuccess && mem == OP_MEM_HOST) e = op::cached_malloc((void**)&d_xyz, npix * 12);
-    if (e == hipSuccess && mem == OP_MEM_HOST && rgb) {
-        e = op::cached_malloc((void**)&d_col, npix * 12);
-        if (e == hipSuccess) e = op::cached_malloc((void**)&d_rgb, npix * 3);
-        if (e == hipSuccess) e = hipMemcpy(d_rgb, rgb, npix * 3, hipMemcpyHostToDevice);
-        rsrc = d_rgb;
+    float *dst = xyz_out, *cdst = colors_out; // OP_MEM_DEVICE: written in place
+    OP_TRY(s.alloc(&d_count, npix));
+    OP_TRY(s.alloc(&d_start, npix));
+    if (mem == OP_MEM_HOST) OP_TRY(s.alloc(&dst, npix * 3));
+    if (rgb) {
+        if (mem == OP_MEM_HOST) OP_TRY(s.alloc(&cdst, npix * 3));
+        OP_TRY(s.input(rgb, npix * 3, mem, &rsrc));
     }
     unsigned total = 0;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_depth_count, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, nullptr, dsrc, depth_fmt == OP_DEPTH_U16,
-                           cam->depth_scale, npix, d_count);
-        rc = device_exclusive_scan(d_count, npix, d_start, nullptr, &total);
-        if (rc == OP_OK) {
-            float* dst = mem == OP_MEM_HOST ? d_xyz : xyz_out;
-            float* cdst = rgb ? (mem == OP_MEM_HOST ? d_col : colors_out) : nullptr;
-            hipLaunchKernelGGL(k_depth_scatter, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, nullptr, dsrc, depth_fmt == OP_DEPTH_U16, *cam,
-                               npix, (const unsigned*)d_start, dst, rsrc, cdst);
-            e = hipDeviceSynchronize();
-            if (e == hipSuccess && mem == OP_MEM_HOST && total) e = hipMemcpy(xyz_out, d_xyz, (size_t)total * 12, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && mem == OP_MEM_HOST && total && rgb) e = hipMemcpy(colors_out, d_col, (size_t)total * 12, hipMemcpyDeviceToHost);
-        }
+    hipLaunchKernelGGL(k_depth_count, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, nullptr, (const void*)dsrc, u16, cam->depth_scale, npix, d_count);
+    OP_TRY(device_exclusive_scan(d_count, npix, d_start, nullptr, &total));
+    hipLaunchKernelGGL(k_depth_scatter, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, nullptr, (const void*)dsrc, u16, *cam, npix, (const unsigned*)d_start, dst,
+                       rsrc, cdst);
+    OP_HIP(hipDeviceSynchronize());
+    if (mem == OP_MEM_HOST && total) {
+        OP_HIP(hipMemcpy(xyz_out, dst, (size_t)total * 12, hipMemcpyDeviceToHost));
+        if (rgb) OP_HIP(hipMemcpy(colors_out, cdst, (size_t)total * 12, hipMemcpyDeviceToHost));
     }
-    if (d_depth) op::cached_free(d_depth);
-    if (d_count) op::cached_free(d_count);
-    if (d_start) op::cached_free(d_start);
-    if (d_xyz) op::cached_free(d_xyz);
-    if (d_col) op::cached_free(d_col);
-    if (d_rgb) op::cached_free(d_rgb);
-    if (rc != OP_OK) return rc;
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "points_from_depth failed: %s", hipGetErrorString(e));
     *n = total;
     return OP_OK;
 }
@@ -616,6 +603,21 @@ int op_points_from_rgbd(const op_camera* cam, const void* depth, int depth_fmt, 
     return points_from_images(cam, depth, depth_fmt, rgb, mem, device, xyz_out, colors_out, n);
 }
 
+static int normals_on_grid(op_icp* c, size_t n, float radius, int knn, int mem, float* normals_out) {
+    op::Scope s; // (ends before the caller destroys the context whose stream it borrows)
+    s.bind(c->stream);
+    float* d_nrm = nullptr;
+    OP_TRY(s.alloc(&d_nrm, n * 3));
+    OP_HIP(hipMemsetAsync(d_nrm, 0, n * 12, c->stream));
+    const float cell = 1.0f / c->grid.inv_cell;
+    hipLaunchKernelGGL(k_estimate_normals, dim3((unsigned)((n + kNrmThreads - 1) / kNrmThreads)), dim3(kNrmThreads), 0, c->stream, c->grid,
+                       (const unsigned*)c->cell_start, (const float4*)c->tgt, n, knn, radius, cell, d_nrm);
+    OP_HIP(hipStreamSynchronize(c->stream));
+    if (mem == OP_MEM_DEVICE) return s.output(normals_out, (const float*)d_nrm, n * 3, mem); // on the stream, and finished on return
+    OP_HIP(hipMemcpy(normals_out, d_nrm, n * 12, hipMemcpyDeviceToHost));
+    return OP_OK;
+}
+
 int op_estimate_normals(const float* xyz, size_t n, float radius, int knn, int mem, int device, float* normals_out) {
     if (!xyz || !normals_out) return fail(OP_ERR_INVALID, "null argument");
     if (knn < 1 || knn > kNrmMaxK) return fail(OP_ERR_INVALID, "knn must be in [1, %d]", kNrmMaxK);
@@ -625,25 +627,9 @@ int op_estimate_normals(const float* xyz, size_t n, float radius, int knn, int m
     // divisors 400 / 300 / 250 / 200 / 150 (tools/ab_normals_cell.sh)
     op_icp* c = nullptr;
     OP_TRY(icp_create(xyz, nullptr, n, 0.0, 300.0, 0.0, mem, device, &c));
-    float* d_nrm = nullptr;
-    hipError_t e = op::cached_malloc((void**)&d_nrm, n * 12);
-    if (e == hipSuccess) e = hipMemsetAsync(d_nrm, 0, n * 12, c->stream);
-    if (e == hipSuccess) {
-        const float cell = 1.0f / c->grid.inv_cell;
-        hipLaunchKernelGGL(k_estimate_normals, dim3((unsigned)((n + kNrmThreads - 1) / kNrmThreads)), dim3(kNrmThreads), 0, c->stream, c->grid,
-                           (const unsigned*)c->cell_start, (const float4*)c->tgt, n, knn, radius, cell, d_nrm);
-        e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess && mem == OP_MEM_DEVICE) { // ordered on the stream and finished before d_nrm goes back to the buffer cache
-        e = hipMemcpyAsync(normals_out, d_nrm, n * 12, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    } else if (e == hipSuccess) {
-        e = hipMemcpy(normals_out, d_nrm, n * 12, hipMemcpyDeviceToHost);
-    }
-    if (d_nrm) op::cached_free(d_nrm);
+    const int rc = normals_on_grid(c, n, radius, knn, mem, normals_out);
     op_icp_destroy(c);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "estimate_normals failed: %s", hipGetErrorString(e));
-    return OP_OK;
+    return rc;
 }
 
 } // extern "C"
@@ -657,23 +643,16 @@ int grid_context_create(const float* tgt_xyz, size_t m, double points_per_cell, 
 int cell_sort_points(const float* d_xyz, size_t n, const Grid& g, size_t ncell, float4* d_sorted, hipStream_t stream) {
     if (!n) return OP_OK;
     const size_t n_tab = ncell + 4;
+    op::Scope s;
+    s.bind(stream);
     unsigned *d_count = nullptr, *d_start = nullptr;
-    hipError_t e = op::cached_malloc((void**)&d_count, n_tab * sizeof(unsigned));
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_start, n_tab * sizeof(unsigned));
-    int rc = OP_OK;
-    if (e == hipSuccess) e = hipMemsetAsync(d_count, 0, n_tab * sizeof(unsigned), stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_xyz, n, g, d_count);
-        rc = device_exclusive_scan(d_count, n_tab, d_start, stream, nullptr);
-        if (rc == OP_OK) {
-            hipLaunchKernelGGL(k_cell_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_xyz, n, g, (const unsigned*)d_start, d_count, d_sorted);
-            e = hipStreamSynchronize(stream); // the two tables go back to the buffer cache below
-        }
-    }
-    if (d_count) op::cached_free(d_count);
-    if (d_start) op::cached_free(d_start);
-    if (rc != OP_OK) return rc;
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "cell sort failed: %s", hipGetErrorString(e));
+    OP_TRY(s.alloc(&d_count, n_tab));
+    OP_TRY(s.alloc(&d_start, n_tab));
+    OP_HIP(hipMemsetAsync(d_count, 0, n_tab * sizeof(unsigned), stream));
+    hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_xyz, n, g, d_count);
+    OP_TRY(device_exclusive_scan(d_count, n_tab, d_start, stream, nullptr));
+    hipLaunchKernelGGL(k_cell_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_xyz, n, g, (const unsigned*)d_start, d_count, d_sorted);
+    OP_HIP(hipStreamSynchronize(stream));
     return OP_OK;
 }
 

@@ -128,23 +128,17 @@ extern "C" int op_bilateral_filter_depth(const void* depth, int depth_format, fl
     }
     const size_t npix = (size_t)width * height * n_images;
     const size_t in_bytes = npix * (depth_format == OP_DEPTH_U16 ? 2 : 4);
-    void* d_in = nullptr;
-    float* d_out = nullptr;
+    op::Scope s; // OP_MEM_HOST: the device images, on the unit's own stream (with device buffers nothing is owned and the caller's stream is not waited for)
     BilateralArgs A{};
+    A.src = depth;
+    A.dst = out;
     if (mem == OP_MEM_HOST) {
-        OP_HIP(op::cached_malloc(&d_in, in_bytes));
-        hipError_t e = op::cached_malloc((void**)&d_out, npix * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_in, depth, in_bytes, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) {
-            op::cached_free(d_in);
-            if (d_out) op::cached_free(d_out);
-            return fail(OP_ERR_HIP, "bilateral filter staging failed: %s", hipGetErrorString(e));
-        }
+        s.bind(st);
+        unsigned char* d_in = nullptr;
+        OP_TRY(s.alloc(&d_in, in_bytes));
+        OP_TRY(s.alloc(&A.dst, npix));
+        OP_HIP(hipMemcpyAsync(d_in, depth, in_bytes, hipMemcpyHostToDevice, st));
         A.src = d_in;
-        A.dst = d_out;
-    } else {
-        A.src = depth;
-        A.dst = out;
     }
     A.width = width;
     A.height = height;
@@ -160,13 +154,8 @@ extern "C" int op_bilateral_filter_depth(const void* depth, int depth_format, fl
         hipLaunchKernelGGL(k_bilateral<3>, grid, block, lds, st, A);
     else
         hipLaunchKernelGGL(k_bilateral<0>, grid, block, lds, st, A);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && mem == OP_MEM_HOST) e = hipMemcpyAsync(out, d_out, npix * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && !stream) e = hipStreamSynchronize(st);
-    if (mem == OP_MEM_HOST) {
-        op::cached_free(d_in);
-        op::cached_free(d_out);
-    }
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "bilateral filter failed: %s", hipGetErrorString(e));
+    OP_HIP(hipGetLastError());
+    if (mem == OP_MEM_HOST) OP_HIP(hipMemcpyAsync(out, A.dst, npix * 4, hipMemcpyDeviceToHost, st));
+    if (!stream) OP_HIP(hipStreamSynchronize(st));
     return OP_OK;
 }

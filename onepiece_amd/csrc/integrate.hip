@@ -606,21 +606,18 @@ int op_debug_voxel_update(const float* s, const float* w, const float* c0, const
     OP_TRY(op::use_device(0));
     if (n == 0) return OP_OK;
     const size_t N = (size_t)n;
+    op::Scope tmp; // (the hooks here run on the null stream)
+    tmp.bind(nullptr);
     float* d_in = nullptr;   // 7 operand planes of n words
     float* d_out = nullptr;  // out_fast, out_ref: n x 5 each
-    OP_HIP(op::cached_malloc((void**)&d_in, 7 * N * 4));
-    hipError_t e = op::cached_malloc((void**)&d_out, 10 * N * 4);
+    OP_TRY(tmp.alloc(&d_in, 7 * N));
+    OP_TRY(tmp.alloc(&d_out, 10 * N));
     const void* src[7] = {s, w, c0, c1, c2, new_sdf, rgba};
-    for (int k = 0; k < 7 && e == hipSuccess; ++k) e = hipMemcpy(d_in + k * N, src[k], N * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_voxel_update, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const float*)d_in, (const float*)(d_in + N), (const float*)(d_in + 2 * N),
-                           (const float*)(d_in + 3 * N), (const float*)(d_in + 4 * N), (const float*)(d_in + 5 * N), (const unsigned*)(d_in + 6 * N), n, d_out, d_out + 5 * N);
-        e = hipMemcpy(out_fast, d_out, 5 * N * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_ref, d_out + 5 * N, 5 * N * 4, hipMemcpyDeviceToHost);
-    }
-    op::cached_free(d_in);
-    if (d_out) op::cached_free(d_out);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_voxel_update failed: %s", hipGetErrorString(e));
+    for (int k = 0; k < 7; ++k) OP_HIP(hipMemcpy(d_in + k * N, src[k], N * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_voxel_update, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const float*)d_in, (const float*)(d_in + N), (const float*)(d_in + 2 * N),
+                       (const float*)(d_in + 3 * N), (const float*)(d_in + 4 * N), (const float*)(d_in + 5 * N), (const unsigned*)(d_in + 6 * N), n, d_out, d_out + 5 * N);
+    OP_HIP(hipMemcpy(out_fast, d_out, 5 * N * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(out_ref, d_out + 5 * N, 5 * N * 4, hipMemcpyDeviceToHost));
     return OP_OK;
 }
 
@@ -630,15 +627,13 @@ int op_debug_rcp(const float* x, long long n, float* out) {
     OP_TRY(op::use_device(0));
     if (n == 0) return OP_OK;
     const size_t N = (size_t)n;
+    op::Scope tmp;
+    tmp.bind(nullptr);
     float* d = nullptr;      // x, then out
-    OP_HIP(op::cached_malloc((void**)&d, 2 * N * 4));
-    hipError_t e = hipMemcpy(d, x, N * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_rcp, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const float*)d, n, d + N);
-        e = hipMemcpy(out, d + N, N * 4, hipMemcpyDeviceToHost);
-    }
-    op::cached_free(d);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_rcp failed: %s", hipGetErrorString(e));
+    OP_TRY(tmp.alloc(&d, 2 * N));
+    OP_HIP(hipMemcpy(d, x, N * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_rcp, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const float*)d, n, d + N);
+    OP_HIP(hipMemcpy(out, d + N, N * 4, hipMemcpyDeviceToHost));
     return OP_OK;
 }
 
@@ -659,17 +654,15 @@ int op_debug_gather2d(const unsigned* images, int width, int height, int n_frame
     OP_TRY(op::use_device(0));
     if (n == 0) return OP_OK;
     const size_t N = (size_t)n, img_bytes = (size_t)width * height * n_frames * 8;
+    op::Scope tmp;
+    tmp.bind(nullptr);
     char* d = nullptr;       // the images, then uv, then out
-    OP_HIP(op::cached_malloc((void**)&d, img_bytes + 16 * N));
-    hipError_t e = hipMemcpy(d, images, img_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + img_bytes, uv, 8 * N, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_gather2d, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const uint2*)d, width, height, frame, column_test, (const int*)(d + img_bytes), n,
-                           (uint2*)(d + img_bytes + 8 * N));
-        e = hipMemcpy(out, d + img_bytes + 8 * N, 8 * N, hipMemcpyDeviceToHost);
-    }
-    op::cached_free(d);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_gather2d failed: %s", hipGetErrorString(e));
+    OP_TRY(tmp.alloc(&d, img_bytes + 16 * N));
+    OP_HIP(hipMemcpy(d, images, img_bytes, hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(d + img_bytes, uv, 8 * N, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_gather2d, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, (const uint2*)d, width, height, frame, column_test, (const int*)(d + img_bytes), n,
+                       (uint2*)(d + img_bytes + 8 * N));
+    OP_HIP(hipMemcpy(out, d + img_bytes + 8 * N, 8 * N, hipMemcpyDeviceToHost));
     return OP_OK;
 }
 

@@ -494,25 +494,25 @@ int op_volume_extract_mesh_processed(op_volume* v, const int32_t* tri_table, con
     if (!(grid_len >= 0.0f) || !std::isfinite(grid_len)) return fail(OP_ERR_INVALID, "grid_len must be 0 (no clustering) or positive and finite (got %g)", (double)grid_len);
     OP_VOL(v);
     const bool fill = points && colors && triangles;
+    Scope soup_bufs;
+    soup_bufs.bind(v->stream);
     float *d_pts = nullptr, *d_col = nullptr;
     size_t soup = 0; // vertices of the soup: three per triangle
     *n_vertices = 0;
     *n_triangles = 0;
-    OP_TRY(opv::vol_mesh_soup(v, tri_table, edge_pairs, only_block, fill, (size_t)-1, &d_pts, &d_col, &soup));
+    OP_TRY(opv::vol_mesh_soup(soup_bufs, v, tri_table, edge_pairs, only_block, fill, (size_t)-1, &d_pts, &d_col, &soup));
     int rc = OP_OK;
     if (!fill) { // the sizing call: upper bounds (the soup's own sizes) -- the exact ones would take the whole pipeline
         *n_vertices = soup;
         *n_triangles = soup / 3;
     } else if (soup) {
-        Scope s; // (returns its buffers before the soup's below)
+        Scope s; // (declared later, so it returns its buffers before the soup's)
         rc = s.open(v->device);
         if (rc == OP_OK)
             rc = processed_device(s, Stage{d_pts, d_col, nullptr, soup, soup / 3}, grid_len, min_points, points, colors, normals, cap_vertices, triangles, cap_triangles,
                                   n_vertices, n_triangles);
         if (rc != OP_OK && rc != OP_ERR_CAPACITY) { *n_vertices = 0; *n_triangles = 0; } // (too small: the counts say what is needed)
     }
-    if (d_pts) op::cached_free(d_pts);
-    if (d_col) op::cached_free(d_col);
     return rc;
 }
 

@@ -682,34 +682,26 @@ int op_volume_render_frame(op_volume* v, const op_camera* cam, const float pose[
     OP_TRY(check_cam(&c));
     const size_t npx = (size_t)c.width * c.height;
     if (!v->rf_count) OP_HIP(op::cached_malloc((void**)&v->rf_count, sizeof(unsigned long long)));
+    op::Scope s;
+    s.bind(v->stream);
     unsigned char* d_rgb = rgb_out;
     float* d_depth = depth_out;
-    auto release_tmp = [&] { // OP_MEM_HOST: device temporaries from the buffer cache, released on every exit
-        if (mem != OP_MEM_HOST) return;
-        if (d_rgb) op::cached_free(d_rgb);
-        if (d_depth) op::cached_free(d_depth);
-        d_rgb = nullptr; d_depth = nullptr;
-    };
-    if (mem == OP_MEM_HOST) {
-        d_rgb = nullptr; d_depth = nullptr;
-        hipError_t ea = op::cached_malloc((void**)&d_rgb, npx * 3);
-        if (ea == hipSuccess) ea = op::cached_malloc((void**)&d_depth, npx * 4);
-        if (ea != hipSuccess) { release_tmp(); return fail(OP_ERR_HIP, "op_volume_render_frame: no device memory for the frame: %s", hipGetErrorString(ea)); }
+    if (mem == OP_MEM_HOST) { // device temporaries
+        OP_TRY(s.alloc(&d_rgb, npx * 3));
+        OP_TRY(s.alloc(&d_depth, npx));
     }
-    const int rc = op::volume_render_frame_enqueue(v, &c, pose, d_rgb, d_depth, v->rf_count, nullptr);
-    if (rc != OP_OK) { (void)hipStreamSynchronize(v->stream); release_tmp(); return rc; }
-    hipError_t e = hipStreamSynchronize(v->stream);
+    OP_TRY(op::volume_render_frame_enqueue(v, &c, pose, d_rgb, d_depth, v->rf_count, nullptr));
     unsigned long long n = 0;
-    if (e == hipSuccess && n_valid) e = hipMemcpy(&n, v->rf_count, sizeof(n), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && mem == OP_MEM_HOST) {
-        e = hipMemcpy(rgb_out, d_rgb, npx * 3, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(depth_out, d_depth, npx * 4, hipMemcpyDeviceToHost);
-    }
-    release_tmp();
-    if (e != hipSuccess) {
-        rc_drop(v);
-        return fail(OP_ERR_HIP, "op_volume_render_frame failed: %s", hipGetErrorString(e));
-    }
+    const int rc = [&]() -> int {
+        OP_HIP(hipStreamSynchronize(v->stream));
+        if (n_valid) OP_HIP(hipMemcpy(&n, v->rf_count, sizeof(n), hipMemcpyDeviceToHost));
+        if (mem == OP_MEM_HOST) {
+            OP_HIP(hipMemcpy(rgb_out, d_rgb, npx * 3, hipMemcpyDeviceToHost));
+            OP_HIP(hipMemcpy(depth_out, d_depth, npx * 4, hipMemcpyDeviceToHost));
+        }
+        return OP_OK;
+    }();
+    if (rc != OP_OK) { rc_drop(v); return rc; }
     if (n_valid) *n_valid = n;
     return OP_OK;
 }
@@ -722,43 +714,35 @@ int op_volume_raycast(op_volume* v, const op_camera* cam, const float pose[16], 
     OP_TRY(vol_check(v));
     const size_t npx = (size_t)c.width * c.height;
     OP_TRY(rc_reserve(v));
+    op::Scope s;
+    s.bind(v->stream);
     float *d_depth = depth_out, *d_nrm = normals_out, *d_col = colors_out;
-    // OP_MEM_HOST: device temporaries from the buffer cache; released on EVERY exit (a failed allocation or launch must not leave them in the cache's live set)
-    auto release_tmp = [&] {
-        if (mem != OP_MEM_HOST) return;
-        if (d_depth) op::cached_free(d_depth);
-        if (d_nrm) op::cached_free(d_nrm);
-        if (d_col) op::cached_free(d_col);
-        d_depth = d_nrm = d_col = nullptr;
-    };
-    if (mem == OP_MEM_HOST) {
-        d_depth = d_nrm = d_col = nullptr;
-        hipError_t ea = op::cached_malloc((void**)&d_depth, npx * 4);
-        if (ea == hipSuccess && normals_out) ea = op::cached_malloc((void**)&d_nrm, npx * 12);
-        if (ea == hipSuccess && colors_out) ea = op::cached_malloc((void**)&d_col, npx * 12);
-        if (ea != hipSuccess) { release_tmp(); return fail(OP_ERR_HIP, "raycast: no device memory for the output images: %s", hipGetErrorString(ea)); }
+    if (mem == OP_MEM_HOST) { // device temporaries
+        OP_TRY(s.alloc(&d_depth, npx));
+        if (normals_out) OP_TRY(s.alloc(&d_nrm, npx * 3));
+        if (colors_out) OP_TRY(s.alloc(&d_col, npx * 3));
     }
-    hipError_t e = hipSuccess;
-    if (!rc_launch(v, c, pose, d_depth, d_nrm, d_col, &e)) { release_tmp(); return fail(OP_ERR_HIP, "raycast: wiping the block summaries failed: %s", hipGetErrorString(e)); }
-    if (e == hipSuccess) e = hipStreamSynchronize(v->stream);
+    hipError_t launched = hipSuccess;
+    if (!rc_launch(v, c, pose, d_depth, d_nrm, d_col, &launched)) return fail(OP_ERR_HIP, "raycast: wiping the block summaries failed: %s", hipGetErrorString(launched));
+    const int rc = [&]() -> int {
+        OP_HIP(launched);
+        OP_HIP(hipStreamSynchronize(v->stream));
 #ifdef RC_STATS
-    {
-        unsigned long long st[8] = {0}, zero[8] = {0};
-        if (hipMemcpyFromSymbol(st, HIP_SYMBOL(g_rc_stats), sizeof(st)) == hipSuccess && hipMemcpyToSymbol(HIP_SYMBOL(g_rc_stats), zero, sizeof(zero)) == hipSuccess)
-            fprintf(stderr, "rc stats: visible blocks %llu, marched %llu, box pixels %llu, pixels marched %llu, samples %llu, previous-sample lookups %llu, crossings %llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6]);
-    }
+        {
+            unsigned long long st[8] = {0}, zero[8] = {0};
+            if (hipMemcpyFromSymbol(st, HIP_SYMBOL(g_rc_stats), sizeof(st)) == hipSuccess && hipMemcpyToSymbol(HIP_SYMBOL(g_rc_stats), zero, sizeof(zero)) == hipSuccess)
+                fprintf(stderr, "rc stats: visible blocks %llu, marched %llu, box pixels %llu, pixels marched %llu, samples %llu, previous-sample lookups %llu, crossings %llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6]);
+        }
 #endif
-    if (mem == OP_MEM_HOST) {
-        if (e == hipSuccess) e = hipMemcpy(depth_out, d_depth, npx * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && normals_out) e = hipMemcpy(normals_out, d_nrm, npx * 12, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && colors_out) e = hipMemcpy(colors_out, d_col, npx * 12, hipMemcpyDeviceToHost);
-    }
-    release_tmp();
-    if (e != hipSuccess) {
-        rc_drop(v);
-        return fail(OP_ERR_HIP, "raycast failed: %s", hipGetErrorString(e));
-    }
-    return OP_OK;
+        if (mem == OP_MEM_HOST) {
+            OP_HIP(hipMemcpy(depth_out, d_depth, npx * 4, hipMemcpyDeviceToHost));
+            if (normals_out) OP_HIP(hipMemcpy(normals_out, d_nrm, npx * 12, hipMemcpyDeviceToHost));
+            if (colors_out) OP_HIP(hipMemcpy(colors_out, d_col, npx * 12, hipMemcpyDeviceToHost));
+        }
+        return OP_OK;
+    }();
+    if (rc != OP_OK) rc_drop(v); // (k_rc_shade may have left hit bytes set)
+    return rc;
 }
 
 int op_volume_raycast_stats(op_volume* v, uint64_t* visible_blocks, uint64_t* dropped_unloaded, uint64_t* loaded_blocks, uint64_t* marched_blocks) {

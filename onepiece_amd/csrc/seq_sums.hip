@@ -281,23 +281,23 @@ int op_debug_seq_sums(int layout, const float* rows, unsigned n_uploaded, unsign
     if (layout < kSeqOneRow || layout > kSeqTwoValues) return op::fail(OP_ERR_INVALID, "op_debug_seq_sums: layout must be 0, 1 or 2");
     if (!out || (!rows && n_uploaded)) return op::fail(OP_ERR_INVALID, "null argument");
     if (n_items > n_uploaded || n_uploaded > kSeqDebugMaxItems) return op::fail(OP_ERR_INVALID, "op_debug_seq_sums: n_items <= n_uploaded <= 2^24");
-    OP_TRY(op::use_device(0));
+    op::Scope scope;
+    OP_TRY(scope.open(0));
     if (!seq_device_ok(0)) return op::fail(OP_ERR_NO_DEVICE, "op_debug_seq_sums: the device cannot run k_seq_sums (dynamic LDS)");
     const SeqLayout l = (SeqLayout)layout;
-    const size_t bytes = (size_t)n_uploaded * seq_item_floats(layout) * sizeof(float);
+    const size_t floats = (size_t)n_uploaded * seq_item_floats(layout);
     float* d = nullptr;      // all n_uploaded items; stays null without any: the kernel may not touch the rows of an empty problem
-    hipStream_t s = nullptr;
-    SeqSums sums;
-    hipError_t e = bytes ? op::cached_malloc((void**)&d, bytes) : hipSuccess;
-    if (e == hipSuccess && bytes) e = hipMemcpy(d, rows, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = op::cached_stream(&s);
-    if (e == hipSuccess) e = sums.reserve(0, false);
-    if (e == hipSuccess) e = sums.run(l, d, &n_items, s, nullptr);
+    if (floats) {
+        OP_TRY(scope.alloc(&d, floats));
+        OP_HIP(hipMemcpy(d, rows, floats * sizeof(float), hipMemcpyHostToDevice));
+    }
+    SeqSums sums; // (its own hipMalloc'ed buffers: released below whatever happened)
+    hipError_t e = sums.reserve(0, false);
+    if (e == hipSuccess) e = sums.run(l, d, &n_items, scope.stream, nullptr);
     if (e == hipSuccess) std::memcpy(out, sums.host, (seq_nacc(l) + 1) * sizeof(float));
-    if (s) { (void)hipStreamSynchronize(s); op::release_stream(s, 0); }
+    (void)hipStreamSynchronize(scope.stream);
     sums.release(0);
-    op::cached_free(d);
-    if (e != hipSuccess) return op::fail(OP_ERR_HIP, "op_debug_seq_sums failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return op::fail(OP_ERR_HIP, "op_debug_seq_sums: the sums failed: %s", hipGetErrorString(e));
     return OP_OK;
 }
 
@@ -312,30 +312,25 @@ int op_debug_seq_sums_many(int layout, const float* const* rows, const unsigned*
         start[i] = total;
         total += ((size_t)n_items[i] * nf + 63) / 64 * 64;
     }
-    OP_TRY(op::use_device(0));
+    op::Scope scope;
+    OP_TRY(scope.open(0));
     if (!seq_device_ok(0)) return op::fail(OP_ERR_NO_DEVICE, "op_debug_seq_sums_many: the device cannot run k_seq_sums_many (dynamic LDS)");
     float* d_rows = nullptr;
     float* d_out = nullptr;  // k x 64 words
     unsigned* d_n = nullptr;
-    hipStream_t s = nullptr;
-    hipError_t e = total ? op::cached_malloc((void**)&d_rows, total * sizeof(float)) : hipSuccess;
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_out, (size_t)k * 64 * sizeof(float));
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_n, (size_t)k * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemcpy(d_n, n_items, (size_t)k * sizeof(unsigned), hipMemcpyHostToDevice);
+    if (total) OP_TRY(scope.alloc(&d_rows, total));
+    OP_TRY(scope.alloc(&d_out, (size_t)k * 64));
+    OP_TRY(scope.alloc(&d_n, (size_t)k));
+    OP_HIP(hipMemcpy(d_n, n_items, (size_t)k * sizeof(unsigned), hipMemcpyHostToDevice));
     SeqBatchTable t{};
-    for (int i = 0; i < k && e == hipSuccess; ++i) {
-        if (n_items[i]) e = hipMemcpy(d_rows + start[i], rows[i], (size_t)n_items[i] * nf * sizeof(float), hipMemcpyHostToDevice);
+    for (int i = 0; i < k; ++i) {
+        if (n_items[i]) OP_HIP(hipMemcpy(d_rows + start[i], rows[i], (size_t)n_items[i] * nf * sizeof(float), hipMemcpyHostToDevice));
         t.rows[i] = n_items[i] ? d_rows + start[i] : nullptr; t.n_pix[i] = d_n + i; t.out[i] = d_out + (size_t)i * 64;
     }
-    if (e == hipSuccess) e = op::cached_stream(&s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(kSeqKernels[layout].many, dim3((unsigned)k), dim3(kSeqThreads), kSeqKernels[layout].lds, s, t); // as SeqRendezvous::flush_locked does
-        e = hipGetLastError();
-    }
-    for (int i = 0; i < k && e == hipSuccess; ++i) e = hipMemcpyAsync(out + (size_t)i * words, d_out + (size_t)i * 64, words * sizeof(float), hipMemcpyDeviceToHost, s);
-    if (s) { const hipError_t es = hipStreamSynchronize(s); if (e == hipSuccess) e = es; op::release_stream(s, 0); }
-    op::cached_free(d_rows); op::cached_free(d_out); op::cached_free(d_n);
-    if (e != hipSuccess) return op::fail(OP_ERR_HIP, "op_debug_seq_sums_many failed: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(kSeqKernels[layout].many, dim3((unsigned)k), dim3(kSeqThreads), kSeqKernels[layout].lds, scope.stream, t); // as SeqRendezvous::flush_locked does
+    OP_HIP(hipGetLastError());
+    for (int i = 0; i < k; ++i) OP_HIP(hipMemcpyAsync(out + (size_t)i * words, d_out + (size_t)i * 64, words * sizeof(float), hipMemcpyDeviceToHost, scope.stream));
+    OP_HIP(hipStreamSynchronize(scope.stream));
     return OP_OK;
 }
 

@@ -735,6 +735,9 @@ int op_runtime_set_option(int option, long long value) {
         case OP_RUNTIME_OPT_MERGE_FAULT:
             if (value < 0) return fail(OP_ERR_INVALID, "op_runtime_set_option: merge fault %lld", value);
             o.merge_fault.store(value); return OP_OK;
+        case OP_RUNTIME_OPT_ALLOC_FAULT:
+            if (value < 0) return fail(OP_ERR_INVALID, "op_runtime_set_option: allocation fault %lld", value);
+            o.alloc_fault.store(value); return OP_OK;
         case OP_RUNTIME_OPT_CACHE_DEVICE_BYTES:
             if (value < 0) return fail(OP_ERR_INVALID, "op_runtime_set_option: cache limit %lld", value);
             o.cache_device_bytes.store(value); return OP_OK;
@@ -751,7 +754,21 @@ int op_runtime_get_option(int option, long long* value) {
     if (option == OP_RUNTIME_OPT_MESH_POSTPROCESS) { *value = op::runtime_options().mesh_postprocess.load(); return OP_OK; }
     if (option == OP_RUNTIME_OPT_COLOR_ALIGNMENT) { *value = op::runtime_options().color_alignment.load(); return OP_OK; }
     if (option == OP_RUNTIME_OPT_NEAREST_BATCH) { *value = op::runtime_options().nearest_batch.load(); return OP_OK; }
+    if (option == OP_RUNTIME_OPT_ALLOC_FAULT) { *value = op::runtime_options().alloc_fault.load(); return OP_OK; }
     return fail(OP_ERR_INVALID, "op_runtime_get_option: option %d cannot be read", option);
+}
+
+int op_debug_cache_live(int device, uint64_t* device_buffers, uint64_t* pinned_buffers) {
+    uint64_t n[2] = {0, 0};
+    op::BufferCache& c = op::buffer_cache();
+    {
+        std::lock_guard<std::mutex> lock(c.mu);
+        for (const op::BufferCache::Slot& s : c.live_slots)
+            if (s.device == device) ++n[s.host ? 1 : 0];
+    }
+    if (device_buffers) *device_buffers = n[0];
+    if (pinned_buffers) *pinned_buffers = n[1];
+    return OP_OK;
 }
 
 const char* op_last_error(void) { return op::g_last_error; }
@@ -851,25 +868,22 @@ int op_debug_project_uv_image(float fx, float fy, float cx, float cy, int width,
     if (width <= 0 || height <= 0 || width >= (1 << 20) || height >= (1 << 20)) return fail(OP_ERR_INVALID, "op_debug_project_uv_image: sides in [1, 2^20)");
     OP_TRY(op::use_device(device));
     if (n == 0) return OP_OK;
+    op::Scope s; // (the kernel runs on the null stream)
+    s.bind(nullptr);
     float* d_in = nullptr;
     int* d_out = nullptr;
-    OP_HIP(op::cached_malloc((void**)&d_in, 3 * n * sizeof(float)));
-    hipError_t e = op::cached_malloc((void**)&d_out, 4 * n * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(d_in, X, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_in + n, Y, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_in + 2 * n, Z, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        CamParams C{};
-        C.fx = fx; C.fy = fy; C.cx = cx; C.cy = cy; C.width = width; C.height = height;
-        C.ax = px_axis(cx, C.width); C.ay = px_axis(cy, C.height);
-        C.fast_px = C.ax.exact && C.ay.exact;
-        hipLaunchKernelGGL(k_debug_project_uv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, C, (const float*)d_in,
-                           (const float*)(d_in + n), (const float*)(d_in + 2 * n), n, d_out);
-        e = hipMemcpy(out, d_out, 4 * n * sizeof(int), hipMemcpyDeviceToHost);
-    }
-    op::cached_free(d_in);
-    if (d_out) op::cached_free(d_out);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "op_debug_project_uv failed: %s", hipGetErrorString(e));
+    OP_TRY(s.alloc(&d_in, 3 * n));
+    OP_TRY(s.alloc(&d_out, 4 * n));
+    OP_HIP(hipMemcpy(d_in, X, n * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(d_in + n, Y, n * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(d_in + 2 * n, Z, n * 4, hipMemcpyHostToDevice));
+    CamParams C{};
+    C.fx = fx; C.fy = fy; C.cx = cx; C.cy = cy; C.width = width; C.height = height;
+    C.ax = px_axis(cx, C.width); C.ay = px_axis(cy, C.height);
+    C.fast_px = C.ax.exact && C.ay.exact;
+    hipLaunchKernelGGL(k_debug_project_uv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, C, (const float*)d_in,
+                       (const float*)(d_in + n), (const float*)(d_in + 2 * n), n, d_out);
+    OP_HIP(hipMemcpy(out, d_out, 4 * n * sizeof(int), hipMemcpyDeviceToHost));
     return OP_OK;
 }
 
@@ -1168,23 +1182,18 @@ int op_volume_integrate_cubes(op_volume* v, const void* depth, int depth_fmt, co
     OP_TRY(vol_reserve(v, (unsigned long long)have + n));
     const unsigned char* c = rgb;
     OP_TRY(vol_stage_images(v, &depth, depth_fmt, &c, mem));
+    op::Scope s;
+    s.bind(v->stream);
     int* d_keys = nullptr;
-    OP_HIP(op::cached_malloc((void**)&d_keys, n * 3 * sizeof(int)));
-    hipError_t e = hipMemcpyAsync(d_keys, keys_xyz, n * 3 * sizeof(int), hipMemcpyHostToDevice, v->stream);
-    int rc = OP_OK;
-    if (e == hipSuccess) {
-        BatchFwd F;
-        BatchInv I;
-        BatchPtrs Q{};
-        frame_params(v, pose, pose_inv, &F.f[0], &I.f[0]);
-        Q.depth[0] = depth; Q.rgb[0] = c;
-        rc = vol_enqueue_batch(v, F, I, Q, 1, depth_fmt, false, false, d_keys, (unsigned)n);
-        if (rc == OP_OK) rc = vol_check(v);
-    }
-    (void)hipStreamSynchronize(v->stream);
-    op::cached_free(d_keys);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "copying the cube list failed: %s", hipGetErrorString(e));
-    return rc;
+    OP_TRY(s.alloc(&d_keys, n * 3));
+    OP_HIP(hipMemcpyAsync(d_keys, keys_xyz, n * 3 * sizeof(int), hipMemcpyHostToDevice, v->stream));
+    BatchFwd F;
+    BatchInv I;
+    BatchPtrs Q{};
+    frame_params(v, pose, pose_inv, &F.f[0], &I.f[0]);
+    Q.depth[0] = depth; Q.rgb[0] = c;
+    OP_TRY(vol_enqueue_batch(v, F, I, Q, 1, depth_fmt, false, false, d_keys, (unsigned)n));
+    return vol_check(v);
 }
 
 int op_volume_integrate_sequence(op_volume* v, const void* depth, size_t depth_stride_bytes, int depth_fmt, const uint8_t* rgb,
@@ -1387,14 +1396,12 @@ int op_volume_has_cube(op_volume* v, int32_t x, int32_t y, int32_t z, int* prese
     OP_VOL(v);
     if (!present) return fail(OP_ERR_INVALID, "null present");
     OP_TRY(vol_check(v));
+    op::Scope s;
+    s.bind(v->stream);
     int* d_out = nullptr;
-    OP_HIP(op::cached_malloc((void**)&d_out, sizeof(int)));
+    OP_TRY(s.alloc(&d_out, 1));
     hipLaunchKernelGGL(k_has_cube, dim3(1), dim3(1), 0, v->stream, v->view(), x, y, z, d_out); // cube_map.find (CubeHandler.h:129-132)
-    hipError_t e = hipMemcpyAsync(present, d_out, sizeof(int), hipMemcpyDeviceToHost, v->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(v->stream);
-    op::cached_free(d_out);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "has_cube failed: %s", hipGetErrorString(e));
-    return OP_OK;
+    return s.output(present, (const int*)d_out, 1, OP_MEM_HOST);
 }
 
 } // extern "C"

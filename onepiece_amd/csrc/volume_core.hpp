@@ -613,6 +613,6 @@ void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int n
 bool vol_fusion_keeps_summaries(const op_volume* v); // integrate.hip: this batch's k_integrate restates the raycaster's summaries of the blocks it changes
 void kc_trace_dump(op_volume* v);            // -DKC_TRACE builds only
 // volume_ops.hip: the count and emit passes of k_mesh into device buffers (op_volume_extract_mesh; mesh_cluster.hip simplifies the soup in place)
-int vol_mesh_soup(op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, bool emit, size_t cap_vertices, float** d_pts_out,
-                  float** d_col_out, size_t* n_vertices);
+int vol_mesh_soup(op::Scope& out, op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, bool emit, size_t cap_vertices,
+                  float** d_pts_out, float** d_col_out, size_t* n_vertices);
 } // namespace opv

@@ -164,19 +164,6 @@ __global__ void __launch_bounds__(256) k_gc_move(float* __restrict__ pool, int* 
     if (threadIdx.x < 3) keys[3 * (size_t)dst + threadIdx.x] = keys[3 * (size_t)src + threadIdx.x];
 }
 
-// temporary device buffers of one call, back to the buffer cache when it ends (the stream is idle by then)
-struct GcScratch {
-    std::vector<void*> owned;
-    ~GcScratch() { for (void* p : owned) op::cached_free(p); }
-    template <class T> hipError_t get(T** out, size_t count) {
-        void* p = nullptr;
-        const hipError_t e = op::cached_malloc(&p, count * sizeof(T));
-        if (e == hipSuccess) owned.push_back(p);
-        *out = static_cast<T*>(p);
-        return e;
-    }
-};
-
 } // namespace
 
 extern "C" {
@@ -198,13 +185,14 @@ int op_volume_collect_garbage(op_volume* v, float min_weight, const int32_t box_
     GcBox box{};
     if (box_lo) { box.use = 1; for (int a = 0; a < 3; ++a) { box.lo[a] = box_lo[a]; box.hi[a] = box_hi[a]; } }
     const unsigned chunks = (n + kGcChunk - 1) / kGcChunk;
-    GcScratch tmp;
+    op::Scope tmp;
+    tmp.bind(v->stream);
     unsigned char* flags = nullptr;
     unsigned *counts = nullptr, *chunk_off = nullptr, *res = nullptr, *holes = nullptr, *tails = nullptr;
-    OP_HIP(tmp.get(&flags, (size_t)chunks * kGcChunk));
-    OP_HIP(tmp.get(&counts, (size_t)chunks * 4));
-    OP_HIP(tmp.get(&chunk_off, (size_t)chunks));
-    OP_HIP(tmp.get(&res, (size_t)kGcResWords));
+    OP_TRY(tmp.alloc(&flags, (size_t)chunks * kGcChunk));
+    OP_TRY(tmp.alloc(&counts, (size_t)chunks * 4));
+    OP_TRY(tmp.alloc(&chunk_off, (size_t)chunks));
+    OP_TRY(tmp.alloc(&res, (size_t)kGcResWords));
     OP_HIP(hipMemsetAsync(flags, kGcBeyond, (size_t)chunks * kGcChunk, v->stream));
     hipLaunchKernelGGL(k_gc_classify, dim3((n + 3) / 4), dim3(256), 0, v->stream, (const float*)v->pool, (const int*)v->keys, n, min_weight, box, flags);
     hipLaunchKernelGGL(k_gc_count, dim3(chunks), dim3(256), 0, v->stream, (const unsigned*)flags, counts);
@@ -220,8 +208,8 @@ int op_volume_collect_garbage(op_volume* v, float min_weight, const int32_t box_
     if (m == n) { v->last_collect = st; if (stats) *stats = st; return OP_OK; } // nothing to drop: the volume is untouched
 
     if (moved) {
-        OP_HIP(tmp.get(&holes, (size_t)moved));
-        OP_HIP(tmp.get(&tails, (size_t)moved));
+        OP_TRY(tmp.alloc(&holes, (size_t)moved));
+        OP_TRY(tmp.alloc(&tails, (size_t)moved));
         OP_HIP(hipMemsetAsync(holes, 0xff, sizeof(unsigned) * (size_t)moved, v->stream)); // an entry the lists did not fill would fail k_gc_move's guard
         OP_HIP(hipMemsetAsync(tails, 0xff, sizeof(unsigned) * (size_t)moved, v->stream));
         hipLaunchKernelGGL(k_gc_lists, dim3(chunks), dim3(256), 0, v->stream, (const unsigned*)flags, (const unsigned*)chunk_off, (const unsigned*)res, holes, tails);

@@ -526,17 +526,16 @@ int op_volume_download(op_volume* v, int32_t* keys_xyz, float* voxels_aos, size_
     if (keys_xyz && take) OP_HIP(hipMemcpy(keys_xyz, v->keys, take * 3 * sizeof(int), hipMemcpyDeviceToHost));
     if (voxels_aos && take) {
         const size_t chunk = 8192; // 80 MiB of staging
+        op::Scope s;
+        s.bind(v->stream);
         float* stage = nullptr;
-        OP_HIP(op::cached_malloc((void**)&stage, std::min(chunk, take) * kBlockFloats * sizeof(float)));
+        OP_TRY(s.alloc(&stage, std::min(chunk, take) * kBlockFloats));
         for (size_t first = 0; first < take; first += chunk) {
             const size_t cnt = std::min(chunk, take - first);
             hipLaunchKernelGGL(k_export_aos, dim3((unsigned)cnt), dim3(512), 0, v->stream, (const float*)v->pool, first, stage);
-            hipError_t e = hipStreamSynchronize(v->stream);
-            if (e == hipSuccess)
-                e = hipMemcpy(voxels_aos + first * kBlockFloats, stage, cnt * kBlockFloats * sizeof(float), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { op::cached_free(stage); return fail(OP_ERR_HIP, "download failed: %s", hipGetErrorString(e)); }
+            OP_HIP(hipStreamSynchronize(v->stream));
+            OP_HIP(hipMemcpy(voxels_aos + first * kBlockFloats, stage, cnt * kBlockFloats * sizeof(float), hipMemcpyDeviceToHost));
         }
-        op::cached_free(stage);
     }
     return OP_OK;
 }
@@ -564,31 +563,27 @@ int op_volume_upload(op_volume* v, const int32_t* keys_xyz, const float* voxels_
     }
     { unsigned nb = 0; OP_TRY(vol_block_count(v, &nb)); vol_mark_foreign(v, (unsigned long long)nb + uniq.size()); } // caller-supplied voxel data in every block that exists after this call
     const size_t chunk = 8192;
+    op::Scope s;
+    s.bind(v->stream);
     int *d_keys = nullptr, *d_slots = nullptr;
     float* d_vox = nullptr;
-    OP_HIP(op::cached_malloc((void**)&d_keys, chunk * 3 * sizeof(int)));
-    OP_HIP(op::cached_malloc((void**)&d_slots, chunk * sizeof(int)));
-    OP_HIP(op::cached_malloc((void**)&d_vox, chunk * kBlockFloats * sizeof(float)));
+    OP_TRY(s.alloc(&d_keys, chunk * 3));
+    OP_TRY(s.alloc(&d_slots, chunk));
+    OP_TRY(s.alloc(&d_vox, chunk * kBlockFloats));
     std::vector<int> hk(chunk * 3);
     std::vector<float> hv(chunk * kBlockFloats);
-    int rc = OP_OK;
-    for (size_t first = 0; first < uniq.size() && rc == OP_OK; first += chunk) {
+    for (size_t first = 0; first < uniq.size(); first += chunk) {
         const size_t cnt = std::min(chunk, uniq.size() - first);
         for (size_t i = 0; i < cnt; ++i) {
             std::memcpy(&hk[3 * i], keys_xyz + 3 * uniq[first + i], 3 * sizeof(int));
             std::memcpy(&hv[i * kBlockFloats], voxels_aos + uniq[first + i] * kBlockFloats, kBlockFloats * sizeof(float));
         }
-        hipError_t e = hipMemcpy(d_keys, hk.data(), cnt * 3 * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_vox, hv.data(), cnt * kBlockFloats * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_insert_keys, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, v->stream, v->view(), (const int*)d_keys, cnt, d_slots, v->state);
-            hipLaunchKernelGGL(k_import_aos, dim3((unsigned)cnt), dim3(512), 0, v->stream, v->pool, (const int*)d_slots, (const int*)v->tvals, (const float*)d_vox);
-            e = hipStreamSynchronize(v->stream);
-        }
-        if (e != hipSuccess) rc = fail(OP_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
+        OP_HIP(hipMemcpy(d_keys, hk.data(), cnt * 3 * sizeof(int), hipMemcpyHostToDevice));
+        OP_HIP(hipMemcpy(d_vox, hv.data(), cnt * kBlockFloats * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_insert_keys, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, v->stream, v->view(), (const int*)d_keys, cnt, d_slots, v->state);
+        hipLaunchKernelGGL(k_import_aos, dim3((unsigned)cnt), dim3(512), 0, v->stream, v->pool, (const int*)d_slots, (const int*)v->tvals, (const float*)d_vox);
+        OP_HIP(hipStreamSynchronize(v->stream));
     }
-    op::cached_free(d_keys); op::cached_free(d_slots); op::cached_free(d_vox);
-    if (rc != OP_OK) return rc;
     return vol_check(v);
 }
 
@@ -606,13 +601,13 @@ int op_volume_merge(op_volume* dst, op_volume* src) {
     if (!ns) return OP_OK;
     OP_TRY(vol_reserve(dst, (unsigned long long)nd + ns)); // worst case: no block in common
     vol_mark_foreign(dst, (unsigned long long)nd + ns); // merged means: general weights in the blocks that exist after this call
+    op::Scope s;
+    s.bind(dst->stream);
     int* d_slots = nullptr;
-    OP_HIP(op::cached_malloc((void**)&d_slots, (size_t)ns * sizeof(int)));
+    OP_TRY(s.alloc(&d_slots, (size_t)ns));
     hipLaunchKernelGGL(k_insert_keys, dim3((ns + 255) / 256), dim3(256), 0, dst->stream, dst->view(), (const int*)src->keys, (size_t)ns, d_slots, dst->state);
     hipLaunchKernelGGL(k_merge_blocks, dim3(ns), dim3(512), 0, dst->stream, dst->pool, (const float*)src->pool, (const int*)d_slots, (const int*)dst->tvals);
-    hipError_t e = hipStreamSynchronize(dst->stream);
-    op::cached_free(d_slots);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "merge failed: %s", hipGetErrorString(e));
+    OP_HIP(hipStreamSynchronize(dst->stream));
     return vol_check(dst);
 }
 
@@ -736,51 +731,41 @@ int op_volume_point_cloud(op_volume* v, float* xyz, float* colors, size_t cap, s
     OP_TRY(vol_block_count(v, &nb));
     *n = 0;
     if (!nb) return OP_OK;
+    op::Scope s;
+    s.bind(v->stream);
     unsigned *d_counts = nullptr, *d_offsets = nullptr;
-    float *d_xyz = nullptr, *d_col = nullptr;
-    int rc = OP_OK;
-    hipError_t e = op::cached_malloc((void**)&d_counts, nb * sizeof(unsigned));
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_offsets, nb * sizeof(unsigned));
+    OP_TRY(s.alloc(&d_counts, nb));
+    OP_TRY(s.alloc(&d_offsets, nb));
     std::vector<unsigned> cnt(nb), off(nb);
+    hipLaunchKernelGGL(k_point_cloud, dim3(nb), dim3(512), 0, v->stream, v->view(), v->res, v->trunc, d_counts, (const unsigned*)nullptr,
+                       (float*)nullptr, (float*)nullptr);
+    OP_HIP(hipStreamSynchronize(v->stream));
+    OP_HIP(hipMemcpy(cnt.data(), d_counts, nb * sizeof(unsigned), hipMemcpyDeviceToHost));
     size_t total = 0;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_point_cloud, dim3(nb), dim3(512), 0, v->stream, v->view(), v->res, v->trunc, d_counts, (const unsigned*)nullptr,
-                           (float*)nullptr, (float*)nullptr);
-        e = hipStreamSynchronize(v->stream);
-        if (e == hipSuccess) e = hipMemcpy(cnt.data(), d_counts, nb * sizeof(unsigned), hipMemcpyDeviceToHost);
-        for (unsigned b = 0; b < nb; ++b) { off[b] = (unsigned)total; total += cnt[b]; }
-    }
+    for (unsigned b = 0; b < nb; ++b) { off[b] = (unsigned)total; total += cnt[b]; }
     *n = total;
-    if (e == hipSuccess && xyz && colors && total) {
-        if (total > cap) rc = fail(OP_ERR_CAPACITY, "point cloud has %zu points, buffer holds %zu", total, cap);
-        else {
-            e = hipMemcpy(d_offsets, off.data(), nb * sizeof(unsigned), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = op::cached_malloc((void**)&d_xyz, total * 12);
-            if (e == hipSuccess) e = op::cached_malloc((void**)&d_col, total * 12);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_point_cloud, dim3(nb), dim3(512), 0, v->stream, v->view(), v->res, v->trunc, (unsigned*)nullptr,
-                                   (const unsigned*)d_offsets, d_xyz, d_col);
-                e = hipStreamSynchronize(v->stream);
-            }
-            if (e == hipSuccess) e = hipMemcpy(xyz, d_xyz, total * 12, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(colors, d_col, total * 12, hipMemcpyDeviceToHost);
-        }
-    }
-    void* ptrs[] = {d_counts, d_offsets, d_xyz, d_col};
-    for (void* p : ptrs)
-        if (p) op::cached_free(p);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "point cloud failed: %s", hipGetErrorString(e));
-    return rc;
+    if (!xyz || !colors || !total) return OP_OK;
+    if (total > cap) return fail(OP_ERR_CAPACITY, "point cloud has %zu points, buffer holds %zu", total, cap);
+    OP_HIP(hipMemcpy(d_offsets, off.data(), nb * sizeof(unsigned), hipMemcpyHostToDevice));
+    float *d_xyz = nullptr, *d_col = nullptr;
+    OP_TRY(s.alloc(&d_xyz, total * 3));
+    OP_TRY(s.alloc(&d_col, total * 3));
+    hipLaunchKernelGGL(k_point_cloud, dim3(nb), dim3(512), 0, v->stream, v->view(), v->res, v->trunc, (unsigned*)nullptr,
+                       (const unsigned*)d_offsets, d_xyz, d_col);
+    OP_HIP(hipStreamSynchronize(v->stream));
+    OP_HIP(hipMemcpy(xyz, d_xyz, total * 12, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(colors, d_col, total * 12, hipMemcpyDeviceToHost));
+    return OP_OK;
 }
 
 
 } // extern "C"
 
-// The count and emit passes of k_mesh into device buffers: *d_pts / *d_col (three unshared vertices per triangle; the caller returns them with
-// op::cached_free) when `emit` and the soup has at most cap_vertices vertices, the vertex count alone otherwise.  Complete on return (the volume's
-// stream is synchronised).
-int opv::vol_mesh_soup(op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, bool emit, size_t cap_vertices, float** d_pts_out,
-                       float** d_col_out, size_t* n_vertices) {
+// The count and emit passes of k_mesh into device buffers: *d_pts_out / *d_col_out (three unshared vertices per triangle, owned by `out`, the caller's Scope
+// bound to the volume's stream) when `emit` and the soup has at most cap_vertices vertices, the vertex count alone otherwise.  Complete on return (the
+// volume's stream is synchronised).
+int opv::vol_mesh_soup(op::Scope& out, op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, bool emit, size_t cap_vertices,
+                       float** d_pts_out, float** d_col_out, size_t* n_vertices) {
     if (!tri_table || !edge_pairs || !n_vertices) return fail(OP_ERR_INVALID, "null argument");
     for (int c = 0; c < 256; ++c)
         for (int i = 0; i < 16; ++i) {
@@ -807,58 +792,40 @@ int opv::vol_mesh_soup(op_volume* v, const int32_t* tri_table, const int32_t* ed
         for (unsigned b = 0; b < nb; ++b) list[b] = b;
     }
     const unsigned nl = (unsigned)list.size();
+    std::vector<signed char> tri8(tri_table, tri_table + 256 * 16); // (validated above: -1 .. 11)
+    op::Scope s; // what the two passes need besides their output
+    s.bind(v->stream);
     unsigned *d_list = nullptr, *d_counts = nullptr, *d_offsets = nullptr;
     signed char* d_tri = nullptr;
     int *d_edge = nullptr, *d_nbs = nullptr;
-    float *d_pts = nullptr, *d_col = nullptr;
-    int rc = OP_OK;
-    signed char tri8[256 * 16];
-    for (int i = 0; i < 256 * 16; ++i) tri8[i] = (signed char)tri_table[i]; // (validated above: -1 .. 11)
-    hipError_t e = op::cached_malloc((void**)&d_list, nl * sizeof(unsigned));
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_counts, nl * sizeof(unsigned));
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_offsets, nl * sizeof(unsigned));
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_tri, 256 * 16);
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_edge, 24 * sizeof(int));
-    if (e == hipSuccess) e = op::cached_malloc((void**)&d_nbs, (size_t)nl * 8 * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(d_list, list.data(), nl * sizeof(unsigned), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_tri, tri8, 256 * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_edge, edge_pairs, 24 * sizeof(int), hipMemcpyHostToDevice);
+    OP_TRY(s.alloc(&d_list, nl));
+    OP_TRY(s.alloc(&d_counts, nl));
+    OP_TRY(s.alloc(&d_offsets, nl));
+    OP_TRY(s.alloc(&d_tri, 256 * 16));
+    OP_TRY(s.alloc(&d_edge, 24));
+    OP_TRY(s.alloc(&d_nbs, (size_t)nl * 8));
+    OP_HIP(hipMemcpy(d_list, list.data(), nl * sizeof(unsigned), hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(d_tri, tri8.data(), 256 * 16, hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(d_edge, edge_pairs, 24 * sizeof(int), hipMemcpyHostToDevice));
     std::vector<unsigned> cnt(nl), off(nl);
+    hipLaunchKernelGGL(k_mesh_neighbours, dim3((nl * 8u + 255u) / 256u), dim3(256), 0, v->stream, v->view(), (const unsigned*)d_list, nl, d_nbs);
+    hipLaunchKernelGGL(k_mesh, dim3(nl), dim3(512), 0, v->stream, v->view(), v->res, (const signed char*)d_tri, (const int*)d_edge, (const unsigned*)d_list,
+                       (const int*)d_nbs, d_counts, (const unsigned*)nullptr, (float*)nullptr, (float*)nullptr);
+    OP_HIP(hipStreamSynchronize(v->stream));
+    OP_HIP(hipMemcpy(cnt.data(), d_counts, nl * sizeof(unsigned), hipMemcpyDeviceToHost));
     size_t total_tri = 0;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_mesh_neighbours, dim3((nl * 8u + 255u) / 256u), dim3(256), 0, v->stream, v->view(), (const unsigned*)d_list, nl, d_nbs);
-        hipLaunchKernelGGL(k_mesh, dim3(nl), dim3(512), 0, v->stream, v->view(), v->res, (const signed char*)d_tri, (const int*)d_edge, (const unsigned*)d_list,
-                           (const int*)d_nbs, d_counts, (const unsigned*)nullptr, (float*)nullptr, (float*)nullptr);
-        e = hipStreamSynchronize(v->stream);
-        if (e == hipSuccess) e = hipMemcpy(cnt.data(), d_counts, nl * sizeof(unsigned), hipMemcpyDeviceToHost);
-        for (unsigned b = 0; b < nl; ++b) { off[b] = (unsigned)total_tri; total_tri += cnt[b]; }
-    }
+    for (unsigned b = 0; b < nl; ++b) { off[b] = (unsigned)total_tri; total_tri += cnt[b]; }
     const size_t total = total_tri * 3;
     *n_vertices = total;
-    if (e == hipSuccess && emit && total) {
-        if (total > cap_vertices) rc = fail(OP_ERR_CAPACITY, "mesh has %zu vertices, buffer holds %zu", total, cap_vertices);
-        else if (total_tri > 0xffffffffull / 3) rc = fail(OP_ERR_CAPACITY, "mesh too large");
-        else {
-            e = hipMemcpy(d_offsets, off.data(), nl * sizeof(unsigned), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = op::cached_malloc((void**)&d_pts, total * 12);
-            if (e == hipSuccess) e = op::cached_malloc((void**)&d_col, total * 12);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_mesh, dim3(nl), dim3(512), 0, v->stream, v->view(), v->res, (const signed char*)d_tri, (const int*)d_edge,
-                                   (const unsigned*)d_list, (const int*)d_nbs, (unsigned*)nullptr, (const unsigned*)d_offsets, d_pts, d_col);
-                e = hipStreamSynchronize(v->stream);
-            }
-        }
-    }
-    void* ptrs[] = {d_list, d_counts, d_offsets, d_tri, d_edge, d_nbs};
-    for (void* p : ptrs)
-        if (p) op::cached_free(p);
-    if (e != hipSuccess || rc != OP_OK) {
-        if (d_pts) op::cached_free(d_pts);
-        if (d_col) op::cached_free(d_col);
-        return e != hipSuccess ? fail(OP_ERR_HIP, "mesh extraction failed: %s", hipGetErrorString(e)) : rc;
-    }
-    *d_pts_out = d_pts;
-    *d_col_out = d_col;
+    if (!emit || !total) return OP_OK;
+    if (total > cap_vertices) return fail(OP_ERR_CAPACITY, "mesh has %zu vertices, buffer holds %zu", total, cap_vertices);
+    if (total_tri > 0xffffffffull / 3) return fail(OP_ERR_CAPACITY, "mesh too large");
+    OP_HIP(hipMemcpy(d_offsets, off.data(), nl * sizeof(unsigned), hipMemcpyHostToDevice));
+    OP_TRY(out.alloc(d_pts_out, total * 3));
+    OP_TRY(out.alloc(d_col_out, total * 3));
+    hipLaunchKernelGGL(k_mesh, dim3(nl), dim3(512), 0, v->stream, v->view(), v->res, (const signed char*)d_tri, (const int*)d_edge,
+                       (const unsigned*)d_list, (const int*)d_nbs, (unsigned*)nullptr, (const unsigned*)d_offsets, *d_pts_out, *d_col_out);
+    OP_HIP(hipStreamSynchronize(v->stream));
     return OP_OK;
 }
 
@@ -867,16 +834,14 @@ extern "C" {
 int op_volume_extract_mesh(op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, float* points,
                            float* colors, size_t cap_vertices, size_t* n_vertices) {
     OP_VOL(v);
+    op::Scope s;
+    s.bind(v->stream);
     float *d_pts = nullptr, *d_col = nullptr;
-    OP_TRY(vol_mesh_soup(v, tri_table, edge_pairs, only_block, points && colors, cap_vertices, &d_pts, &d_col, n_vertices));
-    hipError_t e = hipSuccess;
+    OP_TRY(vol_mesh_soup(s, v, tri_table, edge_pairs, only_block, points && colors, cap_vertices, &d_pts, &d_col, n_vertices));
     if (d_pts && d_col) {
-        e = hipMemcpy(points, d_pts, *n_vertices * 12, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(colors, d_col, *n_vertices * 12, hipMemcpyDeviceToHost);
+        OP_HIP(hipMemcpy(points, d_pts, *n_vertices * 12, hipMemcpyDeviceToHost));
+        OP_HIP(hipMemcpy(colors, d_col, *n_vertices * 12, hipMemcpyDeviceToHost));
     }
-    if (d_pts) op::cached_free(d_pts);
-    if (d_col) op::cached_free(d_col);
-    if (e != hipSuccess) return fail(OP_ERR_HIP, "mesh extraction failed: %s", hipGetErrorString(e));
     return OP_OK;
 }
 

@@ -169,25 +169,22 @@ __global__ __launch_bounds__(256) void k_register_depth_scatter(const void* __re
 }
 
 // ---- host side
-struct Pinned { void* p = nullptr; ~Pinned() { if (p) op::cached_free(p); } };
-
 // one call's device state: the points are on the device, the partial rows and the folded row allocated once
 struct RegRun {
-    op_volume* v = nullptr;
-    op::Scope tmp; // (no stream of its own: everything runs on the volume's)
-    Pinned h_out;
+    op_volume* v;
+    op::Scope tmp; // (everything runs on the volume's stream)
     RegArgs A{};
     unsigned grid = 0;
-    double* d_out = nullptr;
+    double *d_out = nullptr, *h_out = nullptr;
 
-    int open(op_volume* vol, const float* d_xyz, size_t n, float max_distance) {
-        v = vol;
+    explicit RegRun(op_volume* vol) : v(vol) { tmp.bind(v->stream); }
+    int open(const float* d_xyz, size_t n, float max_distance) {
         A.xyz = d_xyz; A.n = n; A.W.res = v->res; A.W.inv_res = 1.0f / v->res; A.max_distance = max_distance;
         grid = (unsigned)std::min<size_t>((n + kRegWg - 1) / kRegWg, kRegMaxGrid);
         if (!grid) return OP_OK;
         OP_TRY(tmp.alloc(&A.partial, (size_t)grid * kRegSlots));
         OP_TRY(tmp.alloc(&d_out, (size_t)kRegSlots));
-        OP_HIP(op::cached_host_malloc(&h_out.p, sizeof(double) * kRegSlots));
+        OP_TRY(tmp.pinned(&h_out, (size_t)kRegSlots));
         return OP_OK;
     }
     // the system at T: 28 sums and 4 counts (d_rows: n x 8 on the device, or NULL)
@@ -202,9 +199,9 @@ struct RegRun {
         else hipLaunchKernelGGL(k_volume_register<false>, dim3(grid), dim3(kRegWg), 0, v->stream, V, A);
         hipLaunchKernelGGL(k_register_fold, dim3(1), dim3(kFoldWg), 0, v->stream, (const double*)A.partial, grid, d_out);
         OP_HIP(hipGetLastError());
-        OP_HIP(hipMemcpyAsync(h_out.p, d_out, sizeof(double) * kRegSlots, hipMemcpyDeviceToHost, v->stream));
+        OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * kRegSlots, hipMemcpyDeviceToHost, v->stream));
         OP_HIP(hipStreamSynchronize(v->stream));
-        const double* r = static_cast<const double*>(h_out.p);
+        const double* r = h_out;
         for (int k = 0; k < 28; ++k) sums[k] = r[k];
         for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k]; // whole numbers below 2^53: exact in any order
         return OP_OK;
@@ -236,8 +233,8 @@ op_volume_register_params reg_defaults(const op_volume* v) {
 
 // the Gauss-Newton loop over points that are on the device
 int reg_loop(op_volume* v, const float* d_xyz, size_t n, const float init_T[16], const op_volume_register_params& P, op_volume_register_result* out) {
-    RegRun R;
-    OP_TRY(R.open(v, d_xyz, n, P.max_distance));
+    RegRun R(v);
+    OP_TRY(R.open(d_xyz, n, P.max_distance));
     op_volume_register_result res{};
     float T[16];
     for (int k = 0; k < 16; ++k) T[k] = init_T[k];
@@ -312,10 +309,10 @@ int op_volume_register_system(op_volume* v, const float* xyz, size_t n, int mem,
     if (!sums) return fail(OP_ERR_INVALID, "op_volume_register_system: null sums");
     OP_VOL(v);
     OP_TRY(vol_check(v)); // every accepted frame is fused, the stream idle
-    RegRun R;
+    RegRun R(v);
     const float* d_xyz = nullptr;
     OP_TRY(R.tmp.input(xyz, 3 * n, mem, &d_xyz));
-    OP_TRY(R.open(v, d_xyz, n, max_distance));
+    OP_TRY(R.open(d_xyz, n, max_distance));
     float* d_rows = rows;
     if (rows && n && mem == OP_MEM_HOST) OP_TRY(R.tmp.alloc(&d_rows, 8 * n));
     uint64_t c[4];
@@ -337,6 +334,7 @@ int op_volume_register_points(op_volume* v, const float* xyz, size_t n, int mem,
     OP_TRY(vol_check(v));
     const op_volume_register_params P = params ? *params : reg_defaults(v);
     op::Scope up;
+    up.bind(v->stream);
     const float* d_xyz = nullptr;
     OP_TRY(up.input(xyz, 3 * n, mem, &d_xyz)); // uploaded once
     return reg_loop(v, d_xyz, n, init_T, P, result);
@@ -361,6 +359,7 @@ int op_volume_register_depth(op_volume* v, const op_camera* cam, const void* dep
     SubGrid G{c.width, c.height, (c.width + pixel_stride - 1) / pixel_stride, (c.height + pixel_stride - 1) / pixel_stride, pixel_stride};
     const size_t npix = (size_t)c.width * c.height, nsub = (size_t)G.sw * G.sh;
     op::Scope tmp;
+    tmp.bind(v->stream);
     const void* d_depth = depth;
     if (mem == OP_MEM_HOST) {
         const unsigned char* d = nullptr;

@@ -184,7 +184,8 @@ int op_volume_sample(op_volume* v, const float* xyz, size_t n, int mem, const fl
     OP_TRY(vol_check(v)); // every accepted frame is fused, the stream idle
     if (n == 0) return OP_OK;
 
-    op::Scope tmp; // (no stream of its own: the kernel runs on the volume's)
+    op::Scope tmp;
+    tmp.bind(v->stream);
     SampleArgs A{};
     A.n = n;
     A.has_T = T ? 1 : 0;
@@ -199,8 +200,8 @@ int op_volume_sample(op_volume* v, const float* xyz, size_t n, int mem, const fl
     }
     const unsigned grid = (unsigned)std::min<size_t>((n + kSampleWg - 1) / kSampleWg, kSampleMaxGrid);
     OP_TRY(tmp.alloc(&A.rows, (size_t)grid));
-    struct Pinned { void* p = nullptr; ~Pinned() { if (p) op::cached_free(p); } } h_rows;
-    if (stats) OP_HIP(op::cached_host_malloc(&h_rows.p, sizeof(SampleRow) * grid));
+    SampleRow* h_rows = nullptr;
+    if (stats) OP_TRY(tmp.pinned(&h_rows, (size_t)grid));
 
     const VolView V = v->view();
     const dim3 g(grid), b(kSampleWg);
@@ -210,7 +211,7 @@ int op_volume_sample(op_volume* v, const float* xyz, size_t n, int mem, const fl
     else if (gradients) hipLaunchKernelGGL((k_volume_sample<OP_SAMPLE_TRILINEAR, false, true>), g, b, 0, v->stream, V, A);
     else hipLaunchKernelGGL((k_volume_sample<OP_SAMPLE_TRILINEAR, false, false>), g, b, 0, v->stream, V, A);
     OP_HIP(hipGetLastError());
-    if (stats) OP_HIP(hipMemcpyAsync(h_rows.p, A.rows, sizeof(SampleRow) * grid, hipMemcpyDeviceToHost, v->stream));
+    if (stats) OP_HIP(hipMemcpyAsync(h_rows, A.rows, sizeof(SampleRow) * grid, hipMemcpyDeviceToHost, v->stream));
     OP_HIP(hipStreamSynchronize(v->stream));
     if (mem == OP_MEM_HOST) {
         if (voxels) OP_HIP(hipMemcpy(voxels, A.voxels, sizeof(float) * 5 * n, hipMemcpyDeviceToHost));
@@ -218,7 +219,7 @@ int op_volume_sample(op_volume* v, const float* xyz, size_t n, int mem, const fl
         if (status) OP_HIP(hipMemcpy(status, A.status, n, hipMemcpyDeviceToHost));
     }
     if (stats) {
-        const SampleRow* rows = static_cast<const SampleRow*>(h_rows.p);
+        const SampleRow* rows = h_rows;
         op_volume_sample_stats s{};
         s.queries = n;
         for (unsigned k = 0; k < grid; ++k) { // in index order, in double

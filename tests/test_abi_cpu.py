@@ -319,11 +319,11 @@ def test_new_volume_entry_points_refuse_without_a_volume(hip):
 
 
 def test_select_option_constants_match_the_header():
-    """OP_VOLUME_OPT_SELECT and its values: _lib.py mirrors include/onepiece_hip.h."""
+    """OP_VOLUME_OPT_SELECT and its values, and the allocation-fault test hook: _lib.py mirrors include/onepiece_hip.h."""
     import re
     from onepiece_amd import _lib as L
     text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "onepiece_hip.h")).read()
-    for name in ("OP_VOLUME_OPT_SELECT", "OP_VOLUME_SELECT_AUTO", "OP_VOLUME_SELECT_DIRECT"):
+    for name in ("OP_VOLUME_OPT_SELECT", "OP_VOLUME_SELECT_AUTO", "OP_VOLUME_SELECT_DIRECT", "OP_RUNTIME_OPT_ALLOC_FAULT"):
         m = re.search(r"#define\s+%s\s+(-?\d+)" % name, text)
         assert m and int(m.group(1)) == getattr(L, name), name
 
