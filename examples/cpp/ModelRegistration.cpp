@@ -3,7 +3,7 @@
 // pose that was found.  The registration is point-to-plane against the field itself (op_volume_register_depth states the definition): the trilinear
 // sdf at a transformed point is the residual, its normalised central difference the normal.
 //
-//   ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused]
+//   ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused] [--color off|on [--color-scale S]]
 //   --synthetic N STRIDE SEED  N frames of the analytic room of LiveFusion.cpp: frame k is step FIRST + k * STRIDE of a 1000-step orbit, SEED picks FIRST
 //   --perturb K                every K-th frame is re-registered (default 20); its start is its true pose moved by 3-4 cm and about a degree
 //   --iters I                  Gauss-Newton iterations per frame (default 10; min_step is 0, so both paths take all of them)
@@ -11,6 +11,9 @@
 //                              doubles come back per iteration
 //   --path sample              the only route there was before it: per iteration op_volume_sample writes sdf, gradient and status of every point
 //                              (33 bytes), the host reads them back and forms the same rows and sums in a loop (in point order, in double)
+//   --color on                 (fused path only; default off) op_volume_register_rgbd: the colour term -- the model's intensity at the point against the
+//                              frame's own -- joins the system with weight --color-scale (default 1); one line per frame (pose error, sdf rmse, colour
+//                              rmse, coloured points) precedes the JSON line, which gains "color_scale", "rmse_color" and "colored_last"
 // Both paths solve with op_ldlt_solve6, update with op_se3_exp and the same float32 product, and gate with the same rules; their sums differ in
 // the order of the additions only.  It prints one JSON line: pose errors before and after, iterations, stage times (host clock).
 #include <algorithm>
@@ -201,8 +204,9 @@ double Median(std::vector<double> v) {
 int main(int argc, char* argv[]) {
     long synthetic[3] = {0, 1, 1}, every = 20, iters = 10;
     bool is_synthetic = false, bad = false;
-    std::string path = "fused";
-    float res = 0.01f;
+    std::string path = "fused", color = "off";
+    float res = 0.01f, color_scale = 1.0f;
+    bool have_scale = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--synthetic" && i + 3 < argc) { is_synthetic = true; for (int k = 0; k < 3; ++k) synthetic[k] = std::atol(argv[++i]); }
@@ -210,11 +214,14 @@ int main(int argc, char* argv[]) {
         else if (a == "--perturb" && i + 1 < argc) every = std::atol(argv[++i]);
         else if (a == "--iters" && i + 1 < argc) iters = std::atol(argv[++i]);
         else if (a == "--path" && i + 1 < argc) path = argv[++i];
+        else if (a == "--color" && i + 1 < argc) color = argv[++i];
+        else if (a == "--color-scale" && i + 1 < argc) { color_scale = static_cast<float>(std::atof(argv[++i])); have_scale = true; }
         else bad = true;
     }
     const long n = synthetic[0], stride = synthetic[1];
-    if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || !(res > 0) || every < 1 || iters < 0 || iters > 1000 || (path != "sample" && path != "fused")) {
-        std::cout << "usage::ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused]" << std::endl;
+    if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || !(res > 0) || every < 1 || iters < 0 || iters > 1000 || (path != "sample" && path != "fused") ||
+        (color != "off" && color != "on") || (color == "on" && path != "fused") || (have_scale && color != "on") || !(color_scale >= 0)) {
+        std::cout << "usage::ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused] [--color off|on [--color-scale S]]" << std::endl;
         return bad || argc > 1 ? 2 : 0;
     }
     const long first = ((synthetic[2] + 999) % 1000) * 97 % 1000;
@@ -239,8 +246,13 @@ int main(int argc, char* argv[]) {
     if (op_volume_register_default_params(volume.Handle(), &params) != OP_OK) return 1;
     params.max_iterations = static_cast<int>(iters);
     params.min_step = 0.0f;
-    std::vector<double> register_ms, per_iteration_ms, before_m, before_deg, after_m, after_deg, rmse, first_rmse;
-    unsigned long long points = 0, used = 0;
+    const bool with_color = color == "on";
+    op_volume_register_color_params color_params;
+    if (op_volume_register_color_default_params(volume.Handle(), &color_params) != OP_OK) return 1;
+    color_params.base = params;
+    color_params.color_scale = color_scale;
+    std::vector<double> register_ms, per_iteration_ms, before_m, before_deg, after_m, after_deg, rmse, first_rmse, rmse_color;
+    unsigned long long points = 0, used = 0, colored = 0;
     long frames = 0, iterations = 0;
     double t_out = 0, t_back = 0;
     for (long k = 0; k < n; k += every, ++frames) {
@@ -256,7 +268,20 @@ int main(int argc, char* argv[]) {
         Perturbed(truth, k, start);
         Outcome got;
         t0 = std::chrono::steady_clock::now();
-        if (path == "fused") {
+        if (with_color) {
+            op_volume_register_color_result c;
+            if (!volume.RegisterRGBD(depth, rgb, FromRowMajor(start), 1, &color_params, &c)) return 1;
+            const op_volume_register_result& r = c.base;
+            for (int a = 0; a < 16; ++a) got.T[a] = r.T[a];
+            got.iterations = r.iterations; got.used = r.used; got.rmse = r.rmse; got.first_rmse = r.first_rmse;
+            points = r.used + r.invalid + r.no_gradient + r.too_far;
+            colored = c.colored;
+            rmse_color.push_back(c.rmse_color);
+            double m = 0, deg = 0;
+            PoseError(got.T, truth, &m, &deg);
+            std::printf("frame %ld: pose error %.3f mm / %.5f deg, rmse %.6f (first %.6f), colour rmse %.6f (first %.6f), coloured %llu of %llu used\n", k, m * 1000.0, deg,
+                        r.rmse, r.first_rmse, c.rmse_color, c.first_rmse_color, static_cast<unsigned long long>(c.colored), static_cast<unsigned long long>(r.used));
+        } else if (path == "fused") {
             op_volume_register_result r;
             if (!volume.RegisterDepth(depth, FromRowMajor(start), 1, &params, &r)) return 1;
             for (int a = 0; a < 16; ++a) got.T[a] = r.T[a];
@@ -298,7 +323,9 @@ int main(int argc, char* argv[]) {
               << ", \"error_before\": {\"mm\": " << Median(before_m) * 1000.0 << ", \"deg\": " << Median(before_deg) << "}"
               << ", \"error_after\": {\"mm\": " << Median(after_m) * 1000.0 << ", \"deg\": " << Median(after_deg) << ", \"max_mm\": " << *std::max_element(after_m.begin(), after_m.end()) * 1000.0
               << ", \"max_deg\": " << *std::max_element(after_deg.begin(), after_deg.end()) << "}"
-              << ", \"rmse\": {\"first\": " << Median(first_rmse) << ", \"final\": " << Median(rmse) << "}"
+              << ", \"rmse\": {\"first\": " << Median(first_rmse) << ", \"final\": " << Median(rmse) << "}";
+    if (with_color) std::cout << ", \"color_scale\": " << color_scale << ", \"rmse_color\": " << Median(rmse_color) << ", \"colored_last\": " << colored;
+    std::cout
               << ", \"ms\": {\"fuse\": " << t_fuse * 1000.0 << ", \"deintegrate\": " << t_out * 1000.0 << ", \"reintegrate\": " << t_back * 1000.0
               << ", \"register_median\": " << Median(register_ms) << ", \"per_iteration_median\": " << Median(per_iteration_ms) << "}}" << std::endl;
     return 0;

@@ -185,6 +185,25 @@ class CubeHandler {
     std::shared_ptr<registration::RegistrationResult> RegisterDepth(const cv::Mat& depth, const geometry::TransformationMatrix& init_pose, int pixel_stride = 1,
                                                                     const op_volume_register_params* params = nullptr, op_volume_register_result* details = nullptr);
     bool RegistrationSystem(const geometry::Point3List& points, const geometry::TransformationMatrix& T, float max_distance, double sums[28], uint64_t counts[4]);
+    // The same with the colour term (op_volume_register_color_points states the definition): the model's intensity at the point against the
+    // observed one is a second residual, which holds a view that the sdf alone lets slide along a wall.  The result's rmse stays the sdf rmse;
+    // the colour rmse and the count of coloured points go to *details.  params == nullptr: the defaults above, color_scale 1, no colour gate.
+    //   RegisterColoredPointCloud  the observed intensity of point i is I(pcd.colors[i]) = (0.114f c0 + 0.587f c1) + 0.299f c2.  LoadFromRGBD leaves
+    //                       the pixel's three bytes / 255.0f there in STORED channel order (PointCloud.cpp:40-42), the order the volume's colour
+    //                       planes have: a cloud loaded from a frame gets the intensities RegisterRGBD gives that frame.  A cloud without colours
+    //                       (colors.size() != points.size()) is registered with color_scale 0: RegisterPointCloud's result.
+    //   RegisterRGBD        depth as RegisterDepth, rgb CV_8UC3 of the same size.
+    //   ColorRegistrationSystem  one evaluation at T: sums[30] = the 28 above with the colour terms added, the sum of rc^2, the geometric sum of
+    //                       s^2; counts[5] = used, invalid, no_gradient, too_far, colored.  false when the call failed.
+    std::shared_ptr<registration::RegistrationResult> RegisterColoredPointCloud(const geometry::PointCloud& pcd,
+                                                                                const geometry::TransformationMatrix& init = geometry::TransformationMatrix::Identity(),
+                                                                                const op_volume_register_color_params* params = nullptr,
+                                                                                op_volume_register_color_result* details = nullptr);
+    std::shared_ptr<registration::RegistrationResult> RegisterRGBD(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& init_pose,
+                                                                   int pixel_stride = 1, const op_volume_register_color_params* params = nullptr,
+                                                                   op_volume_register_color_result* details = nullptr);
+    bool ColorRegistrationSystem(const geometry::Point3List& points, const std::vector<float>& intensity, const geometry::TransformationMatrix& T,
+                                 float max_distance, float color_scale, float max_color_residual, double sums[30], uint64_t counts[5]);
     void GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh);
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;

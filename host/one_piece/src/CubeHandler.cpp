@@ -551,6 +551,84 @@ bool CubeHandler::RegistrationSystem(const geometry::Point3List& points, const g
     ReleaseBorrowed();
     return true;
 }
+namespace {
+op_volume_register_color_result ColorRegistrationNotRun(const geometry::TransformationMatrix& init) {
+    op_volume_register_color_result r = op_volume_register_color_result();
+    r.base = RegistrationNotRun(init);
+    return r;
+}
+} // namespace
+std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterColoredPointCloud(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& init,
+                                                                                         const op_volume_register_color_params* params,
+                                                                                         op_volume_register_color_result* details) {
+    Pending();
+    op_volume_register_color_result r = ColorRegistrationNotRun(init);
+    if (Ensure()) {
+        float t[16];
+        bridge::RowMajor(init, t);
+        const size_t n = pcd.points.size();
+        op_volume_register_color_params p;
+        bool ok = true;
+        if (params) p = *params;
+        else ok = op_volume_register_color_default_params(vol, &p) == OP_OK;
+        std::vector<float> intensity;
+        if (pcd.colors.size() == n) { // stored channel order, byte / 255 (LoadFromRGBD)
+            intensity.resize(n);
+            for (size_t i = 0; i < n; ++i) {
+                const float c0 = pcd.colors[i](0), c1 = pcd.colors[i](1), c2 = pcd.colors[i](2);
+                const float a = 0.114f * c0, b = 0.587f * c1, c = 0.299f * c2; // every product and sum rounded separately
+                const float ab = a + b;
+                intensity[i] = ab + c;
+            }
+        } else {
+            p.color_scale = 0.0f;
+        }
+        if (!ok || op_volume_register_color_points(vol, bridge::Floats(pcd.points), intensity.empty() ? nullptr : intensity.data(), n, OP_MEM_HOST, t, &p, &r) != OP_OK) {
+            Report("RegisterColoredPointCloud");
+            r = ColorRegistrationNotRun(init);
+        } else {
+            ReleaseBorrowed(); // (the call synchronised the volume)
+        }
+    }
+    if (details) *details = r;
+    return RegistrationOutcome(r.base);
+}
+std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterRGBD(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& init_pose,
+                                                                            int pixel_stride, const op_volume_register_color_params* params,
+                                                                            op_volume_register_color_result* details) {
+    Pending();
+    op_volume_register_color_result r = ColorRegistrationNotRun(init_pose);
+    if (Ensure()) {
+        float t[16];
+        bridge::RowMajor(init_pose, t);
+        const op_camera pod = camera.Pod();
+        if (op_volume_register_rgbd(vol, &pod, depth.data, bridge::DepthFormat(depth), rgb.data, OP_MEM_HOST, pixel_stride, t, params, &r) != OP_OK) {
+            Report("RegisterRGBD");
+            r = ColorRegistrationNotRun(init_pose);
+        } else {
+            ReleaseBorrowed();
+        }
+    }
+    if (details) *details = r;
+    return RegistrationOutcome(r.base);
+}
+bool CubeHandler::ColorRegistrationSystem(const geometry::Point3List& points, const std::vector<float>& intensity, const geometry::TransformationMatrix& T,
+                                          float max_distance, float color_scale, float max_color_residual, double sums[30], uint64_t counts[5]) {
+    Pending();
+    for (int k = 0; k < 30; ++k) sums[k] = 0.0;
+    for (int k = 0; k < 5; ++k) counts[k] = 0;
+    if (!Ensure()) return false;
+    float t[16];
+    bridge::RowMajor(T, t);
+    const float* y = intensity.size() == points.size() && !intensity.empty() ? intensity.data() : nullptr; // (a missing intensity is the library's refusal)
+    if (op_volume_register_color_system(vol, bridge::Floats(points), y, points.size(), OP_MEM_HOST, t, max_distance, color_scale, max_color_residual, sums, counts,
+                                        nullptr) != OP_OK) {
+        Report("ColorRegistrationSystem");
+        return false;
+    }
+    ReleaseBorrowed();
+    return true;
+}
 op_volume_sample_stats CubeHandler::DistanceToModel(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& pose) {
     Pending();
     op_volume_sample_stats st = {0, 0, 0, 0, 0.0, 0.0, 0.0f};

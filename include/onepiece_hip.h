@@ -616,6 +616,60 @@ int op_volume_register_depth(op_volume *v, const op_camera *cam /* NULL: the vol
                              int pixel_stride, const float init_pose[16], const op_volume_register_params *params,
                              op_volume_register_result *result);
 
+/* The colour term of the registration against the field (csrc/volume_register.hip, the COLOR instantiations of k_volume_register; NO reference
+ * counterpart).  The sdf says nothing about motion in a surface's own plane; the fused colour does.  Every point carries an observed intensity
+ * y_i (a float in the volume's colour units, byte / 255), and the model's intensity at the transformed point, with its central difference as
+ * gradient, gives a second residual and a second row.  Every per-point operation below is float32 and rounded separately; nothing is contracted.
+ *   1. p, s, d, l2, the USED rule, n, the row j and the counts used / invalid / no_gradient / too_far are exactly op_volume_register_system's.
+ *   2. The intensity of a colour triple in stored channel order is I(c) = (0.114f c0 + 0.587f c1) + 0.299f c2.
+ *   3. The model intensity is m = I(c), c the three colour sums of the same OP_SAMPLE_TRILINEAR sample at p that gives s: the same taps and
+ *      weights, each plane accumulated in tap order from 0.
+ *   4. g_a = (I(c(p + h e_a)) - I(c(p - h e_a))) / res, h = 0.5f * res: the colour sums of the six samples already taken for d, one float32
+ *      subtraction and one float32 divide.  A tap is valid for colour exactly when it is valid for sdf (weight > 0): a used point always has g.
+ *   5. rc = m - y_i.
+ *   6. The point is COLOURED iff it is used, y_i is finite and (max_color_residual <= 0 or fabsf(rc) <= max_color_residual).  A point that is
+ *      used but not coloured keeps its geometric contribution.
+ *   7. jc = color_scale * (g0, g1, g2, p1 g2 - p2 g1, p2 g0 - p0 g2, p0 g1 - p1 g0) and rcs = color_scale * rc: each product one float32
+ *      operation, the scaling applied after the cross products.
+ *   8. Slot k of sums[0..27] receives per used point the geometric term as in op_volume_register_system and, for a coloured point, the
+ *      colour term (double)(jc_a jc_b), (double)(rcs jc_a), (double)rcs * (double)rcs: geometric + colour, added in that order into one double
+ *      before the reduction.
+ *   9. sums[28] += (double)rc * (double)rc over coloured points (unscaled); sums[29] += (double)s * (double)s over used points (the geometric
+ *      part of sums[27] alone).
+ *  10. counts = {used, invalid, no_gradient, too_far, colored}.
+ *  11. Slots 0..27 and the first four counts are reduced exactly as point 9 of op_volume_register_system states.  The three other quantities
+ *      (sums[28], sums[29], colored) are reduced over the wave per trip by a butterfly -- partner lanes 32, 16, 8, 4, 2, 1 apart, in that order --
+ *      and the trips added in order; then, like the rest, the four waves in order, one row of 35 per workgroup, and a second kernel adds the rows
+ *      (at most 1024) in index order -- row r, r + 16, ... per row lane, then the 16 row lanes in order.  Fixed for a given n: two calls give the
+ *      same bits, with and without rows.  No floating-point atomics.
+ * color_scale == 0: the colour planes and the intensities are not read (intensity may be NULL), colored and sums[28] are 0, sums[29] is
+ * sums[27], and sums[0..27], the first four counts, T and every field of result->base are bit for bit those of the geometric entries above (the
+ * geometric kernel runs).  color_scale < 0 or not finite: OP_ERR_INVALID.
+ * op_volume_register_color_system evaluates this once: sums[30], counts[5] (host; counts may be NULL) and optionally rows: n x 16 floats in `mem`,
+ * {j[6], s, used, jc[6], rcs, colored}: sixteen zeros for an unused point, zeros in the second half for an uncoloured one.
+ * op_volume_register_color_points is op_volume_register_points' host loop (op_ldlt_solve6, op_se3_exp, the float32 product, the same stop rules
+ * and statuses) around this system.  result->base describes the geometry as before -- base.rmse = sqrt(sums[29] / used) stays the sdf rmse --;
+ * colored and rmse_color = sqrt(sums[28] / colored) (0 without a coloured point) describe the returned pose, first_colored / first_rmse_color
+ * init_T.  Defaults (params == NULL, op_volume_register_color_default_params): the base as above, color_scale 1 (equal weight, as the dense
+ * tracker's LAMBDA_HYBRID_DEPTH 0.5 gives its two terms), max_color_residual 0 (no gate).
+ * op_volume_register_rgbd back-projects exactly as op_volume_register_depth does (same pixels, same order) and gives each kept pixel
+ * y = I(b0 / 255.0f, b1 / 255.0f, b2 / 255.0f) from its three bytes (W*H*3, stored channel order; an IEEE divide, as the integration rounds
+ * them) into a second buffer the volume owns: its result is, bit for bit, op_volume_register_color_points on those points and intensities.
+ * `mem` says where depth and rgb live.
+ * Refusals as above, decided before any device use; in addition OP_ERR_INVALID for a NULL intensity with n > 0 and color_scale > 0 and for a
+ * NULL rgb. */
+typedef struct { op_volume_register_params base; float color_scale, max_color_residual; } op_volume_register_color_params;
+typedef struct { op_volume_register_result base; uint64_t colored, first_colored; double rmse_color, first_rmse_color; } op_volume_register_color_result;
+int op_volume_register_color_default_params(op_volume *v, op_volume_register_color_params *p);
+int op_volume_register_color_system(op_volume *v, const float *xyz, const float *intensity /* n, in `mem` */, size_t n, int mem, const float T[16],
+                                    float max_distance, float color_scale, float max_color_residual, double sums[30], uint64_t counts[5],
+                                    float *rows /* n x 16 in `mem`, or NULL */);
+int op_volume_register_color_points(op_volume *v, const float *xyz, const float *intensity, size_t n, int mem, const float init_T[16],
+                                    const op_volume_register_color_params *params /* NULL: defaults */, op_volume_register_color_result *result);
+int op_volume_register_rgbd(op_volume *v, const op_camera *cam /* NULL: the volume's */, const void *depth, int depth_fmt, const uint8_t *rgb,
+                            int mem, int pixel_stride, const float init_pose[16], const op_volume_register_color_params *params,
+                            op_volume_register_color_result *result);
+
 /* Frame-sharded multi-GPU merge (the distributed form of CubeHandler::Merge; DESIGN.md "Multi-GPU").
  * All pointers are DEVICE pointers on the volume's device.
  *   keys_device : copy this volume's block keys (n x 3 int32) into d_keys.

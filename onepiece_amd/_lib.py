@@ -58,6 +58,17 @@ class RegisterResult(C.Structure):
                [(k, C.c_double) for k in ("rmse", "first_rmse", "last_step")]
 
 
+class RegisterColorParams(C.Structure):
+    """op_volume_register_color_params of op_volume_register_color_points / _rgbd."""
+    _fields_ = [("base", RegisterParams), ("color_scale", C.c_float), ("max_color_residual", C.c_float)]
+
+
+class RegisterColorResult(C.Structure):
+    """op_volume_register_color_result of op_volume_register_color_points / _rgbd."""
+    _fields_ = [("base", RegisterResult), ("colored", C.c_uint64), ("first_colored", C.c_uint64),
+                ("rmse_color", C.c_double), ("first_rmse_color", C.c_double)]
+
+
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("last_T", C.c_float * 16), ("rmse", C.c_double),
                 ("n_inliers", C.c_uint64), ("iterations", C.c_int32)]
@@ -194,6 +205,11 @@ SIGNATURES = {
     "op_volume_register_system": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp, C.c_float, C.POINTER(C.c_double), _u64p, _vp]),
     "op_volume_register_points": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _fp, C.POINTER(RegisterParams), C.POINTER(RegisterResult)]),
     "op_volume_register_depth": (C.c_int, [_vp, C.POINTER(Camera), _vp, C.c_int, C.c_int, C.c_int, _fp, C.POINTER(RegisterParams), C.POINTER(RegisterResult)]),
+    "op_volume_register_color_default_params": (C.c_int, [_vp, C.POINTER(RegisterColorParams)]),
+    "op_volume_register_color_system": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _fp, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), _u64p, _vp]),
+    "op_volume_register_color_points": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _fp, C.POINTER(RegisterColorParams), C.POINTER(RegisterColorResult)]),
+    "op_volume_register_rgbd": (C.c_int, [_vp, C.POINTER(Camera), _vp, C.c_int, _vp, C.c_int, C.c_int, _fp, C.POINTER(RegisterColorParams),
+                                          C.POINTER(RegisterColorResult)]),
     "op_volume_keys_device": (C.c_int, [_vp, _vp, C.c_size_t, _szp]),
     "op_volume_pack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "op_volume_unpack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

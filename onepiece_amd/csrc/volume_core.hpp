@@ -538,6 +538,8 @@ struct op_volume {
     unsigned long long* rf_count = nullptr;
     float* reg_pts = nullptr;     // volume_register.hip: the back-projected points of the depth frame being registered (reg_cap points)
     size_t reg_cap = 0;
+    float* reg_int = nullptr;     // op_volume_register_rgbd: those points' intensities (reg_int_cap floats)
+    size_t reg_int_cap = 0;
     int* unpack_slots = nullptr; // table slots of the union keys between op_volume_unpack_sum_begin and its chunks
     size_t unpack_n = 0;
     uint64_t generation = 0, unpack_gen = 0; // bumped by whatever moves or drops table slots (growth, clear) or fuses frames; _chunk checks it

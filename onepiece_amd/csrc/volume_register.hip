@@ -11,11 +11,18 @@
 // workgroup, and k_register_fold adds the rows in index order (32 row lanes, then those in order): fixed for a given n, no floating-point
 // atomics.  32 doubles come back per evaluation.
 // The Gauss-Newton loop runs on the host: op_ldlt_solve6, op_se3_exp, a float32 4x4 product.
-// Not built: robust weights, colour terms, multi-resolution, re-ordering the points by block.
+// The COLOR instantiations (op_volume_register_color_* / _rgbd) take the colour sums of the same seven samples (rc_sample_global<true>): the model
+// intensity m = I(c) at p, its central difference g over the six shifted samples, the row jc = color_scale (g ; p x g) and the residual
+// color_scale (m - y) join the geometric terms of slots 0..27 inside the same reduction.  The three quantities that have no slot of the 32 (the
+// unscaled sum of (m - y)^2, the geometric sum of s^2, the count of coloured points) travel by a butterfly of their own: three doubles per lane,
+// six xor steps per trip, every lane ends with the wave's total; lane 0 puts them behind the wave's 32 slots (35 per row) and
+// k_register_fold_color adds the rows.  color_scale == 0 runs the geometric instantiation: the colour planes are never read.
+// Not built: robust weights, multi-resolution, re-ordering the points by block.
 #include "volume_core.hpp"
 #include "trilinear_sample.hpp"
 
 #include <cmath>
+#include <cstring>
 
 namespace opi { int device_exclusive_scan(const unsigned* d_count, size_t n, unsigned* d_start, hipStream_t stream, unsigned* total_out); } // icp_grid.hip
 
@@ -26,6 +33,8 @@ constexpr unsigned kRegMaxGrid = 1024; // rows k_register_fold adds: 4 workgroup
 constexpr int kRegSlots = 32;          // [0, 21) j_a j_b (a <= b, row by row), [21, 27) s j_a, [27] s s, [28, 32) used, invalid, no_gradient, too_far
 constexpr int kFoldWg = 1024;          // k_register_fold: one workgroup, 32 row lanes of 32 slots
 constexpr int kFoldRows = kFoldWg / kRegSlots;
+constexpr int kRegSlotsC = 35;         // COLOR: the 32 above (0..27 with the colour terms added), [32] rc rc, [33] s s alone, [34] colored
+constexpr int kFoldRowsC = kFoldWg / 64; // k_register_fold_color: 16 row lanes of 64 threads, 35 of them at work
 
 struct RegView { float res, inv_res; }; // what trilinear_sample.hpp reads of a view
 
@@ -35,25 +44,45 @@ struct RegArgs {
     float T[16];
     RegView W;
     float max_distance;
-    float* rows;     // n x 8 {j[6], s, used} (ROWS only)
-    double* partial; // gridDim.x x kRegSlots
+    float* rows;     // n x 8 {j[6], s, used} (ROWS only); COLOR: n x 16 {j[6], s, used, jc[6], rcs, colored}
+    double* partial; // gridDim.x x kRegSlots (COLOR: x kRegSlotsC)
+};
+struct RegColor { // what the COLOR instantiations read on top
+    const float* intensity; // n observed intensities
+    float color_scale, max_color_residual;
 };
 
+// intensity of a colour triple in stored channel order
+__device__ __forceinline__ float reg_intensity(const float* c) { return (0.114f * c[0] + 0.587f * c[1]) + 0.299f * c[2]; }
+
 // one sdf sample of the gradient: invalid when its own g is out of range (no conversion to int then)
-__device__ __forceinline__ bool reg_sample_sdf(const VolView& V, const RegView& W, BlockCache& bc, float x, float y, float z, float* s) {
+// (COLOR: and its intensity, from the colour sums of the same taps)
+template <bool COLOR>
+__device__ __forceinline__ bool reg_sample_sdf(const VolView& V, const RegView& W, BlockCache& bc, float x, float y, float z, float* s, float* in) {
     if (!sample_in_range(x * W.inv_res - 0.5f, y * W.inv_res - 0.5f, z * W.inv_res - 0.5f)) return false;
-    return rc_sample_global<false>(V, W, bc, x, y, z, s, nullptr);
+    if constexpr (COLOR) {
+        float c[3];
+        if (!rc_sample_global<true>(V, W, bc, x, y, z, s, c)) return false;
+        *in = reg_intensity(c);
+        return true;
+    } else {
+        return rc_sample_global<false>(V, W, bc, x, y, z, s, nullptr);
+    }
 }
 
-template <bool ROWS>
-__global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A) {
-    __shared__ double s_red[kRegWg / 64][kRegSlots];
+template <bool ROWS, bool COLOR>
+__global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A, RegColor K) {
+    constexpr int kSlots = COLOR ? kRegSlotsC : kRegSlots;
+    __shared__ double s_red[kRegWg / 64][kSlots];
     double total = 0.0; // lane L: slot (L >> 1) & 31 of this wave, over its trips
+    double ext[3] = {0.0, 0.0, 0.0}; // COLOR: the wave's rc rc, s s, colored over its trips (the same in every lane)
     BlockCache bc{INT_MIN, INT_MIN, INT_MIN, -1};
     const size_t step = (size_t)gridDim.x * kRegWg;
     for (size_t base = (size_t)blockIdx.x * kRegWg; base < A.n; base += step) { // (the same trips for every lane of the workgroup)
         const size_t i = base + threadIdx.x;
         float j[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, s = 0.0f;
+        float jc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rcs = 0.0f, rc = 0.0f; // COLOR: zero unless the point is coloured
+        bool colored = false;
         int reason = -1; // 0 used, 1 invalid, 2 no gradient, 3 too far; -1: no point
         if (i < A.n) {
             const float x = A.xyz[3 * i], y = A.xyz[3 * i + 1], z = A.xyz[3 * i + 2];
@@ -63,18 +92,19 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
             const float q2 = ((M[8] * x + M[9] * y) + M[10] * z) + M[11] * 1.0f;
             const float q3 = ((M[12] * x + M[13] * y) + M[14] * z) + M[15] * 1.0f;
             const float p0 = q0 / q3, p1 = q1 / q3, p2 = q2 / q3;
-            float sv = 0.0f;
+            float sv = 0.0f, mv = 0.0f;
             reason = 1;
-            if (reg_sample_sdf(V, A.W, bc, p0, p1, p2, &sv)) {
+            if (reg_sample_sdf<COLOR>(V, A.W, bc, p0, p1, p2, &sv, &mv)) {
                 const float h = 0.5f * A.W.res; // k_rc_shade's central difference
-                float d[3];
+                float d[3], g[3] = {0.0f, 0.0f, 0.0f};
                 bool all = true;
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
-                    float sp = 0.0f, sm = 0.0f;
-                    all = all && reg_sample_sdf(V, A.W, bc, p0 + (a == 0 ? h : 0.0f), p1 + (a == 1 ? h : 0.0f), p2 + (a == 2 ? h : 0.0f), &sp)
-                              && reg_sample_sdf(V, A.W, bc, p0 - (a == 0 ? h : 0.0f), p1 - (a == 1 ? h : 0.0f), p2 - (a == 2 ? h : 0.0f), &sm);
+                    float sp = 0.0f, sm = 0.0f, ip = 0.0f, im = 0.0f;
+                    all = all && reg_sample_sdf<COLOR>(V, A.W, bc, p0 + (a == 0 ? h : 0.0f), p1 + (a == 1 ? h : 0.0f), p2 + (a == 2 ? h : 0.0f), &sp, &ip)
+                              && reg_sample_sdf<COLOR>(V, A.W, bc, p0 - (a == 0 ? h : 0.0f), p1 - (a == 1 ? h : 0.0f), p2 - (a == 2 ? h : 0.0f), &sm, &im);
                     d[a] = sp - sm;
+                    if constexpr (COLOR) g[a] = (ip - im) / A.W.res;
                 }
                 const float l2 = all ? d[0] * d[0] + (d[1] * d[1] + d[2] * d[2]) : 0.0f;
                 if (!(l2 > 0.0f)) reason = 2;
@@ -86,13 +116,28 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
                     j[0] = n0; j[1] = n1; j[2] = n2;
                     j[3] = p1 * n2 - p2 * n1; j[4] = p2 * n0 - p0 * n2; j[5] = p0 * n1 - p1 * n0;
                     s = sv;
+                    if constexpr (COLOR) {
+                        const float y = K.intensity[i], r = mv - y;
+                        if (fabsf(y) < INFINITY && (!(K.max_color_residual > 0.0f) || fabsf(r) <= K.max_color_residual)) { // (false for a NaN y)
+                            colored = true;
+                            const float cs = K.color_scale;
+                            jc[0] = cs * g[0]; jc[1] = cs * g[1]; jc[2] = cs * g[2];
+                            jc[3] = cs * (p1 * g[2] - p2 * g[1]); jc[4] = cs * (p2 * g[0] - p0 * g[2]); jc[5] = cs * (p0 * g[1] - p1 * g[0]);
+                            rc = r; rcs = cs * r;
+                        }
+                    }
                 }
             }
             if (ROWS) {
-                float* o = A.rows + 8 * i;
+                float* o = A.rows + (COLOR ? 16 : 8) * i;
 #pragma unroll
                 for (int a = 0; a < 6; ++a) o[a] = j[a];
                 o[6] = s; o[7] = reason == 0 ? 1.0f : 0.0f;
+                if constexpr (COLOR) {
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) o[8 + a] = jc[a];
+                    o[14] = rcs; o[15] = colored ? 1.0f : 0.0f;
+                }
             }
         }
         // slot k of the point: float products, widened (an unused point's j and s are zero)
@@ -101,25 +146,41 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
             if constexpr (k < 21) {
                 constexpr int a = k < 6 ? 0 : k < 11 ? 1 : k < 15 ? 2 : k < 18 ? 3 : k < 20 ? 4 : 5;
                 constexpr int first = a == 0 ? 0 : a == 1 ? 6 : a == 2 ? 11 : a == 3 ? 15 : a == 4 ? 18 : 20;
-                return (double)(j[a] * j[a + (k - first)]);
+                if constexpr (COLOR) return (double)(j[a] * j[a + (k - first)]) + (double)(jc[a] * jc[a + (k - first)]);
+                else return (double)(j[a] * j[a + (k - first)]);
             } else if constexpr (k < 27) {
-                return (double)(s * j[k - 21]);
+                if constexpr (COLOR) return (double)(s * j[k - 21]) + (double)(rcs * jc[k - 21]);
+                else return (double)(s * j[k - 21]);
             } else if constexpr (k == 27) {
-                return (double)s * (double)s;
+                if constexpr (COLOR) return (double)s * (double)s + (double)rcs * (double)rcs;
+                else return (double)s * (double)s;
             } else {
                 return reason == k - 28 ? 1.0 : 0.0;
             }
         };
         total += op::wave_reduce_scatter32_lazy(val);
+        if constexpr (COLOR) { // the three without a slot: a butterfly, lane masks 32, 16, 8, 4, 2, 1 -- a + b is b + a, so every lane holds the same total
+            double e[3] = {(double)rc * (double)rc, (double)s * (double)s, colored ? 1.0 : 0.0};
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) e[q] += __shfl_xor(e[q], m, 64);
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) ext[q] += e[q];
+        }
     }
     // one row per workgroup (every lane gets here)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if ((lane & 1) == 0) s_red[wave][lane >> 1] = total;
+    if constexpr (COLOR) {
+        if (lane == 0) { s_red[wave][32] = ext[0]; s_red[wave][33] = ext[1]; s_red[wave][34] = ext[2]; }
+    }
     __syncthreads();
-    if (threadIdx.x < kRegSlots) {
+    if (threadIdx.x < kSlots) {
         double t = s_red[0][threadIdx.x];
         for (int w = 1; w < kRegWg / 64; ++w) t += s_red[w][threadIdx.x];
-        A.partial[(size_t)blockIdx.x * kRegSlots + threadIdx.x] = t;
+        A.partial[(size_t)blockIdx.x * kSlots + threadIdx.x] = t;
     }
 }
 
@@ -144,6 +205,29 @@ __global__ __launch_bounds__(kFoldWg) void k_register_fold(const double* __restr
     }
 }
 
+// the same for rows of 35: row lane r (of 16) adds rows r, r + 16, ..., then the 16 row lanes are added in order
+__global__ __launch_bounds__(kFoldWg) void k_register_fold_color(const double* __restrict__ partial, unsigned n_rows, double* __restrict__ out) {
+    __shared__ double s_fin[kFoldRowsC][kRegSlotsC];
+    const unsigned fk = threadIdx.x & 63u, fr = threadIdx.x >> 6;
+    if (fk < (unsigned)kRegSlotsC) {
+        double t = 0.0;
+        unsigned p = fr;
+        for (; p + 3 * kFoldRowsC < n_rows; p += 4 * kFoldRowsC) {
+            const double a0 = partial[(size_t)p * kRegSlotsC + fk], a1 = partial[(size_t)(p + kFoldRowsC) * kRegSlotsC + fk];
+            const double a2 = partial[(size_t)(p + 2 * kFoldRowsC) * kRegSlotsC + fk], a3 = partial[(size_t)(p + 3 * kFoldRowsC) * kRegSlotsC + fk];
+            t += a0; t += a1; t += a2; t += a3;
+        }
+        for (; p < n_rows; p += kFoldRowsC) t += partial[(size_t)p * kRegSlotsC + fk];
+        s_fin[fr][fk] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < (unsigned)kRegSlotsC) {
+        double u = s_fin[0][threadIdx.x];
+        for (int r = 1; r < kFoldRowsC; ++r) u += s_fin[r][threadIdx.x];
+        out[threadIdx.x] = u;
+    }
+}
+
 // ---- the depth entry's points: op_points_from_depth's definition over every stride-th pixel in both directions, row-major, compacted
 struct SubGrid { int w, h, sw, sh, stride; };
 __device__ __forceinline__ float reg_depth_at(const void* depth, int is_u16, float depth_scale, size_t px) {
@@ -155,8 +239,10 @@ __global__ __launch_bounds__(256) void k_register_depth_count(const void* __rest
     const int r = (int)(k / G.sw) * G.stride, c = (int)(k % G.sw) * G.stride;
     count[k] = reg_depth_at(depth, is_u16, depth_scale, (size_t)r * G.w + c) > 0 ? 1u : 0u;
 }
+// (RGB: and the kept pixel's intensity from its three bytes, each b / 255.0f as the integration rounds it)
+template <bool RGB>
 __global__ __launch_bounds__(256) void k_register_depth_scatter(const void* __restrict__ depth, int is_u16, op_camera cam, SubGrid G, const unsigned* __restrict__ start,
-                                                                float* __restrict__ xyz) {
+                                                                float* __restrict__ xyz, const unsigned char* __restrict__ rgb, float* __restrict__ intensity) {
     const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
     if (k >= (size_t)G.sw * G.sh) return;
     const int r = (int)(k / G.sw) * G.stride, c = (int)(k % G.sw) * G.stride;
@@ -166,6 +252,11 @@ __global__ __launch_bounds__(256) void k_register_depth_scatter(const void* __re
     xyz[3 * p] = ((float)c - cam.cx) * z / cam.fx; // PointCloud.cpp:90-93
     xyz[3 * p + 1] = ((float)r - cam.cy) * z / cam.fy;
     xyz[3 * p + 2] = z;
+    if constexpr (RGB) {
+        const unsigned char* b = rgb + 3 * ((size_t)r * G.w + c);
+        const float col[3] = {(float)b[0] / 255.0f, (float)b[1] / 255.0f, (float)b[2] / 255.0f};
+        intensity[p] = reg_intensity(col);
+    }
 }
 
 // ---- host side
@@ -177,15 +268,23 @@ struct RegRun {
     unsigned grid = 0;
     double *d_out = nullptr, *h_out = nullptr;
 
+    RegColor K{nullptr, 0.0f, 0.0f}; // color_scale > 0: the COLOR instantiations
+
     explicit RegRun(op_volume* vol) : v(vol) { tmp.bind(v->stream); }
+    bool color() const { return K.color_scale > 0.0f; }
     int open(const float* d_xyz, size_t n, float max_distance) {
         A.xyz = d_xyz; A.n = n; A.W.res = v->res; A.W.inv_res = 1.0f / v->res; A.max_distance = max_distance;
         grid = (unsigned)std::min<size_t>((n + kRegWg - 1) / kRegWg, kRegMaxGrid);
         if (!grid) return OP_OK;
-        OP_TRY(tmp.alloc(&A.partial, (size_t)grid * kRegSlots));
-        OP_TRY(tmp.alloc(&d_out, (size_t)kRegSlots));
-        OP_TRY(tmp.pinned(&h_out, (size_t)kRegSlots));
+        const size_t slots = color() ? kRegSlotsC : kRegSlots;
+        OP_TRY(tmp.alloc(&A.partial, (size_t)grid * slots));
+        OP_TRY(tmp.alloc(&d_out, slots));
+        OP_TRY(tmp.pinned(&h_out, slots));
         return OP_OK;
+    }
+    int open_color(const float* d_xyz, const float* d_intensity, size_t n, float max_distance, float color_scale, float max_color_residual) {
+        K.intensity = d_intensity; K.color_scale = color_scale; K.max_color_residual = max_color_residual;
+        return open(d_xyz, n, max_distance);
     }
     // the system at T: 28 sums and 4 counts (d_rows: n x 8 on the device, or NULL)
     int eval(const float T[16], float* d_rows, double sums[28], uint64_t counts[4]) {
@@ -195,8 +294,8 @@ struct RegRun {
         for (int k = 0; k < 16; ++k) A.T[k] = T[k];
         A.rows = d_rows;
         const VolView V = v->view();
-        if (d_rows) hipLaunchKernelGGL(k_volume_register<true>, dim3(grid), dim3(kRegWg), 0, v->stream, V, A);
-        else hipLaunchKernelGGL(k_volume_register<false>, dim3(grid), dim3(kRegWg), 0, v->stream, V, A);
+        if (d_rows) hipLaunchKernelGGL((k_volume_register<true, false>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, RegColor{nullptr, 0.0f, 0.0f});
+        else hipLaunchKernelGGL((k_volume_register<false, false>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, RegColor{nullptr, 0.0f, 0.0f});
         hipLaunchKernelGGL(k_register_fold, dim3(1), dim3(kFoldWg), 0, v->stream, (const double*)A.partial, grid, d_out);
         OP_HIP(hipGetLastError());
         OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * kRegSlots, hipMemcpyDeviceToHost, v->stream));
@@ -206,9 +305,36 @@ struct RegRun {
         for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k]; // whole numbers below 2^53: exact in any order
         return OP_OK;
     }
+    // the coloured system at T: 30 sums ([28] rc rc, [29] s s alone) and 5 counts (d_rows: n x 16).  color_scale == 0 IS the geometric evaluation
+    // (d_rows must be NULL then: the system entry widens the geometric rows itself).
+    int eval_color(const float T[16], float* d_rows, double sums[30], uint64_t counts[5]) {
+        if (!color()) {
+            OP_TRY(eval(T, nullptr, sums, counts));
+            sums[28] = 0.0; sums[29] = sums[27]; counts[4] = 0;
+            return OP_OK;
+        }
+        for (int k = 0; k < 30; ++k) sums[k] = 0.0;
+        for (int k = 0; k < 5; ++k) counts[k] = 0;
+        if (!grid) return OP_OK;
+        for (int k = 0; k < 16; ++k) A.T[k] = T[k];
+        A.rows = d_rows;
+        const VolView V = v->view();
+        if (d_rows) hipLaunchKernelGGL((k_volume_register<true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, K);
+        else hipLaunchKernelGGL((k_volume_register<false, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, K);
+        hipLaunchKernelGGL(k_register_fold_color, dim3(1), dim3(kFoldWg), 0, v->stream, (const double*)A.partial, grid, d_out);
+        OP_HIP(hipGetLastError());
+        OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * kRegSlotsC, hipMemcpyDeviceToHost, v->stream));
+        OP_HIP(hipStreamSynchronize(v->stream));
+        const double* r = h_out;
+        for (int k = 0; k < 28; ++k) sums[k] = r[k];
+        sums[28] = r[32]; sums[29] = r[33];
+        for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k];
+        counts[4] = (uint64_t)r[34];
+        return OP_OK;
+    }
 };
 
-inline double reg_rmse(const double sums[28], uint64_t used) { return used ? std::sqrt(sums[27] / (double)used) : 0.0; }
+inline double reg_rmse(double sum_sq, uint64_t count) { return count ? std::sqrt(sum_sq / (double)count) : 0.0; }
 
 // C = A B, float32, each element ((a0 b0 + a1 b1) + a2 b2) + a3 b3
 inline void reg_mul4(const float a[16], const float b[16], float c[16]) {
@@ -221,6 +347,10 @@ int reg_check_params(const op_volume_register_params* p, const char* who) {
     if (p && p->max_iterations < 0) return fail(OP_ERR_INVALID, "%s: max_iterations < 0", who);
     return OP_OK;
 }
+int reg_check_color_scale(float color_scale, const char* who) {
+    if (!(color_scale >= 0.0f) || !std::isfinite(color_scale)) return fail(OP_ERR_INVALID, "%s: color_scale must be finite and >= 0", who);
+    return OP_OK;
+}
 
 op_volume_register_params reg_defaults(const op_volume* v) {
     op_volume_register_params p;
@@ -231,26 +361,35 @@ op_volume_register_params reg_defaults(const op_volume* v) {
     return p;
 }
 
-// the Gauss-Newton loop over points that are on the device
-int reg_loop(op_volume* v, const float* d_xyz, size_t n, const float init_T[16], const op_volume_register_params& P, op_volume_register_result* out) {
+op_volume_register_color_params reg_color_defaults(const op_volume* v) {
+    op_volume_register_color_params p;
+    p.base = reg_defaults(v);
+    p.color_scale = 1.0f;        // equal weight, as LAMBDA_HYBRID_DEPTH 0.5 gives the tracker's two terms
+    p.max_color_residual = 0.0f; // no gate
+    return p;
+}
+
+// the Gauss-Newton loop over points (and, with color_scale > 0, intensities) that are on the device; color_scale == 0: the geometric loop
+int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
+             float max_color_residual, op_volume_register_color_result* out) {
     RegRun R(v);
-    OP_TRY(R.open(d_xyz, n, P.max_distance));
+    OP_TRY(R.open_color(d_xyz, d_intensity, n, P.max_distance, color_scale, max_color_residual));
     op_volume_register_result res{};
     float T[16];
     for (int k = 0; k < 16; ++k) T[k] = init_T[k];
-    double sums[28], first_sums[28];
-    uint64_t counts[4], first_counts[4];
+    double sums[30], first_sums[30];
+    uint64_t counts[5], first_counts[5];
     bool have_first = false, current = false; // current: sums / counts are the system at T
     res.status = OP_REGISTER_MAX_ITERATIONS;
     const uint64_t min_points = P.min_points > 0 ? (uint64_t)P.min_points : 0;
     const double min_step2 = (double)P.min_step * (double)P.min_step;
     for (int it = 0; it < P.max_iterations; ++it) {
-        OP_TRY(R.eval(T, nullptr, sums, counts));
+        OP_TRY(R.eval_color(T, nullptr, sums, counts));
         current = true;
         if (!have_first) {
             have_first = true;
-            for (int k = 0; k < 28; ++k) first_sums[k] = sums[k];
-            for (int k = 0; k < 4; ++k) first_counts[k] = counts[k];
+            for (int k = 0; k < 30; ++k) first_sums[k] = sums[k];
+            for (int k = 0; k < 5; ++k) first_counts[k] = counts[k];
         }
         if (counts[0] < min_points) { res.status = OP_REGISTER_TOO_FEW_POINTS; break; }
         double JTJ[36], JTr[6];
@@ -273,18 +412,64 @@ int reg_loop(op_volume* v, const float* d_xyz, size_t n, const float init_T[16],
         res.last_step = std::sqrt(ss);
         if (ss < min_step2) { res.status = OP_REGISTER_CONVERGED; break; }
     }
-    if (!current) OP_TRY(R.eval(T, nullptr, sums, counts)); // the system at the pose that is returned
+    if (!current) OP_TRY(R.eval_color(T, nullptr, sums, counts)); // the system at the pose that is returned
     if (!have_first) { // max_iterations == 0
-        for (int k = 0; k < 28; ++k) first_sums[k] = sums[k];
-        for (int k = 0; k < 4; ++k) first_counts[k] = counts[k];
+        for (int k = 0; k < 30; ++k) first_sums[k] = sums[k];
+        for (int k = 0; k < 5; ++k) first_counts[k] = counts[k];
         if (counts[0] < min_points) res.status = OP_REGISTER_TOO_FEW_POINTS;
     }
     for (int k = 0; k < 16; ++k) res.T[k] = T[k];
     res.used = counts[0]; res.invalid = counts[1]; res.no_gradient = counts[2]; res.too_far = counts[3];
     res.first_used = first_counts[0];
-    res.rmse = reg_rmse(sums, counts[0]);
-    res.first_rmse = reg_rmse(first_sums, first_counts[0]);
-    *out = res;
+    res.rmse = reg_rmse(sums[29], counts[0]); // the geometric sum of s^2 (sums[27] holds the colour term too)
+    res.first_rmse = reg_rmse(first_sums[29], first_counts[0]);
+    out->base = res;
+    out->colored = counts[4]; out->first_colored = first_counts[4];
+    out->rmse_color = reg_rmse(sums[28], counts[4]);
+    out->first_rmse_color = reg_rmse(first_sums[28], first_counts[4]);
+    return OP_OK;
+}
+int reg_loop(op_volume* v, const float* d_xyz, size_t n, const float init_T[16], const op_volume_register_params& P, op_volume_register_result* out) {
+    op_volume_register_color_result r{};
+    OP_TRY(reg_loop(v, d_xyz, nullptr, n, init_T, P, 0.0f, 0.0f, &r));
+    *out = r.base;
+    return OP_OK;
+}
+
+// the depth entries' points (and intensities) in the volume's buffers
+int reg_back_project(op_volume* v, op::Scope& tmp, const op_camera& c, const void* depth, int depth_fmt, const unsigned char* rgb, int mem, int pixel_stride,
+                     unsigned* total) {
+    SubGrid G{c.width, c.height, (c.width + pixel_stride - 1) / pixel_stride, (c.height + pixel_stride - 1) / pixel_stride, pixel_stride};
+    const size_t npix = (size_t)c.width * c.height, nsub = (size_t)G.sw * G.sh;
+    const void* d_depth = depth;
+    const unsigned char* d_rgb = rgb;
+    if (mem == OP_MEM_HOST) {
+        const unsigned char* d = nullptr;
+        OP_TRY(tmp.input(static_cast<const unsigned char*>(depth), npix * (depth_fmt == OP_DEPTH_U16 ? 2 : 4), mem, &d));
+        d_depth = d;
+        if (rgb) OP_TRY(tmp.input(rgb, npix * 3, mem, &d_rgb));
+    }
+    if (nsub > v->reg_cap) {
+        if (v->reg_pts) op::cached_free(v->reg_pts);
+        v->reg_pts = nullptr; v->reg_cap = 0;
+        OP_HIP(op::cached_malloc((void**)&v->reg_pts, nsub * 12));
+        v->reg_cap = nsub;
+    }
+    if (rgb && nsub > v->reg_int_cap) {
+        if (v->reg_int) op::cached_free(v->reg_int);
+        v->reg_int = nullptr; v->reg_int_cap = 0;
+        OP_HIP(op::cached_malloc((void**)&v->reg_int, nsub * 4));
+        v->reg_int_cap = nsub;
+    }
+    unsigned *d_count = nullptr, *d_start = nullptr;
+    OP_TRY(tmp.alloc(&d_count, nsub));
+    OP_TRY(tmp.alloc(&d_start, nsub));
+    const dim3 g((unsigned)((nsub + 255) / 256)), b(256);
+    hipLaunchKernelGGL(k_register_depth_count, g, b, 0, v->stream, d_depth, depth_fmt == OP_DEPTH_U16, c.depth_scale, G, d_count);
+    OP_TRY(opi::device_exclusive_scan(d_count, nsub, d_start, v->stream, total));
+    if (rgb) hipLaunchKernelGGL(k_register_depth_scatter<true>, g, b, 0, v->stream, d_depth, depth_fmt == OP_DEPTH_U16, c, G, (const unsigned*)d_start, v->reg_pts, d_rgb, v->reg_int);
+    else hipLaunchKernelGGL(k_register_depth_scatter<false>, g, b, 0, v->stream, d_depth, depth_fmt == OP_DEPTH_U16, c, G, (const unsigned*)d_start, v->reg_pts, (const unsigned char*)nullptr, (float*)nullptr);
+    OP_HIP(hipGetLastError());
     return OP_OK;
 }
 
@@ -356,31 +541,103 @@ int op_volume_register_depth(op_volume* v, const op_camera* cam, const void* dep
     OP_TRY(vol_check(v));
     const op_volume_register_params P = params ? *params : reg_defaults(v);
 
-    SubGrid G{c.width, c.height, (c.width + pixel_stride - 1) / pixel_stride, (c.height + pixel_stride - 1) / pixel_stride, pixel_stride};
-    const size_t npix = (size_t)c.width * c.height, nsub = (size_t)G.sw * G.sh;
     op::Scope tmp;
     tmp.bind(v->stream);
-    const void* d_depth = depth;
-    if (mem == OP_MEM_HOST) {
-        const unsigned char* d = nullptr;
-        OP_TRY(tmp.input(static_cast<const unsigned char*>(depth), npix * (depth_fmt == OP_DEPTH_U16 ? 2 : 4), mem, &d));
-        d_depth = d;
-    }
-    if (nsub > v->reg_cap) {
-        if (v->reg_pts) op::cached_free(v->reg_pts);
-        v->reg_pts = nullptr; v->reg_cap = 0;
-        OP_HIP(op::cached_malloc((void**)&v->reg_pts, nsub * 12));
-        v->reg_cap = nsub;
-    }
-    unsigned *d_count = nullptr, *d_start = nullptr, total = 0;
-    OP_TRY(tmp.alloc(&d_count, nsub));
-    OP_TRY(tmp.alloc(&d_start, nsub));
-    const dim3 g((unsigned)((nsub + 255) / 256)), b(256);
-    hipLaunchKernelGGL(k_register_depth_count, g, b, 0, v->stream, d_depth, depth_fmt == OP_DEPTH_U16, c.depth_scale, G, d_count);
-    OP_TRY(opi::device_exclusive_scan(d_count, nsub, d_start, v->stream, &total));
-    hipLaunchKernelGGL(k_register_depth_scatter, g, b, 0, v->stream, d_depth, depth_fmt == OP_DEPTH_U16, c, G, (const unsigned*)d_start, v->reg_pts);
-    OP_HIP(hipGetLastError());
+    unsigned total = 0;
+    OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, nullptr, mem, pixel_stride, &total));
     return reg_loop(v, v->reg_pts, (size_t)total, init_pose, P, result); // (the loop's kernels follow the scatter on the volume's stream)
+}
+
+// ---- the colour term
+int op_volume_register_color_default_params(op_volume* v, op_volume_register_color_params* p) {
+    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_color_default_params: null volume");
+    if (!p) return fail(OP_ERR_INVALID, "op_volume_register_color_default_params: null params");
+    *p = reg_color_defaults(v);
+    return OP_OK;
+}
+
+int op_volume_register_color_system(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float T[16], float max_distance,
+                                    float color_scale, float max_color_residual, double sums[30], uint64_t counts[5], float* rows) {
+    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null volume");
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_color_system: bad mem %d", mem);
+    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null xyz");
+    if (!T) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null T");
+    if (!sums) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null sums");
+    OP_TRY(reg_check_color_scale(color_scale, "op_volume_register_color_system"));
+    if (n > 0 && color_scale > 0.0f && !intensity) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null intensity");
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    RegRun R(v);
+    const float *d_xyz = nullptr, *d_int = nullptr;
+    OP_TRY(R.tmp.input(xyz, 3 * n, mem, &d_xyz));
+    if (color_scale > 0.0f) OP_TRY(R.tmp.input(intensity, n, mem, &d_int)); // (color_scale == 0: the intensities are not read either)
+    OP_TRY(R.open_color(d_xyz, d_int, n, max_distance, color_scale, max_color_residual));
+    const bool want_rows = rows && n;
+    uint64_t c[5];
+    if (R.color()) {
+        float* d_rows = rows;
+        if (want_rows && mem == OP_MEM_HOST) OP_TRY(R.tmp.alloc(&d_rows, 16 * n));
+        OP_TRY(R.eval_color(T, want_rows ? d_rows : nullptr, sums, c));
+        if (want_rows && mem == OP_MEM_HOST) OP_HIP(hipMemcpy(rows, d_rows, sizeof(float) * 16 * n, hipMemcpyDeviceToHost));
+    } else { // the geometric instantiation; its rows of 8 become the first halves of rows of 16, the second halves zero
+        float* d_rows8 = nullptr;
+        if (want_rows) OP_TRY(R.tmp.alloc(&d_rows8, 8 * n));
+        OP_TRY(R.eval(T, d_rows8, sums, c));
+        sums[28] = 0.0; sums[29] = sums[27]; c[4] = 0;
+        if (want_rows) {
+            if (mem == OP_MEM_HOST) std::memset(rows, 0, sizeof(float) * 16 * n);
+            else OP_HIP(hipMemset(rows, 0, sizeof(float) * 16 * n));
+            OP_HIP(hipMemcpy2D(rows, sizeof(float) * 16, d_rows8, sizeof(float) * 8, sizeof(float) * 8, n, mem == OP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        }
+    }
+    if (counts) for (int k = 0; k < 5; ++k) counts[k] = c[k];
+    return OP_OK;
+}
+
+int op_volume_register_color_points(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float init_T[16],
+                                    const op_volume_register_color_params* params, op_volume_register_color_result* result) {
+    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null volume");
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_color_points: bad mem %d", mem);
+    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null xyz");
+    if (!init_T) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null init_T");
+    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null result");
+    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_color_points"));
+    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_color_points"));
+    if (n > 0 && !intensity && (!params || params->color_scale > 0.0f)) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null intensity");
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    op::Scope up;
+    up.bind(v->stream);
+    const float *d_xyz = nullptr, *d_int = nullptr;
+    OP_TRY(up.input(xyz, 3 * n, mem, &d_xyz));
+    if (P.color_scale > 0.0f) OP_TRY(up.input(intensity, n, mem, &d_int));
+    return reg_loop(v, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual, result);
+}
+
+int op_volume_register_rgbd(op_volume* v, const op_camera* cam, const void* depth, int depth_fmt, const uint8_t* rgb, int mem, int pixel_stride,
+                            const float init_pose[16], const op_volume_register_color_params* params, op_volume_register_color_result* result) {
+    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null volume");
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: bad mem %d", mem);
+    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: bad depth format %d", depth_fmt);
+    if (!depth) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null depth");
+    if (!rgb) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null rgb");
+    if (pixel_stride < 1) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: pixel_stride < 1");
+    if (!init_pose) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null init_pose");
+    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null result");
+    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_rgbd"));
+    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_rgbd"));
+    const op_camera c = cam ? *cam : v->cam;
+    OP_TRY(check_cam(&c));
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+
+    op::Scope tmp;
+    tmp.bind(v->stream);
+    unsigned total = 0;
+    OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, rgb, mem, pixel_stride, &total));
+    return reg_loop(v, v->reg_pts, v->reg_int, (size_t)total, init_pose, P.base, P.color_scale, P.max_color_residual, result);
 }
 
 } // extern "C"

@@ -650,6 +650,84 @@ class CubeHandler:
         self._alive = []
         return self._register_result(r)
 
+    # -- the colour term (op_volume_register_color_* / _rgbd: the model's intensity at the point against the observed one, a second residual)
+    def _register_color_params(self, max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual):
+        p = L.RegisterColorParams()
+        L.check(self._lib.op_volume_register_color_default_params(self._h, C.byref(p)))
+        for k, val in (("max_iterations", max_iterations), ("max_distance", max_distance), ("min_step", min_step), ("min_points", min_points)):
+            if val is not None:
+                setattr(p.base, k, val)
+        for k, val in (("color_scale", color_scale), ("max_color_residual", max_color_residual)):
+            if val is not None:
+                setattr(p, k, val)
+        return p
+
+    @staticmethod
+    def _register_color_result(r):
+        out = CubeHandler._register_result(r.base)
+        out.update({k: getattr(r, k) for k in ("colored", "first_colored", "rmse_color", "first_rmse_color")})
+        return out
+
+    @staticmethod
+    def Intensity(colors):
+        """I(c) = (0.114 c0 + 0.587 c1) + 0.299 c2 in float32 of colour triples in stored channel order ([n,3] float32, byte / 255)."""
+        c = _f32(colors).reshape(-1, 3)
+        return (np.float32(0.114) * c[:, 0] + np.float32(0.587) * c[:, 1]) + np.float32(0.299) * c[:, 2]
+
+    def ColorRegistrationSystem(self, points, intensity, T, max_distance, color_scale=1.0, max_color_residual=0.0, rows=False):
+        """The point-to-plane system with the colour term (op_volume_register_color_system) of `points` ([n,3] float32) with observed
+        intensities `intensity` ([n] float32; may be None with color_scale 0) -> (sums [30] float64: 0..27 as RegistrationSystem with the
+        colour terms added, [28] the sum of rc^2, [29] the geometric sum of s^2; counts dict with `colored`[, rows [n,16]: j[6], s, used, jc[6],
+        rcs, colored])."""
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        n = len(pts)
+        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
+        if y is not None and len(y) != n:
+            raise ValueError("one intensity per point")
+        Tm = _f32(T).reshape(16)
+        sums, counts = np.zeros(30, np.float64), np.zeros(5, np.uint64)
+        out = np.empty((n, 16), np.float32) if rows else None
+        L.check(self._lib.op_volume_register_color_system(self._h, C.c_void_p(pts.ctypes.data), C.c_void_p(y.ctypes.data) if y is not None else None, n,
+                                                          L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale), float(max_color_residual),
+                                                          sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(L._u64p),
+                                                          C.c_void_p(out.ctypes.data) if rows else None))
+        self._alive = []
+        cd = dict(zip(("used", "invalid", "no_gradient", "too_far", "colored"), (int(c) for c in counts)))
+        return (sums, cd, out) if rows else (sums, cd)
+
+    def RegisterColoredPoints(self, points, intensity, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
+                              color_scale=None, max_color_residual=None):
+        """RegisterPoints with the colour term: `intensity` [n] float32 in the volume's colour units (Intensity(colors) of a cloud's colours)
+        -> the result dict with colored, first_colored, rmse_color, first_rmse_color.  color_scale None = 1, 0 = RegisterPoints."""
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
+        if y is not None and len(y) != len(pts):
+            raise ValueError("one intensity per point")
+        T0 = _f32(np.eye(4) if init_T is None else init_T).reshape(16)
+        p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
+        r = L.RegisterColorResult()
+        L.check(self._lib.op_volume_register_color_points(self._h, C.c_void_p(pts.ctypes.data), C.c_void_p(y.ctypes.data) if y is not None else None, len(pts),
+                                                          L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(r)))
+        self._alive = []
+        return self._register_color_result(r)
+
+    def RegisterRGBD(self, depth, rgb, init_pose, pixel_stride=1, camera=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
+                     color_scale=None, max_color_residual=None):
+        """RegisterDepth with the colour term: every kept pixel's intensity comes from its three bytes of `rgb` (uint8 [H,W,3], stored channel
+        order; numpy or CUDA torch tensor like `depth`) -> the result dict, T the refined pose."""
+        pd, fmt, mem, k1 = _image_arg(depth, "depth")
+        pr, _f, mem2, k2 = _image_arg(rgb, "rgb")
+        if mem != mem2:
+            raise ValueError("depth and rgb must both be host arrays or both be device tensors")
+        pose = _f32(init_pose).reshape(16)
+        p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
+        r = L.RegisterColorResult()
+        L.check(self._lib.op_volume_register_rgbd(self._h, C.byref(camera) if camera is not None else None, pd, fmt, pr, mem, int(pixel_stride), _fp(pose),
+                                                  C.byref(p), C.byref(r)))
+        del k1, k2
+        self._alive = []
+        return self._register_color_result(r)
+
     def RaycastStats(self):
         """Measurement hook: what the last Raycast call did (op_volume_raycast_stats)."""
         v = [C.c_uint64(0) for _ in range(4)]
