@@ -4,6 +4,7 @@
 // sdf at a transformed point is the residual, its normalised central difference the normal.
 //
 //   ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused] [--color off|on [--color-scale S]]
+//                     [--linearization normal|gradient|metric] [--huber D] [--huber-color D] [--min-step S]
 //   --synthetic N STRIDE SEED  N frames of the analytic room of LiveFusion.cpp: frame k is step FIRST + k * STRIDE of a 1000-step orbit, SEED picks FIRST
 //   --perturb K                every K-th frame is re-registered (default 20); its start is its true pose moved by 3-4 cm and about a degree
 //   --iters I                  Gauss-Newton iterations per frame (default 10; min_step is 0, so both paths take all of them)
@@ -14,6 +15,13 @@
 //   --color on                 (fused path only; default off) op_volume_register_rgbd: the colour term -- the model's intensity at the point against the
 //                              frame's own -- joins the system with weight --color-scale (default 1); one line per frame (pose error, sdf rmse, colour
 //                              rmse, coloured points) precedes the JSON line, which gains "color_scale", "rmse_color" and "colored_last"
+//   --linearization L, --huber D, --huber-color D
+//                              (fused path only) any of them: op_volume_register_robust_frame -- row and residual of the chosen linearisation
+//                              (default metric), Huber weights on the residual (metres) and on the colour residual (default 0: none); with --color
+//                              off the depth image alone.  One line per frame: what --color on prints, then the frame's iteration count, status,
+//                              last step and down-weighted points; the JSON line gains "linearization", "huber", "huber_color", "downweighted_last"
+//                              and "rmse_residual"
+//   --min-step S               (with the three above; default 0) the step below which a frame stops: with it the iteration counts say something
 // Both paths solve with op_ldlt_solve6, update with op_se3_exp and the same float32 product, and gate with the same rules; their sums differ in
 // the order of the additions only.  It prints one JSON line: pose errors before and after, iterations, stage times (host clock).
 #include <algorithm>
@@ -204,9 +212,9 @@ double Median(std::vector<double> v) {
 int main(int argc, char* argv[]) {
     long synthetic[3] = {0, 1, 1}, every = 20, iters = 10;
     bool is_synthetic = false, bad = false;
-    std::string path = "fused", color = "off";
-    float res = 0.01f, color_scale = 1.0f;
-    bool have_scale = false;
+    std::string path = "fused", color = "off", linearization = "metric";
+    float res = 0.01f, color_scale = 1.0f, huber = 0.0f, huber_color = 0.0f, min_step = 0.0f;
+    bool have_scale = false, robust = false, have_min_step = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--synthetic" && i + 3 < argc) { is_synthetic = true; for (int k = 0; k < 3; ++k) synthetic[k] = std::atol(argv[++i]); }
@@ -216,12 +224,19 @@ int main(int argc, char* argv[]) {
         else if (a == "--path" && i + 1 < argc) path = argv[++i];
         else if (a == "--color" && i + 1 < argc) color = argv[++i];
         else if (a == "--color-scale" && i + 1 < argc) { color_scale = static_cast<float>(std::atof(argv[++i])); have_scale = true; }
+        else if (a == "--linearization" && i + 1 < argc) { linearization = argv[++i]; robust = true; }
+        else if (a == "--huber" && i + 1 < argc) { huber = static_cast<float>(std::atof(argv[++i])); robust = true; }
+        else if (a == "--huber-color" && i + 1 < argc) { huber_color = static_cast<float>(std::atof(argv[++i])); robust = true; }
+        else if (a == "--min-step" && i + 1 < argc) { min_step = static_cast<float>(std::atof(argv[++i])); have_min_step = true; }
         else bad = true;
     }
+    const int lin = linearization == "normal" ? OP_REGISTER_LIN_NORMAL : linearization == "gradient" ? OP_REGISTER_LIN_GRADIENT : linearization == "metric" ? OP_REGISTER_LIN_METRIC : -1;
     const long n = synthetic[0], stride = synthetic[1];
     if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || !(res > 0) || every < 1 || iters < 0 || iters > 1000 || (path != "sample" && path != "fused") ||
-        (color != "off" && color != "on") || (color == "on" && path != "fused") || (have_scale && color != "on") || !(color_scale >= 0)) {
-        std::cout << "usage::ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused] [--color off|on [--color-scale S]]" << std::endl;
+        (color != "off" && color != "on") || (color == "on" && path != "fused") || (have_scale && color != "on") || !(color_scale >= 0) || lin < 0 || (robust && path != "fused") || !(huber >= 0) || !(huber_color >= 0) ||
+        (have_min_step && !robust) || !(min_step >= 0)) {
+        std::cout << "usage::ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused] [--color off|on [--color-scale S]]"
+                     " [--linearization normal|gradient|metric] [--huber D] [--huber-color D] [--min-step S]" << std::endl;
         return bad || argc > 1 ? 2 : 0;
     }
     const long first = ((synthetic[2] + 999) % 1000) * 97 % 1000;
@@ -251,6 +266,12 @@ int main(int argc, char* argv[]) {
     if (op_volume_register_color_default_params(volume.Handle(), &color_params) != OP_OK) return 1;
     color_params.base = params;
     color_params.color_scale = color_scale;
+    if (robust) color_params.base.min_step = min_step;
+    op_volume_register_options options;
+    options.linearization = lin; options.huber = huber; options.huber_color = huber_color;
+    const char* const status_names[4] = {"converged", "max_iterations", "too_few_points", "singular"};
+    std::vector<double> rmse_residual;
+    unsigned long long downweighted = 0;
     std::vector<double> register_ms, per_iteration_ms, before_m, before_deg, after_m, after_deg, rmse, first_rmse, rmse_color;
     unsigned long long points = 0, used = 0, colored = 0;
     long frames = 0, iterations = 0;
@@ -268,7 +289,25 @@ int main(int argc, char* argv[]) {
         Perturbed(truth, k, start);
         Outcome got;
         t0 = std::chrono::steady_clock::now();
-        if (with_color) {
+        if (robust) {
+            op_volume_register_robust_result b;
+            if (!volume.RegisterRGBDRobust(depth, with_color ? rgb : cv::Mat(), FromRowMajor(start), 1, &color_params, &options, &b)) return 1;
+            const op_volume_register_color_result& c = b.color;
+            const op_volume_register_result& r = c.base;
+            for (int a = 0; a < 16; ++a) got.T[a] = r.T[a];
+            got.iterations = r.iterations; got.used = r.used; got.rmse = r.rmse; got.first_rmse = r.first_rmse;
+            points = r.used + r.invalid + r.no_gradient + r.too_far;
+            colored = c.colored;
+            downweighted = b.downweighted;
+            rmse_color.push_back(c.rmse_color);
+            rmse_residual.push_back(b.rmse_residual);
+            double m = 0, deg = 0;
+            PoseError(got.T, truth, &m, &deg);
+            std::printf("frame %ld: pose error %.3f mm / %.5f deg, rmse %.6f (first %.6f), colour rmse %.6f (first %.6f), coloured %llu of %llu used, iterations %d, status %s, "
+                        "last step %.3e, residual rmse %.6f, down-weighted %llu / %llu\n", k, m * 1000.0, deg, r.rmse, r.first_rmse, c.rmse_color, c.first_rmse_color,
+                        static_cast<unsigned long long>(c.colored), static_cast<unsigned long long>(r.used), r.iterations, status_names[r.status & 3], r.last_step, b.rmse_residual,
+                        static_cast<unsigned long long>(b.downweighted), static_cast<unsigned long long>(b.color_downweighted));
+        } else if (with_color) {
             op_volume_register_color_result c;
             if (!volume.RegisterRGBD(depth, rgb, FromRowMajor(start), 1, &color_params, &c)) return 1;
             const op_volume_register_result& r = c.base;
@@ -325,6 +364,8 @@ int main(int argc, char* argv[]) {
               << ", \"max_deg\": " << *std::max_element(after_deg.begin(), after_deg.end()) << "}"
               << ", \"rmse\": {\"first\": " << Median(first_rmse) << ", \"final\": " << Median(rmse) << "}";
     if (with_color) std::cout << ", \"color_scale\": " << color_scale << ", \"rmse_color\": " << Median(rmse_color) << ", \"colored_last\": " << colored;
+    if (robust) std::cout << ", \"linearization\": \"" << linearization << "\", \"huber\": " << huber << ", \"huber_color\": " << huber_color << ", \"downweighted_last\": " << downweighted
+                          << ", \"rmse_residual\": " << Median(rmse_residual);
     std::cout
               << ", \"ms\": {\"fuse\": " << t_fuse * 1000.0 << ", \"deintegrate\": " << t_out * 1000.0 << ", \"reintegrate\": " << t_back * 1000.0
               << ", \"register_median\": " << Median(register_ms) << ", \"per_iteration_median\": " << Median(per_iteration_ms) << "}}" << std::endl;

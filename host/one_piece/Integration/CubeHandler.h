@@ -204,6 +204,26 @@ class CubeHandler {
                                                                    op_volume_register_color_result* details = nullptr);
     bool ColorRegistrationSystem(const geometry::Point3List& points, const std::vector<float>& intensity, const geometry::TransformationMatrix& T,
                                  float max_distance, float color_scale, float max_color_residual, double sums[30], uint64_t counts[5]);
+    // The same under a linearisation in which row and residual agree and with Huber weights (op_volume_register_robust_points states the
+    // definition and why: the stored sdf is projective, its gradient is not of length 1, and the entries above overshoot by that length).
+    // options == nullptr: OP_REGISTER_LIN_METRIC without weights (op_volume_register_robust_default_options); all-zero options give the entries
+    // above bit for bit.  The residual rmse in metres and the down-weighted counts go to *details.
+    //   RegisterPointCloudRobust  intensities as RegisterColoredPointCloud takes them; a cloud without colours is registered with color_scale 0.
+    //   RegisterRGBDRobust  an empty rgb (rgb.data == nullptr): the geometric registration of the depth image.
+    //   RobustRegistrationSystem  one evaluation at T: sums[31] = the 30 above from the scaled rows and the sum of the unweighted r^2;
+    //                       counts[7] = the five above, downweighted, color_downweighted.  false when the call failed.
+    std::shared_ptr<registration::RegistrationResult> RegisterPointCloudRobust(const geometry::PointCloud& pcd,
+                                                                               const geometry::TransformationMatrix& init = geometry::TransformationMatrix::Identity(),
+                                                                               const op_volume_register_color_params* params = nullptr,
+                                                                               const op_volume_register_options* options = nullptr,
+                                                                               op_volume_register_robust_result* details = nullptr);
+    std::shared_ptr<registration::RegistrationResult> RegisterRGBDRobust(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& init_pose,
+                                                                         int pixel_stride = 1, const op_volume_register_color_params* params = nullptr,
+                                                                         const op_volume_register_options* options = nullptr,
+                                                                         op_volume_register_robust_result* details = nullptr);
+    bool RobustRegistrationSystem(const geometry::Point3List& points, const std::vector<float>& intensity, const geometry::TransformationMatrix& T,
+                                  float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
+                                  uint64_t counts[7]);
     void GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh);
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;

@@ -557,6 +557,24 @@ op_volume_register_color_result ColorRegistrationNotRun(const geometry::Transfor
     r.base = RegistrationNotRun(init);
     return r;
 }
+op_volume_register_robust_result RobustRegistrationNotRun(const geometry::TransformationMatrix& init) {
+    op_volume_register_robust_result r = op_volume_register_robust_result();
+    r.color = ColorRegistrationNotRun(init);
+    return r;
+}
+// I(c) of a cloud's colours (stored channel order, byte / 255: LoadFromRGBD); false for a cloud without colours
+bool CloudIntensity(const geometry::PointCloud& pcd, std::vector<float>& intensity) {
+    const size_t n = pcd.points.size();
+    if (pcd.colors.size() != n) return false;
+    intensity.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const float c0 = pcd.colors[i](0), c1 = pcd.colors[i](1), c2 = pcd.colors[i](2);
+        const float a = 0.114f * c0, b = 0.587f * c1, c = 0.299f * c2; // every product and sum rounded separately
+        const float ab = a + b;
+        intensity[i] = ab + c;
+    }
+    return true;
+}
 } // namespace
 std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterColoredPointCloud(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& init,
                                                                                          const op_volume_register_color_params* params,
@@ -572,17 +590,7 @@ std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterColoredPo
         if (params) p = *params;
         else ok = op_volume_register_color_default_params(vol, &p) == OP_OK;
         std::vector<float> intensity;
-        if (pcd.colors.size() == n) { // stored channel order, byte / 255 (LoadFromRGBD)
-            intensity.resize(n);
-            for (size_t i = 0; i < n; ++i) {
-                const float c0 = pcd.colors[i](0), c1 = pcd.colors[i](1), c2 = pcd.colors[i](2);
-                const float a = 0.114f * c0, b = 0.587f * c1, c = 0.299f * c2; // every product and sum rounded separately
-                const float ab = a + b;
-                intensity[i] = ab + c;
-            }
-        } else {
-            p.color_scale = 0.0f;
-        }
+        if (!CloudIntensity(pcd, intensity)) p.color_scale = 0.0f;
         if (!ok || op_volume_register_color_points(vol, bridge::Floats(pcd.points), intensity.empty() ? nullptr : intensity.data(), n, OP_MEM_HOST, t, &p, &r) != OP_OK) {
             Report("RegisterColoredPointCloud");
             r = ColorRegistrationNotRun(init);
@@ -624,6 +632,79 @@ bool CubeHandler::ColorRegistrationSystem(const geometry::Point3List& points, co
     if (op_volume_register_color_system(vol, bridge::Floats(points), y, points.size(), OP_MEM_HOST, t, max_distance, color_scale, max_color_residual, sums, counts,
                                         nullptr) != OP_OK) {
         Report("ColorRegistrationSystem");
+        return false;
+    }
+    ReleaseBorrowed();
+    return true;
+}
+std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterPointCloudRobust(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& init,
+                                                                                        const op_volume_register_color_params* params,
+                                                                                        const op_volume_register_options* options,
+                                                                                        op_volume_register_robust_result* details) {
+    Pending();
+    op_volume_register_robust_result r = RobustRegistrationNotRun(init);
+    if (Ensure()) {
+        float t[16];
+        bridge::RowMajor(init, t);
+        op_volume_register_color_params p;
+        op_volume_register_options o;
+        bool ok = true;
+        if (params) p = *params;
+        else ok = op_volume_register_color_default_params(vol, &p) == OP_OK;
+        if (options) o = *options;
+        else ok = ok && op_volume_register_robust_default_options(vol, &o) == OP_OK;
+        std::vector<float> intensity;
+        if (!CloudIntensity(pcd, intensity)) p.color_scale = 0.0f;
+        if (!ok || op_volume_register_robust_points(vol, bridge::Floats(pcd.points), intensity.empty() ? nullptr : intensity.data(), pcd.points.size(), OP_MEM_HOST, t, &p,
+                                                    &o, &r) != OP_OK) {
+            Report("RegisterPointCloudRobust");
+            r = RobustRegistrationNotRun(init);
+        } else {
+            ReleaseBorrowed(); // (the call synchronised the volume)
+        }
+    }
+    if (details) *details = r;
+    return RegistrationOutcome(r.color.base);
+}
+std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterRGBDRobust(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& init_pose,
+                                                                                  int pixel_stride, const op_volume_register_color_params* params,
+                                                                                  const op_volume_register_options* options, op_volume_register_robust_result* details) {
+    Pending();
+    op_volume_register_robust_result r = RobustRegistrationNotRun(init_pose);
+    if (Ensure()) {
+        float t[16];
+        bridge::RowMajor(init_pose, t);
+        const op_camera pod = camera.Pod();
+        op_volume_register_options o;
+        bool ok = true;
+        if (options) o = *options;
+        else ok = op_volume_register_robust_default_options(vol, &o) == OP_OK;
+        if (!ok || op_volume_register_robust_frame(vol, &pod, depth.data, bridge::DepthFormat(depth), rgb.data, OP_MEM_HOST, pixel_stride, t, params, &o, &r) != OP_OK) {
+            Report("RegisterRGBDRobust");
+            r = RobustRegistrationNotRun(init_pose);
+        } else {
+            ReleaseBorrowed();
+        }
+    }
+    if (details) *details = r;
+    return RegistrationOutcome(r.color.base);
+}
+bool CubeHandler::RobustRegistrationSystem(const geometry::Point3List& points, const std::vector<float>& intensity, const geometry::TransformationMatrix& T,
+                                           float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
+                                           uint64_t counts[7]) {
+    Pending();
+    for (int k = 0; k < 31; ++k) sums[k] = 0.0;
+    for (int k = 0; k < 7; ++k) counts[k] = 0;
+    if (!Ensure()) return false;
+    float t[16];
+    bridge::RowMajor(T, t);
+    op_volume_register_options o;
+    if (options) o = *options;
+    else if (op_volume_register_robust_default_options(vol, &o) != OP_OK) { Report("RobustRegistrationSystem"); return false; }
+    const float* y = intensity.size() == points.size() && !intensity.empty() ? intensity.data() : nullptr; // (a missing intensity is the library's refusal)
+    if (op_volume_register_robust_system(vol, bridge::Floats(points), y, points.size(), OP_MEM_HOST, t, max_distance, color_scale, max_color_residual, &o, sums, counts,
+                                         nullptr) != OP_OK) {
+        Report("RobustRegistrationSystem");
         return false;
     }
     ReleaseBorrowed();

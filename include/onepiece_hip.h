@@ -670,6 +670,64 @@ int op_volume_register_rgbd(op_volume *v, const op_camera *cam /* NULL: the volu
                             int mem, int pixel_stride, const float init_pose[16], const op_volume_register_color_params *params,
                             op_volume_register_color_result *result);
 
+/* Consistent linearisations and Huber weights for the registration against the field (csrc/volume_register.hip, the ROBUST instantiations of
+ * k_volume_register; NO reference counterpart).  The stored sdf is projective -- measured along the fusing cameras' rays -- so across a surface
+ * seen at angle theta it changes by about 1 / cos theta per metre: |grad s| = sqrtf(l2) / res is not 1.  The entries above pair the residual s
+ * with the NORMALISED difference n, which understates the Jacobian by |grad s|: every Gauss-Newton step overshoots by that factor (a zig-zag
+ * below 2, an alternation between two poses at 2).  Here row and residual agree.  Every per-point operation below is float32 and rounded
+ * separately; nothing is contracted.
+ *   1. p, s, d, l2, the USED rule (max_distance gates fabsf(s), the stored sdf, in every mode), n = d / sqrtf(l2) and the counts used / invalid /
+ *      no_gradient / too_far are exactly op_volume_register_system's steps 1-5 and 8: the USED set does not depend on the options.
+ *   2. The linearisation sets the geometric row vector a and the residual r:
+ *        OP_REGISTER_LIN_NORMAL   (0)  a = n,                r = s                      (the entries above)
+ *        OP_REGISTER_LIN_GRADIENT (1)  a_k = d_k / res,      r = s                      (the Gauss-Newton of sum s^2)
+ *        OP_REGISTER_LIN_METRIC   (2)  a = n,                r = s / m, m = sqrtf(l2) / res   (the first-order distance in metres)
+ *      and the row is j = (a0, a1, a2, p1 a2 - p2 a1, p2 a0 - p0 a2, p0 a1 - p1 a0).
+ *   3. huber > 0: w = 1 when fabsf(r) <= huber, else w = huber / fabsf(r); q = sqrtf(w); j_a <- q j_a, r <- q r, one product each.  The point
+ *      counts as downweighted iff w < 1.  huber == 0: no weights (no product).
+ *   4. The colour term is op_volume_register_color_system's steps 2-7 (rc, the COLOURED rule, jc, rcs).  huber_color > 0: wc = 1 when
+ *      fabsf(rc) <= huber_color (rc unscaled), else huber_color / fabsf(rc); qc = sqrtf(wc); jc_a <- qc jc_a, rcs <- qc rcs.  A coloured point
+ *      with wc < 1 counts as color_downweighted.
+ *   5. sums[0..27] are formed from the scaled j, r (in s's place), jc, rcs exactly as steps 7 / 8 of the two definitions above form them.
+ *   6. sums[28] += (double)rc * (double)rc over coloured points (unscaled, unweighted); sums[29] += (double)s * (double)s over used points (the
+ *      stored sdf, unweighted); sums[30] += (double)r * (double)r over used points, r of step 2 (unweighted).
+ *   7. counts = {used, invalid, no_gradient, too_far, colored, downweighted, color_downweighted}.
+ *   8. Slots 0..27 and the first four counts are reduced exactly as point 9 of op_volume_register_system states.  The six other quantities are
+ *      reduced over the wave per trip by the colour entry's butterfly (partner lanes 32, 16, 8, 4, 2, 1 apart, in that order), the trips added
+ *      in order, then the four waves in order, one row of 38 per workgroup, and a second kernel adds the rows (at most 1024) in index order --
+ *      row r, r + 16, ... per row lane, then the 16 row lanes in order.  Fixed for a given n: two calls give the same bits, with and without
+ *      rows.  No floating-point atomics.
+ * options == NULL or {0, 0, 0}: sums[0..29], counts[0..4], rows, T and result->color are bit for bit what op_volume_register_color_* give for
+ * the same arguments (those kernels run; with color_scale == 0 that is the geometric entries); sums[30] = sums[29], the two new counts 0.
+ * huber_color is not looked at when color_scale == 0.
+ * op_volume_register_robust_system evaluates this once: sums[31], counts[7] (host; counts may be NULL) and optionally rows: n x 16 floats in
+ * `mem` in op_volume_register_color_system's layout {j[6], r, used, jc[6], rcs, colored}, holding what enters the sums (the scaled values).
+ * op_volume_register_robust_points is the same host loop (op_ldlt_solve6, op_se3_exp, the float32 product, the same stop rules and statuses)
+ * around this system; result->color is filled as op_volume_register_color_points fills it (base.rmse stays sqrt(sums[29] / used), the stored
+ * sdf), downweighted / color_downweighted describe the returned pose, first_downweighted init_T, rmse_residual = sqrt(sums[30] / used) and
+ * first_rmse_residual likewise (0 when used is 0).
+ * op_volume_register_robust_frame back-projects exactly as op_volume_register_rgbd does; rgb == NULL: no intensities, the geometric
+ * registration whatever params->color_scale says.  Its result is, bit for bit, op_volume_register_robust_points on those points and
+ * intensities.  op_volume_register_robust_default_options gives {OP_REGISTER_LIN_METRIC, 0, 0}.
+ * Refusals, decided before any device use: everything the colour entries refuse (a NULL rgb excepted) and OP_ERR_INVALID for a linearisation
+ * outside 0..2 and for a negative or non-finite huber or huber_color. */
+enum { OP_REGISTER_LIN_NORMAL = 0, OP_REGISTER_LIN_GRADIENT = 1, OP_REGISTER_LIN_METRIC = 2 };
+typedef struct { int linearization; float huber, huber_color; } op_volume_register_options;
+typedef struct { op_volume_register_color_result color; uint64_t downweighted, color_downweighted, first_downweighted;
+                 double rmse_residual, first_rmse_residual; } op_volume_register_robust_result;
+int op_volume_register_robust_default_options(op_volume *v, op_volume_register_options *options);
+int op_volume_register_robust_system(op_volume *v, const float *xyz, const float *intensity /* n in `mem`, or NULL */, size_t n, int mem,
+                                     const float T[16], float max_distance, float color_scale, float max_color_residual,
+                                     const op_volume_register_options *options /* NULL: zeros */, double sums[31], uint64_t counts[7],
+                                     float *rows /* n x 16 in `mem`, or NULL */);
+int op_volume_register_robust_points(op_volume *v, const float *xyz, const float *intensity, size_t n, int mem, const float init_T[16],
+                                     const op_volume_register_color_params *params /* NULL: defaults */,
+                                     const op_volume_register_options *options /* NULL: zeros */, op_volume_register_robust_result *result);
+int op_volume_register_robust_frame(op_volume *v, const op_camera *cam /* NULL: the volume's */, const void *depth, int depth_fmt,
+                                    const uint8_t *rgb /* NULL: geometric */, int mem, int pixel_stride, const float init_pose[16],
+                                    const op_volume_register_color_params *params, const op_volume_register_options *options,
+                                    op_volume_register_robust_result *result);
+
 /* Frame-sharded multi-GPU merge (the distributed form of CubeHandler::Merge; DESIGN.md "Multi-GPU").
  * All pointers are DEVICE pointers on the volume's device.
  *   keys_device : copy this volume's block keys (n x 3 int32) into d_keys.

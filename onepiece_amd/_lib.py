@@ -69,6 +69,20 @@ class RegisterColorResult(C.Structure):
                 ("rmse_color", C.c_double), ("first_rmse_color", C.c_double)]
 
 
+OP_REGISTER_LIN_NORMAL, OP_REGISTER_LIN_GRADIENT, OP_REGISTER_LIN_METRIC = 0, 1, 2
+
+
+class RegisterOptions(C.Structure):
+    """op_volume_register_options of op_volume_register_robust_*: the linearisation and the two Huber thresholds."""
+    _fields_ = [("linearization", C.c_int32), ("huber", C.c_float), ("huber_color", C.c_float)]
+
+
+class RegisterRobustResult(C.Structure):
+    """op_volume_register_robust_result of op_volume_register_robust_points / _frame."""
+    _fields_ = [("color", RegisterColorResult), ("downweighted", C.c_uint64), ("color_downweighted", C.c_uint64), ("first_downweighted", C.c_uint64),
+                ("rmse_residual", C.c_double), ("first_rmse_residual", C.c_double)]
+
+
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("last_T", C.c_float * 16), ("rmse", C.c_double),
                 ("n_inliers", C.c_uint64), ("iterations", C.c_int32)]
@@ -210,6 +224,13 @@ SIGNATURES = {
     "op_volume_register_color_points": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _fp, C.POINTER(RegisterColorParams), C.POINTER(RegisterColorResult)]),
     "op_volume_register_rgbd": (C.c_int, [_vp, C.POINTER(Camera), _vp, C.c_int, _vp, C.c_int, C.c_int, _fp, C.POINTER(RegisterColorParams),
                                           C.POINTER(RegisterColorResult)]),
+    "op_volume_register_robust_default_options": (C.c_int, [_vp, C.POINTER(RegisterOptions)]),
+    "op_volume_register_robust_system": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _fp, C.c_float, C.c_float, C.c_float, C.POINTER(RegisterOptions),
+                                                   C.POINTER(C.c_double), _u64p, _vp]),
+    "op_volume_register_robust_points": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _fp, C.POINTER(RegisterColorParams), C.POINTER(RegisterOptions),
+                                                   C.POINTER(RegisterRobustResult)]),
+    "op_volume_register_robust_frame": (C.c_int, [_vp, C.POINTER(Camera), _vp, C.c_int, _vp, C.c_int, C.c_int, _fp, C.POINTER(RegisterColorParams),
+                                                  C.POINTER(RegisterOptions), C.POINTER(RegisterRobustResult)]),
     "op_volume_keys_device": (C.c_int, [_vp, _vp, C.c_size_t, _szp]),
     "op_volume_pack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "op_volume_unpack_sum": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

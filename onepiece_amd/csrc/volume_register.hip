@@ -17,7 +17,12 @@
 // unscaled sum of (m - y)^2, the geometric sum of s^2, the count of coloured points) travel by a butterfly of their own: three doubles per lane,
 // six xor steps per trip, every lane ends with the wave's total; lane 0 puts them behind the wave's 32 slots (35 per row) and
 // k_register_fold_color adds the rows.  color_scale == 0 runs the geometric instantiation: the colour planes are never read.
-// Not built: robust weights, multi-resolution, re-ordering the points by block.
+// The ROBUST instantiations (op_volume_register_robust_*) choose the linearisation -- which vector a the row (a ; p x a) is built from and which
+// residual r goes with it: NORMAL (n, s: the entries above), GRADIENT (d / res, s), METRIC (n, s / (|d| / res)) -- and may scale row and residual
+// by the square root of a Huber weight, the colour term by one of its own.  The mode and the two thresholds are wave-uniform arguments.  The six
+// quantities without a slot (the colour kernel's three, the sum of the unweighted r^2, the two down-weighted counts) travel by the same butterfly:
+// rows of 38, k_register_fold_robust.  All-zero options run the instantiations above: nothing about them changes.
+// Not built: damping, multi-resolution, re-ordering the points by block.
 #include "volume_core.hpp"
 #include "trilinear_sample.hpp"
 
@@ -35,6 +40,7 @@ constexpr int kFoldWg = 1024;          // k_register_fold: one workgroup, 32 row
 constexpr int kFoldRows = kFoldWg / kRegSlots;
 constexpr int kRegSlotsC = 35;         // COLOR: the 32 above (0..27 with the colour terms added), [32] rc rc, [33] s s alone, [34] colored
 constexpr int kFoldRowsC = kFoldWg / 64; // k_register_fold_color: 16 row lanes of 64 threads, 35 of them at work
+constexpr int kRegSlotsR = 38;         // ROBUST: the 35 above, [35] r r (unweighted), [36] downweighted, [37] color_downweighted
 
 struct RegView { float res, inv_res; }; // what trilinear_sample.hpp reads of a view
 
@@ -44,12 +50,18 @@ struct RegArgs {
     float T[16];
     RegView W;
     float max_distance;
-    float* rows;     // n x 8 {j[6], s, used} (ROWS only); COLOR: n x 16 {j[6], s, used, jc[6], rcs, colored}
-    double* partial; // gridDim.x x kRegSlots (COLOR: x kRegSlotsC)
+    float* rows;     // n x 8 {j[6], s, used} (ROWS only); COLOR: n x 16 {j[6], s, used, jc[6], rcs, colored}; ROBUST: the same layouts, the scaled values
+    double* partial; // gridDim.x x kRegSlots (COLOR: x kRegSlotsC, ROBUST: x kRegSlotsR)
 };
 struct RegColor { // what the COLOR instantiations read on top
     const float* intensity; // n observed intensities
     float color_scale, max_color_residual;
+};
+struct RegRobust { // what the ROBUST instantiations take in RegColor's place: the same three first
+    const float* intensity;
+    float color_scale, max_color_residual;
+    int linearization;        // OP_REGISTER_LIN_*
+    float huber, huber_color; // <= 0: no weights
 };
 
 // intensity of a colour triple in stored channel order
@@ -70,12 +82,13 @@ __device__ __forceinline__ bool reg_sample_sdf(const VolView& V, const RegView& 
     }
 }
 
-template <bool ROWS, bool COLOR>
-__global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A, RegColor K) {
-    constexpr int kSlots = COLOR ? kRegSlotsC : kRegSlots;
+template <bool ROWS, bool COLOR, bool ROBUST = false>
+__global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A, std::conditional_t<ROBUST, RegRobust, RegColor> K) {
+    constexpr int kSlots = ROBUST ? kRegSlotsR : COLOR ? kRegSlotsC : kRegSlots;
+    constexpr int kExt = ROBUST ? 6 : 3;
     __shared__ double s_red[kRegWg / 64][kSlots];
     double total = 0.0; // lane L: slot (L >> 1) & 31 of this wave, over its trips
-    double ext[3] = {0.0, 0.0, 0.0}; // COLOR: the wave's rc rc, s s, colored over its trips (the same in every lane)
+    double ext[kExt] = {}; // COLOR: the wave's rc rc, s s, colored over its trips (the same in every lane); ROBUST: and r r, downweighted, color_downweighted
     BlockCache bc{INT_MIN, INT_MIN, INT_MIN, -1};
     const size_t step = (size_t)gridDim.x * kRegWg;
     for (size_t base = (size_t)blockIdx.x * kRegWg; base < A.n; base += step) { // (the same trips for every lane of the workgroup)
@@ -83,6 +96,8 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
         float j[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, s = 0.0f;
         float jc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rcs = 0.0f, rc = 0.0f; // COLOR: zero unless the point is coloured
         bool colored = false;
+        float sraw = 0.0f, runw = 0.0f; // ROBUST: the sdf and the unweighted residual of a used point
+        bool down = false, cdown = false;
         int reason = -1; // 0 used, 1 invalid, 2 no gradient, 3 too far; -1: no point
         if (i < A.n) {
             const float x = A.xyz[3 * i], y = A.xyz[3 * i + 1], z = A.xyz[3 * i + 2];
@@ -112,10 +127,25 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
                 else {
                     reason = 0;
                     const float l = sqrtf(l2);
-                    const float n0 = d[0] / l, n1 = d[1] / l, n2 = d[2] / l;
+                    float n0 = d[0] / l, n1 = d[1] / l, n2 = d[2] / l;
+                    s = sv;
+                    if constexpr (ROBUST) { // the row vector a (in n's place) and the residual r (in s's)
+                        if (K.linearization == OP_REGISTER_LIN_GRADIENT) { n0 = d[0] / A.W.res; n1 = d[1] / A.W.res; n2 = d[2] / A.W.res; }
+                        else if (K.linearization == OP_REGISTER_LIN_METRIC) s = sv / (l / A.W.res);
+                        sraw = sv; runw = s;
+                    }
                     j[0] = n0; j[1] = n1; j[2] = n2;
                     j[3] = p1 * n2 - p2 * n1; j[4] = p2 * n0 - p0 * n2; j[5] = p0 * n1 - p1 * n0;
-                    s = sv;
+                    if constexpr (ROBUST) {
+                        if (K.huber > 0.0f) {
+                            const float w = fabsf(s) <= K.huber ? 1.0f : K.huber / fabsf(s);
+                            const float q = sqrtf(w);
+                            down = w < 1.0f;
+#pragma unroll
+                            for (int a = 0; a < 6; ++a) j[a] = q * j[a];
+                            s = q * s;
+                        }
+                    }
                     if constexpr (COLOR) {
                         const float y = K.intensity[i], r = mv - y;
                         if (fabsf(y) < INFINITY && (!(K.max_color_residual > 0.0f) || fabsf(r) <= K.max_color_residual)) { // (false for a NaN y)
@@ -124,6 +154,16 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
                             jc[0] = cs * g[0]; jc[1] = cs * g[1]; jc[2] = cs * g[2];
                             jc[3] = cs * (p1 * g[2] - p2 * g[1]); jc[4] = cs * (p2 * g[0] - p0 * g[2]); jc[5] = cs * (p0 * g[1] - p1 * g[0]);
                             rc = r; rcs = cs * r;
+                            if constexpr (ROBUST) {
+                                if (K.huber_color > 0.0f) {
+                                    const float wc = fabsf(r) <= K.huber_color ? 1.0f : K.huber_color / fabsf(r);
+                                    const float qc = sqrtf(wc);
+                                    cdown = wc < 1.0f;
+#pragma unroll
+                                    for (int a = 0; a < 6; ++a) jc[a] = qc * jc[a];
+                                    rcs = qc * rcs;
+                                }
+                            }
                         }
                     }
                 }
@@ -159,7 +199,17 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
             }
         };
         total += op::wave_reduce_scatter32_lazy(val);
-        if constexpr (COLOR) { // the three without a slot: a butterfly, lane masks 32, 16, 8, 4, 2, 1 -- a + b is b + a, so every lane holds the same total
+        if constexpr (ROBUST) { // the six without a slot, by the butterfly below (without COLOR three of them are zero and stay at home)
+            double e[6] = {(double)rc * (double)rc, (double)sraw * (double)sraw, colored ? 1.0 : 0.0, (double)runw * (double)runw, down ? 1.0 : 0.0, cdown ? 1.0 : 0.0};
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+                for (int q = 0; q < 6; ++q)
+                    if (COLOR || q == 1 || q == 3 || q == 4) e[q] += __shfl_xor(e[q], m, 64);
+            }
+#pragma unroll
+            for (int q = 0; q < 6; ++q) ext[q] += e[q];
+        } else if constexpr (COLOR) { // the three without a slot: a butterfly, lane masks 32, 16, 8, 4, 2, 1 -- a + b is b + a, so every lane holds the same total
             double e[3] = {(double)rc * (double)rc, (double)s * (double)s, colored ? 1.0 : 0.0};
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) {
@@ -173,8 +223,11 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
     // one row per workgroup (every lane gets here)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if ((lane & 1) == 0) s_red[wave][lane >> 1] = total;
-    if constexpr (COLOR) {
-        if (lane == 0) { s_red[wave][32] = ext[0]; s_red[wave][33] = ext[1]; s_red[wave][34] = ext[2]; }
+    if constexpr (COLOR || ROBUST) {
+        if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < kExt; ++q) s_red[wave][32 + q] = ext[q];
+        }
     }
     __syncthreads();
     if (threadIdx.x < kSlots) {
@@ -205,27 +258,34 @@ __global__ __launch_bounds__(kFoldWg) void k_register_fold(const double* __restr
     }
 }
 
-// the same for rows of 35: row lane r (of 16) adds rows r, r + 16, ..., then the 16 row lanes are added in order
-__global__ __launch_bounds__(kFoldWg) void k_register_fold_color(const double* __restrict__ partial, unsigned n_rows, double* __restrict__ out) {
-    __shared__ double s_fin[kFoldRowsC][kRegSlotsC];
+// the same for rows of 35 (COLOR) or 38 (ROBUST): row lane r (of 16) adds rows r, r + 16, ..., then the 16 row lanes are added in order
+template <int SLOTS>
+__device__ __forceinline__ void register_fold_wide(const double* __restrict__ partial, unsigned n_rows, double* __restrict__ out) {
+    __shared__ double s_fin[kFoldRowsC][SLOTS];
     const unsigned fk = threadIdx.x & 63u, fr = threadIdx.x >> 6;
-    if (fk < (unsigned)kRegSlotsC) {
+    if (fk < (unsigned)SLOTS) {
         double t = 0.0;
         unsigned p = fr;
         for (; p + 3 * kFoldRowsC < n_rows; p += 4 * kFoldRowsC) {
-            const double a0 = partial[(size_t)p * kRegSlotsC + fk], a1 = partial[(size_t)(p + kFoldRowsC) * kRegSlotsC + fk];
-            const double a2 = partial[(size_t)(p + 2 * kFoldRowsC) * kRegSlotsC + fk], a3 = partial[(size_t)(p + 3 * kFoldRowsC) * kRegSlotsC + fk];
+            const double a0 = partial[(size_t)p * SLOTS + fk], a1 = partial[(size_t)(p + kFoldRowsC) * SLOTS + fk];
+            const double a2 = partial[(size_t)(p + 2 * kFoldRowsC) * SLOTS + fk], a3 = partial[(size_t)(p + 3 * kFoldRowsC) * SLOTS + fk];
             t += a0; t += a1; t += a2; t += a3;
         }
-        for (; p < n_rows; p += kFoldRowsC) t += partial[(size_t)p * kRegSlotsC + fk];
+        for (; p < n_rows; p += kFoldRowsC) t += partial[(size_t)p * SLOTS + fk];
         s_fin[fr][fk] = t;
     }
     __syncthreads();
-    if (threadIdx.x < (unsigned)kRegSlotsC) {
+    if (threadIdx.x < (unsigned)SLOTS) {
         double u = s_fin[0][threadIdx.x];
         for (int r = 1; r < kFoldRowsC; ++r) u += s_fin[r][threadIdx.x];
         out[threadIdx.x] = u;
     }
+}
+__global__ __launch_bounds__(kFoldWg) void k_register_fold_color(const double* __restrict__ partial, unsigned n_rows, double* __restrict__ out) {
+    register_fold_wide<kRegSlotsC>(partial, n_rows, out);
+}
+__global__ __launch_bounds__(kFoldWg) void k_register_fold_robust(const double* __restrict__ partial, unsigned n_rows, double* __restrict__ out) {
+    register_fold_wide<kRegSlotsR>(partial, n_rows, out);
 }
 
 // ---- the depth entry's points: op_points_from_depth's definition over every stride-th pixel in both directions, row-major, compacted
@@ -270,13 +330,16 @@ struct RegRun {
 
     RegColor K{nullptr, 0.0f, 0.0f}; // color_scale > 0: the COLOR instantiations
 
+    op_volume_register_options O{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}; // anything else: the ROBUST instantiations
+
     explicit RegRun(op_volume* vol) : v(vol) { tmp.bind(v->stream); }
     bool color() const { return K.color_scale > 0.0f; }
+    bool robust() const { return O.linearization != OP_REGISTER_LIN_NORMAL || O.huber > 0.0f || (color() && O.huber_color > 0.0f); }
     int open(const float* d_xyz, size_t n, float max_distance) {
         A.xyz = d_xyz; A.n = n; A.W.res = v->res; A.W.inv_res = 1.0f / v->res; A.max_distance = max_distance;
         grid = (unsigned)std::min<size_t>((n + kRegWg - 1) / kRegWg, kRegMaxGrid);
         if (!grid) return OP_OK;
-        const size_t slots = color() ? kRegSlotsC : kRegSlots;
+        const size_t slots = robust() ? kRegSlotsR : color() ? kRegSlotsC : kRegSlots;
         OP_TRY(tmp.alloc(&A.partial, (size_t)grid * slots));
         OP_TRY(tmp.alloc(&d_out, slots));
         OP_TRY(tmp.pinned(&h_out, slots));
@@ -332,6 +395,44 @@ struct RegRun {
         counts[4] = (uint64_t)r[34];
         return OP_OK;
     }
+    int open_robust(const float* d_xyz, const float* d_intensity, size_t n, float max_distance, float color_scale, float max_color_residual,
+                    const op_volume_register_options& options) {
+        O = options;
+        return open_color(d_xyz, d_intensity, n, max_distance, color_scale, max_color_residual);
+    }
+    // the system under the options at T: 31 sums ([30] r r, unweighted) and 7 counts (d_rows: n x 16 with the colour term, n x 8 without).
+    // All-zero options ARE the evaluation above (d_rows must be NULL then without the colour term, as there).
+    int eval_robust(const float T[16], float* d_rows, double sums[31], uint64_t counts[7]) {
+        if (!robust()) {
+            OP_TRY(eval_color(T, d_rows, sums, counts));
+            sums[30] = sums[29]; counts[5] = 0; counts[6] = 0;
+            return OP_OK;
+        }
+        for (int k = 0; k < 31; ++k) sums[k] = 0.0;
+        for (int k = 0; k < 7; ++k) counts[k] = 0;
+        if (!grid) return OP_OK;
+        for (int k = 0; k < 16; ++k) A.T[k] = T[k];
+        A.rows = d_rows;
+        const VolView V = v->view();
+        const RegRobust KR{K.intensity, K.color_scale, K.max_color_residual, O.linearization, O.huber, O.huber_color};
+        if (color()) {
+            if (d_rows) hipLaunchKernelGGL((k_volume_register<true, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
+            else hipLaunchKernelGGL((k_volume_register<false, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
+        } else {
+            if (d_rows) hipLaunchKernelGGL((k_volume_register<true, false, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
+            else hipLaunchKernelGGL((k_volume_register<false, false, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
+        }
+        hipLaunchKernelGGL(k_register_fold_robust, dim3(1), dim3(kFoldWg), 0, v->stream, (const double*)A.partial, grid, d_out);
+        OP_HIP(hipGetLastError());
+        OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * kRegSlotsR, hipMemcpyDeviceToHost, v->stream));
+        OP_HIP(hipStreamSynchronize(v->stream));
+        const double* r = h_out;
+        for (int k = 0; k < 28; ++k) sums[k] = r[k];
+        sums[28] = r[32]; sums[29] = r[33]; sums[30] = r[35];
+        for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k];
+        counts[4] = (uint64_t)r[34]; counts[5] = (uint64_t)r[36]; counts[6] = (uint64_t)r[37];
+        return OP_OK;
+    }
 };
 
 inline double reg_rmse(double sum_sq, uint64_t count) { return count ? std::sqrt(sum_sq / (double)count) : 0.0; }
@@ -369,27 +470,29 @@ op_volume_register_color_params reg_color_defaults(const op_volume* v) {
     return p;
 }
 
-// the Gauss-Newton loop over points (and, with color_scale > 0, intensities) that are on the device; color_scale == 0: the geometric loop
+// the Gauss-Newton loop over points (and, with color_scale > 0, intensities) that are on the device; color_scale == 0: the geometric loop;
+// all-zero options: the plain system
 int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
-             float max_color_residual, op_volume_register_color_result* out) {
+             float max_color_residual, const op_volume_register_options& options, op_volume_register_robust_result* robust) {
+    op_volume_register_color_result* out = &robust->color;
     RegRun R(v);
-    OP_TRY(R.open_color(d_xyz, d_intensity, n, P.max_distance, color_scale, max_color_residual));
+    OP_TRY(R.open_robust(d_xyz, d_intensity, n, P.max_distance, color_scale, max_color_residual, options));
     op_volume_register_result res{};
     float T[16];
     for (int k = 0; k < 16; ++k) T[k] = init_T[k];
-    double sums[30], first_sums[30];
-    uint64_t counts[5], first_counts[5];
+    double sums[31], first_sums[31];
+    uint64_t counts[7], first_counts[7];
     bool have_first = false, current = false; // current: sums / counts are the system at T
     res.status = OP_REGISTER_MAX_ITERATIONS;
     const uint64_t min_points = P.min_points > 0 ? (uint64_t)P.min_points : 0;
     const double min_step2 = (double)P.min_step * (double)P.min_step;
     for (int it = 0; it < P.max_iterations; ++it) {
-        OP_TRY(R.eval_color(T, nullptr, sums, counts));
+        OP_TRY(R.eval_robust(T, nullptr, sums, counts));
         current = true;
         if (!have_first) {
             have_first = true;
-            for (int k = 0; k < 30; ++k) first_sums[k] = sums[k];
-            for (int k = 0; k < 5; ++k) first_counts[k] = counts[k];
+            for (int k = 0; k < 31; ++k) first_sums[k] = sums[k];
+            for (int k = 0; k < 7; ++k) first_counts[k] = counts[k];
         }
         if (counts[0] < min_points) { res.status = OP_REGISTER_TOO_FEW_POINTS; break; }
         double JTJ[36], JTr[6];
@@ -412,10 +515,10 @@ int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t 
         res.last_step = std::sqrt(ss);
         if (ss < min_step2) { res.status = OP_REGISTER_CONVERGED; break; }
     }
-    if (!current) OP_TRY(R.eval_color(T, nullptr, sums, counts)); // the system at the pose that is returned
+    if (!current) OP_TRY(R.eval_robust(T, nullptr, sums, counts)); // the system at the pose that is returned
     if (!have_first) { // max_iterations == 0
-        for (int k = 0; k < 30; ++k) first_sums[k] = sums[k];
-        for (int k = 0; k < 5; ++k) first_counts[k] = counts[k];
+        for (int k = 0; k < 31; ++k) first_sums[k] = sums[k];
+        for (int k = 0; k < 7; ++k) first_counts[k] = counts[k];
         if (counts[0] < min_points) res.status = OP_REGISTER_TOO_FEW_POINTS;
     }
     for (int k = 0; k < 16; ++k) res.T[k] = T[k];
@@ -427,12 +530,29 @@ int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t 
     out->colored = counts[4]; out->first_colored = first_counts[4];
     out->rmse_color = reg_rmse(sums[28], counts[4]);
     out->first_rmse_color = reg_rmse(first_sums[28], first_counts[4]);
+    robust->downweighted = counts[5]; robust->color_downweighted = counts[6]; robust->first_downweighted = first_counts[5];
+    robust->rmse_residual = reg_rmse(sums[30], counts[0]);
+    robust->first_rmse_residual = reg_rmse(first_sums[30], first_counts[0]);
+    return OP_OK;
+}
+int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
+             float max_color_residual, op_volume_register_color_result* out) {
+    op_volume_register_robust_result r{};
+    OP_TRY(reg_loop(v, d_xyz, d_intensity, n, init_T, P, color_scale, max_color_residual, op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, &r));
+    *out = r.color;
     return OP_OK;
 }
 int reg_loop(op_volume* v, const float* d_xyz, size_t n, const float init_T[16], const op_volume_register_params& P, op_volume_register_result* out) {
     op_volume_register_color_result r{};
     OP_TRY(reg_loop(v, d_xyz, nullptr, n, init_T, P, 0.0f, 0.0f, &r));
     *out = r.base;
+    return OP_OK;
+}
+int reg_check_options(const op_volume_register_options* o, const char* who) {
+    if (!o) return OP_OK;
+    if (o->linearization < OP_REGISTER_LIN_NORMAL || o->linearization > OP_REGISTER_LIN_METRIC) return fail(OP_ERR_INVALID, "%s: linearization %d", who, o->linearization);
+    if (!(o->huber >= 0.0f) || !std::isfinite(o->huber)) return fail(OP_ERR_INVALID, "%s: huber must be finite and >= 0", who);
+    if (!(o->huber_color >= 0.0f) || !std::isfinite(o->huber_color)) return fail(OP_ERR_INVALID, "%s: huber_color must be finite and >= 0", who);
     return OP_OK;
 }
 
@@ -638,6 +758,110 @@ int op_volume_register_rgbd(op_volume* v, const op_camera* cam, const void* dept
     unsigned total = 0;
     OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, rgb, mem, pixel_stride, &total));
     return reg_loop(v, v->reg_pts, v->reg_int, (size_t)total, init_pose, P.base, P.color_scale, P.max_color_residual, result);
+}
+
+// ---- the linearisation and the Huber weights
+int op_volume_register_robust_default_options(op_volume* v, op_volume_register_options* o) {
+    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_robust_default_options: null volume");
+    if (!o) return fail(OP_ERR_INVALID, "op_volume_register_robust_default_options: null options");
+    o->linearization = OP_REGISTER_LIN_METRIC; o->huber = 0.0f; o->huber_color = 0.0f;
+    return OP_OK;
+}
+
+int op_volume_register_robust_system(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float T[16], float max_distance,
+                                     float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
+                                     uint64_t counts[7], float* rows) {
+    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null volume");
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: bad mem %d", mem);
+    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null xyz");
+    if (!T) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null T");
+    if (!sums) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null sums");
+    OP_TRY(reg_check_color_scale(color_scale, "op_volume_register_robust_system"));
+    if (n > 0 && color_scale > 0.0f && !intensity) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null intensity");
+    OP_TRY(reg_check_options(options, "op_volume_register_robust_system"));
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    RegRun R(v);
+    const float *d_xyz = nullptr, *d_int = nullptr;
+    OP_TRY(R.tmp.input(xyz, 3 * n, mem, &d_xyz));
+    if (color_scale > 0.0f) OP_TRY(R.tmp.input(intensity, n, mem, &d_int));
+    OP_TRY(R.open_robust(d_xyz, d_int, n, max_distance, color_scale, max_color_residual,
+                         options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}));
+    const bool want_rows = rows && n;
+    uint64_t c[7];
+    if (R.color()) {
+        float* d_rows = rows;
+        if (want_rows && mem == OP_MEM_HOST) OP_TRY(R.tmp.alloc(&d_rows, 16 * n));
+        OP_TRY(R.eval_robust(T, want_rows ? d_rows : nullptr, sums, c));
+        if (want_rows && mem == OP_MEM_HOST) OP_HIP(hipMemcpy(rows, d_rows, sizeof(float) * 16 * n, hipMemcpyDeviceToHost));
+    } else { // rows of 8 become the first halves of rows of 16, as op_volume_register_color_system widens them
+        float* d_rows8 = nullptr;
+        if (want_rows) OP_TRY(R.tmp.alloc(&d_rows8, 8 * n));
+        if (R.robust()) OP_TRY(R.eval_robust(T, d_rows8, sums, c));
+        else {
+            OP_TRY(R.eval(T, d_rows8, sums, c));
+            sums[28] = 0.0; sums[29] = sums[27]; sums[30] = sums[27]; c[4] = 0; c[5] = 0; c[6] = 0;
+        }
+        if (want_rows) {
+            if (mem == OP_MEM_HOST) std::memset(rows, 0, sizeof(float) * 16 * n);
+            else OP_HIP(hipMemset(rows, 0, sizeof(float) * 16 * n));
+            OP_HIP(hipMemcpy2D(rows, sizeof(float) * 16, d_rows8, sizeof(float) * 8, sizeof(float) * 8, n, mem == OP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        }
+    }
+    if (counts) for (int k = 0; k < 7; ++k) counts[k] = c[k];
+    return OP_OK;
+}
+
+int op_volume_register_robust_points(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float init_T[16],
+                                     const op_volume_register_color_params* params, const op_volume_register_options* options,
+                                     op_volume_register_robust_result* result) {
+    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null volume");
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: bad mem %d", mem);
+    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null xyz");
+    if (!init_T) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null init_T");
+    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null result");
+    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_robust_points"));
+    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_robust_points"));
+    if (n > 0 && !intensity && (!params || params->color_scale > 0.0f)) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null intensity");
+    OP_TRY(reg_check_options(options, "op_volume_register_robust_points"));
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    op::Scope up;
+    up.bind(v->stream);
+    const float *d_xyz = nullptr, *d_int = nullptr;
+    OP_TRY(up.input(xyz, 3 * n, mem, &d_xyz));
+    if (P.color_scale > 0.0f) OP_TRY(up.input(intensity, n, mem, &d_int));
+    return reg_loop(v, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual,
+                    options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, result);
+}
+
+int op_volume_register_robust_frame(op_volume* v, const op_camera* cam, const void* depth, int depth_fmt, const uint8_t* rgb, int mem, int pixel_stride,
+                                    const float init_pose[16], const op_volume_register_color_params* params, const op_volume_register_options* options,
+                                    op_volume_register_robust_result* result) {
+    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: null volume");
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: bad mem %d", mem);
+    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: bad depth format %d", depth_fmt);
+    if (!depth) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: null depth");
+    if (pixel_stride < 1) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: pixel_stride < 1");
+    if (!init_pose) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: null init_pose");
+    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: null result");
+    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_robust_frame"));
+    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_robust_frame"));
+    OP_TRY(reg_check_options(options, "op_volume_register_robust_frame"));
+    const op_camera c = cam ? *cam : v->cam;
+    OP_TRY(check_cam(&c));
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    const float color_scale = rgb ? P.color_scale : 0.0f; // no colour image: the geometric registration
+
+    op::Scope tmp;
+    tmp.bind(v->stream);
+    unsigned total = 0;
+    OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, rgb, mem, pixel_stride, &total));
+    return reg_loop(v, v->reg_pts, rgb ? v->reg_int : nullptr, (size_t)total, init_pose, P.base, color_scale, P.max_color_residual,
+                    options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, result);
 }
 
 } // extern "C"

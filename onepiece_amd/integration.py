@@ -728,6 +728,86 @@ class CubeHandler:
         self._alive = []
         return self._register_color_result(r)
 
+    # -- consistent linearisations and Huber weights (op_volume_register_robust_*: row and residual agree; the sdf is projective, |grad s| is not 1)
+    LINEARIZATIONS = {"normal": L.OP_REGISTER_LIN_NORMAL, "gradient": L.OP_REGISTER_LIN_GRADIENT, "metric": L.OP_REGISTER_LIN_METRIC}
+    ROBUST_COUNT_NAMES = ("used", "invalid", "no_gradient", "too_far", "colored", "downweighted", "color_downweighted")
+
+    def _register_options(self, linearization, huber, huber_color):
+        o = L.RegisterOptions()
+        L.check(self._lib.op_volume_register_robust_default_options(self._h, C.byref(o)))
+        if linearization is not None:
+            o.linearization = self.LINEARIZATIONS[linearization] if isinstance(linearization, str) else int(linearization)
+        for k, val in (("huber", huber), ("huber_color", huber_color)):
+            if val is not None:
+                setattr(o, k, val)
+        return o
+
+    @staticmethod
+    def _register_robust_result(r):
+        out = CubeHandler._register_color_result(r.color)
+        out.update({k: getattr(r, k) for k in ("downweighted", "color_downweighted", "first_downweighted", "rmse_residual", "first_rmse_residual")})
+        return out
+
+    def RobustRegistrationSystem(self, points, intensity, T, max_distance, color_scale=0.0, max_color_residual=0.0, linearization=None, huber=None,
+                                 huber_color=None, rows=False):
+        """ColorRegistrationSystem under a linearisation ("normal" | "gradient" | "metric" or its number; None = metric) and Huber thresholds
+        (None = 0 = no weights) (op_volume_register_robust_system) -> (sums [31] float64: 0..29 as ColorRegistrationSystem from the scaled rows,
+        [30] the sum of the unweighted r^2; counts dict with `downweighted` and `color_downweighted`[, rows [n,16]: what enters the sums])."""
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        n = len(pts)
+        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
+        if y is not None and len(y) != n:
+            raise ValueError("one intensity per point")
+        Tm = _f32(T).reshape(16)
+        o = self._register_options(linearization, huber, huber_color)
+        sums, counts = np.zeros(31, np.float64), np.zeros(7, np.uint64)
+        out = np.empty((n, 16), np.float32) if rows else None
+        L.check(self._lib.op_volume_register_robust_system(self._h, C.c_void_p(pts.ctypes.data), C.c_void_p(y.ctypes.data) if y is not None else None, n,
+                                                           L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale), float(max_color_residual), C.byref(o),
+                                                           sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(L._u64p),
+                                                           C.c_void_p(out.ctypes.data) if rows else None))
+        self._alive = []
+        cd = dict(zip(self.ROBUST_COUNT_NAMES, (int(c) for c in counts)))
+        return (sums, cd, out) if rows else (sums, cd)
+
+    def RegisterPointsRobust(self, points, intensity=None, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
+                             color_scale=None, max_color_residual=None, linearization=None, huber=None, huber_color=None):
+        """RegisterColoredPoints under a linearisation and Huber thresholds (op_volume_register_robust_points).  intensity None: the geometric
+        registration (color_scale 0) -> the result dict with downweighted, color_downweighted, first_downweighted, rmse_residual,
+        first_rmse_residual.  linearization None = metric; "normal" with no threshold is RegisterColoredPoints bit for bit."""
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
+        if y is not None and len(y) != len(pts):
+            raise ValueError("one intensity per point")
+        if y is None and color_scale is None:
+            color_scale = 0.0
+        T0 = _f32(np.eye(4) if init_T is None else init_T).reshape(16)
+        p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
+        o, r = self._register_options(linearization, huber, huber_color), L.RegisterRobustResult()
+        L.check(self._lib.op_volume_register_robust_points(self._h, C.c_void_p(pts.ctypes.data), C.c_void_p(y.ctypes.data) if y is not None else None, len(pts),
+                                                           L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(o), C.byref(r)))
+        self._alive = []
+        return self._register_robust_result(r)
+
+    def RegisterFrameRobust(self, depth, rgb, init_pose, pixel_stride=1, camera=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
+                            color_scale=None, max_color_residual=None, linearization=None, huber=None, huber_color=None):
+        """RegisterRGBD (rgb None: RegisterDepth) under a linearisation and Huber thresholds (op_volume_register_robust_frame) -> the result dict,
+        T the refined pose."""
+        pd, fmt, mem, k1 = _image_arg(depth, "depth")
+        pr, k2 = None, None
+        if rgb is not None:
+            pr, _f, mem2, k2 = _image_arg(rgb, "rgb")
+            if mem != mem2:
+                raise ValueError("depth and rgb must both be host arrays or both be device tensors")
+        pose = _f32(init_pose).reshape(16)
+        p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
+        o, r = self._register_options(linearization, huber, huber_color), L.RegisterRobustResult()
+        L.check(self._lib.op_volume_register_robust_frame(self._h, C.byref(camera) if camera is not None else None, pd, fmt, pr, mem, int(pixel_stride), _fp(pose),
+                                                          C.byref(p), C.byref(o), C.byref(r)))
+        del k1, k2
+        self._alive = []
+        return self._register_robust_result(r)
+
     def RaycastStats(self):
         """Measurement hook: what the last Raycast call did (op_volume_raycast_stats)."""
         v = [C.c_uint64(0) for _ in range(4)]
