@@ -221,6 +221,10 @@ int op_debug_rcp(const float *x, long long n, float *out);
 /* Test hook (host): the bound on |1 - Z * v_rcp_f32(Z)| that the certified pixel projection's error bound assumes of the unrefined
  * hardware reciprocal (csrc/px_round.hpp kPxRcpErr); tests/test_kc_diet_gpu.py holds op_debug_rcp to it over every significand. */
 double op_debug_px_rcp_err(void);
+/* Test hook (host): out[0..2] = the k_integrate launches this volume has enqueued since it was created (replays included), by the form of the
+ * projection and the gather: exact projection; certified projection without the window test on Z (csrc/zwin_cert.hpp proves its upper side per
+ * frame on the host) with the raw gather; the same with the structured gather.  A batch with a frame the host cannot certify counts under [0]. */
+int op_debug_volume_gather_kinds(op_volume *v, unsigned long long *out);
 /* Test hook (host): what k_prepare_frames is told about a frame of this camera at this pose (csrc/ka_cert.hpp): rect = {j_lo, j_hi, i_lo,
  * i_hi} and z = {z_lo, z_hi}, the pixels and depths certified to lie inside the frame's own frustum (j_lo > j_hi: no certificate), and
  * quot = whether the three-operation quotients by fx, fy and (for 16-bit depth) depth_scale are in use. */

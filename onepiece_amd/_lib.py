@@ -162,6 +162,7 @@ SIGNATURES = {
     "op_debug_voxel_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _vp, _vp]),
     "op_debug_rcp": (C.c_int, [_vp, C.c_longlong, _vp]),
     "op_debug_px_rcp_err": (C.c_double, []),
+    "op_debug_volume_gather_kinds": (C.c_int, [_vp, _vp]),
     "op_debug_ka_certificate": (C.c_int, [C.POINTER(Camera), _fp, C.c_float, C.c_float, _vp, _fp, _vp]),
     "op_debug_gather2d": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, _vp]),
     "op_debug_seq_tile_rows": (C.c_int, []),

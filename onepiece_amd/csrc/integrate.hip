@@ -282,10 +282,10 @@ __global__ __launch_bounds__(512 / ZT, (SUMF ? KC_SUM_MIN_WAVES : SIGNED ? KC_SI
                     zc[z] = q2;
                     if (G2D) { // off-image: a row the descriptor answers with zeros
                         int u, v;
-                        project_pixel_uv<FAST>(C, q0, q1, q2, u, v);
+                        project_pixel_uv<FAST, false>(C, q0, q1, q2, u, v); // (no window test on q2: launch_integrate has the host's bound on it)
                         rec[z] = gather2d(frame2d, u, v, C.width);
                     } else {
-                        const int pix = project_pixel<FAST>(C, q0, q1, q2); // off-image: pixel -1 = an offset the buffer answers with zeros
+                        const int pix = project_pixel<FAST, false>(C, q0, q1, q2); // off-image: pixel -1 = an offset the buffer answers with zeros
                         rec[z] = __builtin_amdgcn_raw_buffer_load_b64(frame, pix * 8, 0, 0);
                     }
                 }
@@ -558,8 +558,12 @@ void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int n
     v->lean_frames += (uint64_t)nf;
     const bool lean = v->plain && v->lean_ok && v->lean_frames <= (1ull << 19);
     const int upd = sign ? kUpdSigned : sum_form ? kUpdSum : lean ? kUpdLean : v->plain ? kUpdPlain : kUpdGeneral;
-    // the structured gather: certified projection and rows that fit the descriptor's stride field (2047 pixels), else the raw form
-    const int gat = !C.fast_px ? kGatExact : gather2d_fits(C.width) ? kGatFast2d : kGatFastRaw;
+    // the structured gather: certified projection and rows that fit the descriptor's stride field (2047 pixels), else the raw form.
+    // The certified kinds project without the window test on Z: they need the host's bound on |Z| for every frame of THIS launch (zwin_cert.hpp;
+    // a replayed batch comes here again with its logged BatchInv).  A batch with a frame it refuses -- an absurd pose or resolution --
+    // takes the exact projection, which needs nothing.
+    const bool zwin = C.fast_px && zwin_certified_batch(&I.f[0].m[0], nf, C.res);
+    const int gat = !zwin ? kGatExact : gather2d_fits(C.width) ? kGatFast2d : kGatFastRaw;
     typedef void (*launch_fn)(op_volume*, const BatchInv&, const CamParams&, int, bmask_t, unsigned*);
     static const launch_fn table[5][3] = {
         {launch_kc<kUpdSum, kGatExact>, launch_kc<kUpdSum, kGatFastRaw>, launch_kc<kUpdSum, kGatFast2d>},
@@ -567,6 +571,7 @@ void launch_integrate(op_volume* v, const BatchInv& I, const CamParams& C, int n
         {launch_kc<kUpdPlain, kGatExact>, launch_kc<kUpdPlain, kGatFastRaw>, launch_kc<kUpdPlain, kGatFast2d>},
         {launch_kc<kUpdGeneral, kGatExact>, launch_kc<kUpdGeneral, kGatFastRaw>, launch_kc<kUpdGeneral, kGatFast2d>},
         {launch_kc<kUpdSigned, kGatExact>, launch_kc<kUpdSigned, kGatFastRaw>, launch_kc<kUpdSigned, kGatFast2d>}};
+    ++v->kc_gather_launches[gat];
     table[upd][gat](v, I, C, nf, sign, rc_sum);
 }
 
@@ -638,6 +643,12 @@ int op_debug_rcp(const float* x, long long n, float* out) {
 }
 
 double op_debug_px_rcp_err(void) { return kPxRcpErr; }
+
+int op_debug_volume_gather_kinds(op_volume* v, unsigned long long* out) {
+    if (!v || !out) return fail(OP_ERR_INVALID, "null argument");
+    for (int k = 0; k < 3; ++k) out[k] = (unsigned long long)v->kc_gather_launches[k];
+    return OP_OK;
+}
 
 int op_debug_gather2d(const unsigned* images, int width, int height, int n_frames, int frame, int column_test, const int* uv, long long n, unsigned* out) {
     if (!images || !uv || !out) return fail(OP_ERR_INVALID, "null argument");

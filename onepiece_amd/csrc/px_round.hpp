@@ -124,8 +124,22 @@ OP_HD double px_cert_bound(double T, double absK) {
 // significands of [1, 2) and of [-2, -1), and 2^16 random ones in each of the binades 2^-60, 2^-1, 2^59, the device shows max |1 - z y| =
 // 9.1483642e-8 = 0.76742 * 2^-23 (at z = +-1.8744549; tests/test_kc_diet_gpu.py repeats the sweep against the constant), rounded up to the short
 // binary constant 2^-23 = 1.1920929e-7 -- which is also what an error of one ulp of y gives at most (|y - 1/z| <= ulp(y) <= 2^-24 for y in [1/2, 1),
-// times |z| < 2), the accuracy div_int_rcp (volume_core.hpp) relies on for integer divisors.  Inside the caller's window 2^-60 <= |z| < 2^60 neither
-// z nor y is denormal, and the significand sweep covers every binade.
+// times |z| < 2), the accuracy div_int_rcp (volume_core.hpp) relies on for integer divisors.
+// What the chain asks of z -- stated without a caller's window, because k_integrate calls the projection without one (project_pixel_uv<true, false>):
+//  * z normal with a normal reciprocal, 2^-126 <= |z| <= 2^126 (the device returns 2^-126 for 2^126 and 0 for everything larger).  v_rcp_f32 works on the
+//    significand and negates the exponent, so the sweep over all 2^23 significands covers every such binade, the ones below 2^-60 included: samples
+//    of each binade from 2^-126 to 2^-60 show at most 0.763 * 2^-23 (tests/test_kc_zwin_gpu.py).  Nothing else in the chain depends on |z|: q = nx / z is
+//    a real number, nx y is formed exactly inside the FMA (the code objects keep fp32 denormals, float_denorm_mode_32 = 3, so a denormal nx enters
+//    it as it is), and |q| is bounded through t'', not through z.  The upper end is the caller's: |z| < 2^60 by the window test, or |z| < 2^59 by
+//    the host's bound for every frame of a k_integrate launch (zwin_cert.hpp).
+//  * z zero or denormal: v_rcp_f32 returns +-inf (measured for +-0 and for denormals across the range, same file), so t'' = fma(nx, +-inf, kb) is
+//    +-inf, or NaN when nx is 0: fract(t'') is NaN and the lane is refused by the certificate itself.  It takes the exact sequence, whose own
+//    exponent test rescales such a z.
+//  * a denormal nx = fl(f X): the same float on both paths (and in the reference), so its rounding is no difference between them; charged as one all
+//    the same it is 2^-150 |y| <= 2^-24.  A denormal quotient a = RN(q) is off by 2^-150 at most instead of a relative 2^-24.  Both fit the 2^-22 in
+//    reserve below: B is unchanged, and so is the share of wave-projections on the exact fallback.
+//  * NaN z gives NaN, a product nx y beyond the floats +-inf: refused.  (z = +-inf, which no caller lets through, gives y = 0 and t'' = kb, the sum of
+//    the quotient 0 the reference forms.)
 // Here |s''| <= |t''| / (1 - 2^-24), so s'' lies in [-L, S] with L = 2 / (1 - 2^-24), S = T / (1 - 2^-24) >= L, and q (1 + dq) = s'' - kb lies in
 // [-L - kb, S - kb]: |q| <= Qf = (max(|S - K|, |L + K|) + 1/4) / (1 - dy) for every kb in [K, K + 1/4] (px_axis refuses an axis whose B2 would exceed
 // 1/4).  px_cert_bound took |q| <= S + |K| over the whole window |t'| <= T instead; for a principal point near the middle of the image that is three

@@ -27,6 +27,7 @@
 #include "host_math.hpp"
 #include "px_round.hpp"
 #include "ka_cert.hpp"
+#include "zwin_cert.hpp"
 
 namespace opv {
 
@@ -94,6 +95,7 @@ constexpr int kPartialGrid = 1024; // slots of the counter arrays k_integrate's 
                                    // them with small pageable copies, and a 16 KB device-to-host copy takes the runtime's pinned-staging path (milliseconds)
 constexpr int kDeiReverted = 0, kDeiReset = kPartialGrid, kDeiSkipped = 2 * kPartialGrid, kDeiFrames = 3 * kPartialGrid; // the slots of op_volume::dei_partial
 constexpr int kCoordLimit = 1 << 20; // |block coordinate| < 2^20 (40 km at 4 cm blocks)
+static_assert(kCoordLimit == kZwinCoordLimit, "zwin_cert.hpp bounds the voxel centres of the blocks pack_key can name");
 
 struct CamParams {
     float fx, fy, cx, cy, depth_scale, res, trunc;
@@ -267,7 +269,11 @@ static __device__ unsigned long long g_px_waves[2];
 // project_pixel_uv is that projection before the bounds test, for project_pixel below and for a caller that leaves the test to a buffer descriptor
 // (gather2d): a certified lane returns trunc(t'') per axis, unchecked (|t''| < 2^23; the axis is inside the image exactly when 0 <= u < extent),
 // every other lane the exact pixel of an axis inside the image and -1 for an axis outside it.
-template <bool FAST>
+// WIN = false drops the window test on Z: for k_integrate alone, whose Z the host has bounded for every frame of the launch (zwin_cert.hpp: finite,
+// |Z| < 2^59) and whose small, zero and denormal Z the certificate refuses or decides correctly by itself (px_round.hpp, px_cert_bound_folded:
+// hypotheses).  Every other caller keeps it: the selection kernels' candidates are not bounded by the key range before they are projected, and the
+// debug hook is fed arbitrary Z.
+template <bool FAST, bool WIN = true>
 __device__ __forceinline__ void project_pixel_uv(const CamParams& C, float X, float Y, float Z, int& u, int& v) {
     bool in_u, in_v;
     if (FAST && OP_PX_CERTIFIED) {
@@ -284,9 +290,10 @@ __device__ __forceinline__ void project_pixel_uv(const CamParams& C, float X, fl
         u = (int)tx; v = (int)ty; // v_cvt_i32_f32 truncates toward zero; a certified |t''| is below 2^23
         // (one ballot per compare: each is the compare's own mask, and the ANDs stay scalar -- a ballot of the combined bool costs
         // a v_cndmask + v_cmp to rebuild the mask; a && chain becomes nested branches)
-        const unsigned long long ok = __builtin_amdgcn_ballot_w64(win) & __builtin_amdgcn_ballot_w64(cx) & __builtin_amdgcn_ballot_w64(cy);
+        const unsigned long long ok = WIN ? __builtin_amdgcn_ballot_w64(win) & __builtin_amdgcn_ballot_w64(cx) & __builtin_amdgcn_ballot_w64(cy)
+                                          : __builtin_amdgcn_ballot_w64(cx) & __builtin_amdgcn_ballot_w64(cy);
         if (__builtin_expect(ok != __builtin_amdgcn_read_exec(), 0)) { // some active lane not certified
-            const bool cert = win & cx & cy;
+            const bool cert = WIN ? win & cx & cy : cx & cy;
             OP_PX_COUNT(1);
             if (!cert) {
                 project_uv_exact<true>(C, X, Y, Z, u, v, in_u, in_v);
@@ -300,12 +307,12 @@ __device__ __forceinline__ void project_pixel_uv(const CamParams& C, float X, fl
         v = in_v ? v : -1;
     }
 }
-template <bool FAST>
+template <bool FAST, bool WIN = true>
 __device__ __forceinline__ int project_pixel(const CamParams& C, float X, float Y, float Z) {
     int u, v;
     bool in_u, in_v;
     if (FAST && OP_PX_CERTIFIED) {
-        project_pixel_uv<true>(C, X, Y, Z, u, v);
+        project_pixel_uv<true, WIN>(C, X, Y, Z, u, v);
         in_u = (unsigned)u < (unsigned)C.width;
         in_v = (unsigned)v < (unsigned)C.height;
     } else {
@@ -521,6 +528,7 @@ struct op_volume {
     // truncation <= 0.5, and the frames those launches held (launch_integrate keeps both)
     bool lean_ok = true;
     uint64_t lean_frames = 0;
+    uint64_t kc_gather_launches[3] = {0, 0, 0}; // k_integrate launches since create by gather kind (exact projection, certified + raw, certified + structured): launch_integrate counts, op_debug_volume_gather_kinds reads
     int select_mode = 0;         // OP_VOLUME_OPT_SELECT: OP_VOLUME_SELECT_AUTO, OP_VOLUME_SELECT_DIRECT, or the largest range (in super-blocks) a frame may vote with
     int update_mode = 0;         // OP_VOLUME_OPT_UPDATE: OP_VOLUME_UPDATE_EXACT (the reference's frame-by-frame running mean, bit for bit) or _SUM_FORM
     unsigned plain_from = 0;     // with !plain: pool slots below this bound may hold foreign data (general update); later blocks are k_integrate's own
