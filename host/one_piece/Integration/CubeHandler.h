@@ -224,6 +224,21 @@ class CubeHandler {
     bool RobustRegistrationSystem(const geometry::Point3List& points, const std::vector<float>& intensity, const geometry::TransformationMatrix& T,
                                   float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
                                   uint64_t counts[7]);
+    // One fused volume against another (op_volume_register_volume states the definition): where the submap `source` belongs in this model, before
+    // Transform + Merge (example/MergeMultipleSubmaps.cpp) fix its place for good.  A fused volume has no surface points, it has a band of voxels
+    // that each carry their own sdf: the residual is this model's sdf at the transformed voxel centre MINUS the source voxel's own sdf, over the
+    // source's band voxels, selected once on the device; its stored colour gives the colour term.  Not in the reference.
+    //   RegisterVolume  init: source to this model.  sel == nullptr: the source's defaults (|sdf| <= 2 voxels, weight >= 1, every voxel);
+    //                   params == nullptr: this model's colour defaults; options == nullptr: OP_REGISTER_LIN_GRADIENT without weights (NOT the
+    //                   point entries' default).  The result's rmse stays this model's sdf rmse at the voxels; everything else goes to *details.
+    //   GetBandVoxels   the list itself (op_volume_band_voxels): centres, stored sdf and I(stored colour) of the selected voxels, blocks in pool
+    //                   order, voxels x + 8y + 64z ascending.  false when the call failed.
+    std::shared_ptr<registration::RegistrationResult> RegisterVolume(const CubeHandler& source,
+                                                                     const geometry::TransformationMatrix& init = geometry::TransformationMatrix::Identity(),
+                                                                     const op_volume_band_params* sel = nullptr, const op_volume_register_color_params* params = nullptr,
+                                                                     const op_volume_register_options* options = nullptr,
+                                                                     op_volume_register_volume_result* details = nullptr);
+    bool GetBandVoxels(geometry::Point3List& points, std::vector<float>& sdf, std::vector<float>& intensity, const op_volume_band_params* sel = nullptr) const;
     void GenerateMeshByCube(const CubeID& cube_id, geometry::TriangleMesh& mesh);
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;

@@ -710,6 +710,40 @@ bool CubeHandler::RobustRegistrationSystem(const geometry::Point3List& points, c
     ReleaseBorrowed();
     return true;
 }
+std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterVolume(const CubeHandler& source, const geometry::TransformationMatrix& init,
+                                                                              const op_volume_band_params* sel, const op_volume_register_color_params* params,
+                                                                              const op_volume_register_options* options, op_volume_register_volume_result* details) {
+    Pending();
+    source.Pending();
+    op_volume_register_volume_result r = op_volume_register_volume_result();
+    r.robust = RobustRegistrationNotRun(init);
+    if (Ensure() && source.Ensure()) {
+        float t[16];
+        bridge::RowMajor(init, t);
+        if (op_volume_register_volume(vol, source.vol, t, sel, params, options, &r) != OP_OK) {
+            Report("RegisterVolume");
+            r = op_volume_register_volume_result();
+            r.robust = RobustRegistrationNotRun(init);
+        } else {
+            ReleaseBorrowed(); // (the call synchronised both volumes)
+            source.ReleaseBorrowed();
+        }
+    }
+    if (details) *details = r;
+    return RegistrationOutcome(r.robust.color.base);
+}
+bool CubeHandler::GetBandVoxels(geometry::Point3List& points, std::vector<float>& sdf, std::vector<float>& intensity, const op_volume_band_params* sel) const {
+    Pending();
+    points.clear(); sdf.clear(); intensity.clear();
+    if (!Ensure()) return false;
+    size_t n = 0;
+    if (op_volume_band_voxels(vol, sel, nullptr, nullptr, nullptr, OP_MEM_HOST, 0, &n) != OP_OK) { Report("GetBandVoxels"); return false; }
+    ReleaseBorrowed(); // (the call synchronised the volume)
+    points.resize(n); sdf.resize(n); intensity.resize(n);
+    if (n == 0) return true;
+    if (op_volume_band_voxels(vol, sel, bridge::Floats(points), sdf.data(), intensity.data(), OP_MEM_HOST, n, &n) != OP_OK) { Report("GetBandVoxels"); return false; }
+    return true;
+}
 op_volume_sample_stats CubeHandler::DistanceToModel(const geometry::PointCloud& pcd, const geometry::TransformationMatrix& pose) {
     Pending();
     op_volume_sample_stats st = {0, 0, 0, 0, 0.0, 0.0, 0.0f};

@@ -732,6 +732,66 @@ int op_volume_register_robust_frame(op_volume *v, const op_camera *cam /* NULL: 
                                     const op_volume_register_color_params *params, const op_volume_register_options *options,
                                     op_volume_register_robust_result *result);
 
+/* The band voxels of a fused volume as a list (csrc/volume_band.hip; NO reference counterpart -- CubeHandler::GetPointCloud returns the whole
+ * truncation band as if it were the surface and drops the sdf).  A fused volume has no surface points: it has a band of voxels, each carrying
+ * its own sdf.  Every operation below is float32 and rounded separately; nothing is contracted.
+ *   1. A voxel of a held block, with stored sdf s, weight w and local coordinates (x, y, z) in 0..7, is SELECTED iff w > 0, w >= min_weight,
+ *      fabsf(s) <= band (false for a NaN s) and x, y and z are all multiples of voxel_stride.
+ *   2. band <= 0 means the volume's truncation.  voxel_stride is 1, 2, 4 or 8 (512, 64, 8 or 1 candidates per block).
+ *   3. Per selected voxel of block id, per axis with local coordinate l: the centre ((float)id * 8.0f) * res + ((float)l * res + res / 2)
+ *      (VoxelCube::GetGlobalPoint, as the integration forms it); the stored sdf; the intensity I(c) = (0.114f c0 + 0.587f c1) + 0.299f c2 of the
+ *      stored colour (op_volume_register_color_system's step 2).
+ *   4. Order: pool slot ascending (op_volume_download's block order), inside a block voxel index x + 8y + 64z ascending.
+ * *n is always the full count.  xyz (n x 3), sdf (n) and intensity (n) live in `mem`, hold `cap` voxels each, and each may be NULL: an output that
+ * is NULL is not written, all three NULL query the count.  More than cap selected voxels with an output asked for: OP_ERR_CAPACITY, as
+ * op_volume_point_cloud returns it, *n set and nothing written.  Like every accessor the call sees all frames accepted before it (the queue is
+ * flushed first) and only reads the volume.  Two passes of one kernel, one workgroup per block: the counts are scanned on the device and only the
+ * total comes back.  Defaults (sel == NULL, op_volume_band_default_params): band = 2 * res, min_weight 1, voxel_stride 1.
+ * Refusals, decided before any device use: OP_ERR_INVALID for a NULL volume or n, a bad mem, a voxel_stride other than 1, 2, 4, 8, a negative or
+ * non-finite min_weight, a NaN band. */
+typedef struct { float band, min_weight; int voxel_stride; } op_volume_band_params;
+int op_volume_band_default_params(op_volume *src, op_volume_band_params *p);
+int op_volume_band_voxels(op_volume *src, const op_volume_band_params *sel /* NULL: defaults */, float *xyz /* n x 3 */, float *sdf /* n */,
+                          float *intensity /* n, or NULL */, int mem, size_t cap, size_t *n);
+
+/* A target value per point, and one fused volume against another (csrc/volume_register.hip, the OFFSET instantiations of k_volume_register; NO
+ * reference counterpart).  The entries above register points that are assumed to lie on the surface: their residual is the target's sdf alone.
+ * Here point i carries the value o_i the field should have at it -- for a band voxel of a second volume its own stored sdf -- and the residual is
+ * s_target(T x_i) - o_i.
+ * The definition is op_volume_register_robust_system's with ONE change, in its step 2: the residual the linearisation starts from is
+ * e = s - o_i, one float32 subtraction, wherever that step says s -- NORMAL r = e, GRADIENT r = e, METRIC r = e / m.  Three things stay on the
+ * target's STORED sdf s: the USED rule and its max_distance gate (fabsf(s) <= max_distance), and sums[29] (hence base.rmse).  sums[30],
+ * rmse_residual and the huber weight see the new r; the Huber scaling is unchanged (row and residual by the same q).  A non-finite o_i (NaN or
+ * +-inf) makes the point unused: it is counted under `invalid`, before any sample is taken.  Reduction, row layout, fold, the host loop, its
+ * stop rules and statuses are the robust entries'.
+ * offset == NULL IS the robust entry: the existing kernels run and sums, counts, rows and every result field are bit for bit
+ * op_volume_register_robust_system's / _points' for the same arguments, all-zero or NULL options included.  With an offset the ROBUST instantiation
+ * runs whatever the options are (all-zero options: NORMAL, no weights).  offset is n floats in `mem`.
+ * op_volume_register_volume registers the band voxels of `source` against `target`: it selects once (op_volume_band_voxels' rule under `sel`) into
+ * buffers of the call -- the source does not change over the iterations -- and runs op_volume_register_offset_points on that list with init_T
+ * (source to target): result->robust is, bit for bit, that entry on op_volume_band_voxels' output (xyz, sdf as offset, intensity; the intensity is
+ * neither formed nor read with color_scale == 0), result->selected the length of the list.
+ *   options == NULL here means {OP_REGISTER_LIN_GRADIENT, 0, 0} -- this default DIFFERS from the point entries' (NULL: zeros): on overlapping
+ *   submaps GRADIENT ends at 3-4 mm where METRIC ends at 6-10 mm.  params == NULL: the target's colour defaults
+ *   (op_volume_register_color_default_params).  sel == NULL: the source's band defaults.
+ *   The volumes may differ in resolution and truncation: the centres use the source's resolution, the samples the target's.  Both must be on one
+ *   device (OP_ERR_INVALID otherwise); source == target is allowed.  Both queues are flushed first; the source's stream is synchronised before the
+ *   target's stream reads the list.  Both volumes are only read.  An empty selection: zero sums, OP_REGISTER_TOO_FEW_POINTS (min_points > 0),
+ *   T = init_T.
+ * Refusals, decided before any device use: everything the robust entries refuse; for op_volume_register_volume OP_ERR_INVALID for a NULL target,
+ * source, init_T or result, what op_volume_band_voxels refuses of `sel`, and volumes on different devices. */
+typedef struct { op_volume_register_robust_result robust; uint64_t selected; } op_volume_register_volume_result;
+int op_volume_register_offset_system(op_volume *v, const float *xyz, const float *offset /* n in `mem`, or NULL */,
+                                     const float *intensity /* n in `mem`, or NULL */, size_t n, int mem, const float T[16], float max_distance,
+                                     float color_scale, float max_color_residual, const op_volume_register_options *options /* NULL: zeros */,
+                                     double sums[31], uint64_t counts[7], float *rows /* n x 16 in `mem`, or NULL */);
+int op_volume_register_offset_points(op_volume *v, const float *xyz, const float *offset, const float *intensity, size_t n, int mem,
+                                     const float init_T[16], const op_volume_register_color_params *params /* NULL: defaults */,
+                                     const op_volume_register_options *options /* NULL: zeros */, op_volume_register_robust_result *result);
+int op_volume_register_volume(op_volume *target, op_volume *source, const float init_T[16] /* source -> target */,
+                              const op_volume_band_params *sel /* NULL: defaults */, const op_volume_register_color_params *params,
+                              const op_volume_register_options *options /* NULL: GRADIENT */, op_volume_register_volume_result *result);
+
 /* Frame-sharded multi-GPU merge (the distributed form of CubeHandler::Merge; DESIGN.md "Multi-GPU").
  * All pointers are DEVICE pointers on the volume's device.
  *   keys_device : copy this volume's block keys (n x 3 int32) into d_keys.

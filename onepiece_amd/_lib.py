@@ -83,6 +83,16 @@ class RegisterRobustResult(C.Structure):
                 ("rmse_residual", C.c_double), ("first_rmse_residual", C.c_double)]
 
 
+class BandParams(C.Structure):
+    """op_volume_band_params of op_volume_band_voxels / op_volume_register_volume: which voxels of a volume make its band list."""
+    _fields_ = [("band", C.c_float), ("min_weight", C.c_float), ("voxel_stride", C.c_int32)]
+
+
+class RegisterVolumeResult(C.Structure):
+    """op_volume_register_volume_result of op_volume_register_volume."""
+    _fields_ = [("robust", RegisterRobustResult), ("selected", C.c_uint64)]
+
+
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("last_T", C.c_float * 16), ("rmse", C.c_double),
                 ("n_inliers", C.c_uint64), ("iterations", C.c_int32)]
@@ -242,6 +252,14 @@ SIGNATURES = {
     "op_icp_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_double, C.c_int, C.c_int, C.POINTER(_vp)]),
     "op_icp_destroy": (C.c_int, [_vp]),
     "op_icp_set_option": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "op_volume_band_default_params": (C.c_int, [_vp, C.POINTER(BandParams)]),
+    "op_volume_band_voxels": (C.c_int, [_vp, C.POINTER(BandParams), _vp, _vp, _vp, C.c_int, C.c_size_t, _szp]),
+    "op_volume_register_offset_system": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int, _fp, C.c_float, C.c_float, C.c_float, C.POINTER(RegisterOptions),
+                                                   C.POINTER(C.c_double), _u64p, _vp]),
+    "op_volume_register_offset_points": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int, _fp, C.POINTER(RegisterColorParams), C.POINTER(RegisterOptions),
+                                                   C.POINTER(RegisterRobustResult)]),
+    "op_volume_register_volume": (C.c_int, [_vp, _vp, _fp, C.POINTER(BandParams), C.POINTER(RegisterColorParams), C.POINTER(RegisterOptions),
+                                            C.POINTER(RegisterVolumeResult)]),
     "op_icp_run_many": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _fp, C.c_int, _vp]),
     "op_icp_tie_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "op_icp_final_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),

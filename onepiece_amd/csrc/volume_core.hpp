@@ -6,6 +6,7 @@
 //   volume_ops.hip  GetCubeMap / SetCubeMap / Merge / sum-form pack + unpack / Transform / GetPointCloud / ExtractTriangleMesh / .map files
 //   raycast.hip     the raycaster, and its view packed as an RGB-D frame (model_frame.hpp: what the dense tracker takes from here)
 //   volume_gc.hip   CollectGarbage;  volume_sample.hip  the point queries (op_volume_sample), over trilinear_sample.hpp and voxel_interp.hpp
+//   volume_band.hip the band voxels of a volume as a list (op_volume_band_voxels)
 // Data layout in HBM: see volume.hip (and DESIGN.md section 2).
 #pragma once
 #include <cfloat>
@@ -625,4 +626,7 @@ void kc_trace_dump(op_volume* v);            // -DKC_TRACE builds only
 // volume_ops.hip: the count and emit passes of k_mesh into device buffers (op_volume_extract_mesh; mesh_cluster.hip simplifies the soup in place)
 int vol_mesh_soup(op::Scope& out, op_volume* v, const int32_t* tri_table, const int32_t* edge_pairs, const int32_t* only_block, bool emit, size_t cap_vertices,
                   float** d_pts_out, float** d_col_out, size_t* n_vertices);
+// volume_band.hip: the band-voxel list of a volume (op_volume_band_voxels; op_volume_register_volume registers it against another volume)
+int vol_band_check(const op_volume_band_params* sel, const char* who); // the refusals, before any device use (NULL: the defaults, nothing to refuse)
+int vol_band_select(op::Scope& out, op_volume* src, const op_volume_band_params* sel, size_t cap, float** d_xyz, float** d_sdf, float** d_intensity, size_t* n);
 } // namespace opv

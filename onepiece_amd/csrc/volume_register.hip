@@ -22,6 +22,10 @@
 // by the square root of a Huber weight, the colour term by one of its own.  The mode and the two thresholds are wave-uniform arguments.  The six
 // quantities without a slot (the colour kernel's three, the sum of the unweighted r^2, the two down-weighted counts) travel by the same butterfly:
 // rows of 38, k_register_fold_robust.  All-zero options run the instantiations above: nothing about them changes.
+// The OFFSET instantiations (op_volume_register_offset_* and, over the band voxels of a second volume -- volume_band.hip --,
+// op_volume_register_volume) give every point a target value o_i of its own: the residual the linearisation starts from is s - o_i, one more
+// load and one subtraction per point; the USED rule, max_distance and the stored-sdf sum keep s.  They are ROBUST instantiations with one more
+// template parameter: the reduction, the rows of 38 and the fold are those; offset == NULL runs the instantiations above.
 // Not built: damping, multi-resolution, re-ordering the points by block.
 #include "volume_core.hpp"
 #include "trilinear_sample.hpp"
@@ -63,6 +67,9 @@ struct RegRobust { // what the ROBUST instantiations take in RegColor's place: t
     int linearization;        // OP_REGISTER_LIN_*
     float huber, huber_color; // <= 0: no weights
 };
+struct RegOffset : RegRobust { // what the OFFSET instantiations take: and the points' target values
+    const float* offset;      // n
+};
 
 // intensity of a colour triple in stored channel order
 __device__ __forceinline__ float reg_intensity(const float* c) { return (0.114f * c[0] + 0.587f * c[1]) + 0.299f * c[2]; }
@@ -82,8 +89,9 @@ __device__ __forceinline__ bool reg_sample_sdf(const VolView& V, const RegView& 
     }
 }
 
-template <bool ROWS, bool COLOR, bool ROBUST = false>
-__global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A, std::conditional_t<ROBUST, RegRobust, RegColor> K) {
+template <bool ROWS, bool COLOR, bool ROBUST = false, bool OFFSET = false>
+__global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A, std::conditional_t<OFFSET, RegOffset, std::conditional_t<ROBUST, RegRobust, RegColor>> K) {
+    static_assert(ROBUST || !OFFSET, "the per-point target value is an option of the ROBUST instantiations");
     constexpr int kSlots = ROBUST ? kRegSlotsR : COLOR ? kRegSlotsC : kRegSlots;
     constexpr int kExt = ROBUST ? 6 : 3;
     __shared__ double s_red[kRegWg / 64][kSlots];
@@ -109,7 +117,10 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
             const float p0 = q0 / q3, p1 = q1 / q3, p2 = q2 / q3;
             float sv = 0.0f, mv = 0.0f;
             reason = 1;
-            if (reg_sample_sdf<COLOR>(V, A.W, bc, p0, p1, p2, &sv, &mv)) {
+            float off = 0.0f; // OFFSET: the point's target value; a non-finite one leaves the point invalid (false for NaN)
+            bool have = true;
+            if constexpr (OFFSET) { off = K.offset[i]; have = fabsf(off) < INFINITY; }
+            if (have && reg_sample_sdf<COLOR>(V, A.W, bc, p0, p1, p2, &sv, &mv)) {
                 const float h = 0.5f * A.W.res; // k_rc_shade's central difference
                 float d[3], g[3] = {0.0f, 0.0f, 0.0f};
                 bool all = true;
@@ -128,10 +139,12 @@ __global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A
                     reason = 0;
                     const float l = sqrtf(l2);
                     float n0 = d[0] / l, n1 = d[1] / l, n2 = d[2] / l;
-                    s = sv;
+                    float e = sv; // what the linearisation starts from (the gate above and sraw below keep the stored sdf)
+                    if constexpr (OFFSET) e = sv - off;
+                    s = e;
                     if constexpr (ROBUST) { // the row vector a (in n's place) and the residual r (in s's)
                         if (K.linearization == OP_REGISTER_LIN_GRADIENT) { n0 = d[0] / A.W.res; n1 = d[1] / A.W.res; n2 = d[2] / A.W.res; }
-                        else if (K.linearization == OP_REGISTER_LIN_METRIC) s = sv / (l / A.W.res);
+                        else if (K.linearization == OP_REGISTER_LIN_METRIC) s = e / (l / A.W.res);
                         sraw = sv; runw = s;
                     }
                     j[0] = n0; j[1] = n1; j[2] = n2;
@@ -331,10 +344,11 @@ struct RegRun {
     RegColor K{nullptr, 0.0f, 0.0f}; // color_scale > 0: the COLOR instantiations
 
     op_volume_register_options O{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}; // anything else: the ROBUST instantiations
+    const float* offset = nullptr; // n target values on the device: the OFFSET instantiations (of the ROBUST ones, whatever the options)
 
     explicit RegRun(op_volume* vol) : v(vol) { tmp.bind(v->stream); }
     bool color() const { return K.color_scale > 0.0f; }
-    bool robust() const { return O.linearization != OP_REGISTER_LIN_NORMAL || O.huber > 0.0f || (color() && O.huber_color > 0.0f); }
+    bool robust() const { return offset || O.linearization != OP_REGISTER_LIN_NORMAL || O.huber > 0.0f || (color() && O.huber_color > 0.0f); }
     int open(const float* d_xyz, size_t n, float max_distance) {
         A.xyz = d_xyz; A.n = n; A.W.res = v->res; A.W.inv_res = 1.0f / v->res; A.max_distance = max_distance;
         grid = (unsigned)std::min<size_t>((n + kRegWg - 1) / kRegWg, kRegMaxGrid);
@@ -396,8 +410,9 @@ struct RegRun {
         return OP_OK;
     }
     int open_robust(const float* d_xyz, const float* d_intensity, size_t n, float max_distance, float color_scale, float max_color_residual,
-                    const op_volume_register_options& options) {
+                    const op_volume_register_options& options, const float* d_offset = nullptr) {
         O = options;
+        offset = n ? d_offset : nullptr;
         return open_color(d_xyz, d_intensity, n, max_distance, color_scale, max_color_residual);
     }
     // the system under the options at T: 31 sums ([30] r r, unweighted) and 7 counts (d_rows: n x 16 with the colour term, n x 8 without).
@@ -415,7 +430,18 @@ struct RegRun {
         A.rows = d_rows;
         const VolView V = v->view();
         const RegRobust KR{K.intensity, K.color_scale, K.max_color_residual, O.linearization, O.huber, O.huber_color};
-        if (color()) {
+        if (offset) {
+            RegOffset KO;
+            static_cast<RegRobust&>(KO) = KR;
+            KO.offset = offset;
+            if (color()) {
+                if (d_rows) hipLaunchKernelGGL((k_volume_register<true, true, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KO);
+                else hipLaunchKernelGGL((k_volume_register<false, true, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KO);
+            } else {
+                if (d_rows) hipLaunchKernelGGL((k_volume_register<true, false, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KO);
+                else hipLaunchKernelGGL((k_volume_register<false, false, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KO);
+            }
+        } else if (color()) {
             if (d_rows) hipLaunchKernelGGL((k_volume_register<true, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
             else hipLaunchKernelGGL((k_volume_register<false, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
         } else {
@@ -471,12 +497,12 @@ op_volume_register_color_params reg_color_defaults(const op_volume* v) {
 }
 
 // the Gauss-Newton loop over points (and, with color_scale > 0, intensities) that are on the device; color_scale == 0: the geometric loop;
-// all-zero options: the plain system
+// all-zero options: the plain system; d_offset: the points' target values (the OFFSET instantiations)
 int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
-             float max_color_residual, const op_volume_register_options& options, op_volume_register_robust_result* robust) {
+             float max_color_residual, const op_volume_register_options& options, op_volume_register_robust_result* robust, const float* d_offset = nullptr) {
     op_volume_register_color_result* out = &robust->color;
     RegRun R(v);
-    OP_TRY(R.open_robust(d_xyz, d_intensity, n, P.max_distance, color_scale, max_color_residual, options));
+    OP_TRY(R.open_robust(d_xyz, d_intensity, n, P.max_distance, color_scale, max_color_residual, options, d_offset));
     op_volume_register_result res{};
     float T[16];
     for (int k = 0; k < 16; ++k) T[k] = init_T[k];
@@ -591,6 +617,76 @@ int reg_back_project(op_volume* v, op::Scope& tmp, const op_camera& c, const voi
     else hipLaunchKernelGGL(k_register_depth_scatter<false>, g, b, 0, v->stream, d_depth, depth_fmt == OP_DEPTH_U16, c, G, (const unsigned*)d_start, v->reg_pts, (const unsigned char*)nullptr, (float*)nullptr);
     OP_HIP(hipGetLastError());
     return OP_OK;
+}
+
+// the one-pass entry and the loop entry of the ROBUST instantiations; offset (n floats in `mem`, or NULL): the OFFSET ones (op_volume_register_offset_*)
+int reg_system_entry(const char* who, op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float T[16],
+                     float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
+                     uint64_t counts[7], float* rows) {
+    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
+    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
+    if (!T) return fail(OP_ERR_INVALID, "%s: null T", who);
+    if (!sums) return fail(OP_ERR_INVALID, "%s: null sums", who);
+    OP_TRY(reg_check_color_scale(color_scale, who));
+    if (n > 0 && color_scale > 0.0f && !intensity) return fail(OP_ERR_INVALID, "%s: null intensity", who);
+    OP_TRY(reg_check_options(options, who));
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    RegRun R(v);
+    const float *d_xyz = nullptr, *d_int = nullptr, *d_off = nullptr;
+    OP_TRY(R.tmp.input(xyz, 3 * n, mem, &d_xyz));
+    if (color_scale > 0.0f) OP_TRY(R.tmp.input(intensity, n, mem, &d_int));
+    if (offset) OP_TRY(R.tmp.input(offset, n, mem, &d_off));
+    OP_TRY(R.open_robust(d_xyz, d_int, n, max_distance, color_scale, max_color_residual,
+                         options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, d_off));
+    const bool want_rows = rows && n;
+    uint64_t c[7];
+    if (R.color()) {
+        float* d_rows = rows;
+        if (want_rows && mem == OP_MEM_HOST) OP_TRY(R.tmp.alloc(&d_rows, 16 * n));
+        OP_TRY(R.eval_robust(T, want_rows ? d_rows : nullptr, sums, c));
+        if (want_rows && mem == OP_MEM_HOST) OP_HIP(hipMemcpy(rows, d_rows, sizeof(float) * 16 * n, hipMemcpyDeviceToHost));
+    } else { // rows of 8 become the first halves of rows of 16, as op_volume_register_color_system widens them
+        float* d_rows8 = nullptr;
+        if (want_rows) OP_TRY(R.tmp.alloc(&d_rows8, 8 * n));
+        if (R.robust()) OP_TRY(R.eval_robust(T, d_rows8, sums, c));
+        else {
+            OP_TRY(R.eval(T, d_rows8, sums, c));
+            sums[28] = 0.0; sums[29] = sums[27]; sums[30] = sums[27]; c[4] = 0; c[5] = 0; c[6] = 0;
+        }
+        if (want_rows) {
+            if (mem == OP_MEM_HOST) std::memset(rows, 0, sizeof(float) * 16 * n);
+            else OP_HIP(hipMemset(rows, 0, sizeof(float) * 16 * n));
+            OP_HIP(hipMemcpy2D(rows, sizeof(float) * 16, d_rows8, sizeof(float) * 8, sizeof(float) * 8, n, mem == OP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        }
+    }
+    if (counts) for (int k = 0; k < 7; ++k) counts[k] = c[k];
+    return OP_OK;
+}
+
+int reg_points_entry(const char* who, op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float init_T[16],
+                     const op_volume_register_color_params* params, const op_volume_register_options* options, op_volume_register_robust_result* result) {
+    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
+    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
+    if (!init_T) return fail(OP_ERR_INVALID, "%s: null init_T", who);
+    if (!result) return fail(OP_ERR_INVALID, "%s: null result", who);
+    OP_TRY(reg_check_params(params ? &params->base : nullptr, who));
+    if (params) OP_TRY(reg_check_color_scale(params->color_scale, who));
+    if (n > 0 && !intensity && (!params || params->color_scale > 0.0f)) return fail(OP_ERR_INVALID, "%s: null intensity", who);
+    OP_TRY(reg_check_options(options, who));
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    op::Scope up;
+    up.bind(v->stream);
+    const float *d_xyz = nullptr, *d_int = nullptr, *d_off = nullptr;
+    OP_TRY(up.input(xyz, 3 * n, mem, &d_xyz));
+    if (P.color_scale > 0.0f) OP_TRY(up.input(intensity, n, mem, &d_int));
+    if (offset) OP_TRY(up.input(offset, n, mem, &d_off));
+    return reg_loop(v, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual,
+                    options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, result, d_off);
 }
 
 } // namespace
@@ -771,69 +867,13 @@ int op_volume_register_robust_default_options(op_volume* v, op_volume_register_o
 int op_volume_register_robust_system(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float T[16], float max_distance,
                                      float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
                                      uint64_t counts[7], float* rows) {
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: bad mem %d", mem);
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null xyz");
-    if (!T) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null T");
-    if (!sums) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null sums");
-    OP_TRY(reg_check_color_scale(color_scale, "op_volume_register_robust_system"));
-    if (n > 0 && color_scale > 0.0f && !intensity) return fail(OP_ERR_INVALID, "op_volume_register_robust_system: null intensity");
-    OP_TRY(reg_check_options(options, "op_volume_register_robust_system"));
-    OP_VOL(v);
-    OP_TRY(vol_check(v));
-    RegRun R(v);
-    const float *d_xyz = nullptr, *d_int = nullptr;
-    OP_TRY(R.tmp.input(xyz, 3 * n, mem, &d_xyz));
-    if (color_scale > 0.0f) OP_TRY(R.tmp.input(intensity, n, mem, &d_int));
-    OP_TRY(R.open_robust(d_xyz, d_int, n, max_distance, color_scale, max_color_residual,
-                         options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}));
-    const bool want_rows = rows && n;
-    uint64_t c[7];
-    if (R.color()) {
-        float* d_rows = rows;
-        if (want_rows && mem == OP_MEM_HOST) OP_TRY(R.tmp.alloc(&d_rows, 16 * n));
-        OP_TRY(R.eval_robust(T, want_rows ? d_rows : nullptr, sums, c));
-        if (want_rows && mem == OP_MEM_HOST) OP_HIP(hipMemcpy(rows, d_rows, sizeof(float) * 16 * n, hipMemcpyDeviceToHost));
-    } else { // rows of 8 become the first halves of rows of 16, as op_volume_register_color_system widens them
-        float* d_rows8 = nullptr;
-        if (want_rows) OP_TRY(R.tmp.alloc(&d_rows8, 8 * n));
-        if (R.robust()) OP_TRY(R.eval_robust(T, d_rows8, sums, c));
-        else {
-            OP_TRY(R.eval(T, d_rows8, sums, c));
-            sums[28] = 0.0; sums[29] = sums[27]; sums[30] = sums[27]; c[4] = 0; c[5] = 0; c[6] = 0;
-        }
-        if (want_rows) {
-            if (mem == OP_MEM_HOST) std::memset(rows, 0, sizeof(float) * 16 * n);
-            else OP_HIP(hipMemset(rows, 0, sizeof(float) * 16 * n));
-            OP_HIP(hipMemcpy2D(rows, sizeof(float) * 16, d_rows8, sizeof(float) * 8, sizeof(float) * 8, n, mem == OP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
-        }
-    }
-    if (counts) for (int k = 0; k < 7; ++k) counts[k] = c[k];
-    return OP_OK;
+    return reg_system_entry("op_volume_register_robust_system", v, xyz, nullptr, intensity, n, mem, T, max_distance, color_scale, max_color_residual, options, sums, counts, rows);
 }
 
 int op_volume_register_robust_points(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float init_T[16],
                                      const op_volume_register_color_params* params, const op_volume_register_options* options,
                                      op_volume_register_robust_result* result) {
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: bad mem %d", mem);
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null xyz");
-    if (!init_T) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null init_T");
-    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null result");
-    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_robust_points"));
-    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_robust_points"));
-    if (n > 0 && !intensity && (!params || params->color_scale > 0.0f)) return fail(OP_ERR_INVALID, "op_volume_register_robust_points: null intensity");
-    OP_TRY(reg_check_options(options, "op_volume_register_robust_points"));
-    OP_VOL(v);
-    OP_TRY(vol_check(v));
-    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
-    op::Scope up;
-    up.bind(v->stream);
-    const float *d_xyz = nullptr, *d_int = nullptr;
-    OP_TRY(up.input(xyz, 3 * n, mem, &d_xyz));
-    if (P.color_scale > 0.0f) OP_TRY(up.input(intensity, n, mem, &d_int));
-    return reg_loop(v, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual,
-                    options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, result);
+    return reg_points_entry("op_volume_register_robust_points", v, xyz, nullptr, intensity, n, mem, init_T, params, options, result);
 }
 
 int op_volume_register_robust_frame(op_volume* v, const op_camera* cam, const void* depth, int depth_fmt, const uint8_t* rgb, int mem, int pixel_stride,
@@ -862,6 +902,45 @@ int op_volume_register_robust_frame(op_volume* v, const op_camera* cam, const vo
     OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, rgb, mem, pixel_stride, &total));
     return reg_loop(v, v->reg_pts, rgb ? v->reg_int : nullptr, (size_t)total, init_pose, P.base, color_scale, P.max_color_residual,
                     options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, result);
+}
+
+// ---- a target value per point, and one fused volume against another
+int op_volume_register_offset_system(op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float T[16],
+                                     float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
+                                     uint64_t counts[7], float* rows) {
+    return reg_system_entry("op_volume_register_offset_system", v, xyz, offset, intensity, n, mem, T, max_distance, color_scale, max_color_residual, options, sums, counts, rows);
+}
+
+int op_volume_register_offset_points(op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float init_T[16],
+                                     const op_volume_register_color_params* params, const op_volume_register_options* options,
+                                     op_volume_register_robust_result* result) {
+    return reg_points_entry("op_volume_register_offset_points", v, xyz, offset, intensity, n, mem, init_T, params, options, result);
+}
+
+int op_volume_register_volume(op_volume* target, op_volume* source, const float init_T[16], const op_volume_band_params* sel,
+                              const op_volume_register_color_params* params, const op_volume_register_options* options,
+                              op_volume_register_volume_result* result) {
+    if (!target) return fail(OP_ERR_INVALID, "op_volume_register_volume: null target");
+    if (!source) return fail(OP_ERR_INVALID, "op_volume_register_volume: null source");
+    if (!init_T) return fail(OP_ERR_INVALID, "op_volume_register_volume: null init_T");
+    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_volume: null result");
+    OP_TRY(vol_band_check(sel, "op_volume_register_volume"));
+    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_volume"));
+    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_volume"));
+    OP_TRY(reg_check_options(options, "op_volume_register_volume"));
+    if (target->device != source->device) return fail(OP_ERR_INVALID, "op_volume_register_volume: the volumes are on devices %d and %d", target->device, source->device);
+    OP_VOL(target);
+    OP_TRY(vol_check(source)); // both queues flushed, both streams idle
+    if (source != target) OP_TRY(vol_check(target));
+    const op_volume_register_color_params P = params ? *params : reg_color_defaults(target);
+    const op_volume_register_options O = options ? *options : op_volume_register_options{OP_REGISTER_LIN_GRADIENT, 0.0f, 0.0f};
+    op::Scope list; // the source's band voxels, selected once: the source does not change over the iterations
+    list.bind(target->stream);
+    float *d_xyz = nullptr, *d_sdf = nullptr, *d_int = nullptr;
+    size_t n = 0;
+    OP_TRY(vol_band_select(list, source, sel, SIZE_MAX, &d_xyz, &d_sdf, P.color_scale > 0.0f ? &d_int : nullptr, &n)); // (the source's stream is idle on return)
+    result->selected = n;
+    return reg_loop(target, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual, O, &result->robust, d_sdf);
 }
 
 } // extern "C"

@@ -808,6 +808,89 @@ class CubeHandler:
         self._alive = []
         return self._register_robust_result(r)
 
+    # -- a target value per point, and one fused volume against another (op_volume_band_voxels, op_volume_register_offset_*, op_volume_register_volume)
+    def _band_params(self, band, min_weight, voxel_stride):
+        p = L.BandParams()
+        L.check(self._lib.op_volume_band_default_params(self._h, C.byref(p)))
+        for k, val in (("band", band), ("min_weight", min_weight), ("voxel_stride", voxel_stride)):
+            if val is not None:
+                setattr(p, k, val)
+        return p
+
+    def BandVoxels(self, band=None, min_weight=None, voxel_stride=None, intensity=True):
+        """The band voxels of this volume (op_volume_band_voxels): weight > 0 and >= min_weight, |sdf| <= band (0: the truncation), every
+        voxel_stride-th voxel per axis (1, 2, 4, 8) -> (centres [n,3], sdf [n], intensity [n] or None) float32, blocks in pool order
+        (GetCubeMap(sort=False)'s), voxels x + 8y + 64z ascending.  None = the default (2 voxels, 1, 1)."""
+        p = self._band_params(band, min_weight, voxel_stride)
+        n = C.c_size_t(0)
+        L.check(self._lib.op_volume_band_voxels(self._h, C.byref(p), None, None, None, L.OP_MEM_HOST, 0, C.byref(n)))
+        cap = n.value
+        xyz, sdf = np.empty((cap, 3), np.float32), np.empty(cap, np.float32)
+        y = np.empty(cap, np.float32) if intensity else None
+        if cap:
+            L.check(self._lib.op_volume_band_voxels(self._h, C.byref(p), C.c_void_p(xyz.ctypes.data), C.c_void_p(sdf.ctypes.data),
+                                                    C.c_void_p(y.ctypes.data) if intensity else None, L.OP_MEM_HOST, cap, C.byref(n)))
+        return xyz, sdf, y
+
+    @staticmethod
+    def _offset_inputs(points, offset, intensity):
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        o = np.ascontiguousarray(_f32(offset).reshape(-1)) if offset is not None else None
+        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
+        if o is not None and len(o) != len(pts):
+            raise ValueError("one target value per point")
+        if y is not None and len(y) != len(pts):
+            raise ValueError("one intensity per point")
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        return pts, o, y, ptr
+
+    def OffsetRegistrationSystem(self, points, offset, intensity, T, max_distance, color_scale=0.0, max_color_residual=0.0, linearization=None, huber=None,
+                                 huber_color=None, rows=False):
+        """RobustRegistrationSystem with a target value per point (op_volume_register_offset_system): the residual starts from s - offset[i];
+        the max_distance gate and sums[29] keep the stored sdf.  offset None IS RobustRegistrationSystem."""
+        pts, o, y, ptr = self._offset_inputs(points, offset, intensity)
+        n = len(pts)
+        Tm = _f32(T).reshape(16)
+        opt = self._register_options(linearization, huber, huber_color)
+        sums, counts = np.zeros(31, np.float64), np.zeros(7, np.uint64)
+        out = np.empty((n, 16), np.float32) if rows else None
+        L.check(self._lib.op_volume_register_offset_system(self._h, ptr(pts), ptr(o), ptr(y), n, L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale),
+                                                           float(max_color_residual), C.byref(opt), sums.ctypes.data_as(C.POINTER(C.c_double)),
+                                                           counts.ctypes.data_as(L._u64p), ptr(out)))
+        self._alive = []
+        cd = dict(zip(self.ROBUST_COUNT_NAMES, (int(c) for c in counts)))
+        return (sums, cd, out) if rows else (sums, cd)
+
+    def RegisterPointsOffset(self, points, offset, intensity=None, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
+                             color_scale=None, max_color_residual=None, linearization=None, huber=None, huber_color=None):
+        """RegisterPointsRobust with a target value per point (op_volume_register_offset_points) -> the same result dict.  offset None IS
+        RegisterPointsRobust."""
+        pts, o, y, ptr = self._offset_inputs(points, offset, intensity)
+        if y is None and color_scale is None:
+            color_scale = 0.0
+        T0 = _f32(np.eye(4) if init_T is None else init_T).reshape(16)
+        p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
+        opt, r = self._register_options(linearization, huber, huber_color), L.RegisterRobustResult()
+        L.check(self._lib.op_volume_register_offset_points(self._h, ptr(pts), ptr(o), ptr(y), len(pts), L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(opt), C.byref(r)))
+        self._alive = []
+        return self._register_robust_result(r)
+
+    def RegisterVolume(self, source, init_T=None, band=None, min_weight=None, voxel_stride=None, max_iterations=None, max_distance=None, min_step=None,
+                       min_points=None, color_scale=None, max_color_residual=None, linearization="gradient", huber=None, huber_color=None):
+        """Registers the band voxels of the CubeHandler `source` against this volume from `init_T` (source to this; default identity)
+        (op_volume_register_volume): each source voxel's own sdf is the value this volume's field should have at its centre -> the robust
+        result dict with `selected`, T the refined source-to-target transform.  Selection None = the source's defaults (2 voxels, weight 1,
+        stride 1); the linearisation defaults to "gradient" here; color_scale None = 1 (a source voxel carries its colour), 0 = geometric."""
+        T0 = _f32(np.eye(4) if init_T is None else init_T).reshape(16)
+        sel = source._band_params(band, min_weight, voxel_stride)
+        p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
+        opt, r = self._register_options(linearization, huber, huber_color), L.RegisterVolumeResult()
+        L.check(self._lib.op_volume_register_volume(self._h, source._h, _fp(T0), C.byref(sel), C.byref(p), C.byref(opt), C.byref(r)))
+        self._alive = []
+        out = self._register_robust_result(r.robust)
+        out["selected"] = int(r.selected)
+        return out
+
     def RaycastStats(self):
         """Measurement hook: what the last Raycast call did (op_volume_raycast_stats)."""
         v = [C.c_uint64(0) for _ in range(4)]
