@@ -4,6 +4,8 @@
 // sdf at a transformed point is the residual, its normalised central difference the normal.
 //
 //   ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused] [--color off|on [--color-scale S]]
+//   --batch K [--batch-stride S]   after the run: the first K frames against the whole model from their perturbed poses, all in ONE call of the batch
+//                              entry (op_volume_register_batch_frames) and one call per frame, at pixel stride S (default 4); the JSON gains "batch"
 //                     [--linearization normal|gradient|metric] [--huber D] [--huber-color D] [--min-step S]
 //   --synthetic N STRIDE SEED  N frames of the analytic room of LiveFusion.cpp: frame k is step FIRST + k * STRIDE of a 1000-step orbit, SEED picks FIRST
 //   --perturb K                every K-th frame is re-registered (default 20); its start is its true pose moved by 3-4 cm and about a degree
@@ -29,6 +31,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -210,7 +213,7 @@ double Median(std::vector<double> v) {
 } // namespace
 
 int main(int argc, char* argv[]) {
-    long synthetic[3] = {0, 1, 1}, every = 20, iters = 10;
+    long synthetic[3] = {0, 1, 1}, every = 20, iters = 10, batch = 0, batch_stride = 4;
     bool is_synthetic = false, bad = false;
     std::string path = "fused", color = "off", linearization = "metric";
     float res = 0.01f, color_scale = 1.0f, huber = 0.0f, huber_color = 0.0f, min_step = 0.0f;
@@ -228,15 +231,17 @@ int main(int argc, char* argv[]) {
         else if (a == "--huber" && i + 1 < argc) { huber = static_cast<float>(std::atof(argv[++i])); robust = true; }
         else if (a == "--huber-color" && i + 1 < argc) { huber_color = static_cast<float>(std::atof(argv[++i])); robust = true; }
         else if (a == "--min-step" && i + 1 < argc) { min_step = static_cast<float>(std::atof(argv[++i])); have_min_step = true; }
+        else if (a == "--batch" && i + 1 < argc) { batch = std::atol(argv[++i]); robust = true; }
+        else if (a == "--batch-stride" && i + 1 < argc) batch_stride = std::atol(argv[++i]);
         else bad = true;
     }
     const int lin = linearization == "normal" ? OP_REGISTER_LIN_NORMAL : linearization == "gradient" ? OP_REGISTER_LIN_GRADIENT : linearization == "metric" ? OP_REGISTER_LIN_METRIC : -1;
     const long n = synthetic[0], stride = synthetic[1];
     if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || !(res > 0) || every < 1 || iters < 0 || iters > 1000 || (path != "sample" && path != "fused") ||
         (color != "off" && color != "on") || (color == "on" && path != "fused") || (have_scale && color != "on") || !(color_scale >= 0) || lin < 0 || (robust && path != "fused") || !(huber >= 0) || !(huber_color >= 0) ||
-        (have_min_step && !robust) || !(min_step >= 0)) {
+        (have_min_step && !robust) || !(min_step >= 0) || batch < 0 || batch_stride < 1) {
         std::cout << "usage::ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused] [--color off|on [--color-scale S]]"
-                     " [--linearization normal|gradient|metric] [--huber D] [--huber-color D] [--min-step S]" << std::endl;
+                     " [--linearization normal|gradient|metric] [--huber D] [--huber-color D] [--min-step S] [--batch K [--batch-stride S]]" << std::endl;
         return bad || argc > 1 ? 2 : 0;
     }
     const long first = ((synthetic[2] + 999) % 1000) * 97 % 1000;
@@ -357,6 +362,37 @@ int main(int argc, char* argv[]) {
         volume.Synchronize();
         t_back += Seconds(t0);
     }
+    // --batch K: the first K frames of the sequence against the whole model from their perturbed poses, K frames per call through the batch entry
+    // (CubeHandler::RegisterFramesRobust) and one call per frame (RegisterRGBDRobust), both timed: the same poses, one launch per round against
+    // one per frame and iteration
+    double batch_ms = 0, batch_single_ms = 0;
+    op_volume_register_batch_stats batch_stats = op_volume_register_batch_stats();
+    bool batch_same = true;
+    if (batch > 0) {
+        const long K = std::min(batch, n);
+        std::vector<cv::Mat> depths(K), rgbs(K);
+        geometry::Mat4List starts(K);
+        for (long k = 0; k < K; ++k) {
+            const geometry::TransformationMatrix pose = RoomPose(first + k * stride);
+            RoomRender(pose, camera, depths[k], rgbs[k]);
+            float truth[16], start[16];
+            RowMajor(pose, truth);
+            Perturbed(truth, k, start);
+            starts[k] = FromRowMajor(start);
+        }
+        const std::vector<cv::Mat> no_rgbs;
+        std::vector<op_volume_register_robust_result> many, one(K);
+        for (int pass = 0; pass < 2; ++pass) { // (the first pass is not timed)
+            t0 = std::chrono::steady_clock::now();
+            if (volume.RegisterFramesRobust(depths, with_color ? rgbs : no_rgbs, starts, static_cast<int>(batch_stride), &color_params, &options, &many, &batch_stats).size() != static_cast<size_t>(K)) return 1;
+            batch_ms = Seconds(t0) * 1000.0;
+            t0 = std::chrono::steady_clock::now();
+            for (long k = 0; k < K; ++k)
+                if (!volume.RegisterRGBDRobust(depths[k], with_color ? rgbs[k] : cv::Mat(), starts[k], static_cast<int>(batch_stride), &color_params, &options, &one[k])) return 1;
+            batch_single_ms = Seconds(t0) * 1000.0;
+        }
+        for (long k = 0; k < K; ++k) batch_same = batch_same && std::memcmp(&many[k], &one[k], sizeof(one[k])) == 0;
+    }
     std::cout << "{\"frames\": " << n << ", \"stride\": " << stride << ", \"first\": " << first << ", \"res\": " << res << ", \"path\": \"" << path << "\", \"registered\": " << frames
               << ", \"iters\": " << iters << ", \"iterations\": " << iterations << ", \"points\": " << points << ", \"used_last\": " << used
               << ", \"error_before\": {\"mm\": " << Median(before_m) * 1000.0 << ", \"deg\": " << Median(before_deg) << "}"
@@ -366,6 +402,9 @@ int main(int argc, char* argv[]) {
     if (with_color) std::cout << ", \"color_scale\": " << color_scale << ", \"rmse_color\": " << Median(rmse_color) << ", \"colored_last\": " << colored;
     if (robust) std::cout << ", \"linearization\": \"" << linearization << "\", \"huber\": " << huber << ", \"huber_color\": " << huber_color << ", \"downweighted_last\": " << downweighted
                           << ", \"rmse_residual\": " << Median(rmse_residual);
+    if (batch > 0) std::cout << ", \"batch\": {\"frames\": " << std::min(batch, n) << ", \"pixel_stride\": " << batch_stride << ", \"ms\": " << batch_ms << ", \"single_ms\": " << batch_single_ms
+                             << ", \"rounds\": " << batch_stats.rounds << ", \"launches\": " << batch_stats.launches << ", \"evaluations\": " << batch_stats.evaluations
+                             << ", \"points\": " << batch_stats.points << ", \"same_bits\": " << (batch_same ? "true" : "false") << "}";
     std::cout
               << ", \"ms\": {\"fuse\": " << t_fuse * 1000.0 << ", \"deintegrate\": " << t_out * 1000.0 << ", \"reintegrate\": " << t_back * 1000.0
               << ", \"register_median\": " << Median(register_ms) << ", \"per_iteration_median\": " << Median(per_iteration_ms) << "}}" << std::endl;

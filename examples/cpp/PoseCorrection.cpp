@@ -14,6 +14,15 @@
 //                              "collect": block counts before and after, the collection's time (median over the runs) and the times of one ExtractTriangleMesh, one
 //                              RenderFrame and one WriteToFile over the volume as it is then
 //   --dump FILE                with --collect: the final volume as (key, block) records sorted by key (device and roundtrip write equal files)
+//   --path refine              the K poses are not handed over but FOUND: the K frames are registered against the volume they were fused into, each
+//                              from its drifted pose (op_volume_register_robust_frame's loop), and then moved to the estimates by
+//                              op_volume_reintegrate_sequence.  The K frames are brought to the device once, before the clock starts.
+//     --refine single|batch    single (default): one op_volume_register_robust_frame call per frame; batch: one op_volume_register_batch_frames call
+//                              for all K -- the same poses bit for bit (with --dump FILE both write the same file: K x 16 numbers)
+//     --stride S --iters I --linearization normal|gradient|metric --color on|off   pixel stride (4), iterations at most (10), linearisation (metric),
+//                              colour term (off) of the registration
+//                              The JSON gains "refine": the estimate's and the move's times, the pose errors of the K frames before and after
+//                              against the synthetic truth, and for batch the rounds, launches and evaluations of the call
 // It prints one JSON line: the stage times (host clock, each stage waited for) and, against a second volume fused at the true poses, the number of
 // voxels whose weights differ and the largest |sdf| and |colour| differences over the others.  A re-fused volume is that volume bit for bit; a
 // re-integrated one has the same weights and differs by the float32 roundings of the inverse running mean (op_volume_deintegrate).
@@ -163,7 +172,8 @@ bool Dump(integration::CubeHandler& h, const std::string& file) {
 int main(int argc, char* argv[]) {
     long synthetic[3] = {0, 1, 1}, perturb = -1, runs = 1;
     bool is_synthetic = false, bad = false, path_given = false;
-    std::string path = "refuse", collect, dump;
+    std::string path = "refuse", collect, dump, refine = "single", linearization = "metric", color = "off";
+    long pixel_stride = 4, iters = 10;
     float res = 0.01f;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -174,14 +184,22 @@ int main(int argc, char* argv[]) {
         else if (a == "--runs" && i + 1 < argc) runs = std::atol(argv[++i]);
         else if (a == "--collect" && i + 1 < argc) collect = argv[++i];
         else if (a == "--dump" && i + 1 < argc) dump = argv[++i];
+        else if (a == "--refine" && i + 1 < argc) refine = argv[++i];
+        else if (a == "--stride" && i + 1 < argc) pixel_stride = std::atol(argv[++i]);
+        else if (a == "--iters" && i + 1 < argc) iters = std::atol(argv[++i]);
+        else if (a == "--linearization" && i + 1 < argc) linearization = argv[++i];
+        else if (a == "--color" && i + 1 < argc) color = argv[++i];
         else bad = true;
     }
     if (!collect.empty() && !path_given) path = "reintegrate"; // a re-fused volume has nothing to collect
     const long n = synthetic[0], stride = synthetic[1];
     if (perturb < 0) perturb = n / 10 > 0 ? n / 10 : 1;
-    if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || perturb < 1 || perturb > n || !(res > 0) || runs < 1 || (path != "refuse" && path != "reintegrate" && path != "split") ||
+    if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || perturb < 1 || perturb > n || !(res > 0) || runs < 1 || (path != "refuse" && path != "reintegrate" && path != "split" && path != "refine") ||
+        (refine != "single" && refine != "batch") || pixel_stride < 1 || iters < 0 || (linearization != "normal" && linearization != "gradient" && linearization != "metric") ||
+        (color != "on" && color != "off") ||
         (!collect.empty() && collect != "none" && collect != "device" && collect != "roundtrip")) {
-        std::cout << "usage::PoseCorrection --synthetic N STRIDE SEED [--perturb K] [--res 0.01] [--path refuse|reintegrate|split] [--runs R] [--collect none|device|roundtrip] [--dump FILE]" << std::endl;
+        std::cout << "usage::PoseCorrection --synthetic N STRIDE SEED [--perturb K] [--res 0.01] [--path refuse|reintegrate|split|refine] [--runs R] [--collect none|device|roundtrip] [--dump FILE] "
+                     "[--refine single|batch] [--stride S] [--iters I] [--linearization normal|gradient|metric] [--color on|off]" << std::endl;
         return bad || argc > 1 ? 2 : 0;
     }
     const long first = ((synthetic[2] + 999) % 1000) * 97 % 1000;
@@ -203,6 +221,39 @@ int main(int argc, char* argv[]) {
     reference.SetVoxelResolution(res);
     if (!volume.Handle()) return 1; // (no device: the class has said so)
 
+    // --path refine: the K frames side by side on the device (frame j at j * bytes of an image), their drifted poses, and what the registration is told
+    const size_t npix = static_cast<size_t>(camera.GetWidth()) * static_cast<size_t>(camera.GetHeight()), dbytes = npix * sizeof(float), cbytes = npix * 3;
+    const char* dev_env = std::getenv("ONEPIECE_HIP_DEVICE");
+    const int device = dev_env ? std::atoi(dev_env) : 0;
+    void *d_depth = nullptr, *d_rgb = nullptr;
+    std::vector<long> moved_index;
+    std::vector<float> old_poses, new_poses;
+    op_volume_register_color_params reg_params;
+    op_volume_register_options reg_options;
+    op_volume_register_batch_stats reg_stats = op_volume_register_batch_stats();
+    std::vector<double> estimate_s, move_s;
+    if (path == "refine") {
+        std::vector<unsigned char> hd, hc;
+        for (long k = 0; k < n; ++k) {
+            if (!moved[k]) continue;
+            moved_index.push_back(k);
+            hd.insert(hd.end(), depth[k].data, depth[k].data + dbytes);
+            hc.insert(hc.end(), rgb[k].data, rgb[k].data + cbytes);
+            for (int r = 0; r < 4; ++r)
+                for (int c = 0; c < 4; ++c) old_poses.push_back(fused_at[k](r, c));
+        }
+        new_poses = old_poses;
+        if (op_device_upload(hd.data(), hd.size(), device, &d_depth) != OP_OK || op_device_upload(hc.data(), hc.size(), device, &d_rgb) != OP_OK ||
+            op_volume_register_color_default_params(volume.Handle(), &reg_params) != OP_OK) {
+            std::cout << RED << "[ERROR]::cannot bring the frames to the device: " << op_last_error() << RESET << std::endl;
+            return 1;
+        }
+        reg_params.base.max_iterations = static_cast<int>(iters);
+        if (color == "off") reg_params.color_scale = 0.0f;
+        reg_options.linearization = linearization == "normal" ? OP_REGISTER_LIN_NORMAL : linearization == "gradient" ? OP_REGISTER_LIN_GRADIENT : OP_REGISTER_LIN_METRIC;
+        reg_options.huber = 0.0f; reg_options.huber_color = 0.0f;
+    }
+
     // with --runs R > 1: one untimed pass, then R timed ones (the volume cleared in between); the medians are reported
     std::vector<double> fuse_s, repair_s, collect_s;
     size_t blocks_drifted = 0, blocks_repaired = 0;
@@ -221,6 +272,30 @@ int main(int argc, char* argv[]) {
         } else if (path == "reintegrate") {
             for (long k = 0; k < n; ++k)
                 if (moved[k]) volume.ReintegrateImage(depth[k], rgb[k], fused_at[k], truth[k]);
+        } else if (path == "refine") { // find the K poses (the queue is flushed by the first registration call), then move the frames there
+            const size_t K = moved_index.size();
+            const op_camera pod = camera.Pod();
+            const uint8_t* c_rgb = color == "on" ? static_cast<const uint8_t*>(d_rgb) : nullptr;
+            std::vector<op_volume_register_robust_result> found(K);
+            int rc = OP_OK;
+            if (refine == "batch") {
+                rc = op_volume_register_batch_frames(volume.Handle(), &pod, d_depth, dbytes, OP_DEPTH_F32, c_rgb, cbytes, OP_MEM_DEVICE, static_cast<int>(pixel_stride),
+                                                     old_poses.data(), K, &reg_params, &reg_options, found.data(), &reg_stats);
+            } else {
+                for (size_t j = 0; j < K && rc == OP_OK; ++j)
+                    rc = op_volume_register_robust_frame(volume.Handle(), &pod, static_cast<const unsigned char*>(d_depth) + j * dbytes, OP_DEPTH_F32, c_rgb ? c_rgb + j * cbytes : nullptr,
+                                                         OP_MEM_DEVICE, static_cast<int>(pixel_stride), old_poses.data() + 16 * j, &reg_params, &reg_options, &found[j]);
+            }
+            if (rc != OP_OK) { std::cout << RED << "[ERROR]::registration failed: " << op_last_error() << RESET << std::endl; return 1; }
+            const double te = Seconds(t0);
+            for (size_t j = 0; j < K; ++j) std::copy(found[j].color.base.T, found[j].color.base.T + 16, new_poses.begin() + 16 * j);
+            const std::chrono::steady_clock::time_point t1 = std::chrono::steady_clock::now();
+            if (op_volume_reintegrate_sequence(volume.Handle(), d_depth, dbytes, OP_DEPTH_F32, static_cast<const uint8_t*>(d_rgb), cbytes, old_poses.data(), new_poses.data(), K) != OP_OK) {
+                std::cout << RED << "[ERROR]::re-integration failed: " << op_last_error() << RESET << std::endl;
+                return 1;
+            }
+            volume.Synchronize();
+            if (pass >= 0) { estimate_s.push_back(te); move_s.push_back(Seconds(t1)); }
         } else { // split: the K de-integrations in launches of their own, then the K frames through the ordinary integration of a volume that is no longer plain
             for (long k = 0; k < n; ++k)
                 if (moved[k]) volume.DeintegrateImage(depth[k], rgb[k], fused_at[k]);
@@ -298,6 +373,37 @@ int main(int argc, char* argv[]) {
         if (!seen[b])
             for (int i = 0; i < 512; ++i)
                 if (got.vox[b * 2560 + 5 * i + 1] != 0.0f) ++extra_observed;
+    // --path refine: how far the K frames were from the truth before and after (translation in mm, rotation in degrees), and the poses themselves
+    double err_before[2] = {0, 0}, err_after[2] = {0, 0}, err_after_max[2] = {0, 0};
+    if (path == "refine") {
+        for (size_t j = 0; j < moved_index.size(); ++j) {
+            const geometry::TransformationMatrix& want_pose = truth[moved_index[j]];
+            for (int which = 0; which < 2; ++which) {
+                const float* T = (which ? new_poses : old_poses).data() + 16 * j;
+                double tt = 0, tr = 0;
+                for (int r = 0; r < 3; ++r) {
+                    tt += (static_cast<double>(T[4 * r + 3]) - want_pose(r, 3)) * (static_cast<double>(T[4 * r + 3]) - want_pose(r, 3));
+                    for (int c = 0; c < 3; ++c) tr += static_cast<double>(T[4 * r + c]) * want_pose(r, c); // trace(R_est^T R_true)
+                }
+                const double mm = 1000.0 * std::sqrt(tt), deg = 180.0 / kPi * std::acos(std::fmin(1.0, std::fmax(-1.0, (tr - 1.0) / 2.0)));
+                double* sum = which ? err_after : err_before;
+                sum[0] += mm / moved_index.size(); sum[1] += deg / moved_index.size();
+                if (which) { err_after_max[0] = std::fmax(err_after_max[0], mm); err_after_max[1] = std::fmax(err_after_max[1], deg); }
+            }
+        }
+        if (!dump.empty()) {
+            FILE* f = fopen(dump.c_str(), "w");
+            if (!f) { std::cout << RED << "[ERROR]::cannot write " << dump << RESET << std::endl; return 1; }
+            for (size_t j = 0; j < moved_index.size(); ++j) {
+                fprintf(f, "%ld", moved_index[j]);
+                for (int a = 0; a < 16; ++a) fprintf(f, " %.9g", new_poses[16 * j + a]);
+                fprintf(f, "\n");
+            }
+            fclose(f);
+        }
+        op_device_release(d_depth, device);
+        op_device_release(d_rgb, device);
+    }
     uint64_t dei[4] = {0, 0, 0, 0};
     op_volume_deintegrate_stats(volume.Handle(), &dei[0], &dei[1], &dei[2], &dei[3]);
     std::cout << "{\"frames\": " << n << ", \"stride\": " << stride << ", \"first\": " << first << ", \"perturbed\": " << perturb << ", \"res\": " << res << ", \"path\": \"" << path
@@ -306,6 +412,16 @@ int main(int argc, char* argv[]) {
               << ", \"blocks_drifted\": " << blocks_drifted << ", \"blocks\": " << got.n << ", \"blocks_reference\": " << want.n << ", \"missing_blocks\": " << missing_blocks
               << ", \"weight_mismatches\": " << weight_mismatch + extra_observed << ", \"max_abs_sdf_diff\": " << max_sdf << ", \"max_abs_colour_diff\": " << max_col
               << ", \"deintegrated\": {\"frames\": " << dei[0] << ", \"reverted\": " << dei[1] << ", \"reset\": " << dei[2] << ", \"skipped\": " << dei[3] << "}";
+    if (path == "refine") {
+        std::sort(estimate_s.begin(), estimate_s.end());
+        std::sort(move_s.begin(), move_s.end());
+        std::cout << ", \"refine\": {\"mode\": \"" << refine << "\", \"pixel_stride\": " << pixel_stride << ", \"iters\": " << iters << ", \"linearization\": \"" << linearization
+                  << "\", \"color\": \"" << color << "\", \"estimate_ms\": " << estimate_s[estimate_s.size() / 2] * 1000.0 << ", \"estimate_ms_min_max\": [" << estimate_s.front() * 1000.0
+                  << ", " << estimate_s.back() * 1000.0 << "], \"move_ms\": " << move_s[move_s.size() / 2] * 1000.0 << ", \"error_before_mm_deg\": [" << err_before[0] << ", "
+                  << err_before[1] << "], \"error_after_mm_deg\": [" << err_after[0] << ", " << err_after[1] << "], \"error_after_max_mm_deg\": [" << err_after_max[0] << ", "
+                  << err_after_max[1] << "], \"rounds\": " << reg_stats.rounds << ", \"launches\": " << reg_stats.launches << ", \"evaluations\": " << reg_stats.evaluations
+                  << ", \"points\": " << reg_stats.points << "}";
+    }
     if (!collect.empty()) {
         const op_volume_collect_stats& cs = volume.CollectStats();
         std::cout << ", \"collect\": {\"route\": \"" << collect << "\", \"blocks_before\": " << blocks_repaired << ", \"blocks_after\": " << blocks_collected << ", \"ms\": " << t_collect * 1000.0

@@ -224,6 +224,27 @@ class CubeHandler {
     bool RobustRegistrationSystem(const geometry::Point3List& points, const std::vector<float>& intensity, const geometry::TransformationMatrix& T,
                                   float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
                                   uint64_t counts[7]);
+    // Many frames, or many clouds, in one call (op_volume_register_batch_frames / _points state the definition): every frame follows
+    // RegisterRGBDRobust's loop on its own -- its own pose, its own stop rule -- and the frames that still iterate share one launch per round, so
+    // a stopped frame costs nothing more.  Element f of the returned list, and of *details, is what RegisterRGBDRobust /
+    // RegisterPointCloudRobust return for frame f alone, bit for bit.  One params and one options serve the whole batch (nullptr as there).
+    // Not in the reference.
+    //   RegisterFramesRobust       depths of one size and type, init_poses one per depth; rgbs empty: the geometric registration, else one CV_8UC3
+    //                              image per depth.  The images are packed into one upload.
+    //   RegisterPointCloudsRobust  inits one per cloud; the colour term needs colours on EVERY cloud, otherwise color_scale 0.
+    // A size mismatch or a failed call: an empty list.  *stats (when given): rounds, launches, evaluations, points.
+    std::vector<std::shared_ptr<registration::RegistrationResult>> RegisterFramesRobust(const std::vector<cv::Mat>& depths, const std::vector<cv::Mat>& rgbs,
+                                                                                        const geometry::Mat4List& init_poses, int pixel_stride = 1,
+                                                                                        const op_volume_register_color_params* params = nullptr,
+                                                                                        const op_volume_register_options* options = nullptr,
+                                                                                        std::vector<op_volume_register_robust_result>* details = nullptr,
+                                                                                        op_volume_register_batch_stats* stats = nullptr);
+    std::vector<std::shared_ptr<registration::RegistrationResult>> RegisterPointCloudsRobust(const std::vector<geometry::PointCloud>& pcds,
+                                                                                             const geometry::Mat4List& inits,
+                                                                                             const op_volume_register_color_params* params = nullptr,
+                                                                                             const op_volume_register_options* options = nullptr,
+                                                                                             std::vector<op_volume_register_robust_result>* details = nullptr,
+                                                                                             op_volume_register_batch_stats* stats = nullptr);
     // One fused volume against another (op_volume_register_volume states the definition): where the submap `source` belongs in this model, before
     // Transform + Merge (example/MergeMultipleSubmaps.cpp) fix its place for good.  A fused volume has no surface points, it has a band of voxels
     // that each carry their own sdf: the residual is this model's sdf at the transformed voxel centre MINUS the source voxel's own sdf, over the

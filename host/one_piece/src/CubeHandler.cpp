@@ -710,6 +710,93 @@ bool CubeHandler::RobustRegistrationSystem(const geometry::Point3List& points, c
     ReleaseBorrowed();
     return true;
 }
+std::vector<std::shared_ptr<registration::RegistrationResult>> CubeHandler::RegisterFramesRobust(const std::vector<cv::Mat>& depths, const std::vector<cv::Mat>& rgbs,
+                                                                                                 const geometry::Mat4List& init_poses, int pixel_stride,
+                                                                                                 const op_volume_register_color_params* params,
+                                                                                                 const op_volume_register_options* options,
+                                                                                                 std::vector<op_volume_register_robust_result>* details,
+                                                                                                 op_volume_register_batch_stats* stats) {
+    Pending();
+    std::vector<std::shared_ptr<registration::RegistrationResult>> out;
+    if (details) details->clear();
+    if (stats) *stats = op_volume_register_batch_stats();
+    const size_t n = depths.size();
+    if (init_poses.size() != n || (!rgbs.empty() && rgbs.size() != n)) { std::fprintf(stderr, "RegisterFramesRobust: one pose (and one colour image) per depth image\n"); return out; }
+    if (!n || !Ensure()) return out;
+    // the frames side by side in one buffer per plane: frame f at f * (bytes of an image)
+    const size_t dbytes = depths[0].total() * depths[0].elemSize(), cbytes = rgbs.empty() ? 0 : rgbs[0].total() * rgbs[0].elemSize();
+    std::vector<unsigned char> d(n * dbytes), c(n * cbytes);
+    std::vector<float> poses(16 * n);
+    for (size_t f = 0; f < n; ++f) {
+        const bool same = depths[f].rows == depths[0].rows && depths[f].cols == depths[0].cols && depths[f].type() == depths[0].type() && depths[f].data &&
+                          (rgbs.empty() || (rgbs[f].rows == depths[0].rows && rgbs[f].cols == depths[0].cols && rgbs[f].type() == CV_8UC3 && rgbs[f].data));
+        if (!same) { std::fprintf(stderr, "RegisterFramesRobust: frame %zu differs from frame 0 in size or type\n", f); return out; }
+        std::memcpy(d.data() + f * dbytes, depths[f].data, dbytes);
+        if (cbytes) std::memcpy(c.data() + f * cbytes, rgbs[f].data, cbytes);
+        bridge::RowMajor(init_poses[f], poses.data() + 16 * f);
+    }
+    const op_camera pod = camera.Pod();
+    op_volume_register_options o;
+    bool ok = true;
+    if (options) o = *options;
+    else ok = op_volume_register_robust_default_options(vol, &o) == OP_OK;
+    std::vector<op_volume_register_robust_result> r(n);
+    op_volume_register_batch_stats st = op_volume_register_batch_stats();
+    if (!ok || op_volume_register_batch_frames(vol, &pod, d.data(), dbytes, bridge::DepthFormat(depths[0]), cbytes ? c.data() : nullptr, cbytes, OP_MEM_HOST, pixel_stride,
+                                               poses.data(), n, params, &o, r.data(), &st) != OP_OK) {
+        Report("RegisterFramesRobust");
+        return out;
+    }
+    ReleaseBorrowed(); // (the call synchronised the volume)
+    for (size_t f = 0; f < n; ++f) out.push_back(RegistrationOutcome(r[f].color.base));
+    if (details) *details = r;
+    if (stats) *stats = st;
+    return out;
+}
+std::vector<std::shared_ptr<registration::RegistrationResult>> CubeHandler::RegisterPointCloudsRobust(const std::vector<geometry::PointCloud>& pcds,
+                                                                                                      const geometry::Mat4List& inits,
+                                                                                                      const op_volume_register_color_params* params,
+                                                                                                      const op_volume_register_options* options,
+                                                                                                      std::vector<op_volume_register_robust_result>* details,
+                                                                                                      op_volume_register_batch_stats* stats) {
+    Pending();
+    std::vector<std::shared_ptr<registration::RegistrationResult>> out;
+    if (details) details->clear();
+    if (stats) *stats = op_volume_register_batch_stats();
+    const size_t n = pcds.size();
+    if (inits.size() != n) { std::fprintf(stderr, "RegisterPointCloudsRobust: one initial transformation per cloud\n"); return out; }
+    if (!n || !Ensure()) return out;
+    op_volume_register_color_params p;
+    op_volume_register_options o;
+    bool ok = true;
+    if (params) p = *params;
+    else ok = op_volume_register_color_default_params(vol, &p) == OP_OK;
+    if (options) o = *options;
+    else ok = ok && op_volume_register_robust_default_options(vol, &o) == OP_OK;
+    std::vector<uint64_t> starts(n + 1, 0);
+    for (size_t c = 0; c < n; ++c) starts[c + 1] = starts[c] + pcds[c].points.size();
+    std::vector<float> xyz(3 * starts[n]), intensity, one, Ts(16 * n);
+    bool colored = true;
+    for (size_t c = 0; c < n; ++c) {
+        if (!pcds[c].points.empty()) std::memcpy(xyz.data() + 3 * starts[c], bridge::Floats(pcds[c].points), sizeof(float) * 3 * pcds[c].points.size());
+        colored = colored && CloudIntensity(pcds[c], one);
+        if (colored) intensity.insert(intensity.end(), one.begin(), one.end());
+        bridge::RowMajor(inits[c], Ts.data() + 16 * c);
+    }
+    if (!colored) p.color_scale = 0.0f;
+    std::vector<op_volume_register_robust_result> r(n);
+    op_volume_register_batch_stats st = op_volume_register_batch_stats();
+    if (!ok || op_volume_register_batch_points(vol, xyz.data(), nullptr, colored && !intensity.empty() ? intensity.data() : nullptr, starts.data(), n, OP_MEM_HOST, Ts.data(),
+                                               &p, &o, r.data(), &st) != OP_OK) {
+        Report("RegisterPointCloudsRobust");
+        return out;
+    }
+    ReleaseBorrowed();
+    for (size_t c = 0; c < n; ++c) out.push_back(RegistrationOutcome(r[c].color.base));
+    if (details) *details = r;
+    if (stats) *stats = st;
+    return out;
+}
 std::shared_ptr<registration::RegistrationResult> CubeHandler::RegisterVolume(const CubeHandler& source, const geometry::TransformationMatrix& init,
                                                                               const op_volume_band_params* sel, const op_volume_register_color_params* params,
                                                                               const op_volume_register_options* options, op_volume_register_volume_result* details) {

@@ -792,6 +792,53 @@ int op_volume_register_volume(op_volume *target, op_volume *source, const float 
                               const op_volume_band_params *sel /* NULL: defaults */, const op_volume_register_color_params *params,
                               const op_volume_register_options *options /* NULL: GRADIENT */, op_volume_register_volume_result *result);
 
+/* Many clouds, or many frames, against the fused field in one call (csrc/volume_register.hip, k_volume_register_batch; NO reference counterpart).
+ * The entries above place one cloud per call and pay a launch, a fold, a copy and a stream synchronisation per Gauss-Newton iteration; at
+ * pixel_stride 4 that latency is most of an iteration.  Here every cloud follows the single entries' loop ON ITS OWN -- its own pose, its own
+ * stop rule -- and the clouds that want an evaluation in a round share ONE launch, one fold, one copy and one synchronisation.
+ * The definition is the single entries': cloud c is points [starts[c], starts[c + 1]) of xyz (and of offset and intensity), and
+ *   results[c], and sums + 31 c / counts + 7 c, are BIT FOR BIT what op_volume_register_offset_points / _offset_system return for cloud c alone
+ *   with the same arguments (offset == NULL: the robust entries; all-zero or NULL options: the colour entries; color_scale == 0: the geometric
+ *   ones); results[f] of the frames entry is op_volume_register_robust_frame on frame f alone.
+ * This holds for every argument combination those entries accept, and does not depend on the order of the clouds, on what else is in the batch
+ * or on the rounds in which the other clouds stop: a cloud's workgroups, their trips, its rows and their fold are the single entry's
+ * (min(ceil(n_c / 256), 1024) workgroups, rows of 32 / 35 / 38, 32 or 16 row lanes), and the host loop is the same code.  One set of params and
+ * options serves the whole batch.
+ * A cloud that has stopped, and has had the evaluation at its returned T (skipped when its last evaluation is already current), is never
+ * evaluated again.  stats (or NULL): evaluations is the sum over the clouds of the evaluations each one's loop made -- what the single entries would
+ * make --, rounds the largest such count of one cloud, launches the kernels of the rounds (a round with no cloud that has a point launches
+ * nothing), points starts[n_clouds], for the frames entry the kept pixels.
+ * An empty cloud, an all-zero depth image or an empty volume is no error: zero sums, OP_REGISTER_TOO_FEW_POINTS (min_points > 0), T = init_T.
+ * n_clouds == 0 (n_frames == 0) returns OP_OK and writes nothing.
+ * Frames use op_volume_integrate_sequence's addressing: frame f's depth image is depth + f * depth_stride_bytes, its colour image
+ * rgb + f * rgb_stride_bytes, both in `mem`; rgb == NULL registers geometrically.  Every frame's sub-grid is counted by one kernel, scanned once
+ * and scattered once; inside a frame the kept pixels are in op_volume_register_depth's row-major order with its arithmetic.  Host images are
+ * uploaded once.  The point, intensity, row and output buffers belong to the call (the volume's own registration buffers are not touched).
+ * starts, T / init_T / init_poses, sums, counts, results and stats are HOST memory whatever `mem` says.  Like every accessor the call sees all
+ * frames accepted before it (the queue is flushed first) and only reads the volume.
+ * Refusals, decided before any device use (OP_ERR_INVALID): everything the single entries refuse; a NULL starts, T / init_T / init_poses, results
+ * or sums; starts that decrease; a depth or colour stride smaller than an image, a depth stride that is no multiple of a depth value's size; more
+ * than 2^32 - 1 sub-grid pixels in all.
+ * Not built: params per cloud, the solve on the device, damping, a batch form of op_volume_register_volume. */
+typedef struct { uint32_t rounds, launches; uint64_t evaluations, points; } op_volume_register_batch_stats;
+/* one evaluation of every cloud at its own T */
+int op_volume_register_batch_system(op_volume *v, const float *xyz, const float *offset /* or NULL */, const float *intensity /* or NULL */,
+                                    const uint64_t *starts /* n_clouds + 1, host, non-decreasing */, size_t n_clouds, int mem,
+                                    const float *T /* n_clouds x 16, host */, float max_distance, float color_scale, float max_color_residual,
+                                    const op_volume_register_options *options /* NULL: zeros */, double *sums /* n_clouds x 31 */,
+                                    uint64_t *counts /* n_clouds x 7, or NULL */);
+/* the loops */
+int op_volume_register_batch_points(op_volume *v, const float *xyz, const float *offset, const float *intensity, const uint64_t *starts,
+                                    size_t n_clouds, int mem, const float *init_T /* n_clouds x 16 */,
+                                    const op_volume_register_color_params *params /* NULL: defaults */,
+                                    const op_volume_register_options *options /* NULL: zeros */,
+                                    op_volume_register_robust_result *results /* n_clouds */, op_volume_register_batch_stats *stats /* or NULL */);
+int op_volume_register_batch_frames(op_volume *v, const op_camera *cam /* NULL: the volume's */, const void *depth, size_t depth_stride_bytes,
+                                    int depth_fmt, const uint8_t *rgb /* or NULL: geometric */, size_t rgb_stride_bytes, int mem, int pixel_stride,
+                                    const float *init_poses /* n_frames x 16 */, size_t n_frames,
+                                    const op_volume_register_color_params *params, const op_volume_register_options *options,
+                                    op_volume_register_robust_result *results /* n_frames */, op_volume_register_batch_stats *stats /* or NULL */);
+
 /* Frame-sharded multi-GPU merge (the distributed form of CubeHandler::Merge; DESIGN.md "Multi-GPU").
  * All pointers are DEVICE pointers on the volume's device.
  *   keys_device : copy this volume's block keys (n x 3 int32) into d_keys.

@@ -93,6 +93,11 @@ class RegisterVolumeResult(C.Structure):
     _fields_ = [("robust", RegisterRobustResult), ("selected", C.c_uint64)]
 
 
+class RegisterBatchStats(C.Structure):
+    """op_volume_register_batch_stats of op_volume_register_batch_points / _frames."""
+    _fields_ = [("rounds", C.c_uint32), ("launches", C.c_uint32), ("evaluations", C.c_uint64), ("points", C.c_uint64)]
+
+
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("last_T", C.c_float * 16), ("rmse", C.c_double),
                 ("n_inliers", C.c_uint64), ("iterations", C.c_int32)]
@@ -260,6 +265,13 @@ SIGNATURES = {
                                                    C.POINTER(RegisterRobustResult)]),
     "op_volume_register_volume": (C.c_int, [_vp, _vp, _fp, C.POINTER(BandParams), C.POINTER(RegisterColorParams), C.POINTER(RegisterOptions),
                                             C.POINTER(RegisterVolumeResult)]),
+    "op_volume_register_batch_system": (C.c_int, [_vp, _vp, _vp, _vp, _u64p, C.c_size_t, C.c_int, _fp, C.c_float, C.c_float, C.c_float, C.POINTER(RegisterOptions),
+                                                  C.POINTER(C.c_double), _u64p]),
+    "op_volume_register_batch_points": (C.c_int, [_vp, _vp, _vp, _vp, _u64p, C.c_size_t, C.c_int, _fp, C.POINTER(RegisterColorParams), C.POINTER(RegisterOptions),
+                                                  C.POINTER(RegisterRobustResult), C.POINTER(RegisterBatchStats)]),
+    "op_volume_register_batch_frames": (C.c_int, [_vp, C.POINTER(Camera), _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, _fp, C.c_size_t,
+                                                  C.POINTER(RegisterColorParams), C.POINTER(RegisterOptions), C.POINTER(RegisterRobustResult),
+                                                  C.POINTER(RegisterBatchStats)]),
     "op_icp_run_many": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _fp, C.c_int, _vp]),
     "op_icp_tie_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "op_icp_final_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),

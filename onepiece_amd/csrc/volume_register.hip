@@ -26,6 +26,10 @@
 // op_volume_register_volume) give every point a target value o_i of its own: the residual the linearisation starts from is s - o_i, one more
 // load and one subtraction per point; the USED rule, max_distance and the stored-sdf sum keep s.  They are ROBUST instantiations with one more
 // template parameter: the reduction, the rows of 38 and the fold are those; offset == NULL runs the instantiations above.
+// The BATCH kernel (op_volume_register_batch_*: k_volume_register_batch) is the same body -- volume_register_body.inc, included by both kernels --
+// behind a prologue that finds the workgroup's cloud in the round's table (a wave-uniform binary search, scalar loads) and points A at that cloud's
+// range, pose and first row; k_register_fold_batch folds every active cloud's rows with one workgroup each, in the single fold's order.  The host
+// loop is RegLoopState: reg_loop drives one, the batch entries one per cloud.
 // Not built: damping, multi-resolution, re-ordering the points by block.
 #include "volume_core.hpp"
 #include "trilinear_sample.hpp"
@@ -89,169 +93,20 @@ __device__ __forceinline__ bool reg_sample_sdf(const VolView& V, const RegView& 
     }
 }
 
+template <bool ROBUST, bool OFFSET>
+using RegExtra = std::conditional_t<OFFSET, RegOffset, std::conditional_t<ROBUST, RegRobust, RegColor>>;
+
 template <bool ROWS, bool COLOR, bool ROBUST = false, bool OFFSET = false>
-__global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A, std::conditional_t<OFFSET, RegOffset, std::conditional_t<ROBUST, RegRobust, RegColor>> K) {
-    static_assert(ROBUST || !OFFSET, "the per-point target value is an option of the ROBUST instantiations");
-    constexpr int kSlots = ROBUST ? kRegSlotsR : COLOR ? kRegSlotsC : kRegSlots;
-    constexpr int kExt = ROBUST ? 6 : 3;
-    __shared__ double s_red[kRegWg / 64][kSlots];
-    double total = 0.0; // lane L: slot (L >> 1) & 31 of this wave, over its trips
-    double ext[kExt] = {}; // COLOR: the wave's rc rc, s s, colored over its trips (the same in every lane); ROBUST: and r r, downweighted, color_downweighted
-    BlockCache bc{INT_MIN, INT_MIN, INT_MIN, -1};
-    const size_t step = (size_t)gridDim.x * kRegWg;
-    for (size_t base = (size_t)blockIdx.x * kRegWg; base < A.n; base += step) { // (the same trips for every lane of the workgroup)
-        const size_t i = base + threadIdx.x;
-        float j[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, s = 0.0f;
-        float jc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rcs = 0.0f, rc = 0.0f; // COLOR: zero unless the point is coloured
-        bool colored = false;
-        float sraw = 0.0f, runw = 0.0f; // ROBUST: the sdf and the unweighted residual of a used point
-        bool down = false, cdown = false;
-        int reason = -1; // 0 used, 1 invalid, 2 no gradient, 3 too far; -1: no point
-        if (i < A.n) {
-            const float x = A.xyz[3 * i], y = A.xyz[3 * i + 1], z = A.xyz[3 * i + 2];
-            const float* M = A.T; // TransformPoints' order (k_prepare_frames)
-            const float q0 = ((M[0] * x + M[1] * y) + M[2] * z) + M[3] * 1.0f;
-            const float q1 = ((M[4] * x + M[5] * y) + M[6] * z) + M[7] * 1.0f;
-            const float q2 = ((M[8] * x + M[9] * y) + M[10] * z) + M[11] * 1.0f;
-            const float q3 = ((M[12] * x + M[13] * y) + M[14] * z) + M[15] * 1.0f;
-            const float p0 = q0 / q3, p1 = q1 / q3, p2 = q2 / q3;
-            float sv = 0.0f, mv = 0.0f;
-            reason = 1;
-            float off = 0.0f; // OFFSET: the point's target value; a non-finite one leaves the point invalid (false for NaN)
-            bool have = true;
-            if constexpr (OFFSET) { off = K.offset[i]; have = fabsf(off) < INFINITY; }
-            if (have && reg_sample_sdf<COLOR>(V, A.W, bc, p0, p1, p2, &sv, &mv)) {
-                const float h = 0.5f * A.W.res; // k_rc_shade's central difference
-                float d[3], g[3] = {0.0f, 0.0f, 0.0f};
-                bool all = true;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    float sp = 0.0f, sm = 0.0f, ip = 0.0f, im = 0.0f;
-                    all = all && reg_sample_sdf<COLOR>(V, A.W, bc, p0 + (a == 0 ? h : 0.0f), p1 + (a == 1 ? h : 0.0f), p2 + (a == 2 ? h : 0.0f), &sp, &ip)
-                              && reg_sample_sdf<COLOR>(V, A.W, bc, p0 - (a == 0 ? h : 0.0f), p1 - (a == 1 ? h : 0.0f), p2 - (a == 2 ? h : 0.0f), &sm, &im);
-                    d[a] = sp - sm;
-                    if constexpr (COLOR) g[a] = (ip - im) / A.W.res;
-                }
-                const float l2 = all ? d[0] * d[0] + (d[1] * d[1] + d[2] * d[2]) : 0.0f;
-                if (!(l2 > 0.0f)) reason = 2;
-                else if (A.max_distance > 0.0f && !(fabsf(sv) <= A.max_distance)) reason = 3;
-                else {
-                    reason = 0;
-                    const float l = sqrtf(l2);
-                    float n0 = d[0] / l, n1 = d[1] / l, n2 = d[2] / l;
-                    float e = sv; // what the linearisation starts from (the gate above and sraw below keep the stored sdf)
-                    if constexpr (OFFSET) e = sv - off;
-                    s = e;
-                    if constexpr (ROBUST) { // the row vector a (in n's place) and the residual r (in s's)
-                        if (K.linearization == OP_REGISTER_LIN_GRADIENT) { n0 = d[0] / A.W.res; n1 = d[1] / A.W.res; n2 = d[2] / A.W.res; }
-                        else if (K.linearization == OP_REGISTER_LIN_METRIC) s = e / (l / A.W.res);
-                        sraw = sv; runw = s;
-                    }
-                    j[0] = n0; j[1] = n1; j[2] = n2;
-                    j[3] = p1 * n2 - p2 * n1; j[4] = p2 * n0 - p0 * n2; j[5] = p0 * n1 - p1 * n0;
-                    if constexpr (ROBUST) {
-                        if (K.huber > 0.0f) {
-                            const float w = fabsf(s) <= K.huber ? 1.0f : K.huber / fabsf(s);
-                            const float q = sqrtf(w);
-                            down = w < 1.0f;
-#pragma unroll
-                            for (int a = 0; a < 6; ++a) j[a] = q * j[a];
-                            s = q * s;
-                        }
-                    }
-                    if constexpr (COLOR) {
-                        const float y = K.intensity[i], r = mv - y;
-                        if (fabsf(y) < INFINITY && (!(K.max_color_residual > 0.0f) || fabsf(r) <= K.max_color_residual)) { // (false for a NaN y)
-                            colored = true;
-                            const float cs = K.color_scale;
-                            jc[0] = cs * g[0]; jc[1] = cs * g[1]; jc[2] = cs * g[2];
-                            jc[3] = cs * (p1 * g[2] - p2 * g[1]); jc[4] = cs * (p2 * g[0] - p0 * g[2]); jc[5] = cs * (p0 * g[1] - p1 * g[0]);
-                            rc = r; rcs = cs * r;
-                            if constexpr (ROBUST) {
-                                if (K.huber_color > 0.0f) {
-                                    const float wc = fabsf(r) <= K.huber_color ? 1.0f : K.huber_color / fabsf(r);
-                                    const float qc = sqrtf(wc);
-                                    cdown = wc < 1.0f;
-#pragma unroll
-                                    for (int a = 0; a < 6; ++a) jc[a] = qc * jc[a];
-                                    rcs = qc * rcs;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            if (ROWS) {
-                float* o = A.rows + (COLOR ? 16 : 8) * i;
-#pragma unroll
-                for (int a = 0; a < 6; ++a) o[a] = j[a];
-                o[6] = s; o[7] = reason == 0 ? 1.0f : 0.0f;
-                if constexpr (COLOR) {
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) o[8 + a] = jc[a];
-                    o[14] = rcs; o[15] = colored ? 1.0f : 0.0f;
-                }
-            }
-        }
-        // slot k of the point: float products, widened (an unused point's j and s are zero)
-        auto val = [&](auto kc) -> double {
-            constexpr int k = decltype(kc)::value;
-            if constexpr (k < 21) {
-                constexpr int a = k < 6 ? 0 : k < 11 ? 1 : k < 15 ? 2 : k < 18 ? 3 : k < 20 ? 4 : 5;
-                constexpr int first = a == 0 ? 0 : a == 1 ? 6 : a == 2 ? 11 : a == 3 ? 15 : a == 4 ? 18 : 20;
-                if constexpr (COLOR) return (double)(j[a] * j[a + (k - first)]) + (double)(jc[a] * jc[a + (k - first)]);
-                else return (double)(j[a] * j[a + (k - first)]);
-            } else if constexpr (k < 27) {
-                if constexpr (COLOR) return (double)(s * j[k - 21]) + (double)(rcs * jc[k - 21]);
-                else return (double)(s * j[k - 21]);
-            } else if constexpr (k == 27) {
-                if constexpr (COLOR) return (double)s * (double)s + (double)rcs * (double)rcs;
-                else return (double)s * (double)s;
-            } else {
-                return reason == k - 28 ? 1.0 : 0.0;
-            }
-        };
-        total += op::wave_reduce_scatter32_lazy(val);
-        if constexpr (ROBUST) { // the six without a slot, by the butterfly below (without COLOR three of them are zero and stay at home)
-            double e[6] = {(double)rc * (double)rc, (double)sraw * (double)sraw, colored ? 1.0 : 0.0, (double)runw * (double)runw, down ? 1.0 : 0.0, cdown ? 1.0 : 0.0};
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-                for (int q = 0; q < 6; ++q)
-                    if (COLOR || q == 1 || q == 3 || q == 4) e[q] += __shfl_xor(e[q], m, 64);
-            }
-#pragma unroll
-            for (int q = 0; q < 6; ++q) ext[q] += e[q];
-        } else if constexpr (COLOR) { // the three without a slot: a butterfly, lane masks 32, 16, 8, 4, 2, 1 -- a + b is b + a, so every lane holds the same total
-            double e[3] = {(double)rc * (double)rc, (double)s * (double)s, colored ? 1.0 : 0.0};
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q) e[q] += __shfl_xor(e[q], m, 64);
-            }
-#pragma unroll
-            for (int q = 0; q < 3; ++q) ext[q] += e[q];
-        }
-    }
-    // one row per workgroup (every lane gets here)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if ((lane & 1) == 0) s_red[wave][lane >> 1] = total;
-    if constexpr (COLOR || ROBUST) {
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < kExt; ++q) s_red[wave][32 + q] = ext[q];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < kSlots) {
-        double t = s_red[0][threadIdx.x];
-        for (int w = 1; w < kRegWg / 64; ++w) t += s_red[w][threadIdx.x];
-        A.partial[(size_t)blockIdx.x * kSlots + threadIdx.x] = t;
-    }
+__global__ __launch_bounds__(kRegWg) void k_volume_register(VolView V, RegArgs A, RegExtra<ROBUST, OFFSET> K) {
+#define REG_WG blockIdx.x
+#define REG_N_WG gridDim.x
+#include "volume_register_body.inc"
+#undef REG_WG
+#undef REG_N_WG
 }
 
 // the rows in index order: row lane r adds rows r, r + 32, ..., then the 32 row lanes are added in order (four loads in flight per lane: the adds keep their order)
-__global__ __launch_bounds__(kFoldWg) void k_register_fold(const double* __restrict__ partial, unsigned n_rows, double* __restrict__ out) {
+__device__ __forceinline__ void register_fold(const double* __restrict__ partial, unsigned n_rows, double* __restrict__ out) {
     __shared__ double s_fin[kFoldRows][kRegSlots];
     const unsigned fk = threadIdx.x & 31u, fr = threadIdx.x >> 5;
     double t = 0.0;
@@ -269,6 +124,9 @@ __global__ __launch_bounds__(kFoldWg) void k_register_fold(const double* __restr
         for (int r = 1; r < kFoldRows; ++r) u += s_fin[r][threadIdx.x];
         out[threadIdx.x] = u;
     }
+}
+__global__ __launch_bounds__(kFoldWg) void k_register_fold(const double* __restrict__ partial, unsigned n_rows, double* __restrict__ out) {
+    register_fold(partial, n_rows, out);
 }
 
 // the same for rows of 35 (COLOR) or 38 (ROBUST): row lane r (of 16) adds rows r, r + 16, ..., then the 16 row lanes are added in order
@@ -306,22 +164,19 @@ struct SubGrid { int w, h, sw, sh, stride; };
 __device__ __forceinline__ float reg_depth_at(const void* depth, int is_u16, float depth_scale, size_t px) {
     return is_u16 ? (float)((const unsigned short*)depth)[px] / depth_scale : ((const float*)depth)[px];
 }
-__global__ __launch_bounds__(256) void k_register_depth_count(const void* __restrict__ depth, int is_u16, float depth_scale, SubGrid G, unsigned* __restrict__ count) {
-    const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
-    if (k >= (size_t)G.sw * G.sh) return;
+// (one sub-grid pixel k of one image: the count kernel's answer and the scatter kernel's stores; the batch kernels below call the same two)
+__device__ __forceinline__ unsigned reg_pixel_kept(const void* __restrict__ depth, int is_u16, float depth_scale, const SubGrid& G, size_t k) {
     const int r = (int)(k / G.sw) * G.stride, c = (int)(k % G.sw) * G.stride;
-    count[k] = reg_depth_at(depth, is_u16, depth_scale, (size_t)r * G.w + c) > 0 ? 1u : 0u;
+    return reg_depth_at(depth, is_u16, depth_scale, (size_t)r * G.w + c) > 0 ? 1u : 0u;
 }
 // (RGB: and the kept pixel's intensity from its three bytes, each b / 255.0f as the integration rounds it)
 template <bool RGB>
-__global__ __launch_bounds__(256) void k_register_depth_scatter(const void* __restrict__ depth, int is_u16, op_camera cam, SubGrid G, const unsigned* __restrict__ start,
-                                                                float* __restrict__ xyz, const unsigned char* __restrict__ rgb, float* __restrict__ intensity) {
-    const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
-    if (k >= (size_t)G.sw * G.sh) return;
+__device__ __forceinline__ void reg_pixel_scatter(const void* __restrict__ depth, int is_u16, const op_camera& cam, const SubGrid& G, size_t k, const unsigned* __restrict__ start_of_k,
+                                                  float* __restrict__ xyz, const unsigned char* __restrict__ rgb, float* __restrict__ intensity) {
     const int r = (int)(k / G.sw) * G.stride, c = (int)(k % G.sw) * G.stride;
     const float z = reg_depth_at(depth, is_u16, cam.depth_scale, (size_t)r * G.w + c);
     if (!(z > 0)) return;
-    const unsigned p = start[k];
+    const unsigned p = *start_of_k;
     xyz[3 * p] = ((float)c - cam.cx) * z / cam.fx; // PointCloud.cpp:90-93
     xyz[3 * p + 1] = ((float)r - cam.cy) * z / cam.fy;
     xyz[3 * p + 2] = z;
@@ -330,6 +185,111 @@ __global__ __launch_bounds__(256) void k_register_depth_scatter(const void* __re
         const float col[3] = {(float)b[0] / 255.0f, (float)b[1] / 255.0f, (float)b[2] / 255.0f};
         intensity[p] = reg_intensity(col);
     }
+}
+__global__ __launch_bounds__(256) void k_register_depth_count(const void* __restrict__ depth, int is_u16, float depth_scale, SubGrid G, unsigned* __restrict__ count) {
+    const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (k >= (size_t)G.sw * G.sh) return;
+    count[k] = reg_pixel_kept(depth, is_u16, depth_scale, G, k);
+}
+template <bool RGB>
+__global__ __launch_bounds__(256) void k_register_depth_scatter(const void* __restrict__ depth, int is_u16, op_camera cam, SubGrid G, const unsigned* __restrict__ start,
+                                                                float* __restrict__ xyz, const unsigned char* __restrict__ rgb, float* __restrict__ intensity) {
+    const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (k >= (size_t)G.sw * G.sh) return;
+    reg_pixel_scatter<RGB>(depth, is_u16, cam, G, k, start + k, xyz, rgb, intensity);
+}
+
+// ---- many clouds in one launch (op_volume_register_batch_*)
+// A round's launch holds the workgroups of every cloud that needs an evaluation in that round, cloud after cloud.  Cloud c has the n_wg workgroups
+// RegRun::open gives it alone, and its workgroup b runs the trips the single kernel's workgroup b runs (volume_register_body.inc), so its n_wg
+// rows, and their fold in k_register_fold's order, are the single entry's bits whatever else the launch holds.  A workgroup finds its cloud by a
+// binary search over the first_wg column of the round's table: blockIdx.x is wave-uniform, so are the addresses, and the table, the pose and
+// the cloud's range come through scalar loads.  The table has one entry per active cloud, never one per workgroup.
+struct RegBatchEntry {
+    unsigned long long start, n; // the cloud's points are [start, start + n) of the call's buffers
+    unsigned first_wg, n_wg;     // its workgroups [first_wg, first_wg + n_wg) of the launch; its rows are those of the partial buffer
+    float T[16];
+};
+struct RegBatchArgs {
+    const float* xyz;
+    const RegBatchEntry* table;
+    unsigned n_active;
+    RegView W;
+    float max_distance;
+    double* partial; // (the launch's workgroups) x slots
+};
+
+template <bool COLOR, bool ROBUST, bool OFFSET>
+__global__ __launch_bounds__(kRegWg) void k_volume_register_batch(VolView V, RegBatchArgs B, RegExtra<ROBUST, OFFSET> K) {
+    constexpr bool ROWS = false;
+    constexpr int kRowSlots = ROBUST ? kRegSlotsR : COLOR ? kRegSlotsC : kRegSlots;
+    const RegBatchEntry* __restrict__ table = B.table;
+    unsigned lo = 0, hi = B.n_active; // the last entry whose first workgroup is not after this one (entry 0 starts at 0)
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (table[mid].first_wg <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    const RegBatchEntry* __restrict__ E = table + lo;
+    const unsigned first_wg = E->first_wg, cloud_wgs = E->n_wg;
+    const size_t start = E->start;
+    RegArgs A;
+    A.xyz = B.xyz + 3 * start;
+    A.n = E->n;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) A.T[k] = E->T[k];
+    A.W = B.W;
+    A.max_distance = B.max_distance;
+    A.rows = nullptr;
+    A.partial = B.partial + (size_t)first_wg * kRowSlots;
+    if constexpr (COLOR) K.intensity += start;
+    if constexpr (OFFSET) K.offset += start;
+    const unsigned cloud_wg = blockIdx.x - first_wg;
+#define REG_WG cloud_wg
+#define REG_N_WG cloud_wgs
+#include "volume_register_body.inc"
+#undef REG_WG
+#undef REG_N_WG
+}
+
+// one workgroup per active cloud: k_register_fold / register_fold_wide over that cloud's rows
+__global__ __launch_bounds__(kFoldWg) void k_register_fold_batch(const double* __restrict__ partial, const RegBatchEntry* __restrict__ table, double* __restrict__ out) {
+    const RegBatchEntry* E = table + blockIdx.x;
+    register_fold(partial + (size_t)E->first_wg * kRegSlots, E->n_wg, out + (size_t)blockIdx.x * kRegSlots);
+}
+template <int SLOTS>
+__global__ __launch_bounds__(kFoldWg) void k_register_fold_batch_wide(const double* __restrict__ partial, const RegBatchEntry* __restrict__ table, double* __restrict__ out) {
+    const RegBatchEntry* E = table + blockIdx.x;
+    register_fold_wide<SLOTS>(partial + (size_t)E->first_wg * SLOTS, E->n_wg, out + (size_t)blockIdx.x * SLOTS);
+}
+
+// the frames entry's points: every frame's sub-grid in one count, one scan and one scatter; frame f's image is base + f stride bytes
+struct FrameSet {
+    const unsigned char* depth;
+    size_t depth_stride;
+    const unsigned char* rgb;
+    size_t rgb_stride;
+    size_t n_sub, n_all; // sub-grid pixels of one frame, of all
+};
+__global__ __launch_bounds__(256) void k_register_depth_count_batch(FrameSet F, int is_u16, float depth_scale, SubGrid G, unsigned* __restrict__ count) {
+    const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (k >= F.n_all) return;
+    const size_t f = k / F.n_sub;
+    count[k] = reg_pixel_kept(F.depth + f * F.depth_stride, is_u16, depth_scale, G, k - f * F.n_sub);
+}
+template <bool RGB>
+__global__ __launch_bounds__(256) void k_register_depth_scatter_batch(FrameSet F, int is_u16, op_camera cam, SubGrid G, const unsigned* __restrict__ start,
+                                                                      float* __restrict__ xyz, float* __restrict__ intensity) {
+    const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (k >= F.n_all) return;
+    const size_t f = k / F.n_sub;
+    reg_pixel_scatter<RGB>(F.depth + f * F.depth_stride, is_u16, cam, G, k - f * F.n_sub, start + k, xyz, RGB ? F.rgb + f * F.rgb_stride : nullptr, intensity);
+}
+// where each frame's points begin, and after the last one the total
+__global__ __launch_bounds__(256) void k_register_frame_starts(const unsigned* __restrict__ count, const unsigned* __restrict__ start, size_t n_sub, size_t n_frames,
+                                                               unsigned* __restrict__ out) {
+    const size_t f = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (f < n_frames) out[f] = start[f * n_sub];
+    else if (f == n_frames) out[f] = start[n_frames * n_sub - 1] + count[n_frames * n_sub - 1];
 }
 
 // ---- host side
@@ -496,69 +456,110 @@ op_volume_register_color_params reg_color_defaults(const op_volume* v) {
     return p;
 }
 
-// the Gauss-Newton loop over points (and, with color_scale > 0, intensities) that are on the device; color_scale == 0: the geometric loop;
-// all-zero options: the plain system; d_offset: the points' target values (the OFFSET instantiations)
-int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
-             float max_color_residual, const op_volume_register_options& options, op_volume_register_robust_result* robust, const float* d_offset = nullptr) {
-    op_volume_register_color_result* out = &robust->color;
-    RegRun R(v);
-    OP_TRY(R.open_robust(d_xyz, d_intensity, n, P.max_distance, color_scale, max_color_residual, options, d_offset));
+// The Gauss-Newton loop of ONE cloud as a state machine: while wants_evaluation(), the caller evaluates the system at T and hands it to take().
+// reg_loop drives it with one cloud's RegRun, the batch entries drive one per cloud with a launch per round: the solve, the update, the stop
+// rules and the result are this one copy.  A cloud that stopped after a step gets ONE more evaluation (the system at the pose that is
+// returned); one that stopped on an evaluation that is current gets none.
+struct RegLoopState {
+    op_volume_register_params P{};
     op_volume_register_result res{};
     float T[16];
-    for (int k = 0; k < 16; ++k) T[k] = init_T[k];
     double sums[31], first_sums[31];
     uint64_t counts[7], first_counts[7];
     bool have_first = false, current = false; // current: sums / counts are the system at T
-    res.status = OP_REGISTER_MAX_ITERATIONS;
-    const uint64_t min_points = P.min_points > 0 ? (uint64_t)P.min_points : 0;
-    const double min_step2 = (double)P.min_step * (double)P.min_step;
-    for (int it = 0; it < P.max_iterations; ++it) {
-        OP_TRY(R.eval_robust(T, nullptr, sums, counts));
+    bool closing = false, done = false;       // closing: the next evaluation is the last one
+    int it = 0;
+    uint32_t evaluations = 0;
+    uint64_t min_points = 0;
+    double min_step2 = 0.0;
+
+    void start(const float init_T[16], const op_volume_register_params& params) {
+        P = params;
+        for (int k = 0; k < 16; ++k) T[k] = init_T[k];
+        for (int k = 0; k < 31; ++k) sums[k] = first_sums[k] = 0.0;
+        for (int k = 0; k < 7; ++k) counts[k] = first_counts[k] = 0;
+        res.status = OP_REGISTER_MAX_ITERATIONS;
+        min_points = P.min_points > 0 ? (uint64_t)P.min_points : 0;
+        min_step2 = (double)P.min_step * (double)P.min_step;
+        closing = !(P.max_iterations > 0);
+    }
+    bool wants_evaluation() const { return !done; }
+    int take(const double s[31], const uint64_t c[7]) { // the system at T
+        for (int k = 0; k < 31; ++k) sums[k] = s[k];
+        for (int k = 0; k < 7; ++k) counts[k] = c[k];
+        ++evaluations;
+        if (closing) { done = true; return OP_OK; }
         current = true;
         if (!have_first) {
             have_first = true;
             for (int k = 0; k < 31; ++k) first_sums[k] = sums[k];
             for (int k = 0; k < 7; ++k) first_counts[k] = counts[k];
         }
-        if (counts[0] < min_points) { res.status = OP_REGISTER_TOO_FEW_POINTS; break; }
-        double JTJ[36], JTr[6];
-        int k = 0;
-        for (int a = 0; a < 6; ++a)
-            for (int b = a; b < 6; ++b) { JTJ[6 * a + b] = sums[k]; JTJ[6 * b + a] = sums[k]; ++k; }
-        for (int a = 0; a < 6; ++a) JTr[a] = sums[21 + a];
-        float x[6];
-        OP_TRY(op_ldlt_solve6(JTJ, JTr, x));
-        double ss = 0.0;
-        bool finite = true;
-        for (int a = 0; a < 6; ++a) { finite = finite && std::isfinite(x[a]); ss += (double)x[a] * (double)x[a]; }
-        if (!finite) { res.status = OP_REGISTER_SINGULAR; break; }
-        float E[16], N[16];
-        OP_TRY(op_se3_exp(x, E));
-        reg_mul4(E, T, N);
-        for (int a = 0; a < 16; ++a) T[a] = N[a];
-        current = false;
-        ++res.iterations;
-        res.last_step = std::sqrt(ss);
-        if (ss < min_step2) { res.status = OP_REGISTER_CONVERGED; break; }
+        bool stop = true;
+        do {
+            if (counts[0] < min_points) { res.status = OP_REGISTER_TOO_FEW_POINTS; break; }
+            double JTJ[36], JTr[6];
+            int k = 0;
+            for (int a = 0; a < 6; ++a)
+                for (int b = a; b < 6; ++b) { JTJ[6 * a + b] = sums[k]; JTJ[6 * b + a] = sums[k]; ++k; }
+            for (int a = 0; a < 6; ++a) JTr[a] = sums[21 + a];
+            float x[6];
+            OP_TRY(op_ldlt_solve6(JTJ, JTr, x));
+            double ss = 0.0;
+            bool finite = true;
+            for (int a = 0; a < 6; ++a) { finite = finite && std::isfinite(x[a]); ss += (double)x[a] * (double)x[a]; }
+            if (!finite) { res.status = OP_REGISTER_SINGULAR; break; }
+            float E[16], N[16];
+            OP_TRY(op_se3_exp(x, E));
+            reg_mul4(E, T, N);
+            for (int a = 0; a < 16; ++a) T[a] = N[a];
+            current = false;
+            ++res.iterations;
+            res.last_step = std::sqrt(ss);
+            if (ss < min_step2) { res.status = OP_REGISTER_CONVERGED; break; }
+            stop = false;
+        } while (false);
+        ++it;
+        if (stop || it >= P.max_iterations) { if (current) done = true; else closing = true; }
+        return OP_OK;
     }
-    if (!current) OP_TRY(R.eval_robust(T, nullptr, sums, counts)); // the system at the pose that is returned
-    if (!have_first) { // max_iterations == 0
-        for (int k = 0; k < 31; ++k) first_sums[k] = sums[k];
-        for (int k = 0; k < 7; ++k) first_counts[k] = counts[k];
-        if (counts[0] < min_points) res.status = OP_REGISTER_TOO_FEW_POINTS;
+    void finish(op_volume_register_robust_result* robust) {
+        op_volume_register_color_result* out = &robust->color;
+        if (!have_first) { // max_iterations == 0
+            for (int k = 0; k < 31; ++k) first_sums[k] = sums[k];
+            for (int k = 0; k < 7; ++k) first_counts[k] = counts[k];
+            if (counts[0] < min_points) res.status = OP_REGISTER_TOO_FEW_POINTS;
+        }
+        for (int k = 0; k < 16; ++k) res.T[k] = T[k];
+        res.used = counts[0]; res.invalid = counts[1]; res.no_gradient = counts[2]; res.too_far = counts[3];
+        res.first_used = first_counts[0];
+        res.rmse = reg_rmse(sums[29], counts[0]); // the geometric sum of s^2 (sums[27] holds the colour term too)
+        res.first_rmse = reg_rmse(first_sums[29], first_counts[0]);
+        out->base = res;
+        out->colored = counts[4]; out->first_colored = first_counts[4];
+        out->rmse_color = reg_rmse(sums[28], counts[4]);
+        out->first_rmse_color = reg_rmse(first_sums[28], first_counts[4]);
+        robust->downweighted = counts[5]; robust->color_downweighted = counts[6]; robust->first_downweighted = first_counts[5];
+        robust->rmse_residual = reg_rmse(sums[30], counts[0]);
+        robust->first_rmse_residual = reg_rmse(first_sums[30], first_counts[0]);
     }
-    for (int k = 0; k < 16; ++k) res.T[k] = T[k];
-    res.used = counts[0]; res.invalid = counts[1]; res.no_gradient = counts[2]; res.too_far = counts[3];
-    res.first_used = first_counts[0];
-    res.rmse = reg_rmse(sums[29], counts[0]); // the geometric sum of s^2 (sums[27] holds the colour term too)
-    res.first_rmse = reg_rmse(first_sums[29], first_counts[0]);
-    out->base = res;
-    out->colored = counts[4]; out->first_colored = first_counts[4];
-    out->rmse_color = reg_rmse(sums[28], counts[4]);
-    out->first_rmse_color = reg_rmse(first_sums[28], first_counts[4]);
-    robust->downweighted = counts[5]; robust->color_downweighted = counts[6]; robust->first_downweighted = first_counts[5];
-    robust->rmse_residual = reg_rmse(sums[30], counts[0]);
-    robust->first_rmse_residual = reg_rmse(first_sums[30], first_counts[0]);
+};
+
+// the Gauss-Newton loop over points (and, with color_scale > 0, intensities) that are on the device; color_scale == 0: the geometric loop;
+// all-zero options: the plain system; d_offset: the points' target values (the OFFSET instantiations)
+int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
+             float max_color_residual, const op_volume_register_options& options, op_volume_register_robust_result* robust, const float* d_offset = nullptr) {
+    RegRun R(v);
+    OP_TRY(R.open_robust(d_xyz, d_intensity, n, P.max_distance, color_scale, max_color_residual, options, d_offset));
+    RegLoopState S;
+    S.start(init_T, P);
+    double sums[31];
+    uint64_t counts[7];
+    while (S.wants_evaluation()) {
+        OP_TRY(R.eval_robust(S.T, nullptr, sums, counts));
+        OP_TRY(S.take(sums, counts));
+    }
+    S.finish(robust);
     return OP_OK;
 }
 int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
@@ -687,6 +688,150 @@ int reg_points_entry(const char* who, op_volume* v, const float* xyz, const floa
     if (offset) OP_TRY(up.input(offset, n, mem, &d_off));
     return reg_loop(v, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual,
                     options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, result, d_off);
+}
+
+// ---- the batch entries
+// one call's device state for many clouds: the points are on the device; the partial rows of every cloud, the round table and the folded rows
+// are allocated once, in the call's Scope
+struct RegBatch {
+    op_volume* v;
+    op::Scope& tmp;
+    RegBatchArgs B{};
+    RegOffset K{};
+    bool color = false, robust = false;
+    int slots = kRegSlots;
+    std::vector<unsigned> n_wg; // per cloud: RegRun::open's grid
+    const uint64_t* starts = nullptr;
+    RegBatchEntry *h_table = nullptr, *d_table = nullptr;
+    double *d_out = nullptr, *h_out = nullptr;
+    uint32_t launches = 0;
+
+    RegBatch(op_volume* vol, op::Scope& scope) : v(vol), tmp(scope) {}
+    int open(const float* d_xyz, const float* d_intensity, const float* d_offset, const uint64_t* cloud_starts, size_t n_clouds, float max_distance, float color_scale,
+             float max_color_residual, const op_volume_register_options& O) {
+        starts = cloud_starts;
+        B.xyz = d_xyz; B.W.res = v->res; B.W.inv_res = 1.0f / v->res; B.max_distance = max_distance;
+        K.intensity = d_intensity; K.color_scale = color_scale; K.max_color_residual = max_color_residual;
+        K.linearization = O.linearization; K.huber = O.huber; K.huber_color = O.huber_color;
+        K.offset = d_offset;
+        color = color_scale > 0.0f; // RegRun::color() and robust()
+        robust = d_offset || O.linearization != OP_REGISTER_LIN_NORMAL || O.huber > 0.0f || (color && O.huber_color > 0.0f);
+        slots = robust ? kRegSlotsR : color ? kRegSlotsC : kRegSlots;
+        n_wg.resize(n_clouds);
+        size_t rows = 0, with_rows = 0;
+        for (size_t c = 0; c < n_clouds; ++c) {
+            const uint64_t n = starts[c + 1] - starts[c];
+            n_wg[c] = (unsigned)std::min<uint64_t>((n + kRegWg - 1) / kRegWg, kRegMaxGrid);
+            rows += n_wg[c];
+            with_rows += n_wg[c] ? 1 : 0;
+        }
+        if (rows > 0x7fffffffu) return fail(OP_ERR_INVALID, "op_volume_register_batch: %zu workgroups in one round", rows);
+        if (!with_rows) return OP_OK;
+        OP_TRY(tmp.alloc(&B.partial, rows * (size_t)slots));
+        OP_TRY(tmp.alloc(&d_table, with_rows));
+        OP_TRY(tmp.pinned(&h_table, with_rows));
+        OP_TRY(tmp.alloc(&d_out, with_rows * (size_t)slots));
+        OP_TRY(tmp.pinned(&h_out, with_rows * (size_t)slots));
+        return OP_OK;
+    }
+    // a folded row of the instantiation family as RegRun::eval / eval_color / eval_robust hand it on
+    void unpack(const double* r, double sums[31], uint64_t counts[7]) const {
+        for (int k = 0; k < 28; ++k) sums[k] = r[k];
+        for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k];
+        if (slots == kRegSlots) { sums[28] = 0.0; sums[29] = sums[27]; counts[4] = 0; }
+        else { sums[28] = r[32]; sums[29] = r[33]; counts[4] = (uint64_t)r[34]; }
+        if (slots == kRegSlotsR) { sums[30] = r[35]; counts[5] = (uint64_t)r[36]; counts[6] = (uint64_t)r[37]; }
+        else { sums[30] = sums[29]; counts[5] = 0; counts[6] = 0; }
+    }
+    // one round: cloud active[k] at the pose Ts[k]; the systems go to sums + 31 k, counts + 7 k.  One launch, one fold, one copy, one synchronisation;
+    // nothing is launched when no active cloud has a point.
+    int round(const std::vector<size_t>& active, const std::vector<const float*>& Ts, double* sums, uint64_t* counts) {
+        unsigned n_tab = 0, wgs = 0;
+        for (size_t k = 0; k < active.size(); ++k) {
+            const size_t c = active[k];
+            if (!n_wg[c]) continue;
+            RegBatchEntry& E = h_table[n_tab++];
+            E.start = starts[c]; E.n = starts[c + 1] - starts[c];
+            E.first_wg = wgs; E.n_wg = n_wg[c];
+            for (int a = 0; a < 16; ++a) E.T[a] = Ts[k][a];
+            wgs += n_wg[c];
+        }
+        if (n_tab) {
+            OP_HIP(hipMemcpyAsync(d_table, h_table, sizeof(RegBatchEntry) * n_tab, hipMemcpyHostToDevice, v->stream));
+            B.table = d_table; B.n_active = n_tab;
+            const VolView V = v->view();
+            const dim3 g(wgs), b(kRegWg), gf(n_tab), bf(kFoldWg);
+            const RegRobust& KR = K;
+            const RegColor KC{K.intensity, K.color_scale, K.max_color_residual};
+            if (!robust) {
+                if (color) hipLaunchKernelGGL((k_volume_register_batch<true, false, false>), g, b, 0, v->stream, V, B, KC);
+                else hipLaunchKernelGGL((k_volume_register_batch<false, false, false>), g, b, 0, v->stream, V, B, RegColor{nullptr, 0.0f, 0.0f});
+            } else if (K.offset) {
+                if (color) hipLaunchKernelGGL((k_volume_register_batch<true, true, true>), g, b, 0, v->stream, V, B, K);
+                else hipLaunchKernelGGL((k_volume_register_batch<false, true, true>), g, b, 0, v->stream, V, B, K);
+            } else {
+                if (color) hipLaunchKernelGGL((k_volume_register_batch<true, true, false>), g, b, 0, v->stream, V, B, KR);
+                else hipLaunchKernelGGL((k_volume_register_batch<false, true, false>), g, b, 0, v->stream, V, B, KR);
+            }
+            if (slots == kRegSlots) hipLaunchKernelGGL(k_register_fold_batch, gf, bf, 0, v->stream, (const double*)B.partial, (const RegBatchEntry*)d_table, d_out);
+            else if (slots == kRegSlotsC) hipLaunchKernelGGL(k_register_fold_batch_wide<kRegSlotsC>, gf, bf, 0, v->stream, (const double*)B.partial, (const RegBatchEntry*)d_table, d_out);
+            else hipLaunchKernelGGL(k_register_fold_batch_wide<kRegSlotsR>, gf, bf, 0, v->stream, (const double*)B.partial, (const RegBatchEntry*)d_table, d_out);
+            OP_HIP(hipGetLastError());
+            OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * n_tab * (size_t)slots, hipMemcpyDeviceToHost, v->stream));
+            OP_HIP(hipStreamSynchronize(v->stream));
+            launches += 2;
+        }
+        unsigned e = 0;
+        for (size_t k = 0; k < active.size(); ++k) {
+            double* s = sums + 31 * k;
+            uint64_t* c = counts + 7 * k;
+            if (!n_wg[active[k]]) { // no point, no workgroup: RegRun::eval's zeros
+                for (int a = 0; a < 31; ++a) s[a] = 0.0;
+                for (int a = 0; a < 7; ++a) c[a] = 0;
+            } else {
+                unpack(h_out + (size_t)(e++) * slots, s, c);
+            }
+        }
+        return OP_OK;
+    }
+};
+
+const op_volume_register_options kRegNoOptions{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f};
+
+// every cloud's loop, a round at a time: the clouds that want an evaluation share one launch
+int reg_batch_loop(op_volume* v, op::Scope& tmp, const float* d_xyz, const float* d_intensity, const float* d_offset, const uint64_t* starts, size_t n_clouds,
+                   const float* init_T, const op_volume_register_color_params& P, float color_scale, const op_volume_register_options& O,
+                   op_volume_register_robust_result* results, op_volume_register_batch_stats* stats) {
+    RegBatch R(v, tmp);
+    OP_TRY(R.open(d_xyz, d_intensity, d_offset, starts, n_clouds, P.base.max_distance, color_scale, P.max_color_residual, O));
+    std::vector<RegLoopState> S(n_clouds);
+    for (size_t c = 0; c < n_clouds; ++c) S[c].start(init_T + 16 * c, P.base);
+    std::vector<size_t> active;
+    std::vector<const float*> Ts;
+    std::vector<double> sums;
+    std::vector<uint64_t> counts;
+    uint32_t rounds = 0;
+    for (;;) {
+        active.clear(); Ts.clear();
+        for (size_t c = 0; c < n_clouds; ++c)
+            if (S[c].wants_evaluation()) { active.push_back(c); Ts.push_back(S[c].T); }
+        if (active.empty()) break;
+        sums.resize(31 * active.size()); counts.resize(7 * active.size());
+        OP_TRY(R.round(active, Ts, sums.data(), counts.data()));
+        for (size_t k = 0; k < active.size(); ++k) OP_TRY(S[active[k]].take(sums.data() + 31 * k, counts.data() + 7 * k));
+        ++rounds;
+    }
+    uint64_t evaluations = 0;
+    for (size_t c = 0; c < n_clouds; ++c) { S[c].finish(results + c); evaluations += S[c].evaluations; }
+    if (stats) { stats->rounds = rounds; stats->launches = R.launches; stats->evaluations = evaluations; stats->points = starts[n_clouds]; }
+    return OP_OK;
+}
+
+int reg_check_starts(const uint64_t* starts, size_t n_clouds, const char* who) {
+    if (!starts) return fail(OP_ERR_INVALID, "%s: null starts", who);
+    for (size_t c = 0; c < n_clouds; ++c)
+        if (starts[c + 1] < starts[c]) return fail(OP_ERR_INVALID, "%s: starts decrease at cloud %zu", who, c);
+    return OP_OK;
 }
 
 } // namespace
@@ -941,6 +1086,134 @@ int op_volume_register_volume(op_volume* target, op_volume* source, const float 
     OP_TRY(vol_band_select(list, source, sel, SIZE_MAX, &d_xyz, &d_sdf, P.color_scale > 0.0f ? &d_int : nullptr, &n)); // (the source's stream is idle on return)
     result->selected = n;
     return reg_loop(target, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual, O, &result->robust, d_sdf);
+}
+
+// ---- many clouds, many frames
+int op_volume_register_batch_system(op_volume* v, const float* xyz, const float* offset, const float* intensity, const uint64_t* starts, size_t n_clouds, int mem,
+                                    const float* T, float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options,
+                                    double* sums, uint64_t* counts) {
+    const char* who = "op_volume_register_batch_system";
+    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
+    OP_TRY(reg_check_starts(starts, n_clouds, who));
+    const size_t n = (size_t)starts[n_clouds];
+    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
+    if (!T) return fail(OP_ERR_INVALID, "%s: null T", who);
+    if (!sums) return fail(OP_ERR_INVALID, "%s: null sums", who);
+    OP_TRY(reg_check_color_scale(color_scale, who));
+    if (n > 0 && color_scale > 0.0f && !intensity) return fail(OP_ERR_INVALID, "%s: null intensity", who);
+    OP_TRY(reg_check_options(options, who));
+    if (!n_clouds) return OP_OK;
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    op::Scope tmp;
+    tmp.bind(v->stream);
+    const float *d_xyz = nullptr, *d_int = nullptr, *d_off = nullptr;
+    OP_TRY(tmp.input(xyz, 3 * n, mem, &d_xyz));
+    if (color_scale > 0.0f) OP_TRY(tmp.input(intensity, n, mem, &d_int));
+    if (offset && n) OP_TRY(tmp.input(offset, n, mem, &d_off));
+    RegBatch R(v, tmp);
+    OP_TRY(R.open(d_xyz, d_int, d_off, starts, n_clouds, max_distance, color_scale, max_color_residual, options ? *options : kRegNoOptions));
+    std::vector<size_t> active(n_clouds);
+    std::vector<const float*> Ts(n_clouds);
+    for (size_t c = 0; c < n_clouds; ++c) { active[c] = c; Ts[c] = T + 16 * c; }
+    std::vector<uint64_t> cnt(7 * n_clouds);
+    OP_TRY(R.round(active, Ts, sums, cnt.data()));
+    if (counts) for (size_t k = 0; k < cnt.size(); ++k) counts[k] = cnt[k];
+    return OP_OK;
+}
+
+int op_volume_register_batch_points(op_volume* v, const float* xyz, const float* offset, const float* intensity, const uint64_t* starts, size_t n_clouds, int mem,
+                                    const float* init_T, const op_volume_register_color_params* params, const op_volume_register_options* options,
+                                    op_volume_register_robust_result* results, op_volume_register_batch_stats* stats) {
+    const char* who = "op_volume_register_batch_points";
+    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
+    OP_TRY(reg_check_starts(starts, n_clouds, who));
+    const size_t n = (size_t)starts[n_clouds];
+    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
+    if (!init_T) return fail(OP_ERR_INVALID, "%s: null init_T", who);
+    if (!results) return fail(OP_ERR_INVALID, "%s: null results", who);
+    OP_TRY(reg_check_params(params ? &params->base : nullptr, who));
+    if (params) OP_TRY(reg_check_color_scale(params->color_scale, who));
+    if (n > 0 && !intensity && (!params || params->color_scale > 0.0f)) return fail(OP_ERR_INVALID, "%s: null intensity", who);
+    OP_TRY(reg_check_options(options, who));
+    if (!n_clouds) return OP_OK;
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    op::Scope tmp;
+    tmp.bind(v->stream);
+    const float *d_xyz = nullptr, *d_int = nullptr, *d_off = nullptr;
+    OP_TRY(tmp.input(xyz, 3 * n, mem, &d_xyz));
+    if (P.color_scale > 0.0f) OP_TRY(tmp.input(intensity, n, mem, &d_int));
+    if (offset && n) OP_TRY(tmp.input(offset, n, mem, &d_off));
+    return reg_batch_loop(v, tmp, d_xyz, d_int, d_off, starts, n_clouds, init_T, P, P.color_scale, options ? *options : kRegNoOptions, results, stats);
+}
+
+int op_volume_register_batch_frames(op_volume* v, const op_camera* cam, const void* depth, size_t depth_stride_bytes, int depth_fmt, const uint8_t* rgb,
+                                    size_t rgb_stride_bytes, int mem, int pixel_stride, const float* init_poses, size_t n_frames,
+                                    const op_volume_register_color_params* params, const op_volume_register_options* options,
+                                    op_volume_register_robust_result* results, op_volume_register_batch_stats* stats) {
+    const char* who = "op_volume_register_batch_frames";
+    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
+    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "%s: bad depth format %d", who, depth_fmt);
+    if (!depth) return fail(OP_ERR_INVALID, "%s: null depth", who);
+    if (pixel_stride < 1) return fail(OP_ERR_INVALID, "%s: pixel_stride < 1", who);
+    if (!init_poses) return fail(OP_ERR_INVALID, "%s: null init_poses", who);
+    if (!results) return fail(OP_ERR_INVALID, "%s: null results", who);
+    OP_TRY(reg_check_params(params ? &params->base : nullptr, who));
+    if (params) OP_TRY(reg_check_color_scale(params->color_scale, who));
+    OP_TRY(reg_check_options(options, who));
+    const op_camera c = cam ? *cam : v->cam;
+    OP_TRY(check_cam(&c));
+    const size_t npix = (size_t)c.width * c.height, depth_elem = depth_fmt == OP_DEPTH_U16 ? 2 : 4;
+    if (depth_stride_bytes < npix * depth_elem) return fail(OP_ERR_INVALID, "%s: depth stride %zu is smaller than an image (%zu bytes)", who, depth_stride_bytes, npix * depth_elem);
+    if (depth_stride_bytes % depth_elem) return fail(OP_ERR_INVALID, "%s: depth stride %zu is no multiple of a depth value's %zu bytes", who, depth_stride_bytes, depth_elem);
+    if (rgb && rgb_stride_bytes < npix * 3) return fail(OP_ERR_INVALID, "%s: rgb stride %zu is smaller than an image (%zu bytes)", who, rgb_stride_bytes, npix * 3);
+    SubGrid G{c.width, c.height, (c.width + pixel_stride - 1) / pixel_stride, (c.height + pixel_stride - 1) / pixel_stride, pixel_stride};
+    const size_t nsub = (size_t)G.sw * G.sh;
+    if (n_frames && nsub > (size_t)0xffffffffu / n_frames) return fail(OP_ERR_INVALID, "%s: %zu frames of %zu pixels are more than 2^32 - 1 candidates", who, n_frames, nsub);
+    if (!n_frames) return OP_OK;
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    const float color_scale = rgb ? P.color_scale : 0.0f; // no colour images: the geometric registration
+
+    op::Scope tmp;
+    tmp.bind(v->stream);
+    FrameSet F{static_cast<const unsigned char*>(depth), depth_stride_bytes, rgb, rgb ? rgb_stride_bytes : 0, nsub, nsub * n_frames};
+    if (mem == OP_MEM_HOST) { // one upload per plane: the frames and whatever lies between them
+        OP_TRY(tmp.input(static_cast<const unsigned char*>(depth), (n_frames - 1) * depth_stride_bytes + npix * depth_elem, mem, &F.depth));
+        if (rgb) OP_TRY(tmp.input(rgb, (n_frames - 1) * rgb_stride_bytes + npix * 3, mem, &F.rgb));
+    }
+    unsigned *d_count = nullptr, *d_start = nullptr, *d_first = nullptr, *h_first = nullptr;
+    OP_TRY(tmp.alloc(&d_count, F.n_all));
+    OP_TRY(tmp.alloc(&d_start, F.n_all));
+    OP_TRY(tmp.alloc(&d_first, n_frames + 1));
+    OP_TRY(tmp.pinned(&h_first, n_frames + 1));
+    const dim3 g((unsigned)((F.n_all + 255) / 256)), b(256);
+    const int is_u16 = depth_fmt == OP_DEPTH_U16;
+    hipLaunchKernelGGL(k_register_depth_count_batch, g, b, 0, v->stream, F, is_u16, c.depth_scale, G, d_count);
+    OP_HIP(hipGetLastError());
+    OP_TRY(opi::device_exclusive_scan(d_count, F.n_all, d_start, v->stream, nullptr));
+    hipLaunchKernelGGL(k_register_frame_starts, dim3((unsigned)((n_frames + 1 + 255) / 256)), b, 0, v->stream, (const unsigned*)d_count, (const unsigned*)d_start, nsub, n_frames, d_first);
+    OP_HIP(hipGetLastError());
+    OP_HIP(hipMemcpyAsync(h_first, d_first, sizeof(unsigned) * (n_frames + 1), hipMemcpyDeviceToHost, v->stream));
+    OP_HIP(hipStreamSynchronize(v->stream));
+    std::vector<uint64_t> starts(n_frames + 1);
+    for (size_t f = 0; f <= n_frames; ++f) starts[f] = h_first[f];
+    const size_t total = (size_t)starts[n_frames];
+    float *d_xyz = nullptr, *d_int = nullptr; // the call's own: exactly the kept pixels
+    OP_TRY(tmp.alloc(&d_xyz, 3 * total));
+    if (rgb) OP_TRY(tmp.alloc(&d_int, total));
+    if (total) {
+        if (rgb) hipLaunchKernelGGL(k_register_depth_scatter_batch<true>, g, b, 0, v->stream, F, is_u16, c, G, (const unsigned*)d_start, d_xyz, d_int);
+        else hipLaunchKernelGGL(k_register_depth_scatter_batch<false>, g, b, 0, v->stream, F, is_u16, c, G, (const unsigned*)d_start, d_xyz, (float*)nullptr);
+        OP_HIP(hipGetLastError());
+    }
+    return reg_batch_loop(v, tmp, d_xyz, rgb ? d_int : nullptr, nullptr, starts.data(), n_frames, init_poses, P, color_scale, options ? *options : kRegNoOptions, results, stats);
 }
 
 } // extern "C"

@@ -891,6 +891,80 @@ class CubeHandler:
         out["selected"] = int(r.selected)
         return out
 
+    # -- many clouds or frames in one call (op_volume_register_batch_*: every cloud follows the single entries' loop, the clouds of a round share a launch)
+    @staticmethod
+    def _batch_stats(st):
+        return {k: int(getattr(st, k)) for k, _t in L.RegisterBatchStats._fields_}
+
+    @staticmethod
+    def _batch_inputs(points, starts, offset, intensity):
+        pts, o, y, ptr = CubeHandler._offset_inputs(points, offset, intensity)
+        st = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        if len(st) < 1 or int(st[-1]) > len(pts):
+            raise ValueError("starts holds n_clouds + 1 offsets into the points")
+        return pts, o, y, ptr, st, len(st) - 1
+
+    def BatchRegistrationSystem(self, points, starts, offset, intensity, T, max_distance, color_scale=0.0, max_color_residual=0.0, linearization=None,
+                                huber=None, huber_color=None):
+        """OffsetRegistrationSystem of many clouds in one launch (op_volume_register_batch_system): cloud c is points[starts[c]:starts[c + 1]]
+        at its own T[c] -> (sums [n_clouds,31] float64, list of counts dicts), each bit for bit the single call's."""
+        pts, o, y, ptr, st, n = self._batch_inputs(points, starts, offset, intensity)
+        Tm = _f32(T).reshape(n, 16) if n else np.zeros((0, 16), np.float32)
+        opt = self._register_options(linearization, huber, huber_color)
+        sums, counts = np.zeros((n, 31), np.float64), np.zeros((n, 7), np.uint64)
+        L.check(self._lib.op_volume_register_batch_system(self._h, ptr(pts), ptr(o), ptr(y), st.ctypes.data_as(L._u64p), n, L.OP_MEM_HOST, _fp(Tm), float(max_distance),
+                                                          float(color_scale), float(max_color_residual), C.byref(opt),
+                                                          sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(L._u64p)))
+        self._alive = []
+        return sums, [dict(zip(self.ROBUST_COUNT_NAMES, (int(c) for c in row))) for row in counts]
+
+    def RegisterPointsBatch(self, points, starts, offset=None, intensity=None, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
+                            color_scale=None, max_color_residual=None, linearization=None, huber=None, huber_color=None):
+        """RegisterPointsOffset of many clouds in one call (op_volume_register_batch_points): cloud c is points[starts[c]:starts[c + 1]], from
+        init_T[c] ([n_clouds,4,4]; None: identities) -> (list of the result dicts RegisterPointsOffset returns, each bit for bit the single call's;
+        stats dict: rounds, launches, evaluations, points)."""
+        pts, o, y, ptr, st, n = self._batch_inputs(points, starts, offset, intensity)
+        if y is None and color_scale is None:
+            color_scale = 0.0
+        T0 = _f32(np.tile(np.eye(4), (n, 1, 1)) if init_T is None else init_T).reshape(n, 16) if n else np.zeros((0, 16), np.float32)
+        p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
+        opt, res, stats = self._register_options(linearization, huber, huber_color), (L.RegisterRobustResult * max(n, 1))(), L.RegisterBatchStats()
+        L.check(self._lib.op_volume_register_batch_points(self._h, ptr(pts), ptr(o), ptr(y), st.ctypes.data_as(L._u64p), n, L.OP_MEM_HOST, _fp(T0), C.byref(p),
+                                                          C.byref(opt), res, C.byref(stats)))
+        self._alive = []
+        return [self._register_robust_result(res[c]) for c in range(n)], self._batch_stats(stats)
+
+    def RegisterFramesRobust(self, depths, rgbs, init_poses, pixel_stride=1, camera=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
+                             color_scale=None, max_color_residual=None, linearization=None, huber=None, huber_color=None):
+        """RegisterFrameRobust of many frames in one call (op_volume_register_batch_frames).  depths: [n,h,w] float32 or uint16, rgbs: [n,h,w,3]
+        uint8 or None (geometric), both numpy arrays (or lists of images) or both contiguous CUDA torch tensors; init_poses [n,4,4]
+        -> (list of the result dicts RegisterFrameRobust returns, each bit for bit the single call's; stats dict)."""
+        if isinstance(depths, (list, tuple)):
+            depths = np.stack([np.asarray(d) for d in depths]) if len(depths) else np.zeros((0, 1, 1), np.float32)
+        if isinstance(rgbs, (list, tuple)):
+            rgbs = np.stack([np.asarray(c) for c in rgbs]) if len(rgbs) else None
+        n = int(depths.shape[0])
+        if rgbs is not None and int(rgbs.shape[0]) != n:
+            raise ValueError("one colour image per depth image")
+        pd, fmt, mem, k1 = _image_arg(depths, "depth")
+        pr, k2 = None, None
+        if rgbs is not None:
+            pr, _f, mem2, k2 = _image_arg(rgbs, "rgb")
+            if mem != mem2:
+                raise ValueError("depths and rgbs must both be host arrays or both be device tensors")
+        cam = camera if camera is not None else self.camera
+        npx = cam.width * cam.height
+        if n and (int(np.prod(depths.shape[1:])) != npx or (rgbs is not None and int(np.prod(rgbs.shape[1:])) != 3 * npx)):
+            raise ValueError("the images do not have the camera's size")
+        poses = _f32(init_poses).reshape(n, 16) if n else np.zeros((0, 16), np.float32)
+        p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
+        opt, res, stats = self._register_options(linearization, huber, huber_color), (L.RegisterRobustResult * max(n, 1))(), L.RegisterBatchStats()
+        L.check(self._lib.op_volume_register_batch_frames(self._h, C.byref(camera) if camera is not None else None, pd, npx * (2 if fmt == L.OP_DEPTH_U16 else 4), fmt,
+                                                          pr, npx * 3, mem, int(pixel_stride), _fp(poses), n, C.byref(p), C.byref(opt), res, C.byref(stats)))
+        del k1, k2
+        self._alive = []
+        return [self._register_robust_result(res[f]) for f in range(n)], self._batch_stats(stats)
+
     def RaycastStats(self):
         """Measurement hook: what the last Raycast call did (op_volume_raycast_stats)."""
         v = [C.c_uint64(0) for _ in range(4)]
