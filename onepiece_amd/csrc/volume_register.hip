@@ -10,7 +10,10 @@
 // and a trip's reduction (32 fp64 adds and the swaps) is small next to its 56 gathered taps.  Then LDS across the four waves, one row of 32 per
 // workgroup, and k_register_fold adds the rows in index order (32 row lanes, then those in order): fixed for a given n, no floating-point
 // atomics.  32 doubles come back per evaluation.
-// The Gauss-Newton loop runs on the host: op_ldlt_solve6, op_se3_exp, a float32 4x4 product.
+// The Gauss-Newton loop runs on the host: op_ldlt_solve6, op_se3_exp, a float32 4x4 product.  The host side has ONE path behind every entry
+// point: reg_family decides which instantiations a call runs and reg_grid on how many workgroups, reg_launch maps a family to its kernel and
+// fold, reg_unpack turns a folded row of 32, 35 or 38 into the 31 sums and 7 counts every entry hands on; an entry of a narrower family
+// (op_volume_register_system, _color_system, the plain and colour loops) copies out its prefix.
 // The COLOR instantiations (op_volume_register_color_* / _rgbd) take the colour sums of the same seven samples (rc_sample_global<true>): the model
 // intensity m = I(c) at p, its central difference g over the six shifted samples, the row jc = color_scale (g ; p x g) and the residual
 // color_scale (m - y) join the geometric terms of slots 0..27 inside the same reduction.  The three quantities that have no slot of the 32 (the
@@ -29,7 +32,8 @@
 // The BATCH kernel (op_volume_register_batch_*: k_volume_register_batch) is the same body -- volume_register_body.inc, included by both kernels --
 // behind a prologue that finds the workgroup's cloud in the round's table (a wave-uniform binary search, scalar loads) and points A at that cloud's
 // range, pose and first row; k_register_fold_batch folds every active cloud's rows with one workgroup each, in the single fold's order.  The host
-// loop is RegLoopState: reg_loop drives one, the batch entries one per cloud.
+// loop is RegLoopState: reg_loop drives one, the batch entries one per cloud; RegRun and RegBatch take family, grid, dispatch and unpacking from
+// the same four functions.
 // Not built: damping, multi-resolution, re-ordering the points by block.
 #include "volume_core.hpp"
 #include "trilinear_sample.hpp"
@@ -293,130 +297,144 @@ __global__ __launch_bounds__(256) void k_register_frame_starts(const unsigned* _
 }
 
 // ---- host side
+const op_volume_register_options kRegNoOptions{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f};
+
+// Which instantiations a call runs.  Decided here and nowhere else: RegRun and RegBatch both take theirs from reg_family and their grids from
+// reg_grid, so a batch cloud's kernel, workgroups and fold are the single entry's.
+struct RegFamily {
+    bool color = false, robust = false, offset = false;
+    int slots() const { return robust ? kRegSlotsR : color ? kRegSlotsC : kRegSlots; }
+    int row_width() const { return color ? 16 : 8; } // of the rows the ROWS instantiations write
+};
+// (d_offset: n target values on the device, or NULL; n: the call's points)
+inline RegFamily reg_family(float color_scale, const op_volume_register_options& O, const float* d_offset, size_t n) {
+    RegFamily F;
+    F.color = color_scale > 0.0f;
+    F.offset = d_offset && n;
+    F.robust = F.offset || O.linearization != OP_REGISTER_LIN_NORMAL || O.huber > 0.0f || (F.color && O.huber_color > 0.0f);
+    return F;
+}
+inline unsigned reg_grid(size_t n) { return (unsigned)std::min<size_t>((n + kRegWg - 1) / kRegWg, kRegMaxGrid); }
+
+// The one place a family becomes an instantiation, and its fold: plain and colour take a RegColor (plain a zeroed one: the colour planes are
+// never read), robust a RegRobust, offset a RegOffset; rows of 32, 35 or 38.  ARGS is RegArgs (one cloud on `wgs` workgroups, the ROWS
+// instantiation when A.rows is set, one fold workgroup) or RegBatchArgs (a round's table, `folds` clouds).
+template <class ARGS>
+void reg_launch(const RegFamily& F, const VolView& V, const ARGS& A, const RegOffset& K, unsigned wgs, unsigned folds, double* d_out, hipStream_t stream) {
+    constexpr bool kSingle = std::is_same<ARGS, RegArgs>::value;
+    const dim3 g(wgs), b(kRegWg), gf(folds), bf(kFoldWg);
+    auto launch = [&](auto color, auto robust, auto offset, const auto& extra) {
+        constexpr bool C = decltype(color)::value, R = decltype(robust)::value, O = decltype(offset)::value;
+        if constexpr (kSingle) {
+            if (A.rows) hipLaunchKernelGGL((k_volume_register<true, C, R, O>), g, b, 0, stream, V, A, extra);
+            else hipLaunchKernelGGL((k_volume_register<false, C, R, O>), g, b, 0, stream, V, A, extra);
+        } else {
+            hipLaunchKernelGGL((k_volume_register_batch<C, R, O>), g, b, 0, stream, V, A, extra);
+        }
+    };
+    const std::true_type yes{};
+    const std::false_type no{};
+    const RegRobust& KR = K;
+    // (The compiler emits the instantiations in the order of these calls.  It is the order the code object has always listed them in -- the
+    // batch kernels' colour before plain, the reason for the two arms below -- so that a change to the host side leaves the code, the kernel
+    // descriptors and the metadata of the unit's code object the same bytes, every kernel at the address it had: DESIGN.md section 3.9.)
+    if (!F.robust) {
+        const RegColor KC = F.color ? RegColor{K.intensity, K.color_scale, K.max_color_residual} : RegColor{nullptr, 0.0f, 0.0f};
+        if constexpr (kSingle) { if (!F.color) launch(no, no, no, KC); else launch(yes, no, no, KC); }
+        else { if (F.color) launch(yes, no, no, KC); else launch(no, no, no, KC); }
+    } else if (F.offset) {
+        if (F.color) launch(yes, yes, yes, K); else launch(no, yes, yes, K);
+    } else {
+        if (F.color) launch(yes, yes, no, KR); else launch(no, yes, no, KR);
+    }
+    const double* partial = A.partial;
+    if constexpr (kSingle) {
+        if (!F.color && !F.robust) hipLaunchKernelGGL(k_register_fold, gf, bf, 0, stream, partial, wgs, d_out);
+        else if (!F.robust) hipLaunchKernelGGL(k_register_fold_color, gf, bf, 0, stream, partial, wgs, d_out);
+        else hipLaunchKernelGGL(k_register_fold_robust, gf, bf, 0, stream, partial, wgs, d_out);
+    } else {
+        if (!F.color && !F.robust) hipLaunchKernelGGL(k_register_fold_batch, gf, bf, 0, stream, partial, A.table, d_out);
+        else if (!F.robust) hipLaunchKernelGGL(k_register_fold_batch_wide<kRegSlotsC>, gf, bf, 0, stream, partial, A.table, d_out);
+        else hipLaunchKernelGGL(k_register_fold_batch_wide<kRegSlotsR>, gf, bf, 0, stream, partial, A.table, d_out);
+    }
+}
+
+// A folded row of `slots` doubles as every entry hands it on: 31 sums ([28] rc rc, [29] s s alone, [30] r r unweighted) and 7 counts; what a
+// narrower family has no slot for is what the wider one computes when the colour term or the options are off.  r == NULL: no point, zeros.
+void reg_unpack(int slots, const double* r, double sums[31], uint64_t counts[7]) {
+    if (!r) {
+        for (int k = 0; k < 31; ++k) sums[k] = 0.0;
+        for (int k = 0; k < 7; ++k) counts[k] = 0;
+        return;
+    }
+    for (int k = 0; k < 28; ++k) sums[k] = r[k];
+    for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k]; // whole numbers below 2^53: exact in any order
+    if (slots == kRegSlots) { sums[28] = 0.0; sums[29] = sums[27]; counts[4] = 0; }
+    else { sums[28] = r[32]; sums[29] = r[33]; counts[4] = (uint64_t)r[34]; }
+    if (slots == kRegSlotsR) { sums[30] = r[35]; counts[5] = (uint64_t)r[36]; counts[6] = (uint64_t)r[37]; }
+    else { sums[30] = sums[29]; counts[5] = 0; counts[6] = 0; }
+}
+
 // one call's device state: the points are on the device, the partial rows and the folded row allocated once
 struct RegRun {
     op_volume* v;
     op::Scope tmp; // (everything runs on the volume's stream)
+    RegFamily F;
     RegArgs A{};
+    RegOffset K{};
     unsigned grid = 0;
     double *d_out = nullptr, *h_out = nullptr;
 
-    RegColor K{nullptr, 0.0f, 0.0f}; // color_scale > 0: the COLOR instantiations
-
-    op_volume_register_options O{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}; // anything else: the ROBUST instantiations
-    const float* offset = nullptr; // n target values on the device: the OFFSET instantiations (of the ROBUST ones, whatever the options)
-
     explicit RegRun(op_volume* vol) : v(vol) { tmp.bind(v->stream); }
-    bool color() const { return K.color_scale > 0.0f; }
-    bool robust() const { return offset || O.linearization != OP_REGISTER_LIN_NORMAL || O.huber > 0.0f || (color() && O.huber_color > 0.0f); }
-    int open(const float* d_xyz, size_t n, float max_distance) {
+    // color_scale == 0: the geometric system; all-zero options: the plain one; d_offset: the points' target values
+    int open(const float* d_xyz, const float* d_intensity, const float* d_offset, size_t n, float max_distance, float color_scale, float max_color_residual,
+             const op_volume_register_options& O) {
+        F = reg_family(color_scale, O, d_offset, n);
         A.xyz = d_xyz; A.n = n; A.W.res = v->res; A.W.inv_res = 1.0f / v->res; A.max_distance = max_distance;
-        grid = (unsigned)std::min<size_t>((n + kRegWg - 1) / kRegWg, kRegMaxGrid);
-        if (!grid) return OP_OK;
-        const size_t slots = robust() ? kRegSlotsR : color() ? kRegSlotsC : kRegSlots;
-        OP_TRY(tmp.alloc(&A.partial, (size_t)grid * slots));
-        OP_TRY(tmp.alloc(&d_out, slots));
-        OP_TRY(tmp.pinned(&h_out, slots));
-        return OP_OK;
-    }
-    int open_color(const float* d_xyz, const float* d_intensity, size_t n, float max_distance, float color_scale, float max_color_residual) {
         K.intensity = d_intensity; K.color_scale = color_scale; K.max_color_residual = max_color_residual;
-        return open(d_xyz, n, max_distance);
-    }
-    // the system at T: 28 sums and 4 counts (d_rows: n x 8 on the device, or NULL)
-    int eval(const float T[16], float* d_rows, double sums[28], uint64_t counts[4]) {
-        for (int k = 0; k < 28; ++k) sums[k] = 0.0;
-        for (int k = 0; k < 4; ++k) counts[k] = 0;
+        K.linearization = O.linearization; K.huber = O.huber; K.huber_color = O.huber_color;
+        K.offset = d_offset;
+        grid = reg_grid(n);
         if (!grid) return OP_OK;
-        for (int k = 0; k < 16; ++k) A.T[k] = T[k];
-        A.rows = d_rows;
-        const VolView V = v->view();
-        if (d_rows) hipLaunchKernelGGL((k_volume_register<true, false>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, RegColor{nullptr, 0.0f, 0.0f});
-        else hipLaunchKernelGGL((k_volume_register<false, false>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, RegColor{nullptr, 0.0f, 0.0f});
-        hipLaunchKernelGGL(k_register_fold, dim3(1), dim3(kFoldWg), 0, v->stream, (const double*)A.partial, grid, d_out);
-        OP_HIP(hipGetLastError());
-        OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * kRegSlots, hipMemcpyDeviceToHost, v->stream));
-        OP_HIP(hipStreamSynchronize(v->stream));
-        const double* r = h_out;
-        for (int k = 0; k < 28; ++k) sums[k] = r[k];
-        for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k]; // whole numbers below 2^53: exact in any order
+        OP_TRY(tmp.alloc(&A.partial, (size_t)grid * F.slots()));
+        OP_TRY(tmp.alloc(&d_out, (size_t)F.slots()));
+        OP_TRY(tmp.pinned(&h_out, (size_t)F.slots()));
         return OP_OK;
     }
-    // the coloured system at T: 30 sums ([28] rc rc, [29] s s alone) and 5 counts (d_rows: n x 16).  color_scale == 0 IS the geometric evaluation
-    // (d_rows must be NULL then: the system entry widens the geometric rows itself).
-    int eval_color(const float T[16], float* d_rows, double sums[30], uint64_t counts[5]) {
-        if (!color()) {
-            OP_TRY(eval(T, nullptr, sums, counts));
-            sums[28] = 0.0; sums[29] = sums[27]; counts[4] = 0;
-            return OP_OK;
-        }
-        for (int k = 0; k < 30; ++k) sums[k] = 0.0;
-        for (int k = 0; k < 5; ++k) counts[k] = 0;
+    // the system at T (d_rows: n x F.row_width() on the device, or NULL); no point: zeros
+    int eval(const float T[16], float* d_rows, double sums[31], uint64_t counts[7]) {
+        reg_unpack(F.slots(), nullptr, sums, counts);
         if (!grid) return OP_OK;
         for (int k = 0; k < 16; ++k) A.T[k] = T[k];
         A.rows = d_rows;
-        const VolView V = v->view();
-        if (d_rows) hipLaunchKernelGGL((k_volume_register<true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, K);
-        else hipLaunchKernelGGL((k_volume_register<false, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, K);
-        hipLaunchKernelGGL(k_register_fold_color, dim3(1), dim3(kFoldWg), 0, v->stream, (const double*)A.partial, grid, d_out);
+        reg_launch(F, v->view(), A, K, grid, 1, d_out, v->stream);
         OP_HIP(hipGetLastError());
-        OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * kRegSlotsC, hipMemcpyDeviceToHost, v->stream));
+        OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * F.slots(), hipMemcpyDeviceToHost, v->stream));
         OP_HIP(hipStreamSynchronize(v->stream));
-        const double* r = h_out;
-        for (int k = 0; k < 28; ++k) sums[k] = r[k];
-        sums[28] = r[32]; sums[29] = r[33];
-        for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k];
-        counts[4] = (uint64_t)r[34];
+        reg_unpack(F.slots(), h_out, sums, counts);
         return OP_OK;
     }
-    int open_robust(const float* d_xyz, const float* d_intensity, size_t n, float max_distance, float color_scale, float max_color_residual,
-                    const op_volume_register_options& options, const float* d_offset = nullptr) {
-        O = options;
-        offset = n ? d_offset : nullptr;
-        return open_color(d_xyz, d_intensity, n, max_distance, color_scale, max_color_residual);
+};
+
+// The rows of a one-pass entry on their way to the caller: the kernel writes rows of `kernel_w` floats, the entry promises rows of `entry_w` in
+// the caller's `mem`.  A device buffer of the kernel's width is written in place; anything else goes through a temporary of the kernel's width.
+// The only place that widens (rows of 8 become the first halves of rows of 16, the second halves zero).
+struct RegRows {
+    float *out = nullptr, *d = nullptr;
+    size_t n = 0;
+    int mem = OP_MEM_HOST, kernel_w = 8, entry_w = 8;
+    int open(op::Scope& tmp, float* rows, size_t n_rows, int rows_mem, int kernel_width, int entry_width) {
+        out = n_rows ? rows : nullptr; n = n_rows; mem = rows_mem; kernel_w = kernel_width; entry_w = entry_width;
+        if (!out) return OP_OK;
+        if (mem == OP_MEM_DEVICE && kernel_w == entry_w) { d = out; return OP_OK; }
+        return tmp.alloc(&d, (size_t)kernel_w * n);
     }
-    // the system under the options at T: 31 sums ([30] r r, unweighted) and 7 counts (d_rows: n x 16 with the colour term, n x 8 without).
-    // All-zero options ARE the evaluation above (d_rows must be NULL then without the colour term, as there).
-    int eval_robust(const float T[16], float* d_rows, double sums[31], uint64_t counts[7]) {
-        if (!robust()) {
-            OP_TRY(eval_color(T, d_rows, sums, counts));
-            sums[30] = sums[29]; counts[5] = 0; counts[6] = 0;
-            return OP_OK;
-        }
-        for (int k = 0; k < 31; ++k) sums[k] = 0.0;
-        for (int k = 0; k < 7; ++k) counts[k] = 0;
-        if (!grid) return OP_OK;
-        for (int k = 0; k < 16; ++k) A.T[k] = T[k];
-        A.rows = d_rows;
-        const VolView V = v->view();
-        const RegRobust KR{K.intensity, K.color_scale, K.max_color_residual, O.linearization, O.huber, O.huber_color};
-        if (offset) {
-            RegOffset KO;
-            static_cast<RegRobust&>(KO) = KR;
-            KO.offset = offset;
-            if (color()) {
-                if (d_rows) hipLaunchKernelGGL((k_volume_register<true, true, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KO);
-                else hipLaunchKernelGGL((k_volume_register<false, true, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KO);
-            } else {
-                if (d_rows) hipLaunchKernelGGL((k_volume_register<true, false, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KO);
-                else hipLaunchKernelGGL((k_volume_register<false, false, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KO);
-            }
-        } else if (color()) {
-            if (d_rows) hipLaunchKernelGGL((k_volume_register<true, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
-            else hipLaunchKernelGGL((k_volume_register<false, true, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
-        } else {
-            if (d_rows) hipLaunchKernelGGL((k_volume_register<true, false, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
-            else hipLaunchKernelGGL((k_volume_register<false, false, true>), dim3(grid), dim3(kRegWg), 0, v->stream, V, A, KR);
-        }
-        hipLaunchKernelGGL(k_register_fold_robust, dim3(1), dim3(kFoldWg), 0, v->stream, (const double*)A.partial, grid, d_out);
-        OP_HIP(hipGetLastError());
-        OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * kRegSlotsR, hipMemcpyDeviceToHost, v->stream));
-        OP_HIP(hipStreamSynchronize(v->stream));
-        const double* r = h_out;
-        for (int k = 0; k < 28; ++k) sums[k] = r[k];
-        sums[28] = r[32]; sums[29] = r[33]; sums[30] = r[35];
-        for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k];
-        counts[4] = (uint64_t)r[34]; counts[5] = (uint64_t)r[36]; counts[6] = (uint64_t)r[37];
+    int deliver() const {
+        if (!out || d == out) return OP_OK;
+        if (kernel_w == entry_w) { OP_HIP(hipMemcpy(out, d, sizeof(float) * kernel_w * n, hipMemcpyDeviceToHost)); return OP_OK; }
+        if (mem == OP_MEM_HOST) std::memset(out, 0, sizeof(float) * entry_w * n);
+        else OP_HIP(hipMemset(out, 0, sizeof(float) * entry_w * n));
+        OP_HIP(hipMemcpy2D(out, sizeof(float) * entry_w, d, sizeof(float) * kernel_w, sizeof(float) * kernel_w, n, mem == OP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
         return OP_OK;
     }
 };
@@ -438,6 +456,17 @@ int reg_check_color_scale(float color_scale, const char* who) {
     if (!(color_scale >= 0.0f) || !std::isfinite(color_scale)) return fail(OP_ERR_INVALID, "%s: color_scale must be finite and >= 0", who);
     return OP_OK;
 }
+int reg_check_options(const op_volume_register_options* o, const char* who) {
+    if (!o) return OP_OK;
+    if (o->linearization < OP_REGISTER_LIN_NORMAL || o->linearization > OP_REGISTER_LIN_METRIC) return fail(OP_ERR_INVALID, "%s: linearization %d", who, o->linearization);
+    if (!(o->huber >= 0.0f) || !std::isfinite(o->huber)) return fail(OP_ERR_INVALID, "%s: huber must be finite and >= 0", who);
+    if (!(o->huber_color >= 0.0f) || !std::isfinite(o->huber_color)) return fail(OP_ERR_INVALID, "%s: huber_color must be finite and >= 0", who);
+    return OP_OK;
+}
+int reg_check_mem(int mem, const char* who) {
+    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
+    return OP_OK;
+}
 
 op_volume_register_params reg_defaults(const op_volume* v) {
     op_volume_register_params p;
@@ -455,6 +484,26 @@ op_volume_register_color_params reg_color_defaults(const op_volume* v) {
     p.max_color_residual = 0.0f; // no gate
     return p;
 }
+
+// The parameters a loop entry was given.  An entry of the first family has no colour part: it is geometric whatever the colour defaults say.
+struct RegParamsArg {
+    const op_volume_register_params* base;        // NULL: reg_defaults
+    const op_volume_register_color_params* color; // NULL where the entry has a colour part: reg_color_defaults
+    bool has_color;
+    RegParamsArg(const op_volume_register_params* p) : base(p), color(nullptr), has_color(false) {}
+    RegParamsArg(const op_volume_register_color_params* p) : base(p ? &p->base : nullptr), color(p), has_color(true) {}
+    int check(const char* who) const {
+        OP_TRY(reg_check_params(base, who));
+        if (color) OP_TRY(reg_check_color_scale(color->color_scale, who));
+        return OP_OK;
+    }
+    bool wants_color() const { return has_color && (!color || color->color_scale > 0.0f); } // (the default color_scale is 1)
+    op_volume_register_color_params resolve(const op_volume* v) const {
+        if (color) return *color;
+        if (has_color) return reg_color_defaults(v);
+        return op_volume_register_color_params{base ? *base : reg_defaults(v), 0.0f, 0.0f};
+    }
+};
 
 // The Gauss-Newton loop of ONE cloud as a state machine: while wants_evaluation(), the caller evaluates the system at T and hands it to take().
 // reg_loop drives it with one cloud's RegRun, the batch entries drive one per cloud with a launch per round: the solve, the update, the stop
@@ -545,41 +594,21 @@ struct RegLoopState {
     }
 };
 
-// the Gauss-Newton loop over points (and, with color_scale > 0, intensities) that are on the device; color_scale == 0: the geometric loop;
-// all-zero options: the plain system; d_offset: the points' target values (the OFFSET instantiations)
-int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
-             float max_color_residual, const op_volume_register_options& options, op_volume_register_robust_result* robust, const float* d_offset = nullptr) {
+// the Gauss-Newton loop over points (and, with color_scale > 0, intensities; with d_offset, target values) that are on the device.  The entries
+// of the narrower families return a prefix of the result: robust.color, robust.color.base.
+int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, const float* d_offset, size_t n, const float init_T[16],
+             const op_volume_register_color_params& P, float color_scale, const op_volume_register_options& options, op_volume_register_robust_result* robust) {
     RegRun R(v);
-    OP_TRY(R.open_robust(d_xyz, d_intensity, n, P.max_distance, color_scale, max_color_residual, options, d_offset));
+    OP_TRY(R.open(d_xyz, d_intensity, d_offset, n, P.base.max_distance, color_scale, P.max_color_residual, options));
     RegLoopState S;
-    S.start(init_T, P);
+    S.start(init_T, P.base);
     double sums[31];
     uint64_t counts[7];
     while (S.wants_evaluation()) {
-        OP_TRY(R.eval_robust(S.T, nullptr, sums, counts));
+        OP_TRY(R.eval(S.T, nullptr, sums, counts));
         OP_TRY(S.take(sums, counts));
     }
     S.finish(robust);
-    return OP_OK;
-}
-int reg_loop(op_volume* v, const float* d_xyz, const float* d_intensity, size_t n, const float init_T[16], const op_volume_register_params& P, float color_scale,
-             float max_color_residual, op_volume_register_color_result* out) {
-    op_volume_register_robust_result r{};
-    OP_TRY(reg_loop(v, d_xyz, d_intensity, n, init_T, P, color_scale, max_color_residual, op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, &r));
-    *out = r.color;
-    return OP_OK;
-}
-int reg_loop(op_volume* v, const float* d_xyz, size_t n, const float init_T[16], const op_volume_register_params& P, op_volume_register_result* out) {
-    op_volume_register_color_result r{};
-    OP_TRY(reg_loop(v, d_xyz, nullptr, n, init_T, P, 0.0f, 0.0f, &r));
-    *out = r.base;
-    return OP_OK;
-}
-int reg_check_options(const op_volume_register_options* o, const char* who) {
-    if (!o) return OP_OK;
-    if (o->linearization < OP_REGISTER_LIN_NORMAL || o->linearization > OP_REGISTER_LIN_METRIC) return fail(OP_ERR_INVALID, "%s: linearization %d", who, o->linearization);
-    if (!(o->huber >= 0.0f) || !std::isfinite(o->huber)) return fail(OP_ERR_INVALID, "%s: huber must be finite and >= 0", who);
-    if (!(o->huber_color >= 0.0f) || !std::isfinite(o->huber_color)) return fail(OP_ERR_INVALID, "%s: huber_color must be finite and >= 0", who);
     return OP_OK;
 }
 
@@ -620,74 +649,112 @@ int reg_back_project(op_volume* v, op::Scope& tmp, const op_camera& c, const voi
     return OP_OK;
 }
 
-// the one-pass entry and the loop entry of the ROBUST instantiations; offset (n floats in `mem`, or NULL): the OFFSET ones (op_volume_register_offset_*)
-int reg_system_entry(const char* who, op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float T[16],
-                     float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
-                     uint64_t counts[7], float* rows) {
+// ---- what the entries share.  Every check names the entry (`who`) and comes before any device use; their order is what a caller with several
+// bad arguments sees.
+// a cloud-taking entry's first checks; starts: the batch entries' n_clouds + 1 offsets (n is then the last of them)
+int reg_check_clouds(const char* who, const op_volume* v, int mem, const uint64_t* starts, size_t n_clouds, bool batch, const float* xyz, size_t* n,
+                     const void* pose, const char* pose_name, const void* out, const char* out_name) {
     if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
-    if (!T) return fail(OP_ERR_INVALID, "%s: null T", who);
-    if (!sums) return fail(OP_ERR_INVALID, "%s: null sums", who);
+    OP_TRY(reg_check_mem(mem, who));
+    if (batch) {
+        if (!starts) return fail(OP_ERR_INVALID, "%s: null starts", who);
+        for (size_t c = 0; c < n_clouds; ++c)
+            if (starts[c + 1] < starts[c]) return fail(OP_ERR_INVALID, "%s: starts decrease at cloud %zu", who, c);
+        *n = (size_t)starts[n_clouds];
+    }
+    if (*n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
+    if (!pose) return fail(OP_ERR_INVALID, "%s: null %s", who, pose_name);
+    if (!out) return fail(OP_ERR_INVALID, "%s: null %s", who, out_name);
+    return OP_OK;
+}
+// a frame-taking entry's checks; rgb_required: a NULL colour image is refused, not taken as "geometric"; c: the camera the frames have
+int reg_check_frames(const char* who, const op_volume* v, const op_camera* cam, const void* depth, int depth_fmt, const uint8_t* rgb, bool rgb_required, int mem,
+                     int pixel_stride, const void* pose, const char* pose_name, const void* out, const char* out_name, const RegParamsArg& params,
+                     const op_volume_register_options* options, op_camera* c) {
+    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
+    OP_TRY(reg_check_mem(mem, who));
+    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "%s: bad depth format %d", who, depth_fmt);
+    if (!depth) return fail(OP_ERR_INVALID, "%s: null depth", who);
+    if (rgb_required && !rgb) return fail(OP_ERR_INVALID, "%s: null rgb", who);
+    if (pixel_stride < 1) return fail(OP_ERR_INVALID, "%s: pixel_stride < 1", who);
+    if (!pose) return fail(OP_ERR_INVALID, "%s: null %s", who, pose_name);
+    if (!out) return fail(OP_ERR_INVALID, "%s: null %s", who, out_name);
+    OP_TRY(params.check(who));
+    OP_TRY(reg_check_options(options, who));
+    *c = cam ? *cam : v->cam;
+    return check_cam(c);
+}
+// the call's points on the device, uploaded once where they are the host's (intensity / offset: only where the call reads them)
+int reg_inputs(op::Scope& tmp, const float* xyz, const float* intensity, bool with_intensity, const float* offset, bool with_offset, size_t n, int mem,
+               const float** d_xyz, const float** d_int, const float** d_off) {
+    OP_TRY(tmp.input(xyz, 3 * n, mem, d_xyz));
+    if (with_intensity) OP_TRY(tmp.input(intensity, n, mem, d_int));
+    if (with_offset) OP_TRY(tmp.input(offset, n, mem, d_off));
+    return OP_OK;
+}
+
+// what a one-pass entry writes: the first `sums` of the 31 sums, the first `counts` of the 7 counts, rows of `row_w` floats
+struct RegExtent { int sums, counts, row_w; };
+constexpr RegExtent kRegPlainExtent{28, 4, 8}, kRegColorExtent{30, 5, 16}, kRegRobustExtent{31, 7, 16};
+
+// the one-pass entries.  offset (n floats in `mem`, or NULL): the OFFSET instantiations; a narrower entry passes the arguments it does not have
+// as 0 / NULL, which the checks for them accept
+int reg_system_entry(const char* who, op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float T[16],
+                     float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, const RegExtent& ext, double* sums,
+                     uint64_t* counts, float* rows) {
+    OP_TRY(reg_check_clouds(who, v, mem, nullptr, 1, false, xyz, &n, T, "T", sums, "sums"));
     OP_TRY(reg_check_color_scale(color_scale, who));
     if (n > 0 && color_scale > 0.0f && !intensity) return fail(OP_ERR_INVALID, "%s: null intensity", who);
     OP_TRY(reg_check_options(options, who));
     OP_VOL(v);
-    OP_TRY(vol_check(v));
+    OP_TRY(vol_check(v)); // every accepted frame is fused, the stream idle
     RegRun R(v);
     const float *d_xyz = nullptr, *d_int = nullptr, *d_off = nullptr;
-    OP_TRY(R.tmp.input(xyz, 3 * n, mem, &d_xyz));
-    if (color_scale > 0.0f) OP_TRY(R.tmp.input(intensity, n, mem, &d_int));
-    if (offset) OP_TRY(R.tmp.input(offset, n, mem, &d_off));
-    OP_TRY(R.open_robust(d_xyz, d_int, n, max_distance, color_scale, max_color_residual,
-                         options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, d_off));
-    const bool want_rows = rows && n;
+    OP_TRY(reg_inputs(R.tmp, xyz, intensity, color_scale > 0.0f, offset, offset != nullptr, n, mem, &d_xyz, &d_int, &d_off)); // (color_scale == 0: the intensities are not read either)
+    OP_TRY(R.open(d_xyz, d_int, d_off, n, max_distance, color_scale, max_color_residual, options ? *options : kRegNoOptions));
+    RegRows W;
+    OP_TRY(W.open(R.tmp, rows, n, mem, R.F.row_width(), ext.row_w));
+    double s[31];
     uint64_t c[7];
-    if (R.color()) {
-        float* d_rows = rows;
-        if (want_rows && mem == OP_MEM_HOST) OP_TRY(R.tmp.alloc(&d_rows, 16 * n));
-        OP_TRY(R.eval_robust(T, want_rows ? d_rows : nullptr, sums, c));
-        if (want_rows && mem == OP_MEM_HOST) OP_HIP(hipMemcpy(rows, d_rows, sizeof(float) * 16 * n, hipMemcpyDeviceToHost));
-    } else { // rows of 8 become the first halves of rows of 16, as op_volume_register_color_system widens them
-        float* d_rows8 = nullptr;
-        if (want_rows) OP_TRY(R.tmp.alloc(&d_rows8, 8 * n));
-        if (R.robust()) OP_TRY(R.eval_robust(T, d_rows8, sums, c));
-        else {
-            OP_TRY(R.eval(T, d_rows8, sums, c));
-            sums[28] = 0.0; sums[29] = sums[27]; sums[30] = sums[27]; c[4] = 0; c[5] = 0; c[6] = 0;
-        }
-        if (want_rows) {
-            if (mem == OP_MEM_HOST) std::memset(rows, 0, sizeof(float) * 16 * n);
-            else OP_HIP(hipMemset(rows, 0, sizeof(float) * 16 * n));
-            OP_HIP(hipMemcpy2D(rows, sizeof(float) * 16, d_rows8, sizeof(float) * 8, sizeof(float) * 8, n, mem == OP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
-        }
-    }
-    if (counts) for (int k = 0; k < 7; ++k) counts[k] = c[k];
+    OP_TRY(R.eval(T, W.d, s, c));
+    OP_TRY(W.deliver());
+    for (int k = 0; k < ext.sums; ++k) sums[k] = s[k];
+    if (counts) for (int k = 0; k < ext.counts; ++k) counts[k] = c[k];
     return OP_OK;
 }
 
+// the loop entries over a cloud; result NULL is refused: a narrower entry passes a local one and copies its prefix out
 int reg_points_entry(const char* who, op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float init_T[16],
-                     const op_volume_register_color_params* params, const op_volume_register_options* options, op_volume_register_robust_result* result) {
-    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
-    if (!init_T) return fail(OP_ERR_INVALID, "%s: null init_T", who);
-    if (!result) return fail(OP_ERR_INVALID, "%s: null result", who);
-    OP_TRY(reg_check_params(params ? &params->base : nullptr, who));
-    if (params) OP_TRY(reg_check_color_scale(params->color_scale, who));
-    if (n > 0 && !intensity && (!params || params->color_scale > 0.0f)) return fail(OP_ERR_INVALID, "%s: null intensity", who);
+                     const RegParamsArg& params, const op_volume_register_options* options, op_volume_register_robust_result* result) {
+    OP_TRY(reg_check_clouds(who, v, mem, nullptr, 1, false, xyz, &n, init_T, "init_T", result, "result"));
+    OP_TRY(params.check(who));
+    if (n > 0 && !intensity && params.wants_color()) return fail(OP_ERR_INVALID, "%s: null intensity", who);
     OP_TRY(reg_check_options(options, who));
     OP_VOL(v);
     OP_TRY(vol_check(v));
-    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    const op_volume_register_color_params P = params.resolve(v);
     op::Scope up;
     up.bind(v->stream);
     const float *d_xyz = nullptr, *d_int = nullptr, *d_off = nullptr;
-    OP_TRY(up.input(xyz, 3 * n, mem, &d_xyz));
-    if (P.color_scale > 0.0f) OP_TRY(up.input(intensity, n, mem, &d_int));
-    if (offset) OP_TRY(up.input(offset, n, mem, &d_off));
-    return reg_loop(v, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual,
-                    options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, result, d_off);
+    OP_TRY(reg_inputs(up, xyz, intensity, P.color_scale > 0.0f, offset, offset != nullptr, n, mem, &d_xyz, &d_int, &d_off)); // uploaded once
+    return reg_loop(v, d_xyz, d_int, d_off, n, init_T, P, P.color_scale, options ? *options : kRegNoOptions, result);
+}
+
+// the loop entries over a depth frame back-projected on the device; no colour image: the geometric registration
+int reg_frame_entry(const char* who, op_volume* v, const op_camera* cam, const void* depth, int depth_fmt, const uint8_t* rgb, bool rgb_required, int mem,
+                    int pixel_stride, const float init_pose[16], const RegParamsArg& params, const op_volume_register_options* options,
+                    op_volume_register_robust_result* result) {
+    op_camera c;
+    OP_TRY(reg_check_frames(who, v, cam, depth, depth_fmt, rgb, rgb_required, mem, pixel_stride, init_pose, "init_pose", result, "result", params, options, &c));
+    OP_VOL(v);
+    OP_TRY(vol_check(v));
+    const op_volume_register_color_params P = params.resolve(v);
+    op::Scope tmp;
+    tmp.bind(v->stream);
+    unsigned total = 0;
+    OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, rgb, mem, pixel_stride, &total));
+    return reg_loop(v, v->reg_pts, rgb ? v->reg_int : nullptr, nullptr, (size_t)total, init_pose, P, rgb ? P.color_scale : 0.0f,
+                    options ? *options : kRegNoOptions, result); // (the loop's kernels follow the scatter on the volume's stream)
 }
 
 // ---- the batch entries
@@ -696,11 +763,10 @@ int reg_points_entry(const char* who, op_volume* v, const float* xyz, const floa
 struct RegBatch {
     op_volume* v;
     op::Scope& tmp;
+    RegFamily F;
     RegBatchArgs B{};
     RegOffset K{};
-    bool color = false, robust = false;
-    int slots = kRegSlots;
-    std::vector<unsigned> n_wg; // per cloud: RegRun::open's grid
+    std::vector<unsigned> n_wg; // per cloud: reg_grid of its points
     const uint64_t* starts = nullptr;
     RegBatchEntry *h_table = nullptr, *d_table = nullptr;
     double *d_out = nullptr, *h_out = nullptr;
@@ -710,38 +776,27 @@ struct RegBatch {
     int open(const float* d_xyz, const float* d_intensity, const float* d_offset, const uint64_t* cloud_starts, size_t n_clouds, float max_distance, float color_scale,
              float max_color_residual, const op_volume_register_options& O) {
         starts = cloud_starts;
+        F = reg_family(color_scale, O, d_offset, (size_t)starts[n_clouds]);
         B.xyz = d_xyz; B.W.res = v->res; B.W.inv_res = 1.0f / v->res; B.max_distance = max_distance;
         K.intensity = d_intensity; K.color_scale = color_scale; K.max_color_residual = max_color_residual;
         K.linearization = O.linearization; K.huber = O.huber; K.huber_color = O.huber_color;
         K.offset = d_offset;
-        color = color_scale > 0.0f; // RegRun::color() and robust()
-        robust = d_offset || O.linearization != OP_REGISTER_LIN_NORMAL || O.huber > 0.0f || (color && O.huber_color > 0.0f);
-        slots = robust ? kRegSlotsR : color ? kRegSlotsC : kRegSlots;
         n_wg.resize(n_clouds);
         size_t rows = 0, with_rows = 0;
         for (size_t c = 0; c < n_clouds; ++c) {
-            const uint64_t n = starts[c + 1] - starts[c];
-            n_wg[c] = (unsigned)std::min<uint64_t>((n + kRegWg - 1) / kRegWg, kRegMaxGrid);
+            n_wg[c] = reg_grid((size_t)(starts[c + 1] - starts[c]));
             rows += n_wg[c];
             with_rows += n_wg[c] ? 1 : 0;
         }
         if (rows > 0x7fffffffu) return fail(OP_ERR_INVALID, "op_volume_register_batch: %zu workgroups in one round", rows);
         if (!with_rows) return OP_OK;
-        OP_TRY(tmp.alloc(&B.partial, rows * (size_t)slots));
+        const size_t slots = (size_t)F.slots();
+        OP_TRY(tmp.alloc(&B.partial, rows * slots));
         OP_TRY(tmp.alloc(&d_table, with_rows));
         OP_TRY(tmp.pinned(&h_table, with_rows));
-        OP_TRY(tmp.alloc(&d_out, with_rows * (size_t)slots));
-        OP_TRY(tmp.pinned(&h_out, with_rows * (size_t)slots));
+        OP_TRY(tmp.alloc(&d_out, with_rows * slots));
+        OP_TRY(tmp.pinned(&h_out, with_rows * slots));
         return OP_OK;
-    }
-    // a folded row of the instantiation family as RegRun::eval / eval_color / eval_robust hand it on
-    void unpack(const double* r, double sums[31], uint64_t counts[7]) const {
-        for (int k = 0; k < 28; ++k) sums[k] = r[k];
-        for (int k = 0; k < 4; ++k) counts[k] = (uint64_t)r[28 + k];
-        if (slots == kRegSlots) { sums[28] = 0.0; sums[29] = sums[27]; counts[4] = 0; }
-        else { sums[28] = r[32]; sums[29] = r[33]; counts[4] = (uint64_t)r[34]; }
-        if (slots == kRegSlotsR) { sums[30] = r[35]; counts[5] = (uint64_t)r[36]; counts[6] = (uint64_t)r[37]; }
-        else { sums[30] = sums[29]; counts[5] = 0; counts[6] = 0; }
     }
     // one round: cloud active[k] at the pose Ts[k]; the systems go to sums + 31 k, counts + 7 k.  One launch, one fold, one copy, one synchronisation;
     // nothing is launched when no active cloud has a point.
@@ -756,47 +811,22 @@ struct RegBatch {
             for (int a = 0; a < 16; ++a) E.T[a] = Ts[k][a];
             wgs += n_wg[c];
         }
+        const int slots = F.slots();
         if (n_tab) {
             OP_HIP(hipMemcpyAsync(d_table, h_table, sizeof(RegBatchEntry) * n_tab, hipMemcpyHostToDevice, v->stream));
             B.table = d_table; B.n_active = n_tab;
-            const VolView V = v->view();
-            const dim3 g(wgs), b(kRegWg), gf(n_tab), bf(kFoldWg);
-            const RegRobust& KR = K;
-            const RegColor KC{K.intensity, K.color_scale, K.max_color_residual};
-            if (!robust) {
-                if (color) hipLaunchKernelGGL((k_volume_register_batch<true, false, false>), g, b, 0, v->stream, V, B, KC);
-                else hipLaunchKernelGGL((k_volume_register_batch<false, false, false>), g, b, 0, v->stream, V, B, RegColor{nullptr, 0.0f, 0.0f});
-            } else if (K.offset) {
-                if (color) hipLaunchKernelGGL((k_volume_register_batch<true, true, true>), g, b, 0, v->stream, V, B, K);
-                else hipLaunchKernelGGL((k_volume_register_batch<false, true, true>), g, b, 0, v->stream, V, B, K);
-            } else {
-                if (color) hipLaunchKernelGGL((k_volume_register_batch<true, true, false>), g, b, 0, v->stream, V, B, KR);
-                else hipLaunchKernelGGL((k_volume_register_batch<false, true, false>), g, b, 0, v->stream, V, B, KR);
-            }
-            if (slots == kRegSlots) hipLaunchKernelGGL(k_register_fold_batch, gf, bf, 0, v->stream, (const double*)B.partial, (const RegBatchEntry*)d_table, d_out);
-            else if (slots == kRegSlotsC) hipLaunchKernelGGL(k_register_fold_batch_wide<kRegSlotsC>, gf, bf, 0, v->stream, (const double*)B.partial, (const RegBatchEntry*)d_table, d_out);
-            else hipLaunchKernelGGL(k_register_fold_batch_wide<kRegSlotsR>, gf, bf, 0, v->stream, (const double*)B.partial, (const RegBatchEntry*)d_table, d_out);
+            reg_launch(F, v->view(), B, K, wgs, n_tab, d_out, v->stream);
             OP_HIP(hipGetLastError());
             OP_HIP(hipMemcpyAsync(h_out, d_out, sizeof(double) * n_tab * (size_t)slots, hipMemcpyDeviceToHost, v->stream));
             OP_HIP(hipStreamSynchronize(v->stream));
             launches += 2;
         }
         unsigned e = 0;
-        for (size_t k = 0; k < active.size(); ++k) {
-            double* s = sums + 31 * k;
-            uint64_t* c = counts + 7 * k;
-            if (!n_wg[active[k]]) { // no point, no workgroup: RegRun::eval's zeros
-                for (int a = 0; a < 31; ++a) s[a] = 0.0;
-                for (int a = 0; a < 7; ++a) c[a] = 0;
-            } else {
-                unpack(h_out + (size_t)(e++) * slots, s, c);
-            }
-        }
+        for (size_t k = 0; k < active.size(); ++k) // (no point, no workgroup: zeros)
+            reg_unpack(slots, n_wg[active[k]] ? h_out + (size_t)(e++) * slots : nullptr, sums + 31 * k, counts + 7 * k);
         return OP_OK;
     }
 };
-
-const op_volume_register_options kRegNoOptions{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f};
 
 // every cloud's loop, a round at a time: the clouds that want an evaluation share one launch
 int reg_batch_loop(op_volume* v, op::Scope& tmp, const float* d_xyz, const float* d_intensity, const float* d_offset, const uint64_t* starts, size_t n_clouds,
@@ -827,13 +857,6 @@ int reg_batch_loop(op_volume* v, op::Scope& tmp, const float* d_xyz, const float
     return OP_OK;
 }
 
-int reg_check_starts(const uint64_t* starts, size_t n_clouds, const char* who) {
-    if (!starts) return fail(OP_ERR_INVALID, "%s: null starts", who);
-    for (size_t c = 0; c < n_clouds; ++c)
-        if (starts[c + 1] < starts[c]) return fail(OP_ERR_INVALID, "%s: starts decrease at cloud %zu", who, c);
-    return OP_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -847,66 +870,23 @@ int op_volume_register_default_params(op_volume* v, op_volume_register_params* p
 
 int op_volume_register_system(op_volume* v, const float* xyz, size_t n, int mem, const float T[16], float max_distance, double sums[28], uint64_t counts[4],
                               float* rows) {
-    // the argument checks need no device
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_system: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_system: bad mem %d", mem);
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_system: null xyz");
-    if (!T) return fail(OP_ERR_INVALID, "op_volume_register_system: null T");
-    if (!sums) return fail(OP_ERR_INVALID, "op_volume_register_system: null sums");
-    OP_VOL(v);
-    OP_TRY(vol_check(v)); // every accepted frame is fused, the stream idle
-    RegRun R(v);
-    const float* d_xyz = nullptr;
-    OP_TRY(R.tmp.input(xyz, 3 * n, mem, &d_xyz));
-    OP_TRY(R.open(d_xyz, n, max_distance));
-    float* d_rows = rows;
-    if (rows && n && mem == OP_MEM_HOST) OP_TRY(R.tmp.alloc(&d_rows, 8 * n));
-    uint64_t c[4];
-    OP_TRY(R.eval(T, n ? d_rows : nullptr, sums, c));
-    if (counts) for (int k = 0; k < 4; ++k) counts[k] = c[k];
-    if (rows && n && mem == OP_MEM_HOST) OP_HIP(hipMemcpy(rows, d_rows, sizeof(float) * 8 * n, hipMemcpyDeviceToHost));
-    return OP_OK;
+    return reg_system_entry("op_volume_register_system", v, xyz, nullptr, nullptr, n, mem, T, max_distance, 0.0f, 0.0f, nullptr, kRegPlainExtent, sums, counts, rows);
 }
 
 int op_volume_register_points(op_volume* v, const float* xyz, size_t n, int mem, const float init_T[16], const op_volume_register_params* params,
                               op_volume_register_result* result) {
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_points: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_points: bad mem %d", mem);
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_points: null xyz");
-    if (!init_T) return fail(OP_ERR_INVALID, "op_volume_register_points: null init_T");
-    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_points: null result");
-    OP_TRY(reg_check_params(params, "op_volume_register_points"));
-    OP_VOL(v);
-    OP_TRY(vol_check(v));
-    const op_volume_register_params P = params ? *params : reg_defaults(v);
-    op::Scope up;
-    up.bind(v->stream);
-    const float* d_xyz = nullptr;
-    OP_TRY(up.input(xyz, 3 * n, mem, &d_xyz)); // uploaded once
-    return reg_loop(v, d_xyz, n, init_T, P, result);
+    op_volume_register_robust_result r{};
+    OP_TRY(reg_points_entry("op_volume_register_points", v, xyz, nullptr, nullptr, n, mem, init_T, params, nullptr, result ? &r : nullptr));
+    *result = r.color.base;
+    return OP_OK;
 }
 
 int op_volume_register_depth(op_volume* v, const op_camera* cam, const void* depth, int depth_fmt, int mem, int pixel_stride, const float init_pose[16],
                              const op_volume_register_params* params, op_volume_register_result* result) {
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_depth: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_depth: bad mem %d", mem);
-    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "op_volume_register_depth: bad depth format %d", depth_fmt);
-    if (!depth) return fail(OP_ERR_INVALID, "op_volume_register_depth: null depth");
-    if (pixel_stride < 1) return fail(OP_ERR_INVALID, "op_volume_register_depth: pixel_stride < 1");
-    if (!init_pose) return fail(OP_ERR_INVALID, "op_volume_register_depth: null init_pose");
-    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_depth: null result");
-    OP_TRY(reg_check_params(params, "op_volume_register_depth"));
-    const op_camera c = cam ? *cam : v->cam;
-    OP_TRY(check_cam(&c));
-    OP_VOL(v);
-    OP_TRY(vol_check(v));
-    const op_volume_register_params P = params ? *params : reg_defaults(v);
-
-    op::Scope tmp;
-    tmp.bind(v->stream);
-    unsigned total = 0;
-    OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, nullptr, mem, pixel_stride, &total));
-    return reg_loop(v, v->reg_pts, (size_t)total, init_pose, P, result); // (the loop's kernels follow the scatter on the volume's stream)
+    op_volume_register_robust_result r{};
+    OP_TRY(reg_frame_entry("op_volume_register_depth", v, cam, depth, depth_fmt, nullptr, false, mem, pixel_stride, init_pose, params, nullptr, result ? &r : nullptr));
+    *result = r.color.base;
+    return OP_OK;
 }
 
 // ---- the colour term
@@ -919,86 +899,24 @@ int op_volume_register_color_default_params(op_volume* v, op_volume_register_col
 
 int op_volume_register_color_system(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float T[16], float max_distance,
                                     float color_scale, float max_color_residual, double sums[30], uint64_t counts[5], float* rows) {
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_color_system: bad mem %d", mem);
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null xyz");
-    if (!T) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null T");
-    if (!sums) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null sums");
-    OP_TRY(reg_check_color_scale(color_scale, "op_volume_register_color_system"));
-    if (n > 0 && color_scale > 0.0f && !intensity) return fail(OP_ERR_INVALID, "op_volume_register_color_system: null intensity");
-    OP_VOL(v);
-    OP_TRY(vol_check(v));
-    RegRun R(v);
-    const float *d_xyz = nullptr, *d_int = nullptr;
-    OP_TRY(R.tmp.input(xyz, 3 * n, mem, &d_xyz));
-    if (color_scale > 0.0f) OP_TRY(R.tmp.input(intensity, n, mem, &d_int)); // (color_scale == 0: the intensities are not read either)
-    OP_TRY(R.open_color(d_xyz, d_int, n, max_distance, color_scale, max_color_residual));
-    const bool want_rows = rows && n;
-    uint64_t c[5];
-    if (R.color()) {
-        float* d_rows = rows;
-        if (want_rows && mem == OP_MEM_HOST) OP_TRY(R.tmp.alloc(&d_rows, 16 * n));
-        OP_TRY(R.eval_color(T, want_rows ? d_rows : nullptr, sums, c));
-        if (want_rows && mem == OP_MEM_HOST) OP_HIP(hipMemcpy(rows, d_rows, sizeof(float) * 16 * n, hipMemcpyDeviceToHost));
-    } else { // the geometric instantiation; its rows of 8 become the first halves of rows of 16, the second halves zero
-        float* d_rows8 = nullptr;
-        if (want_rows) OP_TRY(R.tmp.alloc(&d_rows8, 8 * n));
-        OP_TRY(R.eval(T, d_rows8, sums, c));
-        sums[28] = 0.0; sums[29] = sums[27]; c[4] = 0;
-        if (want_rows) {
-            if (mem == OP_MEM_HOST) std::memset(rows, 0, sizeof(float) * 16 * n);
-            else OP_HIP(hipMemset(rows, 0, sizeof(float) * 16 * n));
-            OP_HIP(hipMemcpy2D(rows, sizeof(float) * 16, d_rows8, sizeof(float) * 8, sizeof(float) * 8, n, mem == OP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
-        }
-    }
-    if (counts) for (int k = 0; k < 5; ++k) counts[k] = c[k];
-    return OP_OK;
+    return reg_system_entry("op_volume_register_color_system", v, xyz, nullptr, intensity, n, mem, T, max_distance, color_scale, max_color_residual, nullptr, kRegColorExtent,
+                            sums, counts, rows);
 }
 
 int op_volume_register_color_points(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float init_T[16],
                                     const op_volume_register_color_params* params, op_volume_register_color_result* result) {
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_color_points: bad mem %d", mem);
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null xyz");
-    if (!init_T) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null init_T");
-    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null result");
-    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_color_points"));
-    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_color_points"));
-    if (n > 0 && !intensity && (!params || params->color_scale > 0.0f)) return fail(OP_ERR_INVALID, "op_volume_register_color_points: null intensity");
-    OP_VOL(v);
-    OP_TRY(vol_check(v));
-    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
-    op::Scope up;
-    up.bind(v->stream);
-    const float *d_xyz = nullptr, *d_int = nullptr;
-    OP_TRY(up.input(xyz, 3 * n, mem, &d_xyz));
-    if (P.color_scale > 0.0f) OP_TRY(up.input(intensity, n, mem, &d_int));
-    return reg_loop(v, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual, result);
+    op_volume_register_robust_result r{};
+    OP_TRY(reg_points_entry("op_volume_register_color_points", v, xyz, nullptr, intensity, n, mem, init_T, params, nullptr, result ? &r : nullptr));
+    *result = r.color;
+    return OP_OK;
 }
 
 int op_volume_register_rgbd(op_volume* v, const op_camera* cam, const void* depth, int depth_fmt, const uint8_t* rgb, int mem, int pixel_stride,
                             const float init_pose[16], const op_volume_register_color_params* params, op_volume_register_color_result* result) {
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: bad mem %d", mem);
-    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: bad depth format %d", depth_fmt);
-    if (!depth) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null depth");
-    if (!rgb) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null rgb");
-    if (pixel_stride < 1) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: pixel_stride < 1");
-    if (!init_pose) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null init_pose");
-    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_rgbd: null result");
-    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_rgbd"));
-    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_rgbd"));
-    const op_camera c = cam ? *cam : v->cam;
-    OP_TRY(check_cam(&c));
-    OP_VOL(v);
-    OP_TRY(vol_check(v));
-    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
-
-    op::Scope tmp;
-    tmp.bind(v->stream);
-    unsigned total = 0;
-    OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, rgb, mem, pixel_stride, &total));
-    return reg_loop(v, v->reg_pts, v->reg_int, (size_t)total, init_pose, P.base, P.color_scale, P.max_color_residual, result);
+    op_volume_register_robust_result r{};
+    OP_TRY(reg_frame_entry("op_volume_register_rgbd", v, cam, depth, depth_fmt, rgb, true, mem, pixel_stride, init_pose, params, nullptr, result ? &r : nullptr));
+    *result = r.color;
+    return OP_OK;
 }
 
 // ---- the linearisation and the Huber weights
@@ -1012,7 +930,8 @@ int op_volume_register_robust_default_options(op_volume* v, op_volume_register_o
 int op_volume_register_robust_system(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float T[16], float max_distance,
                                      float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
                                      uint64_t counts[7], float* rows) {
-    return reg_system_entry("op_volume_register_robust_system", v, xyz, nullptr, intensity, n, mem, T, max_distance, color_scale, max_color_residual, options, sums, counts, rows);
+    return reg_system_entry("op_volume_register_robust_system", v, xyz, nullptr, intensity, n, mem, T, max_distance, color_scale, max_color_residual, options, kRegRobustExtent,
+                            sums, counts, rows);
 }
 
 int op_volume_register_robust_points(op_volume* v, const float* xyz, const float* intensity, size_t n, int mem, const float init_T[16],
@@ -1024,36 +943,15 @@ int op_volume_register_robust_points(op_volume* v, const float* xyz, const float
 int op_volume_register_robust_frame(op_volume* v, const op_camera* cam, const void* depth, int depth_fmt, const uint8_t* rgb, int mem, int pixel_stride,
                                     const float init_pose[16], const op_volume_register_color_params* params, const op_volume_register_options* options,
                                     op_volume_register_robust_result* result) {
-    if (!v) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: null volume");
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: bad mem %d", mem);
-    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: bad depth format %d", depth_fmt);
-    if (!depth) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: null depth");
-    if (pixel_stride < 1) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: pixel_stride < 1");
-    if (!init_pose) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: null init_pose");
-    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_robust_frame: null result");
-    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_robust_frame"));
-    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_robust_frame"));
-    OP_TRY(reg_check_options(options, "op_volume_register_robust_frame"));
-    const op_camera c = cam ? *cam : v->cam;
-    OP_TRY(check_cam(&c));
-    OP_VOL(v);
-    OP_TRY(vol_check(v));
-    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
-    const float color_scale = rgb ? P.color_scale : 0.0f; // no colour image: the geometric registration
-
-    op::Scope tmp;
-    tmp.bind(v->stream);
-    unsigned total = 0;
-    OP_TRY(reg_back_project(v, tmp, c, depth, depth_fmt, rgb, mem, pixel_stride, &total));
-    return reg_loop(v, v->reg_pts, rgb ? v->reg_int : nullptr, (size_t)total, init_pose, P.base, color_scale, P.max_color_residual,
-                    options ? *options : op_volume_register_options{OP_REGISTER_LIN_NORMAL, 0.0f, 0.0f}, result);
+    return reg_frame_entry("op_volume_register_robust_frame", v, cam, depth, depth_fmt, rgb, false, mem, pixel_stride, init_pose, params, options, result);
 }
 
 // ---- a target value per point, and one fused volume against another
 int op_volume_register_offset_system(op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float T[16],
                                      float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options, double sums[31],
                                      uint64_t counts[7], float* rows) {
-    return reg_system_entry("op_volume_register_offset_system", v, xyz, offset, intensity, n, mem, T, max_distance, color_scale, max_color_residual, options, sums, counts, rows);
+    return reg_system_entry("op_volume_register_offset_system", v, xyz, offset, intensity, n, mem, T, max_distance, color_scale, max_color_residual, options, kRegRobustExtent,
+                            sums, counts, rows);
 }
 
 int op_volume_register_offset_points(op_volume* v, const float* xyz, const float* offset, const float* intensity, size_t n, int mem, const float init_T[16],
@@ -1065,19 +963,20 @@ int op_volume_register_offset_points(op_volume* v, const float* xyz, const float
 int op_volume_register_volume(op_volume* target, op_volume* source, const float init_T[16], const op_volume_band_params* sel,
                               const op_volume_register_color_params* params, const op_volume_register_options* options,
                               op_volume_register_volume_result* result) {
-    if (!target) return fail(OP_ERR_INVALID, "op_volume_register_volume: null target");
-    if (!source) return fail(OP_ERR_INVALID, "op_volume_register_volume: null source");
-    if (!init_T) return fail(OP_ERR_INVALID, "op_volume_register_volume: null init_T");
-    if (!result) return fail(OP_ERR_INVALID, "op_volume_register_volume: null result");
-    OP_TRY(vol_band_check(sel, "op_volume_register_volume"));
-    OP_TRY(reg_check_params(params ? &params->base : nullptr, "op_volume_register_volume"));
-    if (params) OP_TRY(reg_check_color_scale(params->color_scale, "op_volume_register_volume"));
-    OP_TRY(reg_check_options(options, "op_volume_register_volume"));
-    if (target->device != source->device) return fail(OP_ERR_INVALID, "op_volume_register_volume: the volumes are on devices %d and %d", target->device, source->device);
+    const char* who = "op_volume_register_volume";
+    const RegParamsArg PA(params);
+    if (!target) return fail(OP_ERR_INVALID, "%s: null target", who);
+    if (!source) return fail(OP_ERR_INVALID, "%s: null source", who);
+    if (!init_T) return fail(OP_ERR_INVALID, "%s: null init_T", who);
+    if (!result) return fail(OP_ERR_INVALID, "%s: null result", who);
+    OP_TRY(vol_band_check(sel, who));
+    OP_TRY(PA.check(who));
+    OP_TRY(reg_check_options(options, who));
+    if (target->device != source->device) return fail(OP_ERR_INVALID, "%s: the volumes are on devices %d and %d", who, target->device, source->device);
     OP_VOL(target);
     OP_TRY(vol_check(source)); // both queues flushed, both streams idle
     if (source != target) OP_TRY(vol_check(target));
-    const op_volume_register_color_params P = params ? *params : reg_color_defaults(target);
+    const op_volume_register_color_params P = PA.resolve(target);
     const op_volume_register_options O = options ? *options : op_volume_register_options{OP_REGISTER_LIN_GRADIENT, 0.0f, 0.0f};
     op::Scope list; // the source's band voxels, selected once: the source does not change over the iterations
     list.bind(target->stream);
@@ -1085,7 +984,7 @@ int op_volume_register_volume(op_volume* target, op_volume* source, const float 
     size_t n = 0;
     OP_TRY(vol_band_select(list, source, sel, SIZE_MAX, &d_xyz, &d_sdf, P.color_scale > 0.0f ? &d_int : nullptr, &n)); // (the source's stream is idle on return)
     result->selected = n;
-    return reg_loop(target, d_xyz, d_int, n, init_T, P.base, P.color_scale, P.max_color_residual, O, &result->robust, d_sdf);
+    return reg_loop(target, d_xyz, d_int, d_sdf, n, init_T, P, P.color_scale, O, &result->robust);
 }
 
 // ---- many clouds, many frames
@@ -1093,13 +992,8 @@ int op_volume_register_batch_system(op_volume* v, const float* xyz, const float*
                                     const float* T, float max_distance, float color_scale, float max_color_residual, const op_volume_register_options* options,
                                     double* sums, uint64_t* counts) {
     const char* who = "op_volume_register_batch_system";
-    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
-    OP_TRY(reg_check_starts(starts, n_clouds, who));
-    const size_t n = (size_t)starts[n_clouds];
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
-    if (!T) return fail(OP_ERR_INVALID, "%s: null T", who);
-    if (!sums) return fail(OP_ERR_INVALID, "%s: null sums", who);
+    size_t n = 0;
+    OP_TRY(reg_check_clouds(who, v, mem, starts, n_clouds, true, xyz, &n, T, "T", sums, "sums"));
     OP_TRY(reg_check_color_scale(color_scale, who));
     if (n > 0 && color_scale > 0.0f && !intensity) return fail(OP_ERR_INVALID, "%s: null intensity", who);
     OP_TRY(reg_check_options(options, who));
@@ -1109,9 +1003,7 @@ int op_volume_register_batch_system(op_volume* v, const float* xyz, const float*
     op::Scope tmp;
     tmp.bind(v->stream);
     const float *d_xyz = nullptr, *d_int = nullptr, *d_off = nullptr;
-    OP_TRY(tmp.input(xyz, 3 * n, mem, &d_xyz));
-    if (color_scale > 0.0f) OP_TRY(tmp.input(intensity, n, mem, &d_int));
-    if (offset && n) OP_TRY(tmp.input(offset, n, mem, &d_off));
+    OP_TRY(reg_inputs(tmp, xyz, intensity, color_scale > 0.0f, offset, offset && n, n, mem, &d_xyz, &d_int, &d_off));
     RegBatch R(v, tmp);
     OP_TRY(R.open(d_xyz, d_int, d_off, starts, n_clouds, max_distance, color_scale, max_color_residual, options ? *options : kRegNoOptions));
     std::vector<size_t> active(n_clouds);
@@ -1127,27 +1019,20 @@ int op_volume_register_batch_points(op_volume* v, const float* xyz, const float*
                                     const float* init_T, const op_volume_register_color_params* params, const op_volume_register_options* options,
                                     op_volume_register_robust_result* results, op_volume_register_batch_stats* stats) {
     const char* who = "op_volume_register_batch_points";
-    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
-    OP_TRY(reg_check_starts(starts, n_clouds, who));
-    const size_t n = (size_t)starts[n_clouds];
-    if (n > 0 && !xyz) return fail(OP_ERR_INVALID, "%s: null xyz", who);
-    if (!init_T) return fail(OP_ERR_INVALID, "%s: null init_T", who);
-    if (!results) return fail(OP_ERR_INVALID, "%s: null results", who);
-    OP_TRY(reg_check_params(params ? &params->base : nullptr, who));
-    if (params) OP_TRY(reg_check_color_scale(params->color_scale, who));
-    if (n > 0 && !intensity && (!params || params->color_scale > 0.0f)) return fail(OP_ERR_INVALID, "%s: null intensity", who);
+    const RegParamsArg PA(params);
+    size_t n = 0;
+    OP_TRY(reg_check_clouds(who, v, mem, starts, n_clouds, true, xyz, &n, init_T, "init_T", results, "results"));
+    OP_TRY(PA.check(who));
+    if (n > 0 && !intensity && PA.wants_color()) return fail(OP_ERR_INVALID, "%s: null intensity", who);
     OP_TRY(reg_check_options(options, who));
     if (!n_clouds) return OP_OK;
     OP_VOL(v);
     OP_TRY(vol_check(v));
-    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    const op_volume_register_color_params P = PA.resolve(v);
     op::Scope tmp;
     tmp.bind(v->stream);
     const float *d_xyz = nullptr, *d_int = nullptr, *d_off = nullptr;
-    OP_TRY(tmp.input(xyz, 3 * n, mem, &d_xyz));
-    if (P.color_scale > 0.0f) OP_TRY(tmp.input(intensity, n, mem, &d_int));
-    if (offset && n) OP_TRY(tmp.input(offset, n, mem, &d_off));
+    OP_TRY(reg_inputs(tmp, xyz, intensity, P.color_scale > 0.0f, offset, offset && n, n, mem, &d_xyz, &d_int, &d_off));
     return reg_batch_loop(v, tmp, d_xyz, d_int, d_off, starts, n_clouds, init_T, P, P.color_scale, options ? *options : kRegNoOptions, results, stats);
 }
 
@@ -1156,18 +1041,9 @@ int op_volume_register_batch_frames(op_volume* v, const op_camera* cam, const vo
                                     const op_volume_register_color_params* params, const op_volume_register_options* options,
                                     op_volume_register_robust_result* results, op_volume_register_batch_stats* stats) {
     const char* who = "op_volume_register_batch_frames";
-    if (!v) return fail(OP_ERR_INVALID, "%s: null volume", who);
-    if (mem != OP_MEM_HOST && mem != OP_MEM_DEVICE) return fail(OP_ERR_INVALID, "%s: bad mem %d", who, mem);
-    if (depth_fmt != OP_DEPTH_F32 && depth_fmt != OP_DEPTH_U16) return fail(OP_ERR_INVALID, "%s: bad depth format %d", who, depth_fmt);
-    if (!depth) return fail(OP_ERR_INVALID, "%s: null depth", who);
-    if (pixel_stride < 1) return fail(OP_ERR_INVALID, "%s: pixel_stride < 1", who);
-    if (!init_poses) return fail(OP_ERR_INVALID, "%s: null init_poses", who);
-    if (!results) return fail(OP_ERR_INVALID, "%s: null results", who);
-    OP_TRY(reg_check_params(params ? &params->base : nullptr, who));
-    if (params) OP_TRY(reg_check_color_scale(params->color_scale, who));
-    OP_TRY(reg_check_options(options, who));
-    const op_camera c = cam ? *cam : v->cam;
-    OP_TRY(check_cam(&c));
+    const RegParamsArg PA(params);
+    op_camera c;
+    OP_TRY(reg_check_frames(who, v, cam, depth, depth_fmt, rgb, false, mem, pixel_stride, init_poses, "init_poses", results, "results", PA, options, &c));
     const size_t npix = (size_t)c.width * c.height, depth_elem = depth_fmt == OP_DEPTH_U16 ? 2 : 4;
     if (depth_stride_bytes < npix * depth_elem) return fail(OP_ERR_INVALID, "%s: depth stride %zu is smaller than an image (%zu bytes)", who, depth_stride_bytes, npix * depth_elem);
     if (depth_stride_bytes % depth_elem) return fail(OP_ERR_INVALID, "%s: depth stride %zu is no multiple of a depth value's %zu bytes", who, depth_stride_bytes, depth_elem);
@@ -1178,7 +1054,7 @@ int op_volume_register_batch_frames(op_volume* v, const op_camera* cam, const vo
     if (!n_frames) return OP_OK;
     OP_VOL(v);
     OP_TRY(vol_check(v));
-    const op_volume_register_color_params P = params ? *params : reg_color_defaults(v);
+    const op_volume_register_color_params P = PA.resolve(v);
     const float color_scale = rgb ? P.color_scale : 0.0f; // no colour images: the geometric registration
 
     op::Scope tmp;

@@ -613,35 +613,61 @@ class CubeHandler:
         out["status_name"] = CubeHandler.REGISTER_STATUS[r.status]
         return out
 
+    # what every cloud-taking method makes of its arrays, every system method of its outputs and every frame method of its images
+    @staticmethod
+    def _offset_inputs(points, offset, intensity):
+        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        o = np.ascontiguousarray(_f32(offset).reshape(-1)) if offset is not None else None
+        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
+        if o is not None and len(o) != len(pts):
+            raise ValueError("one target value per point")
+        if y is not None and len(y) != len(pts):
+            raise ValueError("one intensity per point")
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        return pts, o, y, ptr
+
+    def _registration_system(self, n, n_sums, n_counts, row_width, rows, call):
+        """call(sums, counts, rows or None) is the C entry on buffers of the extent it writes -> (sums, counts dict[, rows])"""
+        sums, counts = np.zeros(n_sums, np.float64), np.zeros(n_counts, np.uint64)
+        out = np.empty((n, row_width), np.float32) if rows else None
+        L.check(call(sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(L._u64p), C.c_void_p(out.ctypes.data) if rows else None))
+        self._alive = []
+        cd = dict(zip(self.ROBUST_COUNT_NAMES, (int(c) for c in counts)))
+        return (sums, cd, out) if rows else (sums, cd)
+
+    @staticmethod
+    def _frame_images(depth, rgb, names="depth and rgb"):
+        """-> (depth pointer, depth format, rgb pointer, mem, what keeps them alive); rgb None: no colour image, a NULL pointer"""
+        pd, fmt, mem, k1 = _image_arg(depth, "depth")
+        pr, k2 = None, None
+        if rgb is not None:
+            pr, _f, mem2, k2 = _image_arg(rgb, "rgb")
+            if mem != mem2:
+                raise ValueError("%s must both be host arrays or both be device tensors" % names)
+        return pd, fmt, pr, mem, (k1, k2)
+
     def RegistrationSystem(self, points, T, max_distance, rows=False):
         """The point-to-plane system of `points` ([n,3] float32, host) at the 4x4 `T` against the model (op_volume_register_system)
         -> (sums [28] float64: the upper triangle of JtJ row by row, Jtr, sum of s^2; counts dict[, rows [n,8]: j[6], s, used])."""
-        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
-        n = len(pts)
+        pts, _o, _y, ptr = self._offset_inputs(points, None, None)
         Tm = _f32(T).reshape(16)
-        sums, counts = np.zeros(28, np.float64), np.zeros(4, np.uint64)
-        out = np.empty((n, 8), np.float32) if rows else None
-        L.check(self._lib.op_volume_register_system(self._h, C.c_void_p(pts.ctypes.data), n, L.OP_MEM_HOST, _fp(Tm), float(max_distance),
-                                                    sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(L._u64p),
-                                                    C.c_void_p(out.ctypes.data) if rows else None))
-        self._alive = []
-        cd = dict(zip(("used", "invalid", "no_gradient", "too_far"), (int(c) for c in counts)))
-        return (sums, cd, out) if rows else (sums, cd)
+        return self._registration_system(len(pts), 28, 4, 8, rows, lambda sums, counts, out: self._lib.op_volume_register_system(
+            self._h, ptr(pts), len(pts), L.OP_MEM_HOST, _fp(Tm), float(max_distance), sums, counts, out))
 
     def RegisterPoints(self, points, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None):
         """Gauss-Newton registration of `points` ([n,3] float32, host) against the model from `init_T` (default identity) -> dict of
         op_volume_register_result's fields (T [4,4]: points to model).  None = the default (30 iterations, the truncation, 1e-5, 6)."""
-        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
+        pts, _o, _y, ptr = self._offset_inputs(points, None, None)
         T0 = _f32(np.eye(4) if init_T is None else init_T).reshape(16)
         p, r = self._register_params(max_iterations, max_distance, min_step, min_points), L.RegisterResult()
-        L.check(self._lib.op_volume_register_points(self._h, C.c_void_p(pts.ctypes.data), len(pts), L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(r)))
+        L.check(self._lib.op_volume_register_points(self._h, ptr(pts), len(pts), L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(r)))
         self._alive = []
         return self._register_result(r)
 
     def RegisterDepth(self, depth, init_pose, pixel_stride=1, camera=None, max_iterations=None, max_distance=None, min_step=None, min_points=None):
         """The same for a depth image (numpy or CUDA torch tensor) back-projected on the device (every pixel_stride-th pixel in both directions)
         from `init_pose` (camera to world) -> the result dict, T the refined pose."""
-        pd, fmt, mem, keep = _image_arg(depth, "depth")
+        pd, fmt, _pr, mem, keep = self._frame_images(depth, None)
         pose = _f32(init_pose).reshape(16)
         p, r = self._register_params(max_iterations, max_distance, min_step, min_points), L.RegisterResult()
         L.check(self._lib.op_volume_register_depth(self._h, C.byref(camera) if camera is not None else None, pd, fmt, mem, int(pixel_stride), _fp(pose),
@@ -679,35 +705,20 @@ class CubeHandler:
         intensities `intensity` ([n] float32; may be None with color_scale 0) -> (sums [30] float64: 0..27 as RegistrationSystem with the
         colour terms added, [28] the sum of rc^2, [29] the geometric sum of s^2; counts dict with `colored`[, rows [n,16]: j[6], s, used, jc[6],
         rcs, colored])."""
-        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
-        n = len(pts)
-        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
-        if y is not None and len(y) != n:
-            raise ValueError("one intensity per point")
+        pts, _o, y, ptr = self._offset_inputs(points, None, intensity)
         Tm = _f32(T).reshape(16)
-        sums, counts = np.zeros(30, np.float64), np.zeros(5, np.uint64)
-        out = np.empty((n, 16), np.float32) if rows else None
-        L.check(self._lib.op_volume_register_color_system(self._h, C.c_void_p(pts.ctypes.data), C.c_void_p(y.ctypes.data) if y is not None else None, n,
-                                                          L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale), float(max_color_residual),
-                                                          sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(L._u64p),
-                                                          C.c_void_p(out.ctypes.data) if rows else None))
-        self._alive = []
-        cd = dict(zip(("used", "invalid", "no_gradient", "too_far", "colored"), (int(c) for c in counts)))
-        return (sums, cd, out) if rows else (sums, cd)
+        return self._registration_system(len(pts), 30, 5, 16, rows, lambda sums, counts, out: self._lib.op_volume_register_color_system(
+            self._h, ptr(pts), ptr(y), len(pts), L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale), float(max_color_residual), sums, counts, out))
 
     def RegisterColoredPoints(self, points, intensity, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
                               color_scale=None, max_color_residual=None):
         """RegisterPoints with the colour term: `intensity` [n] float32 in the volume's colour units (Intensity(colors) of a cloud's colours)
         -> the result dict with colored, first_colored, rmse_color, first_rmse_color.  color_scale None = 1, 0 = RegisterPoints."""
-        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
-        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
-        if y is not None and len(y) != len(pts):
-            raise ValueError("one intensity per point")
+        pts, _o, y, ptr = self._offset_inputs(points, None, intensity)
         T0 = _f32(np.eye(4) if init_T is None else init_T).reshape(16)
         p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
         r = L.RegisterColorResult()
-        L.check(self._lib.op_volume_register_color_points(self._h, C.c_void_p(pts.ctypes.data), C.c_void_p(y.ctypes.data) if y is not None else None, len(pts),
-                                                          L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(r)))
+        L.check(self._lib.op_volume_register_color_points(self._h, ptr(pts), ptr(y), len(pts), L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(r)))
         self._alive = []
         return self._register_color_result(r)
 
@@ -715,16 +726,13 @@ class CubeHandler:
                      color_scale=None, max_color_residual=None):
         """RegisterDepth with the colour term: every kept pixel's intensity comes from its three bytes of `rgb` (uint8 [H,W,3], stored channel
         order; numpy or CUDA torch tensor like `depth`) -> the result dict, T the refined pose."""
-        pd, fmt, mem, k1 = _image_arg(depth, "depth")
-        pr, _f, mem2, k2 = _image_arg(rgb, "rgb")
-        if mem != mem2:
-            raise ValueError("depth and rgb must both be host arrays or both be device tensors")
+        pd, fmt, pr, mem, keep = self._image_pair(depth, rgb)
         pose = _f32(init_pose).reshape(16)
         p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
         r = L.RegisterColorResult()
         L.check(self._lib.op_volume_register_rgbd(self._h, C.byref(camera) if camera is not None else None, pd, fmt, pr, mem, int(pixel_stride), _fp(pose),
                                                   C.byref(p), C.byref(r)))
-        del k1, k2
+        del keep
         self._alive = []
         return self._register_color_result(r)
 
@@ -753,39 +761,25 @@ class CubeHandler:
         """ColorRegistrationSystem under a linearisation ("normal" | "gradient" | "metric" or its number; None = metric) and Huber thresholds
         (None = 0 = no weights) (op_volume_register_robust_system) -> (sums [31] float64: 0..29 as ColorRegistrationSystem from the scaled rows,
         [30] the sum of the unweighted r^2; counts dict with `downweighted` and `color_downweighted`[, rows [n,16]: what enters the sums])."""
-        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
-        n = len(pts)
-        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
-        if y is not None and len(y) != n:
-            raise ValueError("one intensity per point")
+        pts, _o, y, ptr = self._offset_inputs(points, None, intensity)
         Tm = _f32(T).reshape(16)
-        o = self._register_options(linearization, huber, huber_color)
-        sums, counts = np.zeros(31, np.float64), np.zeros(7, np.uint64)
-        out = np.empty((n, 16), np.float32) if rows else None
-        L.check(self._lib.op_volume_register_robust_system(self._h, C.c_void_p(pts.ctypes.data), C.c_void_p(y.ctypes.data) if y is not None else None, n,
-                                                           L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale), float(max_color_residual), C.byref(o),
-                                                           sums.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(L._u64p),
-                                                           C.c_void_p(out.ctypes.data) if rows else None))
-        self._alive = []
-        cd = dict(zip(self.ROBUST_COUNT_NAMES, (int(c) for c in counts)))
-        return (sums, cd, out) if rows else (sums, cd)
+        opt = self._register_options(linearization, huber, huber_color)
+        return self._registration_system(len(pts), 31, 7, 16, rows, lambda sums, counts, out: self._lib.op_volume_register_robust_system(
+            self._h, ptr(pts), ptr(y), len(pts), L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale), float(max_color_residual), C.byref(opt),
+            sums, counts, out))
 
     def RegisterPointsRobust(self, points, intensity=None, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
                              color_scale=None, max_color_residual=None, linearization=None, huber=None, huber_color=None):
         """RegisterColoredPoints under a linearisation and Huber thresholds (op_volume_register_robust_points).  intensity None: the geometric
         registration (color_scale 0) -> the result dict with downweighted, color_downweighted, first_downweighted, rmse_residual,
         first_rmse_residual.  linearization None = metric; "normal" with no threshold is RegisterColoredPoints bit for bit."""
-        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
-        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
-        if y is not None and len(y) != len(pts):
-            raise ValueError("one intensity per point")
+        pts, _o, y, ptr = self._offset_inputs(points, None, intensity)
         if y is None and color_scale is None:
             color_scale = 0.0
         T0 = _f32(np.eye(4) if init_T is None else init_T).reshape(16)
         p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
         o, r = self._register_options(linearization, huber, huber_color), L.RegisterRobustResult()
-        L.check(self._lib.op_volume_register_robust_points(self._h, C.c_void_p(pts.ctypes.data), C.c_void_p(y.ctypes.data) if y is not None else None, len(pts),
-                                                           L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(o), C.byref(r)))
+        L.check(self._lib.op_volume_register_robust_points(self._h, ptr(pts), ptr(y), len(pts), L.OP_MEM_HOST, _fp(T0), C.byref(p), C.byref(o), C.byref(r)))
         self._alive = []
         return self._register_robust_result(r)
 
@@ -793,18 +787,13 @@ class CubeHandler:
                             color_scale=None, max_color_residual=None, linearization=None, huber=None, huber_color=None):
         """RegisterRGBD (rgb None: RegisterDepth) under a linearisation and Huber thresholds (op_volume_register_robust_frame) -> the result dict,
         T the refined pose."""
-        pd, fmt, mem, k1 = _image_arg(depth, "depth")
-        pr, k2 = None, None
-        if rgb is not None:
-            pr, _f, mem2, k2 = _image_arg(rgb, "rgb")
-            if mem != mem2:
-                raise ValueError("depth and rgb must both be host arrays or both be device tensors")
+        pd, fmt, pr, mem, keep = self._frame_images(depth, rgb)
         pose = _f32(init_pose).reshape(16)
         p = self._register_color_params(max_iterations, max_distance, min_step, min_points, color_scale, max_color_residual)
         o, r = self._register_options(linearization, huber, huber_color), L.RegisterRobustResult()
         L.check(self._lib.op_volume_register_robust_frame(self._h, C.byref(camera) if camera is not None else None, pd, fmt, pr, mem, int(pixel_stride), _fp(pose),
                                                           C.byref(p), C.byref(o), C.byref(r)))
-        del k1, k2
+        del keep
         self._alive = []
         return self._register_robust_result(r)
 
@@ -832,34 +821,16 @@ class CubeHandler:
                                                     C.c_void_p(y.ctypes.data) if intensity else None, L.OP_MEM_HOST, cap, C.byref(n)))
         return xyz, sdf, y
 
-    @staticmethod
-    def _offset_inputs(points, offset, intensity):
-        pts = np.ascontiguousarray(_f32(points).reshape(-1, 3))
-        o = np.ascontiguousarray(_f32(offset).reshape(-1)) if offset is not None else None
-        y = np.ascontiguousarray(_f32(intensity).reshape(-1)) if intensity is not None else None
-        if o is not None and len(o) != len(pts):
-            raise ValueError("one target value per point")
-        if y is not None and len(y) != len(pts):
-            raise ValueError("one intensity per point")
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
-        return pts, o, y, ptr
-
     def OffsetRegistrationSystem(self, points, offset, intensity, T, max_distance, color_scale=0.0, max_color_residual=0.0, linearization=None, huber=None,
                                  huber_color=None, rows=False):
         """RobustRegistrationSystem with a target value per point (op_volume_register_offset_system): the residual starts from s - offset[i];
         the max_distance gate and sums[29] keep the stored sdf.  offset None IS RobustRegistrationSystem."""
         pts, o, y, ptr = self._offset_inputs(points, offset, intensity)
-        n = len(pts)
         Tm = _f32(T).reshape(16)
         opt = self._register_options(linearization, huber, huber_color)
-        sums, counts = np.zeros(31, np.float64), np.zeros(7, np.uint64)
-        out = np.empty((n, 16), np.float32) if rows else None
-        L.check(self._lib.op_volume_register_offset_system(self._h, ptr(pts), ptr(o), ptr(y), n, L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale),
-                                                           float(max_color_residual), C.byref(opt), sums.ctypes.data_as(C.POINTER(C.c_double)),
-                                                           counts.ctypes.data_as(L._u64p), ptr(out)))
-        self._alive = []
-        cd = dict(zip(self.ROBUST_COUNT_NAMES, (int(c) for c in counts)))
-        return (sums, cd, out) if rows else (sums, cd)
+        return self._registration_system(len(pts), 31, 7, 16, rows, lambda sums, counts, out: self._lib.op_volume_register_offset_system(
+            self._h, ptr(pts), ptr(o), ptr(y), len(pts), L.OP_MEM_HOST, _fp(Tm), float(max_distance), float(color_scale), float(max_color_residual), C.byref(opt),
+            sums, counts, out))
 
     def RegisterPointsOffset(self, points, offset, intensity=None, init_T=None, max_iterations=None, max_distance=None, min_step=None, min_points=None,
                              color_scale=None, max_color_residual=None, linearization=None, huber=None, huber_color=None):
@@ -946,12 +917,7 @@ class CubeHandler:
         n = int(depths.shape[0])
         if rgbs is not None and int(rgbs.shape[0]) != n:
             raise ValueError("one colour image per depth image")
-        pd, fmt, mem, k1 = _image_arg(depths, "depth")
-        pr, k2 = None, None
-        if rgbs is not None:
-            pr, _f, mem2, k2 = _image_arg(rgbs, "rgb")
-            if mem != mem2:
-                raise ValueError("depths and rgbs must both be host arrays or both be device tensors")
+        pd, fmt, pr, mem, keep = self._frame_images(depths, rgbs, "depths and rgbs")
         cam = camera if camera is not None else self.camera
         npx = cam.width * cam.height
         if n and (int(np.prod(depths.shape[1:])) != npx or (rgbs is not None and int(np.prod(rgbs.shape[1:])) != 3 * npx)):
@@ -961,7 +927,7 @@ class CubeHandler:
         opt, res, stats = self._register_options(linearization, huber, huber_color), (L.RegisterRobustResult * max(n, 1))(), L.RegisterBatchStats()
         L.check(self._lib.op_volume_register_batch_frames(self._h, C.byref(camera) if camera is not None else None, pd, npx * (2 if fmt == L.OP_DEPTH_U16 else 4), fmt,
                                                           pr, npx * 3, mem, int(pixel_stride), _fp(poses), n, C.byref(p), C.byref(opt), res, C.byref(stats)))
-        del k1, k2
+        del keep
         self._alive = []
         return [self._register_robust_result(res[f]) for f in range(n)], self._batch_stats(stats)
 

@@ -173,12 +173,15 @@ def test_bindings_and_refusals_without_a_device(hip):
     fp = T.ctypes.data_as(hip._fp)
     r, n = hip.RegisterVolumeResult(), C.c_size_t(0)
     assert lib.op_volume_register_volume(None, None, fp, None, None, None, C.byref(r)) == hip.OP_ERR_INVALID
+    assert lib.op_last_error().startswith(b"op_volume_register_volume:"), lib.op_last_error()             # the entry's own name
     assert lib.op_volume_band_voxels(None, None, None, None, None, hip.OP_MEM_HOST, 0, C.byref(n)) == hip.OP_ERR_INVALID
     assert lib.op_volume_band_default_params(None, C.byref(hip.BandParams())) == hip.OP_ERR_INVALID
     sums = np.zeros(31)
     assert lib.op_volume_register_offset_system(None, None, None, None, 0, hip.OP_MEM_HOST, fp, 0.1, 0.0, 0.0, None, sums.ctypes.data_as(C.POINTER(C.c_double)), None,
                                                 None) == hip.OP_ERR_INVALID
+    assert lib.op_last_error().startswith(b"op_volume_register_offset_system:"), lib.op_last_error()
     assert lib.op_volume_register_offset_points(None, None, None, None, 0, hip.OP_MEM_HOST, fp, None, None, C.byref(hip.RegisterRobustResult())) == hip.OP_ERR_INVALID
+    assert lib.op_last_error().startswith(b"op_volume_register_offset_points:"), lib.op_last_error()
     from onepiece_amd import integration as I
     for name in ("BandVoxels", "RegisterPointsOffset", "OffsetRegistrationSystem", "RegisterVolume"):
         assert callable(getattr(I.CubeHandler, name)), name

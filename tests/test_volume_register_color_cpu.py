@@ -223,7 +223,9 @@ def test_abi_refusals_binding_and_struct_sizes(hip, tmp_path):
     }
     for what, call in cases.items():
         assert call() == hip.OP_ERR_INVALID, what
-        assert b"op_volume_register_" in lib.op_last_error(), what
+        entry = what.split(":")[0]
+        name = b"op_volume_register_rgbd:" if entry == "rgbd" else b"op_volume_register_color_%s:" % entry.encode()
+        assert lib.op_last_error().startswith(name), (what, lib.op_last_error())                               # the entry's own name
     assert (sums == 7.0).all() and (counts == 7).all() and (rows == 7.0).all() and res.base.iterations == 77      # nothing was written
     from onepiece_amd import integration as I
     for name in ("RegisterColoredPoints", "RegisterRGBD", "ColorRegistrationSystem", "Intensity"):
