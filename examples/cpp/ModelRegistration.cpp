@@ -24,6 +24,9 @@
 //                              last step and down-weighted points; the JSON line gains "linearization", "huber", "huber_color", "downweighted_last"
 //                              and "rmse_residual"
 //   --min-step S               (with the three above; default 0) the step below which a frame stops: with it the iteration counts say something
+//   --coarse L                 (plain fused path only; default 0) every frame is ALSO registered, from the same start, against the model coarsened L times
+//                              (CubeHandler::Coarsen, then the same RegisterDepth): two rows after the run -- coarse 0 and coarse L, per-iteration time and
+//                              final pose error -- and "coarse" in the JSON.  The frame is fused again at the pose the fine model gave, as without the flag
 // Both paths solve with op_ldlt_solve6, update with op_se3_exp and the same float32 product, and gate with the same rules; their sums differ in
 // the order of the additions only.  It prints one JSON line: pose errors before and after, iterations, stage times (host clock).
 #include <algorithm>
@@ -213,7 +216,7 @@ double Median(std::vector<double> v) {
 } // namespace
 
 int main(int argc, char* argv[]) {
-    long synthetic[3] = {0, 1, 1}, every = 20, iters = 10, batch = 0, batch_stride = 4;
+    long synthetic[3] = {0, 1, 1}, every = 20, iters = 10, batch = 0, batch_stride = 4, coarse = 0;
     bool is_synthetic = false, bad = false;
     std::string path = "fused", color = "off", linearization = "metric";
     float res = 0.01f, color_scale = 1.0f, huber = 0.0f, huber_color = 0.0f, min_step = 0.0f;
@@ -233,15 +236,17 @@ int main(int argc, char* argv[]) {
         else if (a == "--min-step" && i + 1 < argc) { min_step = static_cast<float>(std::atof(argv[++i])); have_min_step = true; }
         else if (a == "--batch" && i + 1 < argc) { batch = std::atol(argv[++i]); robust = true; }
         else if (a == "--batch-stride" && i + 1 < argc) batch_stride = std::atol(argv[++i]);
+        else if (a == "--coarse" && i + 1 < argc) coarse = std::atol(argv[++i]);
         else bad = true;
     }
     const int lin = linearization == "normal" ? OP_REGISTER_LIN_NORMAL : linearization == "gradient" ? OP_REGISTER_LIN_GRADIENT : linearization == "metric" ? OP_REGISTER_LIN_METRIC : -1;
     const long n = synthetic[0], stride = synthetic[1];
     if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || !(res > 0) || every < 1 || iters < 0 || iters > 1000 || (path != "sample" && path != "fused") ||
         (color != "off" && color != "on") || (color == "on" && path != "fused") || (have_scale && color != "on") || !(color_scale >= 0) || lin < 0 || (robust && path != "fused") || !(huber >= 0) || !(huber_color >= 0) ||
-        (have_min_step && !robust) || !(min_step >= 0) || batch < 0 || batch_stride < 1) {
+        (have_min_step && !robust) || !(min_step >= 0) || batch < 0 || batch_stride < 1 ||
+        coarse < 0 || coarse > 4 || (coarse > 0 && (path != "fused" || color == "on" || robust))) {
         std::cout << "usage::ModelRegistration --synthetic N STRIDE SEED [--res 0.01] [--perturb K] [--iters I] [--path sample|fused] [--color off|on [--color-scale S]]"
-                     " [--linearization normal|gradient|metric] [--huber D] [--huber-color D] [--min-step S] [--batch K [--batch-stride S]]" << std::endl;
+                     " [--linearization normal|gradient|metric] [--huber D] [--huber-color D] [--min-step S] [--batch K [--batch-stride S]] [--coarse L]" << std::endl;
         return bad || argc > 1 ? 2 : 0;
     }
     const long first = ((synthetic[2] + 999) % 1000) * 97 % 1000;
@@ -281,6 +286,8 @@ int main(int argc, char* argv[]) {
     unsigned long long points = 0, used = 0, colored = 0;
     long frames = 0, iterations = 0;
     double t_out = 0, t_back = 0;
+    std::vector<double> coarse_ms, coarse_iteration_ms, coarse_after_m, coarse_after_deg, coarse_rmse, coarsen_ms;
+    unsigned long long coarse_blocks = 0;
     for (long k = 0; k < n; k += every, ++frames) {
         cv::Mat depth, rgb;
         const geometry::TransformationMatrix pose = RoomPose(first + k * stride);
@@ -331,6 +338,26 @@ int main(int argc, char* argv[]) {
             for (int a = 0; a < 16; ++a) got.T[a] = r.T[a];
             got.iterations = r.iterations; got.used = r.used; got.rmse = r.rmse; got.first_rmse = r.first_rmse;
             points = r.used + r.invalid + r.no_gradient + r.too_far;
+            if (coarse > 0) { // the same frame, the same start, the model coarsened `coarse` times (timed apart from the fine registration)
+                const double fine_ms = Seconds(t0) * 1000.0;
+                std::chrono::steady_clock::time_point t1 = std::chrono::steady_clock::now();
+                op_volume_coarsen_stats cs;
+                std::shared_ptr<integration::CubeHandler> lod = volume.Coarsen(static_cast<int>(coarse), 0.0f, &cs);
+                if (!lod) return 1;
+                coarsen_ms.push_back(Seconds(t1) * 1000.0);
+                coarse_blocks = cs.dst_blocks;
+                op_volume_register_result rc;
+                t1 = std::chrono::steady_clock::now();
+                if (!lod->RegisterDepth(depth, FromRowMajor(start), 1, &params, &rc)) return 1;
+                const double ms = Seconds(t1) * 1000.0;
+                coarse_ms.push_back(ms);
+                coarse_iteration_ms.push_back(ms / static_cast<double>(rc.iterations + 1));
+                double m = 0, deg = 0;
+                PoseError(rc.T, truth, &m, &deg);
+                coarse_after_m.push_back(m); coarse_after_deg.push_back(deg);
+                coarse_rmse.push_back(rc.rmse);
+                t0 = std::chrono::steady_clock::now() - std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(fine_ms / 1000.0));
+            }
         } else {
             std::vector<float> xyz; // op_points_from_depth's definition, on the host
             const float fx = camera.GetFx(), fy = camera.GetFy(), cx = camera.GetCx(), cy = camera.GetCy();
@@ -393,6 +420,13 @@ int main(int argc, char* argv[]) {
         }
         for (long k = 0; k < K; ++k) batch_same = batch_same && std::memcmp(&many[k], &one[k], sizeof(one[k])) == 0;
     }
+    if (coarse > 0) {
+        std::printf("coarse 0: per iteration %.3f ms, final pose error %.3f mm / %.5f deg (max %.3f mm), rmse %.6f\n", Median(per_iteration_ms), Median(after_m) * 1000.0, Median(after_deg),
+                    *std::max_element(after_m.begin(), after_m.end()) * 1000.0, Median(rmse));
+        std::printf("coarse %ld: per iteration %.3f ms, final pose error %.3f mm / %.5f deg (max %.3f mm), rmse %.6f, %llu blocks, coarsening %.3f ms\n", coarse, Median(coarse_iteration_ms),
+                    Median(coarse_after_m) * 1000.0, Median(coarse_after_deg), *std::max_element(coarse_after_m.begin(), coarse_after_m.end()) * 1000.0, Median(coarse_rmse), coarse_blocks,
+                    Median(coarsen_ms));
+    }
     std::cout << "{\"frames\": " << n << ", \"stride\": " << stride << ", \"first\": " << first << ", \"res\": " << res << ", \"path\": \"" << path << "\", \"registered\": " << frames
               << ", \"iters\": " << iters << ", \"iterations\": " << iterations << ", \"points\": " << points << ", \"used_last\": " << used
               << ", \"error_before\": {\"mm\": " << Median(before_m) * 1000.0 << ", \"deg\": " << Median(before_deg) << "}"
@@ -405,6 +439,9 @@ int main(int argc, char* argv[]) {
     if (batch > 0) std::cout << ", \"batch\": {\"frames\": " << std::min(batch, n) << ", \"pixel_stride\": " << batch_stride << ", \"ms\": " << batch_ms << ", \"single_ms\": " << batch_single_ms
                              << ", \"rounds\": " << batch_stats.rounds << ", \"launches\": " << batch_stats.launches << ", \"evaluations\": " << batch_stats.evaluations
                              << ", \"points\": " << batch_stats.points << ", \"same_bits\": " << (batch_same ? "true" : "false") << "}";
+    if (coarse > 0) std::cout << ", \"coarse\": {\"levels\": " << coarse << ", \"blocks\": " << coarse_blocks << ", \"error_after\": {\"mm\": " << Median(coarse_after_m) * 1000.0 << ", \"deg\": "
+                              << Median(coarse_after_deg) << ", \"max_mm\": " << *std::max_element(coarse_after_m.begin(), coarse_after_m.end()) * 1000.0 << "}, \"rmse\": " << Median(coarse_rmse)
+                              << ", \"per_iteration_median\": " << Median(coarse_iteration_ms) << ", \"register_median\": " << Median(coarse_ms) << ", \"coarsen_median\": " << Median(coarsen_ms) << "}";
     std::cout
               << ", \"ms\": {\"fuse\": " << t_fuse * 1000.0 << ", \"deintegrate\": " << t_out * 1000.0 << ", \"reintegrate\": " << t_back * 1000.0
               << ", \"register_median\": " << Median(register_ms) << ", \"per_iteration_median\": " << Median(per_iteration_ms) << "}}" << std::endl;

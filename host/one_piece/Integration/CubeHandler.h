@@ -264,6 +264,13 @@ class CubeHandler {
     std::shared_ptr<geometry::PointCloud> GetPointCloud() const;
     std::shared_ptr<CubeHandler> Transform(const geometry::TransformationMatrix& trans) const;
     std::shared_ptr<CubeHandler> TransformNearest(const geometry::TransformationMatrix& trans);
+    // EXTENSION (not in the reference, whose only way to a cheaper model is to fuse every frame again at a larger voxel): a NEW handler of
+    // 2^levels times the voxel size, on the device (op_volume_coarsen states the definition).  A voxel centre is (index + 0.5) * res, so a voxel
+    // of twice the size covers exactly 2 x 2 x 2 fine voxels: its sdf and colour are their weighted means over the children of weight > 0 and
+    // >= min_weight, summed in a fixed order, and its weight is their sum / 8.  This handler is not changed; the result's
+    // c_para.VoxelResolution is the doubled one, and it is an ordinary handler (meshing, rendering, sampling, registration, Merge, fusion).
+    // An empty pointer (after a message) when the call failed.  stats: the last level's counts.
+    std::shared_ptr<CubeHandler> Coarsen(int levels = 1, float min_weight = 0, op_volume_coarsen_stats* stats = nullptr) const;
     CubeMap GetCubeMap();
     void SetCubeMap(const CubeMap& _cube_map);
     void SetFarPlane(float _far);

@@ -336,6 +336,16 @@ std::shared_ptr<CubeHandler> CubeHandler::TransformNearest(const geometry::Trans
     return std::shared_ptr<CubeHandler>(new CubeHandler(out, *this, CubePara().VoxelResolution));
 }
 
+std::shared_ptr<CubeHandler> CubeHandler::Coarsen(int levels, float min_weight, op_volume_coarsen_stats* stats) const {
+    Pending();
+    if (!Ensure()) return std::shared_ptr<CubeHandler>();
+    op_volume* out = nullptr;
+    if (op_volume_coarsen(vol, levels, min_weight, 0, &out, stats) != OP_OK) { Report("Coarsen"); return std::shared_ptr<CubeHandler>(); }
+    float res = c_para.VoxelResolution;
+    if (op_volume_resolution(out, &res) != OP_OK) { Report("Coarsen"); op_volume_destroy(out); return std::shared_ptr<CubeHandler>(); }
+    return std::shared_ptr<CubeHandler>(new CubeHandler(out, *this, res)); // 2^levels * VoxelResolution, as the device doubled it
+}
+
 std::shared_ptr<geometry::PointCloud> CubeHandler::GetPointCloud() const {
     std::shared_ptr<geometry::PointCloud> pcd = std::make_shared<geometry::PointCloud>();
     Pending();

@@ -477,6 +477,30 @@ int op_volume_merge(op_volume *dst, op_volume *src);
 int op_volume_transform(op_volume *src, const float T[16], const float *T_inv, int nearest,
                         uint64_t max_blocks, op_volume **out);
 int op_volume_resolution(op_volume *v, float *voxel_res);
+/* CubeHandler::Coarsen (no reference counterpart): a half-resolution copy of a fused model, on the device.  Voxel centres sit at
+ * (index + 0.5) * res (Integration/VoxelCube.h:49-58), so a voxel of twice the size covers exactly a 2 x 2 x 2 group of fine voxels and its centre is
+ * their centroid: nothing is resampled or interpolated.  THE DEFINITION of one level:
+ *   - The result is a NEW volume on the source's device (destroy it with op_volume_destroy) with the source's camera, truncation, near and far and
+ *     voxel_res = 2 * the source's (exact in float32).  It is marked foreign over all of its blocks, as op_volume_transform's result is: its
+ *     weights are no integers, and fusion into it takes the general update.  The source is not changed.
+ *   - Result block B exists iff at least one of the eight source blocks 2B + {0,1}^3 exists: the id on each axis is the arithmetic shift b >> 1
+ *     (source blocks -1, -2, -3 go to -1, -1, -2).  A block whose voxels all come out unobserved is kept (op_volume_collect_garbage drops it).
+ *   - Coarse global voxel g has the children f = 2g + (i, j, k), i, j, k in {0, 1}, visited in the order c = i + 2j + 4k ascending.  A child in a
+ *     missing block is the default voxel.  A child CONTRIBUTES iff w_c > 0 && w_c >= min_weight -- false for NaN, so whatever sdf lies under a
+ *     weight of 0 (999, NaN, inf) never reaches the sums.
+ *   - Over the contributing children, in that order, in float32, every product and every sum rounded on its own, starting from 0.0f:
+ *       W = W + w_c;  S = S + w_c * s_c;  C_m = C_m + w_c * col_c[m]  (m = 0, 1, 2)
+ *   - No child contributes: the default voxel {999, 0, -1, -1, -1}.  Otherwise sdf = S / W, colour[m] = C_m / W (IEEE divisions) and
+ *     weight = W * 0.125f -- the mean over all EIGHT cells, exact: a fully observed region keeps its weight, a half-observed coarse cell carries
+ *     half of it, and later fusion or op_volume_merge into the result weighs it as what it is.
+ * levels in 1..4: that many applications, one after the other, the intermediates released.  max_blocks = 0 sizes the result automatically (it
+ * never needs more than the source's block count); a max_blocks that is too small grows and the allocation pass runs again, as
+ * op_volume_transform's does.  stats (may be NULL), for the LAST level: source and result blocks, result voxels with 8, with 1..7 and with 0
+ * contributing children, and fine voxels of weight > 0 that min_weight kept out.  Refused with OP_ERR_INVALID before any device work: NULL src or
+ * out, levels outside 1..4, min_weight negative or NaN. */
+typedef struct { uint64_t src_blocks, dst_blocks, voxels_full, voxels_partial, voxels_empty, dropped_min_weight; } op_volume_coarsen_stats;
+int op_volume_coarsen(op_volume *src, int levels, float min_weight, uint64_t max_blocks, op_volume **out,
+                      op_volume_coarsen_stats *stats /* may be NULL */);
 /* CubeHandler::GetPointCloud (CubeHandler.cpp:45-69): points and grey colours |sdf|/truncation
  * (n x 3 floats each, host).  *n is the full count; xyz/colors may be NULL to query it. */
 int op_volume_point_cloud(op_volume *v, float *xyz, float *colors, size_t cap, size_t *n);

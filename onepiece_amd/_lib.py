@@ -40,6 +40,11 @@ class CollectStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("blocks_before", "blocks_kept", "removed_outside", "removed_unobserved", "blocks_moved")]
 
 
+class CoarsenStats(C.Structure):
+    """op_volume_coarsen_stats of op_volume_coarsen."""
+    _fields_ = [(k, C.c_uint64) for k in ("src_blocks", "dst_blocks", "voxels_full", "voxels_partial", "voxels_empty", "dropped_min_weight")]
+
+
 class SampleStats(C.Structure):
     """op_volume_sample_stats of op_volume_sample."""
     _fields_ = [(k, C.c_uint64) for k in ("queries", "valid", "gradients", "out_of_range")] + \
@@ -223,6 +228,7 @@ SIGNATURES = {
     "op_volume_merge": (C.c_int, [_vp, _vp]),
     "op_volume_transform": (C.c_int, [_vp, _fp, _fp, C.c_int, C.c_uint64, C.POINTER(_vp)]),
     "op_volume_resolution": (C.c_int, [_vp, _fp]),
+    "op_volume_coarsen": (C.c_int, [_vp, C.c_int, C.c_float, C.c_uint64, C.POINTER(_vp), C.POINTER(CoarsenStats)]),
     "op_volume_point_cloud": (C.c_int, [_vp, _fp, _fp, C.c_size_t, _szp]),
     "op_volume_extract_mesh": (C.c_int, [_vp, _ip, _ip, _ip, _fp, _fp, C.c_size_t, _szp]),
     "op_volume_write_file": (C.c_int, [_vp, C.c_char_p]),

@@ -7,6 +7,7 @@
 //   raycast.hip     the raycaster, and its view packed as an RGB-D frame (model_frame.hpp: what the dense tracker takes from here)
 //   volume_gc.hip   CollectGarbage;  volume_sample.hip  the point queries (op_volume_sample), over trilinear_sample.hpp and voxel_interp.hpp
 //   volume_band.hip the band voxels of a volume as a list (op_volume_band_voxels)
+//   volume_coarsen.hip  the half-resolution copy of a volume (op_volume_coarsen)
 // Data layout in HBM: see volume.hip (and DESIGN.md section 2).
 #pragma once
 #include <cfloat>

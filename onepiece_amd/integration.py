@@ -448,6 +448,18 @@ class CubeHandler:
         the DEFAULT voxel resolution 0.01 (c_para is not copied there)."""
         return self._transform(trans, True, max_blocks)
 
+    def Coarsen(self, levels=1, min_weight=0.0, max_blocks=0):
+        """Extension (op_volume_coarsen states the definition; not in the reference): a NEW CubeHandler of 2^levels times the voxel size, each
+        level's voxel the weighted mean of its 2 x 2 x 2 fine voxels of weight > 0 and >= min_weight, its weight their sum / 8.  This volume is
+        not changed.  The last level's counts are the result's `coarsen_stats`: {"src_blocks", "dst_blocks", "voxels_full", "voxels_partial",
+        "voxels_empty", "dropped_min_weight"}."""
+        h, st = C.c_void_p(), L.CoarsenStats()
+        L.check(self._lib.op_volume_coarsen(self._h, int(levels), float(min_weight), int(max_blocks), C.byref(h), C.byref(st)))
+        out = CubeHandler._wrap(h, self.camera, self.device)
+        out._trunc, out._far, out._near = self._trunc, self._far, self._near
+        out.coarsen_stats = {k: int(getattr(st, k)) for k, _t in L.CoarsenStats._fields_}
+        return out
+
     def GetVoxelResolution(self):
         return self._res
 
