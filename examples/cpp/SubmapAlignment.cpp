@@ -5,7 +5,8 @@
 // so far, and Transform + Merge fix it at the pose that was found.
 //
 //   SubmapAlignment --synthetic N STRIDE SEED [--submaps K] [--overlap F] [--perturb P] [--res R] [--band B] [--voxel-stride S] [--iters I]
-//                   [--linearization normal|gradient|metric] [--color on|off] [--path cloud|mesh|volume] [--out DIR]
+//                   [--linearization normal|gradient|metric] [--color on|off] [--path cloud|mesh|volume] [--merge two-step|fused]
+//                   [--recompose single|batch] [--out DIR]
 //   --synthetic N STRIDE SEED  N frames of the analytic room of LiveFusion.cpp: frame k is step FIRST + k * STRIDE of a 1000-step orbit, SEED picks FIRST
 //   --submaps K                (default 2) submap i holds the frames [i * step, i * step + L), L = N / (K - (K - 1) F), step = L (1 - F)
 //   --overlap F                (default 0.4) the share of a submap's frames that the next one holds too
@@ -17,7 +18,12 @@
 //                              through RegisterPointCloudRobust (no colour: GetPointCloud's colours are |sdf| / truncation)
 //   --path mesh                the other one: ExtractTriangleMesh of the submap, its vertices through RegisterPointCloudRobust (--color on: their colours)
 //   --linearization L          (default gradient)   --iters I  Gauss-Newton iterations at the most (default 30; min_step 1e-5)
-//   --out DIR                  writes model_<i>.map (the model submap i was registered against) and submap_<i>.map
+//   --merge two-step (default) Merge(part, T): Transform into an intermediate volume, then Merge, as example/MergeMultipleSubmaps.cpp places a submap
+//   --merge fused              MergeTransformed(part, T) (op_volume_merge_transformed): the same voxels, resampled straight into the model's blocks
+//   --recompose single|batch   after the loop a fresh, empty model receives ALL submaps at their final poses (submap 0 at the identity), as a system
+//                              that re-composes its global model after a pose-graph update does: K MergeTransformed calls, or one call with K sources
+//   --out DIR                  writes model_<i>.map (the model submap i was registered against), submap_<i>.map, the final model.map and, with
+//                              --recompose, recomposed.map
 // One line per submap (pose error before and after, points, iterations, status, times), then one JSON line with the same, the stage times and the
 // doubled-surface figure: the rmse of the distance (DistanceToModel) of the merged model's mesh vertices to a model fused from all frames at their
 // true poses.
@@ -139,7 +145,7 @@ struct Row {
 int main(int argc, char* argv[]) {
     long synthetic[3] = {0, 1, 1}, submaps = 2, perturb = 1, voxel_stride = 1, iters = 30;
     bool is_synthetic = false, bad = false;
-    std::string path = "volume", color = "on", linearization = "gradient", out_dir;
+    std::string path = "volume", color = "on", linearization = "gradient", out_dir, merge = "two-step", recompose;
     float res = 0.01f, band = 0.0f, overlap = 0.4f;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -154,6 +160,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--linearization" && i + 1 < argc) linearization = argv[++i];
         else if (a == "--color" && i + 1 < argc) color = argv[++i];
         else if (a == "--path" && i + 1 < argc) path = argv[++i];
+        else if (a == "--merge" && i + 1 < argc) merge = argv[++i];
+        else if (a == "--recompose" && i + 1 < argc) recompose = argv[++i];
         else if (a == "--out" && i + 1 < argc) out_dir = argv[++i];
         else bad = true;
     }
@@ -161,9 +169,10 @@ int main(int argc, char* argv[]) {
     const long n = synthetic[0], stride = synthetic[1];
     if (bad || !is_synthetic || n < 1 || stride < 1 || synthetic[2] < 0 || submaps < 2 || submaps > n || !(overlap >= 0) || !(overlap < 1) || perturb < 0 || !(res > 0) ||
         !(band == band) || (voxel_stride != 1 && voxel_stride != 2 && voxel_stride != 4 && voxel_stride != 8) || iters < 0 || iters > 1000 || lin < 0 ||
-        (color != "off" && color != "on") || (path != "cloud" && path != "mesh" && path != "volume")) {
+        (color != "off" && color != "on") || (path != "cloud" && path != "mesh" && path != "volume") ||
+        (merge != "two-step" && merge != "fused") || (!recompose.empty() && recompose != "single" && recompose != "batch")) {
         std::cout << "usage::SubmapAlignment --synthetic N STRIDE SEED [--submaps K] [--overlap F] [--perturb P] [--res R] [--band B] [--voxel-stride S] [--iters I]"
-                     " [--linearization normal|gradient|metric] [--color on|off] [--path cloud|mesh|volume] [--out DIR]" << std::endl;
+                     " [--linearization normal|gradient|metric] [--color on|off] [--path cloud|mesh|volume] [--merge two-step|fused] [--recompose single|batch] [--out DIR]" << std::endl;
         return bad || argc > 1 ? 2 : 0;
     }
     const long first = ((synthetic[2] + 999) % 1000) * 97 % 1000;
@@ -213,8 +222,12 @@ int main(int argc, char* argv[]) {
     options.linearization = lin; options.huber = 0.0f; options.huber_color = 0.0f;
     const char* const status_names[4] = {"converged", "max_iterations", "too_few_points", "singular"};
 
+    // submap 0 becomes the model the others are merged into: the re-composition needs it as it was
+    std::shared_ptr<integration::CubeHandler> first_submap;
+    if (!recompose.empty()) first_submap = std::make_shared<integration::CubeHandler>(*owned[0]);
     integration::CubeHandler& model = *owned[0];
     std::vector<Row> rows;
+    op_volume_merge_transformed_stats merge_stats = op_volume_merge_transformed_stats(); // --merge fused: summed over the submaps
     for (long i = 1; i < submaps; ++i) {
         Row row = Row();
         integration::CubeHandler& part = *owned[i];
@@ -260,13 +273,50 @@ int main(int argc, char* argv[]) {
         row.rmse = b.rmse; row.rmse_residual = got.rmse_residual;
         PoseError(row.T, &row.after_mm, &row.after_deg);
         t0 = std::chrono::steady_clock::now();
-        model.Merge(part, row.T); // Transform + Merge, as example/MergeMultipleSubmaps.cpp places a submap
+        if (merge == "fused") {
+            op_volume_merge_transformed_stats ms;
+            model.MergeTransformed(part, row.T, &ms);
+            merge_stats.sources += ms.sources; merge_stats.src_blocks += ms.src_blocks; merge_stats.touched_blocks += ms.touched_blocks;
+            merge_stats.created_blocks += ms.created_blocks; merge_stats.pairs += ms.pairs; merge_stats.voxels_copied += ms.voxels_copied;
+            merge_stats.voxels_kept += ms.voxels_kept; merge_stats.voxels_blended += ms.voxels_blended; merge_stats.voxels_reset += ms.voxels_reset;
+        } else {
+            model.Merge(part, row.T); // Transform + Merge, as example/MergeMultipleSubmaps.cpp places a submap
+        }
         model.Synchronize();
         row.merge_ms = Seconds(t0) * 1000.0;
         std::printf("submap %ld (frames %ld..%ld): pose error %.3f mm / %.5f deg -> %.3f mm / %.5f deg, %llu points, %llu used, %d iterations, status %s, rmse %.6f, residual rmse %.6f, "
                     "select %.3f ms, register %.3f ms, merge %.3f ms\n", i, begin[i], end[i] - 1, row.before_mm * 1000.0, row.before_deg, row.after_mm * 1000.0, row.after_deg, row.points,
                     row.used, row.iterations, status_names[row.status & 3], row.rmse, row.rmse_residual, row.select_ms, row.register_ms, row.merge_ms);
         rows.push_back(row);
+    }
+    if (!out_dir.empty() && !model.WriteToFile(out_dir + "/model.map")) return 1;
+    // the global model composed again from all submaps at their final poses, into a fresh volume
+    double recompose_ms = 0.0;
+    op_volume_merge_transformed_stats recompose_stats = op_volume_merge_transformed_stats();
+    if (!recompose.empty()) {
+        std::vector<const integration::CubeHandler*> parts(1, first_submap.get());
+        std::vector<geometry::TransformationMatrix> at(1, geometry::TransformationMatrix::Identity());
+        for (long i = 1; i < submaps; ++i) { parts.push_back(owned[i].get()); at.push_back(rows[i - 1].T); }
+        integration::CubeHandler global(camera);
+        global.SetVoxelResolution(res);
+        if (!global.Handle()) return 1;
+        global.Synchronize();
+        t0 = std::chrono::steady_clock::now();
+        if (recompose == "batch") {
+            global.MergeTransformed(parts, at, &recompose_stats);
+        } else {
+            for (size_t k = 0; k < parts.size(); ++k) {
+                op_volume_merge_transformed_stats ms;
+                global.MergeTransformed(*parts[k], at[k], &ms);
+                recompose_stats.sources += ms.sources; recompose_stats.src_blocks += ms.src_blocks; recompose_stats.touched_blocks += ms.touched_blocks;
+                recompose_stats.created_blocks += ms.created_blocks; recompose_stats.pairs += ms.pairs; recompose_stats.voxels_copied += ms.voxels_copied;
+                recompose_stats.voxels_kept += ms.voxels_kept; recompose_stats.voxels_blended += ms.voxels_blended; recompose_stats.voxels_reset += ms.voxels_reset;
+            }
+        }
+        global.Synchronize();
+        recompose_ms = Seconds(t0) * 1000.0;
+        std::printf("recompose %s: %zu submaps, %llu blocks touched, %.3f ms\n", recompose.c_str(), parts.size(), static_cast<unsigned long long>(recompose_stats.touched_blocks), recompose_ms);
+        if (!out_dir.empty() && !global.WriteToFile(out_dir + "/recomposed.map")) return 1;
     }
     // the doubled surface: how far the merged model's mesh lies from the model every frame was fused into at its true pose
     t0 = std::chrono::steady_clock::now();
@@ -279,8 +329,16 @@ int main(int argc, char* argv[]) {
     const double doubled = st.valid ? std::sqrt(st.sum_sq_sdf / static_cast<double>(st.valid)) : 0.0;
 
     std::printf("{\"frames\": %ld, \"stride\": %ld, \"first\": %ld, \"res\": %g, \"submaps\": %ld, \"length\": %ld, \"overlap\": %g, \"path\": \"%s\", \"color\": \"%s\", "
-                "\"linearization\": \"%s\", \"band\": %.9g, \"voxel_stride\": %ld, \"iters\": %ld, \"registered\": [", n, stride, first, static_cast<double>(res), submaps, length,
-                static_cast<double>(overlap), path.c_str(), with_color ? "on" : "off", linearization.c_str(), static_cast<double>(sel.band), voxel_stride, iters);
+                "\"linearization\": \"%s\", \"band\": %.9g, \"voxel_stride\": %ld, \"iters\": %ld, \"merge\": \"%s\", \"recompose\": \"%s\", \"recompose_ms\": %g, ", n, stride, first, static_cast<double>(res), submaps, length,
+                static_cast<double>(overlap), path.c_str(), with_color ? "on" : "off", linearization.c_str(), static_cast<double>(sel.band), voxel_stride, iters, merge.c_str(), recompose.empty() ? "none" : recompose.c_str(), recompose_ms);
+    const op_volume_merge_transformed_stats* const both[2] = {&merge_stats, &recompose_stats};
+    for (int k = 0; k < 2; ++k) // (touched_blocks of --recompose single and of --merge fused: summed per call, not a union)
+        std::printf("\"%s\": {\"sources\": %llu, \"src_blocks\": %llu, \"touched_blocks\": %llu, \"created_blocks\": %llu, \"pairs\": %llu, \"voxels_copied\": %llu, "
+                    "\"voxels_kept\": %llu, \"voxels_blended\": %llu, \"voxels_reset\": %llu}, ", k ? "recompose_stats" : "merge_stats",
+                    static_cast<unsigned long long>(both[k]->sources), static_cast<unsigned long long>(both[k]->src_blocks), static_cast<unsigned long long>(both[k]->touched_blocks),
+                    static_cast<unsigned long long>(both[k]->created_blocks), static_cast<unsigned long long>(both[k]->pairs), static_cast<unsigned long long>(both[k]->voxels_copied),
+                    static_cast<unsigned long long>(both[k]->voxels_kept), static_cast<unsigned long long>(both[k]->voxels_blended), static_cast<unsigned long long>(both[k]->voxels_reset));
+    std::printf("\"registered\": [");
     for (size_t k = 0; k < rows.size(); ++k) {
         const Row& r = rows[k];
         std::printf("%s{\"submap\": %zu, \"points\": %llu, \"used\": %llu, \"first_used\": %llu, \"colored\": %llu, \"iterations\": %d, \"status\": %d, \"rmse\": %.17g, "

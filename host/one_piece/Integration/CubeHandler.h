@@ -113,6 +113,13 @@ class CubeHandler {
     void SetTruncation(float trunc);
     void Merge(const CubeHandler& another);
     void Merge(const CubeHandler& another, const geometry::TransformationMatrix& trans);
+    // EXTENSION (not in the reference): what Merge(another, trans) -- for the list form, one such call per entry, in order -- leaves in this
+    // volume, bit for bit, in ONE device call and without the intermediate volume of Transform: every source is resampled straight into this
+    // volume's blocks (op_volume_merge_transformed_many states the definition).  A resolution that is not identical (or lists of different
+    // lengths): the reference's warning line (a message), nothing changes.  stats: the call's counts.
+    void MergeTransformed(const CubeHandler& another, const geometry::TransformationMatrix& trans, op_volume_merge_transformed_stats* stats = nullptr);
+    void MergeTransformed(const std::vector<const CubeHandler*>& others, const std::vector<geometry::TransformationMatrix>& trans,
+                          op_volume_merge_transformed_stats* stats = nullptr);
     void ComputeBounding(const cv::Mat& depth, const geometry::TransformationMatrix& pose, geometry::Point3& max_pos, geometry::Point3& min_pos);
     void PrepareCubes(const cv::Mat& depth, const geometry::TransformationMatrix& pose, std::vector<CubeID>& cube_id_list);
     void IntegrateImage(const cv::Mat& depth, const cv::Mat& rgb, const geometry::TransformationMatrix& pose);

@@ -314,6 +314,39 @@ void CubeHandler::Merge(const CubeHandler& another, const geometry::Transformati
     if (moved) Merge(*moved);
 }
 
+void CubeHandler::MergeTransformed(const CubeHandler& another, const geometry::TransformationMatrix& trans, op_volume_merge_transformed_stats* stats) {
+    MergeTransformed(std::vector<const CubeHandler*>(1, &another), std::vector<geometry::TransformationMatrix>(1, trans), stats);
+}
+void CubeHandler::MergeTransformed(const std::vector<const CubeHandler*>& others, const std::vector<geometry::TransformationMatrix>& trans,
+                                   op_volume_merge_transformed_stats* stats) {
+    if (stats) *stats = op_volume_merge_transformed_stats();
+    if (others.size() != trans.size()) {
+        std::cout << YELLOW << "[Warning]::[MergeTransformed]::" << others.size() << " volumes, " << trans.size() << " transformations." << RESET << std::endl;
+        return;
+    }
+    for (size_t k = 0; k < others.size(); ++k)
+        if (!others[k] || c_para.VoxelResolution != others[k]->c_para.VoxelResolution) {
+            std::cout << YELLOW << "[Warning]::[MergeVoxelHash]::Voxel resolution is not identical." << RESET << std::endl;
+            return;
+        }
+    Pending();
+    std::vector<op_volume*> vols;
+    std::vector<float> T, Ti;
+    for (size_t k = 0; k < others.size(); ++k) {
+        others[k]->Pending();
+        if (!others[k]->vol) continue; // never used: no blocks (Transform of it is empty, Merge of that changes nothing)
+        float m[16], mi[16];
+        bridge::RowMajor(trans[k], m);
+        bridge::RowMajor(trans[k].inverse(), mi);
+        vols.push_back(others[k]->vol);
+        T.insert(T.end(), m, m + 16);
+        Ti.insert(Ti.end(), mi, mi + 16);
+    }
+    if (vols.empty() || !Ensure()) return;
+    Touch();
+    if (op_volume_merge_transformed_many(vol, vols.data(), T.data(), Ti.data(), vols.size(), stats) != OP_OK) Report("MergeTransformed");
+}
+
 std::shared_ptr<CubeHandler> CubeHandler::Transform(const geometry::TransformationMatrix& trans) const {
     Pending();
     if (!Ensure()) return std::shared_ptr<CubeHandler>();

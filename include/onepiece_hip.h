@@ -501,6 +501,40 @@ int op_volume_resolution(op_volume *v, float *voxel_res);
 typedef struct { uint64_t src_blocks, dst_blocks, voxels_full, voxels_partial, voxels_empty, dropped_min_weight; } op_volume_coarsen_stats;
 int op_volume_coarsen(op_volume *src, int levels, float min_weight, uint64_t max_blocks, op_volume **out,
                       op_volume_coarsen_stats *stats /* may be NULL */);
+/* CubeHandler::Merge(another, trans) (CubeHandler.h:168-177; example/MergeMultipleSubmaps.cpp:34-42 places its submaps with it) for one source or
+ * for n of them, WITHOUT the intermediate volume: the sources are resampled straight into dst's blocks.  op_volume_merge_transformed is
+ * op_volume_merge_transformed_many with n = 1.  THE DEFINITION: after the call dst holds, as a map from block id to block, bit for bit what
+ *     for k = 0 .. n-1 in order:  op_volume_transform(srcs[k], Ts + 16 k, T_invs ? T_invs + 16 k : NULL, 0, 0, &tmp);  op_volume_merge(dst, tmp);  op_volume_destroy(tmp);
+ * leaves (the order of the pool is unspecified, as everywhere).  Spelled out:
+ *   - The claim set C_k is AddTransformedCube's (CubeHandler.h:199-225): each of the 512 voxel centres of EVERY block of source k, observed or not,
+ *     goes through T_k and the division by w; res / 2 is subtracted and the result floored by res; C_k is the blocks (>> 3) of that voxel and of
+ *     its + {0,1}^3 neighbours.  Every block of C_k that dst lacks is created with default voxels (AddCube).
+ *   - For every voxel of every block of C_k, and only those, r = ReadVoxelInterpolate (VoxelCube.cpp:6-50) of source k at T_k^-1 * centre, a
+ *     missing block reading as default voxels (T_invs NULL: the inverse is formed as op_volume_transform forms it).
+ *   - With t the destination voxel as sources 0 .. k-1 left it, TSDFVoxel::operator+= as op_volume_merge has it: t.w == 0 -> t = r (all five
+ *     values); else r.w == 0 -> unchanged; else w = t.w + r.w and, if w != 0, sdf and colour = (t.w * t_x + r.w * r_x) / w, every product, sum and
+ *     division rounded on its own, otherwise sdf = 999, colour = -1; the weight is w.
+ *   - Membership matters: a block that source j brought into the union and that is not in C_k receives nothing from source k, even where source
+ *     k's taps would reach observed voxels.
+ * stats (may be NULL): sources = n; src_blocks = the sum of the sources' block counts; pairs = sum |C_k|; touched_blocks = |union of the C_k|;
+ * created_blocks = how many of those dst lacked; the four voxel counts classify every (block of C_k, voxel) visit by the comparisons above, in
+ * that order: copied (t.w == 0), kept (r.w == 0), blended (w != 0; a NaN weight lands here), reset (otherwise) -- they sum to 512 * pairs.
+ * Integer counters: exact and repeatable.
+ * Refused before any device work, dst untouched: OP_ERR_INVALID for a NULL dst, NULL srcs or Ts with n > 0, a NULL srcs[k], srcs[k] == dst, a
+ * source on another device; OP_ERR_MISMATCH for a source whose resolution differs from dst's (op_last_error is the reference's warning line, as
+ * op_volume_merge gives it).  Not refused: n == 0 and sources without blocks (OP_OK); the same source twice at two poses.  A block coordinate
+ * outside the key range or a table that cannot grow is reported as op_volume_transform reports it; dst may then have gained default blocks and
+ * the merges of the groups that had completed (sources are taken in consecutive groups of 64).
+ * Like every accessor the call first flushes what is queued on dst and on every source; the kernels run on dst's stream after the sources' work
+ * is complete, and dst is final on return.  dst is marked as op_volume_merge marks it (general weights in every block that exists afterwards).
+ * Not built: a nearest-neighbour form, un-merging, per-source weights, sources on other devices. */
+typedef struct { uint64_t sources, src_blocks, touched_blocks, created_blocks, pairs,
+                 voxels_copied, voxels_kept, voxels_blended, voxels_reset; } op_volume_merge_transformed_stats;
+int op_volume_merge_transformed(op_volume *dst, op_volume *src, const float T[16], const float *T_inv /* or NULL */,
+                                op_volume_merge_transformed_stats *stats /* or NULL */);
+int op_volume_merge_transformed_many(op_volume *dst, op_volume *const *srcs, const float *Ts /* n x 16 */,
+                                     const float *T_invs /* NULL or n x 16 */, size_t n,
+                                     op_volume_merge_transformed_stats *stats /* or NULL */);
 /* CubeHandler::GetPointCloud (CubeHandler.cpp:45-69): points and grey colours |sdf|/truncation
  * (n x 3 floats each, host).  *n is the full count; xyz/colors may be NULL to query it. */
 int op_volume_point_cloud(op_volume *v, float *xyz, float *colors, size_t cap, size_t *n);

@@ -45,6 +45,12 @@ class CoarsenStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("src_blocks", "dst_blocks", "voxels_full", "voxels_partial", "voxels_empty", "dropped_min_weight")]
 
 
+class MergeTransformedStats(C.Structure):
+    """op_volume_merge_transformed_stats of op_volume_merge_transformed / _many."""
+    _fields_ = [(k, C.c_uint64) for k in ("sources", "src_blocks", "touched_blocks", "created_blocks", "pairs",
+                                          "voxels_copied", "voxels_kept", "voxels_blended", "voxels_reset")]
+
+
 class SampleStats(C.Structure):
     """op_volume_sample_stats of op_volume_sample."""
     _fields_ = [(k, C.c_uint64) for k in ("queries", "valid", "gradients", "out_of_range")] + \
@@ -229,6 +235,8 @@ SIGNATURES = {
     "op_volume_transform": (C.c_int, [_vp, _fp, _fp, C.c_int, C.c_uint64, C.POINTER(_vp)]),
     "op_volume_resolution": (C.c_int, [_vp, _fp]),
     "op_volume_coarsen": (C.c_int, [_vp, C.c_int, C.c_float, C.c_uint64, C.POINTER(_vp), C.POINTER(CoarsenStats)]),
+    "op_volume_merge_transformed": (C.c_int, [_vp, _vp, _fp, _fp, C.POINTER(MergeTransformedStats)]),
+    "op_volume_merge_transformed_many": (C.c_int, [_vp, C.POINTER(_vp), _fp, _fp, C.c_size_t, C.POINTER(MergeTransformedStats)]),
     "op_volume_point_cloud": (C.c_int, [_vp, _fp, _fp, C.c_size_t, _szp]),
     "op_volume_extract_mesh": (C.c_int, [_vp, _ip, _ip, _ip, _fp, _fp, C.c_size_t, _szp]),
     "op_volume_write_file": (C.c_int, [_vp, C.c_char_p]),

@@ -7,6 +7,7 @@
 //   CubeHandler::WriteToFile / ReadFromFile / ReadFromFileFloat            Integration/CubeHandler.h:40-128
 #include "volume_core.hpp"
 #include "voxel_interp.hpp"
+#include "transform_body.hpp"
 
 namespace {
 
@@ -133,56 +134,14 @@ __device__ __forceinline__ void wg_min_max(int v_lo, int v_hi, int* s_red, int* 
 }
 
 // pass 1: AddTransformedCube / AddTransformedCubeNearest (CubeHandler.h:199-241), executed with the
-// RESULT's CubePara (alloc_res).  One workgroup per source block.  A block's 512 voxels land in a handful of result blocks: the
-// workgroup gathers the distinct ids in a small LDS set and claims each ONCE in the result's hash table (a voxel-by-voxel claim
-// was ~2 000 hash probes per source block, most of them for ids another voxel had just entered).
-constexpr int kClaimSet = 128; // slots of the set (a power of two); a workgroup whose voxels reach more distinct blocks claims the overflow directly
+// RESULT's CubePara (alloc_res).  One workgroup per source block; the body (positions, the LDS set of distinct ids, one claim per id) is
+// transform_body.hpp's, shared with the merge that resamples straight into an existing volume.
 template <bool NEAREST>
 __global__ __launch_bounds__(512) void k_transform_alloc(VolView S, VolView D, State* dst_state, Mat4 T, float alloc_res) {
     __shared__ unsigned long long s_set[kClaimSet];
-    const int b = blockIdx.x, vid = threadIdx.x;
-    if (vid < kClaimSet) s_set[vid] = kEmptyKey;
-    __syncthreads();
-    const int kx = S.keys[3 * b], ky = S.keys[3 * b + 1], kz = S.keys[3 * b + 2];
-    const float half = alloc_res / 2;
-    const float px = ((float)kx * 8.0f) * alloc_res + ((float)(vid & 7) * alloc_res + half);
-    const float py = ((float)ky * 8.0f) * alloc_res + ((float)((vid >> 3) & 7) * alloc_res + half);
-    const float pz = ((float)kz * 8.0f) * alloc_res + ((float)(vid >> 6) * alloc_res + half);
-    const float* M = T.m;
-    const float q0 = ((M[0] * px + M[1] * py) + M[2] * pz) + M[3] * 1.0f;
-    const float q1 = ((M[4] * px + M[5] * py) + M[6] * pz) + M[7] * 1.0f;
-    const float q2 = ((M[8] * px + M[9] * py) + M[10] * pz) + M[11] * 1.0f;
-    const float q3 = ((M[12] * px + M[13] * py) + M[14] * pz) + M[15] * 1.0f;
-    const float n0 = NEAREST ? q0 / q3 : q0 / q3 - half, n1 = NEAREST ? q1 / q3 : q1 / q3 - half,
-                n2 = NEAREST ? q2 / q3 : q2 / q3 - half;
-    const int p0 = (int)floorf(n0 / alloc_res), p1 = (int)floorf(n1 / alloc_res), p2 = (int)floorf(n2 / alloc_res);
-    int lx = INT_MIN, ly = INT_MIN, lz = INT_MIN;
-#pragma unroll
-    for (int k = 0; k < (NEAREST ? 1 : 8); ++k) {
-        const int cx = (p0 + (k & 1)) >> 3, cy = (p1 + ((k >> 1) & 1)) >> 3, cz = (p2 + ((k >> 2) & 1)) >> 3;
-        if (cx == lx && cy == ly && cz == lz) continue;
-        lx = cx; ly = cy; lz = cz;
-        if (!key_in_range(cx, cy, cz)) { atomicOr(&dst_state->overflow, 8u); continue; }
-        // enter the id into the workgroup's set; a full set (never, for a rigid motion) falls back to the direct claim
-        const unsigned long long key = pack_key(cx, cy, cz);
-        unsigned sl = (unsigned)(hash_key_dev(cx, cy, cz) * 0x9E3779B97F4A7C15ULL >> 57) & (kClaimSet - 1);
-        bool placed = false;
-        for (int probe = 0; probe < kClaimSet; ++probe, sl = (sl + 1) & (kClaimSet - 1)) {
-            const unsigned long long cur = s_set[sl];
-            if (cur == key) { placed = true; break; }
-            if (cur == kEmptyKey) {
-                const unsigned long long old = atomicCAS(&s_set[sl], kEmptyKey, key);
-                if (old == kEmptyKey || old == key) { placed = true; break; }
-            }
-        }
-        if (!placed) { bool created; table_claim(D, dst_state, cx, cy, cz, &created); }
-    }
-    __syncthreads();
-    if (vid < kClaimSet && s_set[vid] != kEmptyKey) {
-        const unsigned long long key = s_set[vid];
-        bool created;
-        table_claim(D, dst_state, (int)(key >> 42) - kCoordLimit, (int)((key >> 21) & 0x1FFFFFull) - kCoordLimit, (int)(key & 0x1FFFFFull) - kCoordLimit, &created); // AddCube
-    }
+    const int b = blockIdx.x;
+    transform_claim_body<NEAREST>(s_set, S.keys[3 * b], S.keys[3 * b + 1], S.keys[3 * b + 2], dst_state, T.m, alloc_res,
+                                  [&](int cx, int cy, int cz) { bool created; table_claim(D, dst_state, cx, cy, cz, &created); });
 }
 
 // pass 2: every voxel of the result reads the source through trans^-1 (CubeHandler.h:257-294 /
@@ -191,12 +150,6 @@ __global__ __launch_bounds__(512) void k_transform_alloc(VolView S, VolView D, S
 // The taps of a block's 512 voxels fall into a few source blocks (a rotated 8^3 cube spans at most three per axis): the workgroup
 // takes the bounding box of its taps in block coordinates, looks every block of the box up ONCE (up to kSrcBox of them) and the taps
 // index that LDS table -- eight hash probes per voxel become none.  A box beyond kSrcBox blocks (a projective `trans`, NaN) probes per tap.
-constexpr int kSrcBox = 64;
-__device__ __forceinline__ Vox5 load_voxel(const VolView& S, int idx, int px, int py, int pz) {
-    if (idx < 0) return default_voxel();
-    const float* t = S.pool + (size_t)idx * kBlockFloats + ((px & 7) + (py & 7) * 8 + (pz & 7) * 64);
-    return Vox5{t[0], t[kVox], t[2 * kVox], t[3 * kVox], t[4 * kVox]};
-}
 template <bool NEAREST>
 __global__ __launch_bounds__(512) void k_transform_fill(VolView S, VolView D, Mat4 Tinv, float src_res) {
     __shared__ int s_red3[3][16];
@@ -274,59 +227,14 @@ __global__ __launch_bounds__(512) void k_transform_fill(VolView S, VolView D, Ma
 // flight per CU.  Same positions, same taps, same arithmetic as the form above.  2.82 -> 2.61 ms on the 164 k-block room volume.
 // (Also measured, on top of this form, and not kept: the result blocks in Morton order of their keys with one compact region per XCD -- the kernel
 // fetches 5.8 GB for a 1.7 GB source at 40 % L2 hits, so locality looked like the lever -- 2.69 ms, and 1.39 against 1.20 ms for the nearest form.)
+// The body is transform_body.hpp's (shared with the merge that resamples straight into an existing volume); here its results are stored as they come.
 __global__ __launch_bounds__(64) void k_transform_fill_wave(VolView S, VolView D, Mat4 Tinv, float src_res) {
     __shared__ int s_slot[kSrcBox];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int kx = D.keys[3 * b], ky = D.keys[3 * b + 1], kz = D.keys[3 * b + 2];
-    const float half = src_res / 2;
-    const float* M = Tinv.m;
-    float n0[8], n1[8], n2[8];
-    int p0[8], p1[8], p2[8];
-    int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
-#pragma unroll
-    for (int zs = 0; zs < 8; ++zs) {
-        const int vid = lane + 64 * zs;
-        const float px = ((float)kx * 8.0f) * src_res + ((float)(vid & 7) * src_res + half);
-        const float py = ((float)ky * 8.0f) * src_res + ((float)((vid >> 3) & 7) * src_res + half);
-        const float pz = ((float)kz * 8.0f) * src_res + ((float)(vid >> 6) * src_res + half);
-        const float q0 = ((M[0] * px + M[1] * py) + M[2] * pz) + M[3] * 1.0f;
-        const float q1 = ((M[4] * px + M[5] * py) + M[6] * pz) + M[7] * 1.0f;
-        const float q2 = ((M[8] * px + M[9] * py) + M[10] * pz) + M[11] * 1.0f;
-        const float q3 = ((M[12] * px + M[13] * py) + M[14] * pz) + M[15] * 1.0f;
-        n0[zs] = q0 / q3 - half; n1[zs] = q1 / q3 - half; n2[zs] = q2 / q3 - half;
-        p0[zs] = (int)floorf(n0[zs] / src_res); p1[zs] = (int)floorf(n1[zs] / src_res); p2[zs] = (int)floorf(n2[zs] / src_res);
-        lo[0] = min(lo[0], p0[zs] >> 3); hi[0] = max(hi[0], (int)(((long long)p0[zs] + 1) >> 3));
-        lo[1] = min(lo[1], p1[zs] >> 3); hi[1] = max(hi[1], (int)(((long long)p1[zs] + 1) >> 3));
-        lo[2] = min(lo[2], p2[zs] >> 3); hi[2] = max(hi[2], (int)(((long long)p2[zs] + 1) >> 3));
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        for (int o = 32; o > 0; o >>= 1) { lo[a] = min(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = max(hi[a], __shfl_xor(hi[a], o, 64)); }
-    const int x0 = lo[0], y0 = lo[1], z0 = lo[2];
-    const long long ex = (long long)hi[0] - x0 + 1, ey = (long long)hi[1] - y0 + 1, ez = (long long)hi[2] - z0 + 1;
-    const bool boxed = ex * ey <= kSrcBox && ex * ey * ez <= kSrcBox; // (uniform)
-    if (boxed) {
-        if (lane < (int)(ex * ey * ez)) s_slot[lane] = table_find(S, x0 + lane % (int)ex, y0 + (lane / (int)ex) % (int)ey, z0 + lane / (int)(ex * ey));
-        __syncthreads(); // (one wave: orders the LDS writes before the reads below)
-    }
-    auto fetch = [&](int tx, int ty, int tz) -> Vox5 {
-        if (!boxed) return fetch_voxel(S, tx, ty, tz);
-        return load_voxel(S, s_slot[((tx >> 3) - x0) + (int)ex * (((ty >> 3) - y0) + (int)ey * ((tz >> 3) - z0))], tx, ty, tz);
-    };
-#pragma unroll 2
-    for (int zs = 0; zs < 8; ++zs) {
-        Vox5 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = fetch(p0[zs] + (k & 1), p1[zs] + ((k >> 1) & 1), p2[zs] + ((k >> 2) & 1));
-        // ReadVoxelInterpolate (VoxelCube.cpp:6-50)
-        const float xw = (n0[zs] - (float)p0[zs] * src_res) / src_res, yw = (n1[zs] - (float)p1[zs] * src_res) / src_res,
-                    zw = (n2[zs] - (float)p2[zs] * src_res) / src_res;
-        const Vox5 z1v = interp_stage(interp_stage(v[0], v[1], xw), interp_stage(v[2], v[3], xw), yw);
-        const Vox5 z2v = interp_stage(interp_stage(v[4], v[5], xw), interp_stage(v[6], v[7], xw), yw);
-        const Vox5 r = interp_stage(z1v, z2v, zw);
+    transform_fill_wave_body<2>(S, s_slot, D.keys[3 * b], D.keys[3 * b + 1], D.keys[3 * b + 2], Tinv.m, src_res, [&](int zs, const Vox5& r) {
         float* t = D.pool + (size_t)b * kBlockFloats + (lane + 64 * zs);
         t[0] = r.s; t[kVox] = r.w; t[2 * kVox] = r.c0; t[3 * kVox] = r.c1; t[4 * kVox] = r.c2;
-    }
+    });
 }
 
 // GetPointCloud: voxels with weight != 0 and |sdf| < truncation, in the reference's x,y,z loop order

@@ -419,6 +419,27 @@ class CubeHandler:
             return
         L.check(rc)
 
+    def MergeTransformed(self, others, transforms):
+        """Extension (op_volume_merge_transformed_many states the definition): what `for o, T in zip(others, transforms): self.Merge(o, T)`
+        leaves in this volume, bit for bit, in one device call and without the intermediate volumes -- every source is resampled straight into
+        this volume's blocks.  `others`: one CubeHandler or a list; `transforms`: one 4 x 4 matrix or as many as there are sources.  A source of
+        another resolution -> the reference's warning line, no change, None.  Returns the call's counts: {"sources", "src_blocks",
+        "touched_blocks", "created_blocks", "pairs", "voxels_copied", "voxels_kept", "voxels_blended", "voxels_reset"}."""
+        if isinstance(others, CubeHandler):
+            others, transforms = [others], [transforms]
+        others = list(others)
+        Ts = np.ascontiguousarray(np.stack([_f32(T).reshape(16) for T in transforms]) if len(others) else np.zeros((0, 16), np.float32))
+        if Ts.shape[0] != len(others):
+            raise ValueError("MergeTransformed: %d sources, %d transforms" % (len(others), Ts.shape[0]))
+        handles = (C.c_void_p * max(len(others), 1))(*[o._h for o in others])
+        st = L.MergeTransformedStats()
+        rc = self._lib.op_volume_merge_transformed_many(self._h, handles, _fp(Ts), None, len(others), C.byref(st))
+        if rc == L.OP_ERR_MISMATCH:
+            print(self._lib.op_last_error().decode())
+            return None
+        L.check(rc)
+        return {k: int(getattr(st, k)) for k, _t in L.MergeTransformedStats._fields_}
+
     # -- resampling, point cloud, .map files (CubeHandler.h:40-128,242-338; CubeHandler.cpp:45-69)
     @classmethod
     def _wrap(cls, handle, camera, device):
