@@ -66,8 +66,7 @@ __device__ __forceinline__ void transform_claim_body(unsigned long long* s_set, 
 constexpr int kSrcBox = 64;
 __device__ __forceinline__ Vox5 load_voxel(const VolView& S, int idx, int px, int py, int pz) {
     if (idx < 0) return default_voxel();
-    const float* t = S.pool + (size_t)idx * kBlockFloats + ((px & 7) + (py & 7) * 8 + (pz & 7) * 64);
-    return Vox5{t[0], t[kVox], t[2 * kVox], t[3 * kVox], t[4 * kVox]};
+    return load_planes(S.pool + (size_t)idx * kBlockFloats + ((px & 7) + (py & 7) * 8 + (pz & 7) * 64));
 }
 template <int UNROLL, class Put>
 __device__ __forceinline__ void transform_fill_wave_body(const VolView& S, int* s_slot, int kx, int ky, int kz, const float* M, float src_res, Put put) {

@@ -279,6 +279,22 @@ int vol_block_count(op_volume* v, unsigned* n) {
     return OP_OK;
 }
 
+void load_transform(const float* T, const float* T_inv, Mat4* M, Mat4* Mi) {
+    std::memcpy(M->m, T, sizeof(M->m));
+    if (T_inv) std::memcpy(Mi->m, T_inv, sizeof(Mi->m));
+    else op_host::mat4_inverse(T, Mi->m);
+}
+
+int vol_offsets_from_counts(const unsigned* d_counts, size_t n, unsigned* d_offsets, size_t* total) {
+    std::vector<unsigned> cnt(n), off(n);
+    OP_HIP(hipMemcpy(cnt.data(), d_counts, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    size_t sum = 0;
+    for (size_t b = 0; b < n; ++b) { off[b] = (unsigned)sum; sum += cnt[b]; }
+    *total = sum;
+    if (d_offsets) OP_HIP(hipMemcpy(d_offsets, off.data(), n * sizeof(unsigned), hipMemcpyHostToDevice));
+    return OP_OK;
+}
+
 // Single-frame scratch of the synchronous calls (ComputeBounding / PrepareCubes): host images are copied to the device
 // stream-ordered; device images are used in place.  (op_volume_integrate stages through the pinned ring below.)
 int vol_stage_images(op_volume* v, const void** depth, int depth_fmt, const unsigned char** rgb, int mem, int slot = 0) {
@@ -1113,12 +1129,8 @@ int op_volume_prepare_cubes(op_volume* v, const void* depth, int depth_fmt, int 
     BatchPtrs Q{};
     frame_params(v, pose, pose_inv, &F.f[0], &I.f[0]);
     Q.depth[0] = depth;
-    for (;;) { // a selection that outgrows the pool grows it (vol_check) and is then simply run again
-        const unsigned cap_before = v->max_blocks;
-        OP_TRY(vol_enqueue_batch(v, F, I, Q, 1, depth_fmt, /*select_only=*/true, /*record=*/true));
-        OP_TRY(vol_check(v));
-        if (v->max_blocks == cap_before) break;
-    }
+    unsigned n_blocks = 0; // a selection that outgrows the pool grows it and is then simply run again
+    OP_TRY(vol_claim_until_fit(v, [&]() -> int { return vol_enqueue_batch(v, F, I, Q, 1, depth_fmt, /*select_only=*/true, /*record=*/true); }, &n_blocks));
     StateHead st;
     OP_HIP(hipMemcpy(&st, v->state, sizeof(st), hipMemcpyDeviceToHost));
     unsigned long long n_cand0 = 0;

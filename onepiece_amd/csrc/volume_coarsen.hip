@@ -14,6 +14,7 @@
 //                     Per result block: at most 8 x 10 KB read, 10 KB written, 16 bytes of counts.
 //   k_coarsen_stats   folds the per-block counts into 64 partial rows (plain stores); the host adds those.
 #include "volume_core.hpp"
+#include "voxel_interp.hpp"
 
 namespace {
 
@@ -69,9 +70,9 @@ __global__ __launch_bounds__(512) void k_coarsen_fill(VolView S, VolView D, floa
     }
     float* o = D.pool + (size_t)b * kBlockFloats + vid;
     if (n) {
-        o[0] = Sd / W; o[kVox] = W * 0.125f; o[2 * kVox] = C0 / W; o[3 * kVox] = C1 / W; o[4 * kVox] = C2 / W;
+        store_planes(o, Vox5{Sd / W, W * 0.125f, C0 / W, C1 / W, C2 / W});
     } else {
-        o[0] = 999.0f; o[kVox] = 0.0f; o[2 * kVox] = -1.0f; o[3 * kVox] = -1.0f; o[4 * kVox] = -1.0f;
+        store_planes(o, default_voxel());
     }
     // the block's counts: per wave at most 64 voxels of a kind (7 bits each) and 512 dropped children (10 bits)
     const unsigned packed = wave_sum((n == 8 ? 1u : 0u) | ((n > 0 && n < 8) ? 1u << 7 : 0u) | (n == 0 ? 1u << 14 : 0u) | (dropped << 21));
@@ -115,12 +116,10 @@ int coarsen_once(op_volume* src, float min_weight, uint64_t max_blocks, op_volum
     int rc = OP_OK;
     unsigned nd = 0;
     if (ns) {
-        for (;;) { // if the result outgrows a pool the caller sized, vol_block_count grows it and the (idempotent) allocation pass runs again
-            const unsigned cap_before = dst->max_blocks;
+        rc = vol_claim_until_fit(dst, [&]() -> int { // the (idempotent) allocation pass, again if the result outgrew a pool the caller sized
             hipLaunchKernelGGL(k_coarsen_alloc, dim3((ns + 255) / 256), dim3(256), 0, dst->stream, src->view(), dst->view(), dst->state, ns);
-            rc = vol_block_count(dst, &nd);
-            if (rc != OP_OK || dst->max_blocks == cap_before) break;
-        }
+            return OP_OK;
+        }, &nd);
         if (rc == OP_OK && nd) {
             op::Scope tmp;
             tmp.bind(dst->stream);

@@ -8,6 +8,10 @@
 //   volume_gc.hip   CollectGarbage;  volume_sample.hip  the point queries (op_volume_sample), over trilinear_sample.hpp and voxel_interp.hpp
 //   volume_band.hip the band voxels of a volume as a list (op_volume_band_voxels)
 //   volume_coarsen.hip  the half-resolution copy of a volume (op_volume_coarsen)
+//   volume_merge_transformed.hip  Merge with a pose, one or many sources, without the intermediate volume (op_volume_merge_transformed / _many)
+//   volume_register.hip  registration of clouds, frames and volumes against the fused field (op_volume_register_*)
+// The reference's arithmetic on voxels (plane access, TSDFVoxel::operator+, ReadVoxelInterpolate) is voxel_interp.hpp's, the two passes of Transform
+// are transform_body.hpp's: one copy each.
 // Data layout in HBM: see volume.hip (and DESIGN.md section 2).
 #pragma once
 #include <cfloat>
@@ -605,6 +609,21 @@ int vol_check(op_volume* v);                 // flush, synchronise, grow + repla
 int vol_reset(op_volume* v);
 int vol_reserve(op_volume* v, unsigned long long need);
 int vol_block_count(op_volume* v, unsigned* n);
+// launch() enqueues an idempotent pass that claims blocks in dst; vol_block_count then synchronises and, if the claims outgrew the pool, grows it
+// (which re-hashes the table): the pass runs again until the pool no longer changes.  Returns the first error of either; *n_blocks as vol_block_count.
+template <class F>
+int vol_claim_until_fit(op_volume* dst, F launch, unsigned* n_blocks) {
+    for (;;) {
+        const unsigned cap_before = dst->max_blocks;
+        OP_TRY(launch());
+        OP_TRY(vol_block_count(dst, n_blocks));
+        if (dst->max_blocks == cap_before) return OP_OK;
+    }
+}
+void load_transform(const float* T, const float* T_inv, Mat4* M, Mat4* Mi); // M = T; Mi = T_inv, or trans.inverse() (CubeHandler.h:265,320) where it is NULL
+// counts[0, n) on the device (complete: the caller has synchronised their stream) -> *total and, where d_offsets is not NULL, their exclusive prefix sums there;
+// a host scan over blocking copies, the total in 64 bits
+int vol_offsets_from_counts(const unsigned* d_counts, size_t n, unsigned* d_offsets, size_t* total);
 void vol_mark_foreign(op_volume* v, unsigned long long bound);
 void vol_launch_fill_pool(op_volume* v, size_t first_block, size_t n_blocks); // k_fill_pool over pool slots [first_block, first_block + n_blocks), on the volume's stream
 void vol_launch_rehash(op_volume* v, unsigned n_valid);                       // k_clear_table, then k_rehash of keys[0, n_valid), on the volume's stream

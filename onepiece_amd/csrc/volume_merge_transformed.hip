@@ -16,7 +16,7 @@
 //                   unrolled -- the compiler reports 244 VGPRs and 2 waves per SIMD; in LDS 142 and 3, with the LDS itself admitting 15 waves per
 //                   CU: DESIGN.md section 3.11), then for each set bit k of its mask, ascending, pass 2 of
 //                   Transform (transform_body.hpp, the body of k_transform_fill_wave) with source k's T^-1 yields r for every voxel and
-//                   TSDFVoxel::operator+= (the arithmetic of k_merge_blocks) folds it in; the block is stored ONCE.  A destination block is owned
+//                   TSDFVoxel::operator+= (voxel_merge, voxel_interp.hpp: what k_merge_blocks calls) folds it in; the block is stored ONCE.  A destination block is owned
 //                   by exactly one wave; blocks outside the union are neither read nor written.  No floating-point atomics anywhere; the counts
 //                   go through integer atomics on kParts rows of words (a wave adds to row blockIdx % kParts), which the host adds up.
 // Per-call device scratch (op::Scope): the mask (8 B per table slot), the list (4 B per pool slot), the group's source table, the counters -- no
@@ -83,23 +83,13 @@ __global__ __launch_bounds__(64) void k_merge_fill(const MtSource* __restrict__ 
         const VolView S = tab[k].S;
         const Mat4 Ti = tab[k].Ti;
         transform_fill_wave_body<2>(S, s_slot, kx, ky, kz, Ti.m, res, [&](int zs, const Vox5& r) {
-            // voxels[voxel_id] += r: TSDFVoxel::operator+ with general weights, the comparisons and the arithmetic of k_merge_blocks
-            float* d = t + 64 * zs;
-            const float dw = d[kVox];
-            if (dw == 0) { d[0] = r.s; d[kVox] = r.w; d[2 * kVox] = r.c0; d[3 * kVox] = r.c1; d[4 * kVox] = r.c2; ck += 1u; return; }
-            if (r.w == 0) { ck += 1u << 16; return; }
-            const float w = dw + r.w;
-            if (w != 0) {
-                d[0] = (dw * d[0] + r.w * r.s) / w;
-                d[2 * kVox] = (dw * d[2 * kVox] + r.w * r.c0) / w;
-                d[3 * kVox] = (dw * d[3 * kVox] + r.w * r.c1) / w;
-                d[4 * kVox] = (dw * d[4 * kVox] + r.w * r.c2) / w;
-                br += 1u;
-            } else {
-                d[0] = 999.0f; d[2 * kVox] = d[3 * kVox] = d[4 * kVox] = -1.0f;
-                br += 1u << 16;
-            }
-            d[kVox] = w;
+            // voxels[voxel_id] += r (never a fresh block: a newly claimed one holds default voxels, whose weight of 0 means "copy")
+            voxel_merge(t + 64 * zs, r, false, [&](int kind) {
+                if (kind == kMergeCopied) ck += 1u;
+                else if (kind == kMergeKept) ck += 1u << 16;
+                else if (kind == kMergeBlended) br += 1u;
+                else br += 1u << 16;
+            });
         });
         __syncthreads(); // (one wave: the taps of this source have read s_slot before the next source's look-ups overwrite it)
     }
@@ -158,9 +148,7 @@ int merge_transformed(const char* who, op_volume* dst, op_volume* const* srcs, c
         for (size_t j = 0; j < gn; ++j) {
             const size_t k = g0 + j;
             tab[j].S = srcs[k]->view();
-            std::memcpy(tab[j].T.m, Ts + 16 * k, sizeof(tab[j].T.m));
-            if (T_invs) std::memcpy(tab[j].Ti.m, T_invs + 16 * k, sizeof(tab[j].Ti.m));
-            else op_host::mat4_inverse(Ts + 16 * k, tab[j].Ti.m); // trans.inverse() (CubeHandler.h:265)
+            load_transform(Ts + 16 * k, T_invs ? T_invs + 16 * k : nullptr, &tab[j].T, &tab[j].Ti);
             tab[j].first = (unsigned)total;
             total += ns[k];
         }
@@ -176,8 +164,9 @@ int merge_transformed(const char* who, op_volume* dst, op_volume* const* srcs, c
         OP_TRY(s.alloc(&d_count, 1));
         OP_TRY(s.alloc(&d_parts, (size_t)kParts * kCnt));
         unsigned nd = 0, touched = 0;
-        for (;;) { // if the claims outgrow the pool, vol_block_count grows it (and re-hashes): mask and list are rebuilt from zero by another pass
-            const unsigned cap_before = dst->max_blocks;
+        // if the claims outgrow the pool, vol_block_count grows it (and re-hashes): mask and list are rebuilt from zero by another pass.  (A coordinate
+        // outside the key range is reported by vol_block_count, as op_volume_transform reports it.)
+        OP_TRY(vol_claim_until_fit(dst, [&]() -> int {
             OP_TRY(s.alloc(&d_mask, (size_t)dst->table_size));
             OP_TRY(s.alloc(&d_list, (size_t)dst->max_blocks));
             OP_HIP(hipMemsetAsync(d_mask, 0, sizeof(unsigned long long) * (size_t)dst->table_size, dst->stream));
@@ -185,11 +174,9 @@ int merge_transformed(const char* who, op_volume* dst, op_volume* const* srcs, c
             hipLaunchKernelGGL(k_merge_claim, dim3((unsigned)total), dim3(512), 0, dst->stream, (const MtSource*)d_tab, (int)gn, dst->view(), dst->state, dst->res,
                                d_mask, d_list, dst->max_blocks, d_count);
             OP_HIP(hipGetLastError());
-            OP_TRY(vol_block_count(dst, &nd)); // (a coordinate outside the key range is reported here, as op_volume_transform reports it)
-            if (dst->max_blocks != cap_before) continue;
-            OP_HIP(hipMemcpy(&touched, d_count, sizeof(touched), hipMemcpyDeviceToHost));
-            break;
-        }
+            return OP_OK;
+        }, &nd));
+        OP_HIP(hipMemcpy(&touched, d_count, sizeof(touched), hipMemcpyDeviceToHost));
         if (!touched) continue;
         if (touched > dst->max_blocks) return fail(OP_ERR_HIP, "%s: %u touched blocks in a pool of %u", who, touched, dst->max_blocks); // (never: every one of them holds a pool slot)
         vol_mark_foreign(dst, nd); // merged means: general weights in the blocks that exist after this group

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(512) void k_export_aos(const float* __restrict__ po
 }
 
 // insert keys; slots[i] receives the TABLE slot of key i, encoded -(slot+2) when newly created; the
-// consumers below translate it to the pool slot through tvals (next kernel => visible)
+// consumers below translate it to the pool slot through tvals (next kernel => visible): slot_to_pool, voxel_interp.hpp
 __global__ void k_insert_keys(VolView V, const int* __restrict__ keys, size_t n, int* __restrict__ slots, State* st) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -34,10 +34,9 @@ __global__ void k_insert_keys(VolView V, const int* __restrict__ keys, size_t n,
 // AoS voxels -> pool planes for the given slots (SetCubeMap / AddCube + assignment)
 __global__ __launch_bounds__(512) void k_import_aos(float* __restrict__ pool, const int* __restrict__ slots,
                                                     const int* __restrict__ tvals, const float* __restrict__ in) {
-    int idx = slots[blockIdx.x];
-    if (idx == -1) return;
-    if (idx <= -2) idx = -(idx + 2);
-    idx = tvals[idx]; // table slot -> pool slot
+    const int slot = slots[blockIdx.x];
+    if (slot == -1) return;
+    const int idx = slot_to_pool(slot, tvals);
     if (idx < 0) return;
     const float* src = in + ((size_t)blockIdx.x * kVox + threadIdx.x) * 5;
     float* dst = pool + (size_t)idx * kBlockFloats + threadIdx.x;
@@ -49,32 +48,13 @@ __global__ __launch_bounds__(512) void k_import_aos(float* __restrict__ pool, co
 // general weights), or plain copy when the block was just created in dst.
 __global__ __launch_bounds__(512) void k_merge_blocks(float* __restrict__ dpool, const float* __restrict__ spool,
                                                       const int* __restrict__ slots, const int* __restrict__ tvals) {
-    int idx = slots[blockIdx.x];
-    if (idx == -1) return;
-    const bool fresh = idx <= -2;
-    if (fresh) idx = -(idx + 2);
-    idx = tvals[idx]; // table slot -> pool slot
+    const int slot = slots[blockIdx.x];
+    if (slot == -1) return;
+    bool fresh;
+    const int idx = slot_to_pool(slot, tvals, &fresh);
     if (idx < 0) return;
     const float* a = spool + (size_t)blockIdx.x * kBlockFloats + threadIdx.x; // src block i lives in src pool slot i
-    float* t = dpool + (size_t)idx * kBlockFloats + threadIdx.x;
-    const float bs = a[0], bw = a[kVox], b0 = a[2 * kVox], b1 = a[3 * kVox], b2 = a[4 * kVox];
-    const float tw = t[kVox];
-    if (fresh || tw == 0) { // copy / "weight == 0 -> return other"
-        t[0] = bs; t[kVox] = bw; t[2 * kVox] = b0; t[3 * kVox] = b1; t[4 * kVox] = b2;
-        return;
-    }
-    if (bw == 0) return;
-    const float w = tw + bw;
-    if (w != 0) {
-        const float ts = t[0], t0 = t[2 * kVox], t1 = t[3 * kVox], t2 = t[4 * kVox];
-        t[0] = (tw * ts + bw * bs) / w;
-        t[2 * kVox] = (tw * t0 + bw * b0) / w;
-        t[3 * kVox] = (tw * t1 + bw * b1) / w;
-        t[4 * kVox] = (tw * t2 + bw * b2) / w;
-    } else {
-        t[0] = 999.0f; t[2 * kVox] = t[3 * kVox] = t[4 * kVox] = -1.0f;
-    }
-    t[kVox] = w;
+    voxel_merge(dpool + (size_t)idx * kBlockFloats + threadIdx.x, load_planes(a), fresh, [](int) {});
 }
 
 // K4a: sum-form pack for the RCCL reduce: [w*sdf, w, w*c0, w*c1, w*c2] planes per union key.
@@ -97,10 +77,9 @@ __global__ __launch_bounds__(512) void k_pack_sum(VolView V, const int* __restri
 // K4b: normalise the reduced sums back to mean form into the (re-keyed) volume.
 __global__ __launch_bounds__(512) void k_unpack_sum(float* __restrict__ pool, const int* __restrict__ slots,
                                                     const int* __restrict__ tvals, const float* __restrict__ sum) {
-    int idx = slots[blockIdx.x];
-    if (idx == -1) return;
-    if (idx <= -2) idx = -(idx + 2);
-    idx = tvals[idx]; // table slot -> pool slot
+    const int slot = slots[blockIdx.x];
+    if (slot == -1) return;
+    const int idx = slot_to_pool(slot, tvals);
     if (idx < 0) return;
     const float* a = sum + (size_t)blockIdx.x * kBlockFloats + threadIdx.x;
     float* t = pool + (size_t)idx * kBlockFloats + threadIdx.x;
@@ -108,7 +87,8 @@ __global__ __launch_bounds__(512) void k_unpack_sum(float* __restrict__ pool, co
     if (w > 0) {
         t[0] = a[0] / w; t[kVox] = w; t[2 * kVox] = a[2 * kVox] / w; t[3 * kVox] = a[3 * kVox] / w; t[4 * kVox] = a[4 * kVox] / w;
     } else {
-        t[0] = 999.0f; t[kVox] = 0.0f; t[2 * kVox] = t[3 * kVox] = t[4 * kVox] = -1.0f;
+        const Vox5 d = default_voxel();
+        t[0] = d.s; t[kVox] = d.w; t[2 * kVox] = t[3 * kVox] = t[4 * kVox] = d.c2;
     }
 }
 
@@ -117,21 +97,7 @@ __global__ __launch_bounds__(512) void k_unpack_sum(float* __restrict__ pool, co
 // GetPointCloud (CubeHandler.cpp:45-69)
 // ---------------------------------------------------------------------------------------------
 
-// the voxel fetch and the stages of ReadVoxelInterpolate (fetch_voxel, vox_scale, vox_add_direct, interp_stage): voxel_interp.hpp (shared with the
-// point queries of volume_sample.hip)
-
-// workgroup-wide minimum / maximum of an int (512 threads = 8 waves), result in every thread
-__device__ __forceinline__ void wg_min_max(int v_lo, int v_hi, int* s_red, int* out_lo, int* out_hi) {
-    for (int o = 32; o > 0; o >>= 1) { v_lo = min(v_lo, __shfl_xor(v_lo, o, 64)); v_hi = max(v_hi, __shfl_xor(v_hi, o, 64)); }
-    const int wave = threadIdx.x >> 6;
-    __syncthreads(); // (s_red may still be read from a previous call)
-    if ((threadIdx.x & 63) == 0) { s_red[wave] = v_lo; s_red[8 + wave] = v_hi; }
-    __syncthreads();
-    int lo = s_red[0], hi = s_red[8];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) { lo = min(lo, s_red[k]); hi = max(hi, s_red[8 + k]); }
-    *out_lo = lo; *out_hi = hi;
-}
+// the voxel fetch, the plane access and the stages of ReadVoxelInterpolate: voxel_interp.hpp (shared with the point queries of volume_sample.hip)
 
 // pass 1: AddTransformedCube / AddTransformedCubeNearest (CubeHandler.h:199-241), executed with the
 // RESULT's CubePara (alloc_res).  One workgroup per source block; the body (positions, the LDS set of distinct ids, one claim per id) is
@@ -144,16 +110,13 @@ __global__ __launch_bounds__(512) void k_transform_alloc(VolView S, VolView D, S
                                   [&](int cx, int cy, int cz) { bool created; table_claim(D, dst_state, cx, cy, cz, &created); });
 }
 
-// pass 2: every voxel of the result reads the source through trans^-1 (CubeHandler.h:257-294 /
-// :312-334) with the SOURCE's CubePara (this->c_para).  One workgroup per result block; result
-// voxels are still default, so `voxels[voxel_id] += result` stores `result` (weight == 0 -> other).
-// The taps of a block's 512 voxels fall into a few source blocks (a rotated 8^3 cube spans at most three per axis): the workgroup
-// takes the bounding box of its taps in block coordinates, looks every block of the box up ONCE (up to kSrcBox of them) and the taps
-// index that LDS table -- eight hash probes per voxel become none.  A box beyond kSrcBox blocks (a projective `trans`, NaN) probes per tap.
+// pass 2 of TransformNearest: every voxel of the result reads the source through trans^-1 (CubeHandler.h:312-334) with the SOURCE's
+// CubePara (this->c_para).  One workgroup per result block, one thread per voxel; result voxels are still default, so
+// `voxels[voxel_id] += result` stores `result` (weight == 0 -> other).  ONE tap per voxel, probed directly (measured: a table of the
+// source blocks the workgroup's taps touch, as the trilinear form keeps one, costs this form more than it saves).
 template <bool NEAREST>
 __global__ __launch_bounds__(512) void k_transform_fill(VolView S, VolView D, Mat4 Tinv, float src_res) {
-    __shared__ int s_red3[3][16];
-    __shared__ int s_slot[kSrcBox];
+    static_assert(NEAREST, "the trilinear form of pass 2 is k_transform_fill_wave");
     const int b = blockIdx.x, vid = threadIdx.x;
     const int kx = D.keys[3 * b], ky = D.keys[3 * b + 1], kz = D.keys[3 * b + 2];
     const float half = src_res / 2;
@@ -165,66 +128,16 @@ __global__ __launch_bounds__(512) void k_transform_fill(VolView S, VolView D, Ma
     const float q1 = ((M[4] * px + M[5] * py) + M[6] * pz) + M[7] * 1.0f;
     const float q2 = ((M[8] * px + M[9] * py) + M[10] * pz) + M[11] * 1.0f;
     const float q3 = ((M[12] * px + M[13] * py) + M[14] * pz) + M[15] * 1.0f;
-    const float n0 = NEAREST ? q0 / q3 : q0 / q3 - half, n1 = NEAREST ? q1 / q3 : q1 / q3 - half,
-                n2 = NEAREST ? q2 / q3 : q2 / q3 - half;
+    const float n0 = q0 / q3, n1 = q1 / q3, n2 = q2 / q3;
     const int p0 = (int)floorf(n0 / src_res), p1 = (int)floorf(n1 / src_res), p2 = (int)floorf(n2 / src_res);
-    // the source blocks this workgroup's taps touch (taps at p and p + 1; the nearest form has ONE tap per voxel and probes directly: measured, the
-    // box costs it more than it saves).  An int overflow of p + 1 only ever widens the box: fallback.
-    int x0 = 0, x1 = 0, y0 = 0, y1 = 0, z0 = 0, z1 = 0;
-    if (!NEAREST) { // the three axes in ONE pass over the workgroup (two barriers instead of six)
-        int lo[3] = {p0 >> 3, p1 >> 3, p2 >> 3};
-        int hi[3] = {(int)(((long long)p0 + 1) >> 3), (int)(((long long)p1 + 1) >> 3), (int)(((long long)p2 + 1) >> 3)};
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-            for (int o = 32; o > 0; o >>= 1) { lo[a] = min(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = max(hi[a], __shfl_xor(hi[a], o, 64)); }
-        const int wave = vid >> 6;
-        if ((vid & 63) == 0) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { s_red3[a][wave] = lo[a]; s_red3[a][8 + wave] = hi[a]; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            int l = s_red3[a][0], h = s_red3[a][8];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) { l = min(l, s_red3[a][k]); h = max(h, s_red3[a][8 + k]); }
-            lo[a] = l; hi[a] = h;
-        }
-        x0 = lo[0]; x1 = hi[0]; y0 = lo[1]; y1 = hi[1]; z0 = lo[2]; z1 = hi[2];
-    }
-    const long long ex = (long long)x1 - x0 + 1, ey = (long long)y1 - y0 + 1, ez = (long long)z1 - z0 + 1;
-    const bool boxed = !NEAREST && ex * ey <= kSrcBox && ex * ey * ez <= kSrcBox; // (uniform)
-    if (boxed) {
-        if (vid < (int)(ex * ey * ez)) s_slot[vid] = table_find(S, x0 + vid % (int)ex, y0 + (vid / (int)ex) % (int)ey, z0 + vid / (int)(ex * ey));
-        __syncthreads();
-    }
-    auto fetch = [&](int tx, int ty, int tz) -> Vox5 { // cube_map.find(GetCubeID(p)) + GetVoxel(GetVoxelID(p)); default voxel if absent
-        if (!boxed) return fetch_voxel(S, tx, ty, tz);
-        return load_voxel(S, s_slot[((tx >> 3) - x0) + (int)ex * (((ty >> 3) - y0) + (int)ey * ((tz >> 3) - z0))], tx, ty, tz);
-    };
-    Vox5 r;
-    if (NEAREST) {
-        r = fetch(p0, p1, p2);
-    } else {
-        Vox5 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = fetch(p0 + (k & 1), p1 + ((k >> 1) & 1), p2 + ((k >> 2) & 1));
-        // ReadVoxelInterpolate (VoxelCube.cpp:6-50)
-        const float xw = (n0 - (float)p0 * src_res) / src_res, yw = (n1 - (float)p1 * src_res) / src_res,
-                    zw = (n2 - (float)p2 * src_res) / src_res;
-        const Vox5 z1v = interp_stage(interp_stage(v[0], v[1], xw), interp_stage(v[2], v[3], xw), yw);
-        const Vox5 z2v = interp_stage(interp_stage(v[4], v[5], xw), interp_stage(v[6], v[7], xw), yw);
-        r = interp_stage(z1v, z2v, zw);
-    }
-    float* t = D.pool + (size_t)b * kBlockFloats + vid;
-    t[0] = r.s; t[kVox] = r.w; t[2 * kVox] = r.c0; t[3 * kVox] = r.c1; t[4 * kVox] = r.c2;
+    store_planes(D.pool + (size_t)b * kBlockFloats + vid, fetch_voxel(S, p0, p1, p2));
 }
 
-// The trilinear form as ONE WAVE per result block (eight z-slices of 64 voxels in turn).  The 512-thread form above is a chain of dependent
-// phases -- key, positions, box reduction, hash probes, taps, stores -- with workgroup barriers between them and only four workgroups per CU to
+// The trilinear form as ONE WAVE per result block (eight z-slices of 64 voxels in turn).  Its 512-thread form (k_transform_fill<false>, until round 5)
+// was a chain of dependent phases -- key, positions, box reduction, hash probes, taps, stores -- with workgroup barriers between them and only four workgroups per CU to
 // overlap one block's waiting with another's work (measured: neither staging the tap box in LDS nor halving the number of tap loads moved it).
 // A wave needs no barriers: the box is a shuffle reduction, the probed slots sit in the wave's own 64 LDS words, and 32 independent blocks are in
-// flight per CU.  Same positions, same taps, same arithmetic as the form above.  2.82 -> 2.61 ms on the 164 k-block room volume.
+// flight per CU.  Same positions, same taps, same arithmetic as that form.  2.82 -> 2.61 ms on the 164 k-block room volume.
 // (Also measured, on top of this form, and not kept: the result blocks in Morton order of their keys with one compact region per XCD -- the kernel
 // fetches 5.8 GB for a 1.7 GB source at 40 % L2 hits, so locality looked like the lever -- 2.69 ms, and 1.39 against 1.20 ms for the nearest form.)
 // The body is transform_body.hpp's (shared with the merge that resamples straight into an existing volume); here its results are stored as they come.
@@ -232,8 +145,7 @@ __global__ __launch_bounds__(64) void k_transform_fill_wave(VolView S, VolView D
     __shared__ int s_slot[kSrcBox];
     const int b = blockIdx.x, lane = threadIdx.x;
     transform_fill_wave_body<2>(S, s_slot, D.keys[3 * b], D.keys[3 * b + 1], D.keys[3 * b + 2], Tinv.m, src_res, [&](int zs, const Vox5& r) {
-        float* t = D.pool + (size_t)b * kBlockFloats + (lane + 64 * zs);
-        t[0] = r.s; t[kVox] = r.w; t[2 * kVox] = r.c0; t[3 * kVox] = r.c1; t[4 * kVox] = r.c2;
+        store_planes(D.pool + (size_t)b * kBlockFloats + (lane + 64 * zs), r);
     });
 }
 
@@ -600,19 +512,15 @@ int op_volume_transform(op_volume* src, const float T[16], const float* T_inv, i
     OP_TRY(op_volume_create(&src->cam, dst_res, src->trunc, src->far_d, src->near_d, src->device, max_blocks, &dst));
     vol_mark_foreign(dst, max_blocks); // resampled values (the reference's own divisions may even leave NaN / inf in them); the bound is tightened below
     Mat4 M, Mi;
-    std::memcpy(M.m, T, sizeof(M.m));
-    if (T_inv) std::memcpy(Mi.m, T_inv, sizeof(Mi.m));
-    else op_host::mat4_inverse(T, Mi.m); // trans.inverse() (CubeHandler.h:265,320)
+    load_transform(T, T_inv, &M, &Mi);
     int rc = OP_OK;
     if (ns) {
         unsigned nd = 0;
-        for (;;) { // if the result outgrows its pool, vol_block_count grows it and the (idempotent) allocation pass runs again
-            const unsigned cap_before = dst->max_blocks;
+        rc = vol_claim_until_fit(dst, [&]() -> int { // the (idempotent) allocation pass, again if the result outgrew its pool
             if (nearest) hipLaunchKernelGGL(k_transform_alloc<true>, dim3(ns), dim3(512), 0, dst->stream, src->view(), dst->view(), dst->state, M, dst_res);
             else hipLaunchKernelGGL(k_transform_alloc<false>, dim3(ns), dim3(512), 0, dst->stream, src->view(), dst->view(), dst->state, M, dst_res);
-            rc = vol_block_count(dst, &nd);
-            if (rc != OP_OK || dst->max_blocks == cap_before) break;
-        }
+            return OP_OK;
+        }, &nd);
         if (rc == OP_OK && nd) {
             if (nearest) hipLaunchKernelGGL(k_transform_fill<true>, dim3(nd), dim3(512), 0, dst->stream, src->view(), dst->view(), Mi, src->res);
             else hipLaunchKernelGGL(k_transform_fill_wave, dim3(nd), dim3(64), 0, dst->stream, src->view(), dst->view(), Mi, src->res);
@@ -644,17 +552,14 @@ int op_volume_point_cloud(op_volume* v, float* xyz, float* colors, size_t cap, s
     unsigned *d_counts = nullptr, *d_offsets = nullptr;
     OP_TRY(s.alloc(&d_counts, nb));
     OP_TRY(s.alloc(&d_offsets, nb));
-    std::vector<unsigned> cnt(nb), off(nb);
     hipLaunchKernelGGL(k_point_cloud, dim3(nb), dim3(512), 0, v->stream, v->view(), v->res, v->trunc, d_counts, (const unsigned*)nullptr,
                        (float*)nullptr, (float*)nullptr);
     OP_HIP(hipStreamSynchronize(v->stream));
-    OP_HIP(hipMemcpy(cnt.data(), d_counts, nb * sizeof(unsigned), hipMemcpyDeviceToHost));
     size_t total = 0;
-    for (unsigned b = 0; b < nb; ++b) { off[b] = (unsigned)total; total += cnt[b]; }
+    OP_TRY(vol_offsets_from_counts(d_counts, nb, (xyz && colors) ? d_offsets : nullptr, &total)); // (a count-only call uploads no offsets)
     *n = total;
     if (!xyz || !colors || !total) return OP_OK;
     if (total > cap) return fail(OP_ERR_CAPACITY, "point cloud has %zu points, buffer holds %zu", total, cap);
-    OP_HIP(hipMemcpy(d_offsets, off.data(), nb * sizeof(unsigned), hipMemcpyHostToDevice));
     float *d_xyz = nullptr, *d_col = nullptr;
     OP_TRY(s.alloc(&d_xyz, total * 3));
     OP_TRY(s.alloc(&d_col, total * 3));
@@ -715,20 +620,17 @@ int opv::vol_mesh_soup(op::Scope& out, op_volume* v, const int32_t* tri_table, c
     OP_HIP(hipMemcpy(d_list, list.data(), nl * sizeof(unsigned), hipMemcpyHostToDevice));
     OP_HIP(hipMemcpy(d_tri, tri8.data(), 256 * 16, hipMemcpyHostToDevice));
     OP_HIP(hipMemcpy(d_edge, edge_pairs, 24 * sizeof(int), hipMemcpyHostToDevice));
-    std::vector<unsigned> cnt(nl), off(nl);
     hipLaunchKernelGGL(k_mesh_neighbours, dim3((nl * 8u + 255u) / 256u), dim3(256), 0, v->stream, v->view(), (const unsigned*)d_list, nl, d_nbs);
     hipLaunchKernelGGL(k_mesh, dim3(nl), dim3(512), 0, v->stream, v->view(), v->res, (const signed char*)d_tri, (const int*)d_edge, (const unsigned*)d_list,
                        (const int*)d_nbs, d_counts, (const unsigned*)nullptr, (float*)nullptr, (float*)nullptr);
     OP_HIP(hipStreamSynchronize(v->stream));
-    OP_HIP(hipMemcpy(cnt.data(), d_counts, nl * sizeof(unsigned), hipMemcpyDeviceToHost));
     size_t total_tri = 0;
-    for (unsigned b = 0; b < nl; ++b) { off[b] = (unsigned)total_tri; total_tri += cnt[b]; }
+    OP_TRY(vol_offsets_from_counts(d_counts, nl, emit ? d_offsets : nullptr, &total_tri)); // (a count-only call uploads no offsets)
     const size_t total = total_tri * 3;
     *n_vertices = total;
     if (!emit || !total) return OP_OK;
     if (total > cap_vertices) return fail(OP_ERR_CAPACITY, "mesh has %zu vertices, buffer holds %zu", total, cap_vertices);
     if (total_tri > 0xffffffffull / 3) return fail(OP_ERR_CAPACITY, "mesh too large");
-    OP_HIP(hipMemcpy(d_offsets, off.data(), nl * sizeof(unsigned), hipMemcpyHostToDevice));
     OP_TRY(out.alloc(d_pts_out, total * 3));
     OP_TRY(out.alloc(d_col_out, total * 3));
     hipLaunchKernelGGL(k_mesh, dim3(nl), dim3(512), 0, v->stream, v->view(), v->res, (const signed char*)d_tri, (const int*)d_edge,

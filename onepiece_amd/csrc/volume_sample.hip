@@ -3,7 +3,7 @@
 //   OP_SAMPLE_TRILINEAR   the raycaster's strict trilinear sample, its central-difference gradient and trilinear colour (trilinear_sample.hpp:
 //                         rc_cell, rc_weight and the gather through the hash, the functions raycast.hip marches and shades with)
 //   OP_SAMPLE_REFERENCE   VoxelCube::ReadVoxelInterpolate as CubeHandler::Transform evaluates it (voxel_interp.hpp: the voxel fetch and the lerp
-//                         stages of volume_ops.hip's k_transform_fill*)
+//                         stages of k_transform_fill_wave)
 // k_volume_sample: one lane per query, grid-stride, read-only.  A lane keeps its last block (id -> pool slot), so the eight taps of a sample cost
 // one hash lookup unless they straddle blocks; the seven samples of a gradient query are gathered one after the other through that cache (their 56
 // taps are 32 distinct voxels: the repeats hit the L1).  The colour planes are read only where voxels are asked for.  Every lane accumulates the
@@ -67,8 +67,7 @@ __device__ __forceinline__ Vox5 fetch_voxel_cached(const VolView& V, BlockCache&
     const int bx = px >> 3, by = py >> 3, bz = pz >> 3;
     if (!(bx == bc.cx && by == bc.cy && bz == bc.cz)) { bc.cx = bx; bc.cy = by; bc.cz = bz; bc.idx = table_find(V, bx, by, bz); }
     if (bc.idx < 0) return default_voxel();
-    const float* t = V.pool + (size_t)bc.idx * kBlockFloats + ((px - bx * 8) + (py - by * 8) * 8 + (pz - bz * 8) * 64);
-    return Vox5{t[0], t[kVox], t[2 * kVox], t[3 * kVox], t[4 * kVox]};
+    return load_planes(V.pool + (size_t)bc.idx * kBlockFloats + ((px - bx * 8) + (py - by * 8) * 8 + (pz - bz * 8) * 64));
 }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(kSampleWg) void k_volume_sample(VolView V, SampleAr
                     if (!all) { d[0] = d[1] = d[2] = 0.0f; st |= OP_SAMPLE_NO_GRADIENT; }
                 }
             }
-        } else { // ReadVoxelInterpolate as k_transform_fill evaluates it
+        } else { // ReadVoxelInterpolate as k_transform_fill_wave evaluates it
             const float half = A.W.res / 2;
             const float n0 = x - half, n1 = y - half, n2 = z - half;
             const float e0 = n0 / A.W.res, e1 = n1 / A.W.res, e2 = n2 / A.W.res;

@@ -1,6 +1,9 @@
-// voxel_interp.hpp -- VoxelCube::ReadVoxelInterpolate (Integration/VoxelCube.cpp:6-50) in pieces: the voxel fetch and the TSDFVoxel operators
-// one lerp stage is made of.  Shared by CubeHandler::Transform (volume_ops.hip: k_transform_fill*) and the point queries (volume_sample.hip:
-// OP_SAMPLE_REFERENCE).  One copy of the arithmetic.
+// voxel_interp.hpp -- the reference's arithmetic on TSDFVoxels, once: the plane access of a voxel in the pool, TSDFVoxel::operator+ with general
+// weights (voxel_merge), and VoxelCube::ReadVoxelInterpolate (Integration/VoxelCube.cpp:6-50) in pieces -- the voxel fetch and the TSDFVoxel
+// operators one lerp stage is made of.  Users: CubeHandler::Merge (volume_ops.hip: k_merge_blocks; volume_merge_transformed.hip: k_merge_fill),
+// CubeHandler::Transform (transform_body.hpp, the body of k_transform_fill_wave and k_merge_fill; volume_ops.hip: k_transform_fill, the nearest
+// form) and the point queries (volume_sample.hip: OP_SAMPLE_REFERENCE).  Also here, because the same kernels share it: the decode of
+// k_insert_keys' coded slot.
 #pragma once
 #include "volume_core.hpp"
 
@@ -8,14 +11,52 @@ namespace opv {
 
 __device__ __forceinline__ Vox5 default_voxel() { return Vox5{999.0f, 0.0f, -1.0f, -1.0f, -1.0f}; }
 
+// the five planes of one voxel of a block (pool or LDS copy): t points at its sdf, plane p is t[p * kVox]
+__device__ __forceinline__ Vox5 load_planes(const float* t) { return Vox5{t[0], t[kVox], t[2 * kVox], t[3 * kVox], t[4 * kVox]}; }
+__device__ __forceinline__ void store_planes(float* t, const Vox5& v) {
+    t[0] = v.s; t[kVox] = v.w; t[2 * kVox] = v.c0; t[3 * kVox] = v.c1; t[4 * kVox] = v.c2;
+}
+
+// voxels[id] += b on the planes at t: TSDFVoxel::operator+ with general weights (TSDFVoxel.h:24-39), or a plain copy when the block was just
+// created (`fresh`: CubeHandler::Merge assigns the whole cube, CubeHandler.h:160-163).  note(kind) is called inside the branch taken.
+enum { kMergeCopied = 0, kMergeKept = 1, kMergeBlended = 2, kMergeReset = 3 };
+template <class Note>
+__device__ __forceinline__ void voxel_merge(float* t, const Vox5& b, bool fresh, Note note) {
+    const float tw = t[kVox];
+    if (fresh || tw == 0) { store_planes(t, b); note(kMergeCopied); return; } // copy / "weight == 0 -> return other"
+    if (b.w == 0) { note(kMergeKept); return; }
+    const float w = tw + b.w;
+    if (w != 0) {
+        const Vox5 a = load_planes(t);
+        t[0] = (tw * a.s + b.w * b.s) / w;
+        t[2 * kVox] = (tw * a.c0 + b.w * b.c0) / w;
+        t[3 * kVox] = (tw * a.c1 + b.w * b.c1) / w;
+        t[4 * kVox] = (tw * a.c2 + b.w * b.c2) / w;
+        note(kMergeBlended);
+    } else { // the default voxel but for its weight, which is w (= 0) below
+        const Vox5 d = default_voxel();
+        t[0] = d.s; t[2 * kVox] = t[3 * kVox] = t[4 * kVox] = d.c2;
+        note(kMergeReset);
+    }
+    t[kVox] = w;
+}
+
+// The slot k_insert_keys left for a key that has one (the kernels leave on -1, "none", before they come here): the table slot, or
+// -(slot + 2) when that insert created it (*fresh, where asked for).  Returns the pool slot (through tvals; < 0: none).
+__device__ __forceinline__ int slot_to_pool(int idx, const int* __restrict__ tvals, bool* fresh = nullptr) {
+    const bool created = idx <= -2;
+    if (created) idx = -(idx + 2);
+    if (fresh) *fresh = created;
+    return tvals[idx];
+}
+
 // cube_map.find(GetCubeID(p)) + GetVoxel(GetVoxelID(p)) (VoxelCube.h:63-67,81-86); default voxel if absent
 static __device__ Vox5 fetch_voxel(const VolView& S, int px, int py, int pz) {
     const int cx = px >> 3, cy = py >> 3, cz = pz >> 3; // floor((p + 0.0) / 8)
     const int idx = table_find(S, cx, cy, cz);
     if (idx < 0) return default_voxel();
     const int vid = (px - cx * 8) + (py - cy * 8) * 8 + (pz - cz * 8) * 64;
-    const float* t = S.pool + (size_t)idx * kBlockFloats + vid;
-    return Vox5{t[0], t[kVox], t[2 * kVox], t[3 * kVox], t[4 * kVox]};
+    return load_planes(S.pool + (size_t)idx * kBlockFloats + vid);
 }
 // TSDFVoxel::operator*(float) (TSDFVoxel.h:56-67)
 __device__ __forceinline__ Vox5 vox_scale(const Vox5& a, float wgt) {
